@@ -2,14 +2,19 @@
 """Headline benchmark: helical-parameter candidates/s on a 512x512 image over a 100k-point
 (twist, rise) grid (BASELINE.json configs[1] = SURVEY.md section 8d "C2").
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C2|C3|C4|C5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C2|C3|C4|C5] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 `--config` picks the BASELINE configuration whose grid is sharded over the ranks: C2 (default; configs[1]), C3 (C2's grid
 x Csym 1..6, configs[2]), C4 (1024^2, 500 x 500 grid, configs[3]), C5 (64 segments x 512^2 against one 200 x 100 grid,
-per-segment arg-max, configs[4]).  At N = 1 with the default config the line also carries one timed leg per other
-configuration, a general (non-power-of-two) size and the batched Path-A scorer under "pipelines", each with its own
-roofline object.
+per-segment arg-max, configs[4]).
+
+A plain run sets up, warms up, times K steps and prints the headline line (with the roofline of the timed launches).
+`--full` adds everything else: the CPU baseline, the checks of what was timed (device arg-max against a host arg-max),
+the per-phase times of a step, the host-pointer API's rate and, at N = 1 with the default config, one timed leg per
+other configuration, a general (non-power-of-two) size and the batched Path-A scorer under "pipelines", each with its
+own roofline object.  `--dump-outputs DIR` writes what the last timed step delivered to the caller (rank 0):
+DIR/scores.npy (float32 [segments, candidates]) and DIR/best_index.npy (float64 [segments]).
 
 A step = one pass of the sweep over the C2 grid with the candidate list and the experimental spectrum
 already resident in HBM: every rank sweeps its contiguous shard of the ONE 400 x 250 grid (whole twists per
@@ -136,8 +141,10 @@ def parse_args(argv=None):
                          "weak = a full grid per rank (rot = 7.5 deg x rank)")
     ap.add_argument("--csyms", type=int, nargs="+", default=None, help="Csym values of the grid (default: the configuration's)")
     ap.add_argument("--max-batch", type=int, default=0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra-legs", action="store_true", help="skip the run-tables / transform / C3 legs at N = 1")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the CPU baseline, the checks, the step phases, the host-pointer API and the extra legs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-extra-legs", action="store_true", help="--full without the run-tables / transform / C3 / config legs")
     ap.add_argument("--no-profile", action="store_true", help="skip the per-launch HIP events")
     ap.add_argument("--profile-period", type=int, default=16,
                     help="HIP events around the launches of every k-th batch of the timed sweeps (1 = all)")
@@ -149,6 +156,8 @@ def parse_args(argv=None):
                          "second pass through the HBM intermediate; transform: raster + two transforms per candidate")
     ap.add_argument("--engine", default="helicon_amd:SweepEngine", help=argparse.SUPPRESS)
     ap.add_argument("--dump-scores", default=None, help="rank 0 writes the gathered scores [S, G] of the last step (.npy)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 writes the last timed step's outputs as DIR/<name>.npy (scores, best_index)")
     return ap.parse_args(argv)
 
 
@@ -208,7 +217,7 @@ def main():
 
     # CPU baseline first, before this process touches the GPU (it uses worker processes)
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.config == "C2":
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and args.config == "C2":
         cpu = cpu_baseline_leg(w)
 
     import torch
@@ -288,25 +297,28 @@ def main():
         eng.profile(0)
     pipeline = eng.last_first_pass
 
-    # correctness of what was timed: the arg-max of the gathered scores must be the synthetic truth
+    # the arg-max of the last timed step (the line says whether it is the synthetic truth)
     best_all = sh.best_index()
     best = int(best_all[0])
-    scores = sh.scores()
-    for seg in range(scores.shape[0]):
-        assert int(best_all[seg]) == int(np.argmax(np.where(np.isnan(scores[seg]), -np.inf, scores[seg]))), "device arg-max != host arg-max"
-    if sh.host_scores is not None and world == 1:   # what the timed step left in host memory is the same thing
-        assert np.array_equal(np.asarray(sh.host_scores).reshape(scores.shape[0], -1)[:, : scores.shape[1]], scores, equal_nan=True)
+    if args.full:   # correctness of what was timed: the device arg-max is the host arg-max of the gathered scores
+        scores = sh.scores()
+        for seg in range(scores.shape[0]):
+            assert int(best_all[seg]) == int(np.argmax(np.where(np.isnan(scores[seg]), -np.inf, scores[seg]))), "device arg-max != host arg-max"
+        if sh.host_scores is not None and world == 1:   # what the timed step left in host memory is the same thing
+            assert np.array_equal(np.asarray(sh.host_scores).reshape(scores.shape[0], -1)[:, : scores.shape[1]], scores, equal_nan=True)
     best_pair = (round(float(params_all[best, 0]), 6), round(float(params_all[best, 1]), 6), int(params_all[best, 2]))
     if rank == 0 and args.dump_scores:
-        np.save(args.dump_scores, scores)
+        np.save(args.dump_scores, sh.scores())
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, sh, best_all)
 
     # where a step's time goes on this rank (untimed extra steps, device events between the phases)
-    phases = phase_times(torch, sh, dev, on_gpu) if on_gpu else None
+    phases = phase_times(torch, sh, dev, on_gpu) if (args.full and on_gpu) else None
 
     # the host-pointer API (params H2D + scores D2H inside the call), reported beside `value`
     host_api = None
     extra = {}
-    if world == 1 and on_gpu:
+    if args.full and world == 1 and on_gpu:
         eng.set_stream(None)
         eng.sweep(params_all)   # (untimed: the host-side buffers of this entry point; a whole sweep, so that every
         th = time.perf_counter()  #  k_fused_pass launch of this process is one — the profiler's average means something)
@@ -362,6 +374,27 @@ def main():
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.destroy_process_group()
+
+
+DUMP_BYTES = 48 << 20   # --dump-outputs budget; larger score arrays are written as a fixed sample of candidates
+
+
+def dump_outputs(out_dir, sh, best_index):
+    """What the last timed step handed to its caller, as DIR/<name>.npy: `scores` [S, G] float32 (the pinned host copy the
+    step made, in flat candidate order) and `best_index` [S] float64 (each segment's arg-max as a flat candidate index).
+    Beyond DUMP_BYTES, `scores` keeps a sorted default_rng(0) sample of the candidates, whose indices are `scores_columns`."""
+    from helicon_amd.distributed import assemble_scores
+
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    scores = assemble_scores(sh.host_scores.cpu().numpy(), sh.n_total).astype(np.float32, copy=False)
+    cap = DUMP_BYTES // (4 * scores.shape[0])
+    if scores.shape[1] > cap:
+        cols = np.sort(np.random.default_rng(0).choice(scores.shape[1], cap, replace=False))
+        scores = scores[:, cols]
+        np.save(out / "scores_columns.npy", cols.astype(np.float64))
+    np.save(out / "scores.npy", np.ascontiguousarray(scores))
+    np.save(out / "best_index.npy", np.asarray(best_index, dtype=np.float64))
 
 
 def phase_times(torch, sh, dev, on_gpu, reps=5):

@@ -177,3 +177,22 @@ def test_bench_config_c5_world2_matches_world1(tmp_path):
     assert s4.shape == (1, 10 * 500) and c4["config"]["image"] == 64        # (--side 64 overrides the configuration's 1024)
     c3, s3 = _run_bench(tmp_path, 2, ["--config", "C3", "--grid-stride", "40"])
     assert s3.shape == (1, 6 * 10 * 250)
+
+
+def test_bench_dump_outputs_are_the_last_steps_results(tmp_path):
+    """`--dump-outputs DIR`: the last timed step's scores (float32 [S, G], what --dump-scores writes) and every segment's
+    arg-max (float64), the same in two runs with the same arguments; `steps` and `ms_per_step` in the line."""
+    extra = ["--config", "C5", "--segments", "3", "--grid-stride", "10"]
+    runs = []
+    for k in range(2):
+        line, scores = _run_bench(tmp_path, 1, [*extra, "--dump-outputs", str(tmp_path / f"out{k}")])
+        got = {f.stem: np.load(f) for f in (tmp_path / f"out{k}").glob("*.npy")}
+        assert set(got) == {"scores", "best_index"}
+        assert got["scores"].dtype == np.float32 and got["best_index"].dtype == np.float64
+        np.testing.assert_array_equal(got["scores"], scores)
+        assert got["best_index"].tolist() == np.argmax(scores, axis=1).tolist()
+        assert got["best_index"][0] == line["argmax"]["index"]
+        assert line["steps"] == 2 and line["ms_per_step"] > 0
+        runs.append(got)
+    for name in runs[0]:
+        np.testing.assert_array_equal(runs[0][name], runs[1][name])

@@ -293,7 +293,7 @@ def _task(data, twist, rise, n=16, image_file=None, image_index=0, target_apix2d
 
 
 def test_process_one_task_host_logic_with_a_stub_engine(tmp_path, monkeypatch):
-    """pipeline.py:211-218, 268-272 without a GPU: 1-based imageIndex, blank image -> None, the app's default
+    """pipeline.py:211-218, 268-272 with a stand-in engine: 1-based imageIndex, blank image -> None, the app's default
     target_apix2d (5) accepted when it does not exceed the image's pixel size, one reference upload for many calls
     on the same image, and loud refusal of the options that need scikit-image."""
     from helicon_amd import denovo3D as D
@@ -321,8 +321,15 @@ def test_process_one_task_host_logic_with_a_stub_engine(tmp_path, monkeypatch):
     D.process_one_task(*_task(img, 29.0, 25.0, target_apix2d=2.0))                  # finer than the image: no rescale
     assert stub.ref_calls == calls + 1
     # coarser than the image: down_scale runs on the device (hh_rescale_2d) — without one that is a loud error, not a fallback
-    with pytest.raises(H.HeliconHipError, match="no such HIP device"):
-        D.process_one_task(*_task(img, 29.0, 25.0, target_apix2d=10.0))
+    import torch
+    if torch.cuda.is_available():
+        img2 = 2.0 * img          # (other content: the call with the stand-in down_scale below must not find this prepared image)
+        out = D.process_one_task(*_task(img2, 29.0, 25.0, target_apix2d=10.0))
+        np.testing.assert_allclose(out[2][0], D.down_scale(img2, 10.0, 5.0), rtol=1e-6, atol=1e-6)
+        assert out[2][0].shape == (8, 8) and out[2][4] == 10.0
+    else:
+        with pytest.raises(H.HeliconHipError, match="no such HIP device"):
+            D.process_one_task(*_task(img, 29.0, 25.0, target_apix2d=10.0))
     with monkeypatch.context() as mp:
         mp.setattr(D, "down_scale", lambda d, target, orig, device=0: np.asarray(d)[::2, ::2] * 1.0)
         out = D.process_one_task(*_task(img, 29.0, 25.0, target_apix2d=10.0))

@@ -8,10 +8,10 @@
 set -o pipefail
 R=$PWD; O=$R/gpurun_out/$1; mkdir -p $O; export TMPDIR=/tmp
 T="timeout -k 10"
-$T 500 python bench.py > $O/bench.json 2> $O/bench.err || exit 1
+$T 500 python bench.py --full > $O/bench.json 2> $O/bench.err || exit 1
 echo bench done >> $O/progress.log
 cd /tmp
-$T 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python $R/bench.py --no-cpu-baseline --no-extra-legs > $O/bench_under_rocprof.json 2> $O/stats.log || exit 1
+$T 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python $R/bench.py --full --no-cpu-baseline --no-extra-legs > $O/bench_under_rocprof.json 2> $O/stats.log || exit 1
 echo stats512 done >> $O/progress.log
 $T 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats1024 -- python $R/tools/configs.py C4 > $O/c4_under_rocprof.txt 2> $O/stats1024.log || exit 1
 echo stats1024 done >> $O/progress.log

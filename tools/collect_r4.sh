@@ -12,10 +12,10 @@ T="timeout -k 10"
 stats_csv() { f=$(ls $1/*/*kernel_stats.csv | head -1); cp $f $2; rm -rf $1; }
 if [ $PART = A ]; then
   $T 1000 python -m pytest tests -m gpu -q > $O/suite.log 2>&1; tail -3 $O/suite.log
-  $T 700 python bench.py > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
+  $T 700 python bench.py --full > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
   echo bench done
   cd /tmp
-  $T 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 $R/bench.py --no-cpu-baseline --no-extra-legs > $O/bench_under_rocprof.json 2> $O/stats.log || exit 1
+  $T 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 $R/bench.py --full --no-cpu-baseline --no-extra-legs > $O/bench_under_rocprof.json 2> $O/stats.log || exit 1
   cd $R; stats_csv $O/stats $O/kernel_stats.csv
   python3 tools/bench_summary.py $O/bench.json > $O/bench_summary.txt 2>&1
   echo collected A
