@@ -48,88 +48,9 @@
 #include "../../include/helicon_hip.h"
 #include "gen_rows.h"  // the general-size sweep's two-step row kernel (second translation unit, gen_rows.hip)
 
-// Tuning knobs (compile-time; defaults are the measured best)
-#ifndef HH_ABLATE
-#define HH_ABLATE 0        // timing-only builds: 1 no raster, 2 no K_A FFT, 4 no K_A store, 8 no twiddle loads,
-                           // 16 no K_B FFT, 32 no K_B epilogue math, 64 no K_B weight loads; run-table first pass:
-                           // 128 no stores, 256 no accumulation, 1024 no table staging; fused pass: 2048 no panel
-                           // accumulation, 4096 no column-factor prefetch (16 / 32 as for K_B), 8192 no second exchange,
-                           // 65536 compact q stores of every candidate into 64 rows (no HBM write stream)
-#endif
-#ifndef HH_KA_WPS
-#define HH_KA_WPS 8        // K_A: waves per SIMD the register allocator must leave room for (4 workgroups per CU)
-#endif
-#ifndef HH_KB_TWLDS
-#define HH_KB_TWLDS 0      // K_B: twiddles from a per-workgroup LDS table instead of registers
-#endif
-#ifndef HH_KA_FPW_BIG
-#define HH_KA_FPW_BIG 4      // K_A: transforms per workgroup and tile when a transform spans two wavefronts (N = 1024)
-#endif
-#ifndef HH_KA_BAND
-#define HH_KA_BAND 64       // K_A: image columns per workgroup (N >= 256)
-#endif
-#ifndef HH_KB_CPW
-#define HH_KB_CPW 16       // K_B: candidates per workgroup (one ky block of 8 rows of each)
-#endif
-#ifndef HH_KT_PAIRS
-#define HH_KT_PAIRS 32     // run-table first pass: column pairs per workgroup
-#endif
-#ifndef HH_KT_KYW
-#define HH_KT_KYW 128      // run-table first pass: ky rows per workgroup
-#endif
-#ifndef HH_KF_CPW
-#define HH_KF_CPW 0        // fused pass: candidates per workgroup (of one run); 0 = chosen per launch (fused_groups_per_run)
-#endif
-#ifndef HH_FUSED_BATCH
-#define HH_FUSED_BATCH 131072  // fused pass: most candidates per launch (whole runs); 6 GB of column factors + moments at N = 512
-#endif
-#ifndef HH_FUSED_BYTES
-#define HH_FUSED_BYTES (8LL << 30)  // fused pass: the launch is shortened so that its column factors (two halves) fit this
-#endif
-#ifndef HH_SEG_BATCH
-#define HH_SEG_BATCH 24576  // fused pass with several segments: most candidates per launch (C5: 11.6 ms at 1024, 9.5 ms at 20k)
-#endif
-#ifndef HH_SEG_BYTES
-#define HH_SEG_BYTES (12LL << 30)  // ... shortened so that the batch's masked q (0.5 MB per candidate at N = 512) fits this
-#endif
-#ifndef HH_KF_WPS
-#define HH_KF_WPS 4        // fused pass: waves per SIMD the register allocator must leave room for
-#endif
-#ifndef HH_FFT_SWZ
-#define HH_FFT_SWZ 1       // xor-swizzled slots for the first exchange of every transform (bank conflicts)
-#endif
-#ifndef HH_FFT_SWZ2
-#define HH_FFT_SWZ2 1      // second exchange of the 512 / 1024-point transforms kept in bank-conflict-free slots
-#endif
-#ifndef HH_KF_PSWZ
-#define HH_KF_PSWZ 1       // fused pass: 16-byte chunks of the panel row xor-swizzled (conflict-free b128 stores)
-#endif
-#ifndef HH_KF_STAGGER
-#define HH_KF_STAGGER 1    // fused pass (N = 512): wavefronts 4-7 run half a candidate behind wavefronts 0-3
-#endif
-#ifndef HH_KF_DEFER_Q
-#define HH_KF_DEFER_Q 1    // fused pass, several segments: the early wavefronts store a candidate's q at the top of the next round
-#endif
-#ifndef HH_KF_EGLOBAL
-#define HH_KF_EGLOBAL 0    // fused pass (N = 512): column factors read straight from global memory (vector L1) instead of LDS copies
-#endif
-#ifndef HH_KF_CUT
-#define HH_KF_CUT 1        // fused pass: part A of a candidate ends after the butterflies of this transform stage
-#endif
-#ifndef HH_KF_SPLIT
-#define HH_KF_SPLIT 1      // fused pass, N = 1024: one radix-2 step across a row's two wavefronts, then a 512-point
-#endif                     // transform inside each (one workgroup barrier per candidate instead of six)
-#ifndef HH_KF_PRIO
-#define HH_KF_PRIO 0       // fused pass: s_setprio level of the late wavefronts (0 = off)
-#endif
+// Tuning values are constants beside what they tune (the measured best).
 #ifndef HH_POISON
 #define HH_POISON 0        // test builds: NaN in every factor row the fused pass has no business reading
-#endif
-#ifndef HH_XCD_MAP
-#define HH_XCD_MAP 1       // fused pass: all ky blocks of a layer of candidates on one XCD (shared L2)
-#endif
-#ifndef HH_KB_WPS
-#define HH_KB_WPS 4        // K_B: waves per SIMD the register allocator must leave room for
 #endif
 
 namespace {
@@ -298,7 +219,7 @@ __device__ __forceinline__ void fft_stage(float2 (&v)[8], const TW& tw, int t, f
   // therefore kept in slot o ^ (((o >> 6) & 1) << 3): the writer's r becomes r ^ b with b = (j >> 3) & 1, i.e. even r
   // go to base + 8 b + 8 r and odd r to base - 8 b + 8 r (two base registers, the immediates stay), and the reader of
   // element n = t + m T looks in n ^ (((n >> 6) & 1) << 3).  No extra vector instructions.
-  constexpr bool SWZ2 = SWZ1 && HH_FFT_SWZ2 && NS == 8 && R == 8 && !LAST && NB == 1 && (T == 64 || T == 128);
+  constexpr bool SWZ2 = SWZ1 && NS == 8 && R == 8 && !LAST && NB == 1 && (T == 64 || T == 128);
   if constexpr (PART != 2) {
 #pragma unroll
   for (int q = 0; q < NB; ++q) {
@@ -322,10 +243,6 @@ __device__ __forceinline__ void fft_stage(float2 (&v)[8], const TW& tw, int t, f
       char* const base = reinterpret_cast<char*>(buf);
 #pragma unroll
       for (int r = 0; r < R; ++r) *reinterpret_cast<float2*>(base + (bs ^ (unsigned)(r << 3))) = a[r];
-    } else if constexpr (SWZ2 && (HH_ABLATE & 8192) != 0) {
-      // timing-only: the second exchange costs nothing (values stay where they are)
-#pragma unroll
-      for (int r = 0; r < 8; ++r) v[r] = a[r];
     } else if constexpr (SWZ2) {
       const int j = t;  // NB == 1
       const int k = j & 7, b8 = ((j >> 3) & 1) * 8;
@@ -344,8 +261,7 @@ __device__ __forceinline__ void fft_stage(float2 (&v)[8], const TW& tw, int t, f
   }  // PART != 2
   if constexpr (!LAST && PART != 1) {
     group_sync<T>();
-    if constexpr (SWZ2 && (HH_ABLATE & 8192) != 0) {
-    } else if constexpr (SWZ2) {
+    if constexpr (SWZ2) {
       if constexpr (T == 64) {  // (n >> 6) & 1 = m & 1
         const int e0 = t, e1 = t ^ 8;
 #pragma unroll
@@ -619,10 +535,13 @@ constexpr int MODE_RASTER = 0, MODE_IMAGE = 1, MODE_RASTER_OUT = 2;  // 2: also 
 template <int N>
 struct KA {
   static constexpr int T = N / 8;            // lanes per FFT
-  static constexpr int FPW = T > 64 ? HH_KA_FPW_BIG : 8;  // FFTs per workgroup and tile
+  static constexpr int WPS = 8;              // N >= 512: waves per SIMD the register allocator must leave room for (4 workgroups per CU)
+  static constexpr int FPW_BIG = 4;          // transforms per workgroup and tile when a transform spans two wavefronts (N = 1024)
+  static constexpr int BAND_COLS = 64;       // N >= 256: image columns per workgroup
+  static constexpr int FPW = T > 64 ? FPW_BIG : 8;  // FFTs per workgroup and tile
   static constexpr int COLS = 2 * FPW;       // image columns per tile
   static constexpr int THREADS = FPW * T;    // == N
-  static constexpr int NQ = N >= 256 ? (N / HH_KA_BAND > 0 ? N / HH_KA_BAND : 1) : 1;  // workgroups per candidate
+  static constexpr int NQ = N >= 256 ? (N / BAND_COLS > 0 ? N / BAND_COLS : 1) : 1;  // workgroups per candidate
   static constexpr int TPW = (N / COLS) / NQ;            // tiles per workgroup
   static constexpr int BAND = TPW * COLS;                // image columns per workgroup
   static constexpr int BUF = N;              // complex slots per FFT exchange buffer
@@ -785,7 +704,7 @@ __device__ __forceinline__ void first_pass_tiles(const FirstArgs& a, const size_
           fill_centres(cent, c, g, a.units, cb, cnt, tid, K::THREADS);
           __syncthreads();
         }
-        if (!(HH_ABLATE & 1)) raster_pair<N>(r, cent, cnt, g, xa, t, tid & 63);
+        raster_pair<N>(r, cent, cnt, g, xa, t, tid & 63);
       }
 #pragma unroll
       for (int m = 0; m < 8; ++m) v[m] = make_float2(r[2 * m], r[2 * m + 1]);
@@ -800,7 +719,7 @@ __device__ __forceinline__ void first_pass_tiles(const FirstArgs& a, const size_
       for (int m = 0; m < 8; ++m) v[m] = *reinterpret_cast<const float2*>(img + (size_t)(t + m * T) * N + xa);
     }
 
-    if (!(HH_ABLATE & 2)) fft_lanes<N>(v, tw, t, buf);  // v[m] = Z[t + m*T], Z = DFT_y(col_a + i col_b)
+    fft_lanes<N>(v, tw, t, buf);  // v[m] = Z[t + m*T], Z = DFT_y(col_a + i col_b)
 
     // Split Z into the two real columns' spectra: A[k] = (Z[k] + conj Z[N-k]) / 2,
     // B[k] = (Z[k] - conj Z[N-k]) / (2i), k < N/2; ky = 0 and ky = N/2 (both real) share row 0.
@@ -822,7 +741,7 @@ __device__ __forceinline__ void first_pass_tiles(const FirstArgs& a, const size_
     float2* const out = a.inter + b * (size_t)(N / 2) * N;
     const int pair = (x0 >> 1) + f;
 #pragma unroll
-    for (int m = 0; m < ((HH_ABLATE & 4) ? 1 : 4); ++m) {
+    for (int m = 0; m < 4; ++m) {
       const int k = t + m * T;
       // ky blocks the mask never looks at are not written (K_B skips them as well)
       if ((a.kb_mask >> (k >> 3)) & 1ull) *reinterpret_cast<float4*>(out + inter_index<N>(k, pair)) = ab[m];
@@ -832,7 +751,7 @@ __device__ __forceinline__ void first_pass_tiles(const FirstArgs& a, const size_
 }
 
 template <int N, int MODE>
-__global__ __launch_bounds__(KA<N>::THREADS, (N >= 512 ? HH_KA_WPS : 1)) void k_first_pass(FirstArgs a) {
+__global__ __launch_bounds__(KA<N>::THREADS, (N >= 512 ? KA<N>::WPS : 1)) void k_first_pass(FirstArgs a) {
   using K = KA<N>;
   constexpr int T = K::T;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -879,7 +798,7 @@ __global__ __launch_bounds__(KA<N>::THREADS, (N >= 512 ? HH_KA_WPS : 1)) void k_
   // Twiddles: one compact LDS copy per workgroup, written by the LAST transform group while the
   // first lanes are busy with the float64 centre list; one barrier publishes both.
   float2* const twl = reinterpret_cast<float2*>(smem + K::LDS_FFT + K::LDS_CENT);
-  if (f == K::FPW - 1 && !(HH_ABLATE & 8)) fill_twiddles_lds<N>(twl, t, a.twtab);
+  if (f == K::FPW - 1) fill_twiddles_lds<N>(twl, t, a.twtab);
   __syncthreads();
   const TwLds tw{twl, t};
 
@@ -887,10 +806,8 @@ __global__ __launch_bounds__(KA<N>::THREADS, (N >= 512 ? HH_KA_WPS : 1)) void k_
   // trigonometry of the refill cannot raise its register pressure.
   if (resident)
     first_pass_tiles<N, MODE, true>(a, b, c, c_lo, c_hi, tw, bufs, cent);
-#ifndef HH_NO_CHUNKED
   else
     first_pass_tiles<N, MODE, false>(a, b, c, c_lo, c_hi, tw, bufs, cent);
-#endif
 }
 
 // ------------------------------------------------------------------------------------------
@@ -922,11 +839,13 @@ struct TableArgs {
 template <int N>
 struct KT {
   static constexpr int NKY = N / 2;
-  static constexpr int KYW = NKY < HH_KT_KYW ? NKY : HH_KT_KYW;   // ky rows per workgroup
+  static constexpr int KYW_MAX = 128;                 // ky rows per workgroup, at most
+  static constexpr int PAIRS_MAX = 32;                // column pairs per workgroup, at most
+  static constexpr int KYW = NKY < KYW_MAX ? NKY : KYW_MAX;   // ky rows per workgroup
   static constexpr int LANES = KYW < 64 ? KYW : 64;   // lanes of a wavefront that own ky rows
   static constexpr int KPL = KYW / LANES;             // ky rows per lane: ky = ky0 + lane + 64 m
   static constexpr int THREADS = 256, WAVES = 4;
-  static constexpr int PAIRS_WG = NKY < HH_KT_PAIRS ? NKY : HH_KT_PAIRS;  // column pairs per workgroup
+  static constexpr int PAIRS_WG = NKY < PAIRS_MAX ? NKY : PAIRS_MAX;  // column pairs per workgroup
   static constexpr int COLS = 2 * PAIRS_WG;
   static constexpr int PPW = PAIRS_WG / WAVES;          // ... and per wavefront, taken two at a time
   static constexpr int NQX = NKY / PAIRS_WG, NQY = NKY / KYW;
@@ -1058,8 +977,8 @@ __global__ __launch_bounds__(256) void k_first_pass_table(TableArgs a) {
     const int ihi = min(c.imax, (int)ceilf(fminf(i1, 2.0e9f)));
     rows = ihi < ilo ? 0 : min(a.rows_lds, (ihi - ilo + 1) * g.n_units);
   }
-  if (!(HH_ABLATE & 1024)) {
-    // stage the rows: all of a thread's loads are issued before the first LDS write waits for one
+  // stage the rows: all of a thread's loads are issued before the first LDS write waits for one
+  {
     const float2* const src = tab + ((size_t)(ilo + imax_t) * g.n_units) * K::NKY + ky0;
     constexpr int PER = K::KYW / 2;                 // float4 per staged row
     constexpr int STEP = K::THREADS / PER;          // rows covered by one pass of the workgroup
@@ -1105,7 +1024,7 @@ __global__ __launch_bounds__(256) void k_first_pass_table(TableArgs a) {
       w[q] = in ? __builtin_amdgcn_exp2f(-dx * dx * k2) : 0.f;
       any |= in;
     }
-    unsigned long long todo = (HH_ABLATE & 256) ? 0ull : __ballot(any);
+    unsigned long long todo = __ballot(any);
     float2 acc[4][K::KPL];
 #pragma unroll
     for (int q = 0; q < 4; ++q)
@@ -1135,7 +1054,7 @@ __global__ __launch_bounds__(256) void k_first_pass_table(TableArgs a) {
 #pragma unroll
         for (int m = 0; m < K::KPL; ++m) {
           const int k = ky0 + lane + 64 * m;
-          if (((a.kb_mask >> (k >> 3)) & 1ull) && (!(HH_ABLATE & 128) || acc[0][m].x == 12345.678f))
+          if ((a.kb_mask >> (k >> 3)) & 1ull)
             *reinterpret_cast<float4*>(out + inter_index<N>(k, pair + h)) =
                 make_float4(acc[2 * h][m].x, acc[2 * h][m].y, acc[2 * h + 1][m].x, acc[2 * h + 1][m].y);
         }
@@ -1212,15 +1131,15 @@ struct KB {
   static constexpr int THREADS = GROUPS * T;  // == N
   static constexpr int ROWS = N / 2;
   static constexpr int NKB = ROWS / 8;        // ky blocks per candidate
-  static constexpr int CPW = HH_KB_CPW;       // candidates per workgroup (one ky block of each)
+  static constexpr int CPW = 16;              // candidates per workgroup (one ky block of each)
   static constexpr int WPR = T > 64 ? T / 64 : 1;   // wavefronts per spectrum row
   static constexpr int NPART = (ROWS + 1) * WPR;    // partial-moment slots per candidate: [ky 0..N/2][wavefront]
   static constexpr int BUF = N;               // complex slots per FFT exchange buffer
   static constexpr int PROW = N + 2;          // complex slots per panel row (+16 B: conflict-free b128 writes)
   static constexpr size_t LDS_PANEL = (size_t)8 * PROW * sizeof(float2);
   static constexpr size_t LDS_FFT = (size_t)GROUPS * BUF * sizeof(float2);
-  static constexpr size_t LDS = LDS_PANEL + LDS_FFT + (HH_KB_TWLDS ? (size_t)(TwN<N>::lds_total + 1) * sizeof(float2) : 0);
-  static constexpr int WAVES_PER_SIMD = HH_KB_WPS;  // register budget (512 / WPS VGPRs)
+  static constexpr size_t LDS = LDS_PANEL + LDS_FFT;
+  static constexpr int WAVES_PER_SIMD = 4;    // waves per SIMD the register allocator must leave room for (512 / 4 VGPRs)
 };
 
 // q = log1p(|F|) or |F| (transforms.py:807-810), up to a constant factor: the Pearson coefficient is
@@ -1314,39 +1233,30 @@ __global__ __launch_bounds__(KB<N>::THREADS, (N >= 256 ? KB<N>::WAVES_PER_SIMD :
   const size_t cand_stride = (size_t)K::ROWS * N;
   const float2* const in0 = a.inter + (size_t)c0 * cand_stride + (size_t)kb * 8 * N;
 
-#if HH_KB_TWLDS
-  float2* const twl = reinterpret_cast<float2*>(smem + K::LDS_PANEL + K::LDS_FFT);
-  if (gi == 0) fill_twiddles_lds<N>(twl, t, a.twtab);
-  __syncthreads();
-  const TwLds twsrc{twl, t};
-#else
   float2 tw[TwN<N>::total];
   load_twiddles<N>(tw, t, a.twtab);
   const TwRegs twsrc{tw};
-#endif
 
   // this row's weights {w, w (E - Ebar)} for the lane's 8 bins; the packed row 0 carries ky = 0 and
   // ky = N/2, so its group also keeps the weights of row N/2
   float2 w[8], wn[8];
 #pragma unroll
-  for (int m = 0; m < 8; ++m) w[m] = wn[m] = make_float2((HH_ABLATE & 64) ? 1.f : 0.f, (HH_ABLATE & 64) ? 0.5f : 0.f);
+  for (int m = 0; m < 8; ++m) w[m] = wn[m] = make_float2(0.f, 0.f);
   if constexpr (EPI != EPI_STORE) {
-    if (!(HH_ABLATE & 64)) {
-      const float4* const wrow = reinterpret_cast<const float4*>(a.w2 + ((size_t)row * T + t) * 8);
+    const float4* const wrow = reinterpret_cast<const float4*>(a.w2 + ((size_t)row * T + t) * 8);
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+      const float4 q = wrow[m];
+      w[2 * m] = make_float2(q.x, q.y);
+      w[2 * m + 1] = make_float2(q.z, q.w);
+    }
+    if (row == 0) {
+      const float4* const nrow = reinterpret_cast<const float4*>(a.w2 + ((size_t)(N / 2) * T + t) * 8);
 #pragma unroll
       for (int m = 0; m < 4; ++m) {
-        const float4 q = wrow[m];
-        w[2 * m] = make_float2(q.x, q.y);
-        w[2 * m + 1] = make_float2(q.z, q.w);
-      }
-      if (row == 0) {
-        const float4* const nrow = reinterpret_cast<const float4*>(a.w2 + ((size_t)(N / 2) * T + t) * 8);
-#pragma unroll
-        for (int m = 0; m < 4; ++m) {
-          const float4 q = nrow[m];
-          wn[2 * m] = make_float2(q.x, q.y);
-          wn[2 * m + 1] = make_float2(q.z, q.w);
-        }
+        const float4 q = nrow[m];
+        wn[2 * m] = make_float2(q.x, q.y);
+        wn[2 * m + 1] = make_float2(q.z, q.w);
       }
     }
   }
@@ -1401,7 +1311,7 @@ __global__ __launch_bounds__(KB<N>::THREADS, (N >= 256 ? KB<N>::WAVES_PER_SIMD :
       ld2 = src[2 * K::THREADS];
       ld3 = src[3 * K::THREADS];
     }
-    if (!(HH_ABLATE & 16)) fft_lanes<N, HH_FFT_SWZ != 0>(v, twsrc, t, buf);  // v[m] = C[kx = t + m*T]
+    fft_lanes<N, true>(v, twsrc, t, buf);  // v[m] = C[kx = t + m*T]
 
     if (kb == 0 && (gi == 0 || T > 64)) {
       // Row 0 of H packs two real sequences: C = DFT(F1[0,:]) + i DFT(F1[N/2,:]); un-pack it into the
@@ -1470,7 +1380,7 @@ __global__ __launch_bounds__(KB<N>::THREADS, (N >= 256 ? KB<N>::WAVES_PER_SIMD :
       float* const qrow = (EPI == EPI_QSTORE) ? a.q_out + (b * (size_t)(N / 2 + 1) + row) * N : nullptr;
 #pragma unroll
       for (int m = 0; m < 8; ++m) {
-        const float q = (HH_ABLATE & 32) ? v[m].x + v[m].y : amp_to_q<LOG>(v[m]);
+        const float q = amp_to_q<LOG>(v[m]);
         s1 += w[m].x * q;
         s2 += w[m].x * q * q;
         if constexpr (EPI == EPI_QSTORE) {
@@ -1661,16 +1571,17 @@ template <int N>
 struct KF {
   static constexpr int T = N / 8;
   static constexpr int THREADS = N;
+  static constexpr int WPS = 4;                    // N >= 256: waves per SIMD the register allocator must leave room for
   static constexpr int BROW = N + 4;               // complex slots per panel row (+32 B against bank conflicts)
   static constexpr size_t LDS_BUF = (size_t)8 * BROW * sizeof(float2);
-  static constexpr size_t LDS_R2 = (HH_KF_SPLIT && N == 1024) ? (size_t)(N / 2) * sizeof(float2) : 0;  // W_N^n, n < N/2
+  static constexpr size_t LDS_R2 = N == 1024 ? (size_t)(N / 2) * sizeof(float2) : 0;  // W_N^n, n < N/2 (k_fused_pass's SPLIT)
   static size_t lds(int rows_lds, int kg) {
     return LDS_BUF + (size_t)8 * rows_lds * sizeof(float2) + 2 * ((size_t)kg * N * sizeof(float) + (size_t)cgs_stride<N>() * sizeof(int)) + LDS_R2;
   }
 };
 
 template <int N, int EPI, int LOG>
-__global__ __launch_bounds__(N, (N >= 256 ? HH_KF_WPS : 1)) void k_fused_pass(FusedArgs a) {
+__global__ __launch_bounds__(N, (N >= 256 ? KF<N>::WPS : 1)) void k_fused_pass(FusedArgs a) {
   using K = KF<N>;
   using KP = KB<N>;  // the partial-moment layout is k_second_pass's
   constexpr int T = K::T, TL = T < 64 ? T : 64, NKY = N / 2;
@@ -1700,7 +1611,6 @@ __global__ __launch_bounds__(N, (N >= 256 ? HH_KF_WPS : 1)) void k_fused_pass(Fu
   // XCD's L2 fetch them once instead of all eight L2s once each (placement is a speed matter only).
   int gy = blockIdx.y - a.factor_layers - (a.fin.n > 0 ? 1 : 0);
   int kbi = blockIdx.x;
-#if HH_XCD_MAP
   {
     const int nkb = gridDim.x, work_layers = gridDim.y - a.factor_layers - (a.fin.n > 0 ? 1 : 0);
     const int lw = gy * nkb + kbi;
@@ -1710,7 +1620,6 @@ __global__ __launch_bounds__(N, (N >= 256 ? HH_KF_WPS : 1)) void k_fused_pass(Fu
       kbi = seq % nkb;
     }
   }
-#endif
   const int kb = a.kb_list ? a.kb_list[kbi] : kbi;
   const int row = kb * 8 + gi;
   int run, off, cpw;
@@ -1736,7 +1645,7 @@ __global__ __launch_bounds__(N, (N >= 256 ? HH_KF_WPS : 1)) void k_fused_pass(Fu
   // Wavefront h then transforms y_h (N/2 = 512 points, exchanges inside the wavefront, no workgroup barrier) and
   // scores the bins kx = 2k + h.  One workgroup barrier per candidate (both wavefronts write both halves) replaces
   // the six of the 8 x 8 x 8 x 2 plan, whose every exchange crossed the two wavefronts.
-  constexpr bool SPLIT = HH_KF_SPLIT && N == 1024;
+  constexpr bool SPLIT = N == 1024;
   constexpr int NF = SPLIT ? N / 2 : N, TF = NF / 8;   // transform length and lanes of one transform
   const int h = SPLIT ? (t >> 6) : 0, tf = SPLIT ? (t & 63) : t;
   float2* const fbuf = SPLIT ? buf + h * (NF + 2) : buf;   // the wavefront's half of the row's panel (16-byte aligned)
@@ -1775,7 +1684,7 @@ __global__ __launch_bounds__(N, (N >= 256 ? HH_KF_WPS : 1)) void k_fused_pass(Fu
   // candidate b's eight q of this lane -> its compact row
   auto store_q_compact = [&](size_t b, const float (&qv)[8]) {
     if constexpr (T <= 64) {
-      float* const qb = a.q_out + ((HH_ABLATE & 65536) ? (b & 63) : b) * a.q_stride;   // (65536: timing only — every candidate's q into 64 cache-resident rows)
+      float* const qb = a.q_out + b * a.q_stride;
       int base = qrow_base;
 #pragma unroll
       for (int m = 0; m < 8; ++m) {
@@ -1807,8 +1716,7 @@ __global__ __launch_bounds__(N, (N >= 256 ? HH_KF_WPS : 1)) void k_fused_pass(Fu
     for (int e = tid; e < n_e4; e += K::THREADS) reinterpret_cast<float4*>(eg)[e] = src[e];
     if (tid < CGS) cgs[tid] = a.cgs[(size_t)b * CGS + tid];
   };
-  constexpr bool EGLOBAL = HH_KF_EGLOBAL && T == 64 && !(HH_KF_SPLIT && N == 1024);
-  if constexpr (!EGLOBAL) stage_factors(cfirst);  // buffer 0
+  stage_factors(cfirst);  // buffer 0
   // Every load issued so far (twiddles, weights, slice, factors) is retired HERE, explicitly: the barrier's fence only
   // waits for LDS traffic, and with register loads still pending at the loop's entry the compiler guards their first
   // uses INSIDE the loop with counted waits — the last of them a vmcnt(0) in the middle of part B, which in every later
@@ -1821,31 +1729,23 @@ __global__ __launch_bounds__(N, (N >= 256 ? HH_KF_WPS : 1)) void k_fused_pass(Fu
 
   // One candidate = part A (build the row from the table slice and the candidate's factors, first butterflies, data
   // left in the group's exchange buffer) + part B (rest of the transform, amplitudes, moments).  A is LDS-heavy, B is
-  // vector-heavy.  With HH_KF_STAGGER (N = 512: a transform group is one wavefront, the exchanges need no workgroup
+  // vector-heavy.  With the stagger (N = 512: a transform group is one wavefront, the exchanges need no workgroup
   // barrier) wavefronts 4-7 — the SIMD partners of 0-3 — run half a candidate behind: in round `it` wavefronts 0-3 do
   // A(it) B(it), wavefronts 4-7 do B(it-1) A(it), so a SIMD's two wavefronts of this workgroup are in different parts
   // most of the time instead of hitting the LDS and then the vector pipe together.  Nothing of a candidate lives in
   // registers between A and B, and the factor buffers are used exactly as without the stagger: A(it) reads buffer
   // it & 1 in round it, the copies for it + 1 go to the other buffer, one workgroup barrier closes the round.
-  constexpr bool STAGGER = HH_KF_STAGGER && T == 64;
-  constexpr int KCUT = (HH_KF_CUT < Plan<NF>::n) ? HH_KF_CUT : 1;  // A ends at the exchange after this stage
+  // A ends at the exchange after the transform's first stage.
+  constexpr bool STAGGER = T == 64;
   const bool late = STAGGER && __builtin_amdgcn_readfirstlane(tid >> 6) >= (N / 64) / 2;
-  if (HH_KF_PRIO && late) __builtin_amdgcn_s_setprio(HH_KF_PRIO);
 
   // (see flush_q) — not for the packed row's group (its two rows are un-packed through the exchange buffer)
-  const bool defer_q = EPI == EPI_QSTORE && STAGGER && HH_KF_DEFER_Q && !late && !(kb == 0 && gi == 0);
+  const bool defer_q = EPI == EPI_QSTORE && STAGGER && !late && !(kb == 0 && gi == 0);
 
   auto part_a = [&](int cc) {
     const int cur = cc & 1;
-    const float* egc;
-    const int* cgc;
-    if constexpr (EGLOBAL) {
-      egc = a.eg + (size_t)(cfirst + cc) * a.kg * N;
-      cgc = a.cgs + (size_t)(cfirst + cc) * CGS;
-    } else {
-      egc = eg + (size_t)cur * a.kg * N;
-      cgc = cgs + cur * CGS;
-    }
+    const float* const egc = eg + (size_t)cur * a.kg * N;
+    const int* const cgc = cgs + cur * CGS;
     // ---- this group's row of H, built by the group itself into its own exchange buffer (no workgroup barrier).
     // A lane owns two groups of four consecutive columns (x = 4 t + c and 4 (t + T) + c): two independent
     // accumulation chains, and the operands of the next table row are in flight while this row's FMAs issue.
@@ -1854,7 +1754,7 @@ __global__ __launch_bounds__(N, (N >= 256 ? HH_KF_WPS : 1)) void k_fused_pass(Fu
       // (clamped to the buffer's kg: whatever the word holds, the walk is bounded)
       // (at least one: a candidate that reaches no column has a first factor row of zeros, so the sums need no
       // separate zero fill)
-      const int kgn = (HH_ABLATE & 2048) ? 0 : max(1, min(a.kg, __builtin_amdgcn_readfirstlane(cgc[N / 4])));
+      const int kgn = max(1, min(a.kg, __builtin_amdgcn_readfirstlane(cgc[N / 4])));
       // sums of the two column groups xg0, xg1 (four columns each).  The first table row initialises the sums (no zero
       // fill), the others accumulate; the operand addresses are base + k x constant, so the unrolled loop addresses
       // them with instruction offsets.
@@ -1864,38 +1764,34 @@ __global__ __launch_bounds__(N, (N >= 256 ? HH_KF_WPS : 1)) void k_fused_pass(Fu
         const float2* const grow1 = gs + gi * a.rows_lds + cgc[xg1];
         const float* const erow0 = egc + 4 * xg0;
         const float* const erow1 = egc + 4 * xg1;
-        if (!(HH_ABLATE & 2048)) {
-          {
-            const float2 ga = grow0[0], gb = grow1[0];
-            const float4 ea = *reinterpret_cast<const float4*>(erow0), eb = *reinterpret_cast<const float4*>(erow1);
-            p0 = make_float2(ea.x * ga.x, ea.x * ga.y); p1 = make_float2(ea.y * ga.x, ea.y * ga.y);
-            p2 = make_float2(ea.z * ga.x, ea.z * ga.y); p3 = make_float2(ea.w * ga.x, ea.w * ga.y);
-            q0 = make_float2(eb.x * gb.x, eb.x * gb.y); q1 = make_float2(eb.y * gb.x, eb.y * gb.y);
-            q2 = make_float2(eb.z * gb.x, eb.z * gb.y); q3 = make_float2(eb.w * gb.x, eb.w * gb.y);
-          }
+        {
+          const float2 ga = grow0[0], gb = grow1[0];
+          const float4 ea = *reinterpret_cast<const float4*>(erow0), eb = *reinterpret_cast<const float4*>(erow1);
+          p0 = make_float2(ea.x * ga.x, ea.x * ga.y); p1 = make_float2(ea.y * ga.x, ea.y * ga.y);
+          p2 = make_float2(ea.z * ga.x, ea.z * ga.y); p3 = make_float2(ea.w * ga.x, ea.w * ga.y);
+          q0 = make_float2(eb.x * gb.x, eb.x * gb.y); q1 = make_float2(eb.y * gb.x, eb.y * gb.y);
+          q2 = make_float2(eb.z * gb.x, eb.z * gb.y); q3 = make_float2(eb.w * gb.x, eb.w * gb.y);
+        }
 #pragma unroll 2
-          for (int k = 1; k < kgn; ++k) {
-            const float2 ga = grow0[k], gb = grow1[k];
-            const float4 ea = *reinterpret_cast<const float4*>(erow0 + (size_t)k * N);
-            const float4 eb = *reinterpret_cast<const float4*>(erow1 + (size_t)k * N);
-            p0.x = fmaf(ea.x, ga.x, p0.x); p0.y = fmaf(ea.x, ga.y, p0.y);
-            p1.x = fmaf(ea.y, ga.x, p1.x); p1.y = fmaf(ea.y, ga.y, p1.y);
-            p2.x = fmaf(ea.z, ga.x, p2.x); p2.y = fmaf(ea.z, ga.y, p2.y);
-            p3.x = fmaf(ea.w, ga.x, p3.x); p3.y = fmaf(ea.w, ga.y, p3.y);
-            q0.x = fmaf(eb.x, gb.x, q0.x); q0.y = fmaf(eb.x, gb.y, q0.y);
-            q1.x = fmaf(eb.y, gb.x, q1.x); q1.y = fmaf(eb.y, gb.y, q1.y);
-            q2.x = fmaf(eb.z, gb.x, q2.x); q2.y = fmaf(eb.z, gb.y, q2.y);
-            q3.x = fmaf(eb.w, gb.x, q3.x); q3.y = fmaf(eb.w, gb.y, q3.y);
-          }
-        } else {
-          p0 = p1 = p2 = p3 = q0 = q1 = q2 = q3 = make_float2(0.f, 0.f);
+        for (int k = 1; k < kgn; ++k) {
+          const float2 ga = grow0[k], gb = grow1[k];
+          const float4 ea = *reinterpret_cast<const float4*>(erow0 + (size_t)k * N);
+          const float4 eb = *reinterpret_cast<const float4*>(erow1 + (size_t)k * N);
+          p0.x = fmaf(ea.x, ga.x, p0.x); p0.y = fmaf(ea.x, ga.y, p0.y);
+          p1.x = fmaf(ea.y, ga.x, p1.x); p1.y = fmaf(ea.y, ga.y, p1.y);
+          p2.x = fmaf(ea.z, ga.x, p2.x); p2.y = fmaf(ea.z, ga.y, p2.y);
+          p3.x = fmaf(ea.w, ga.x, p3.x); p3.y = fmaf(ea.w, ga.y, p3.y);
+          q0.x = fmaf(eb.x, gb.x, q0.x); q0.y = fmaf(eb.x, gb.y, q0.y);
+          q1.x = fmaf(eb.y, gb.x, q1.x); q1.y = fmaf(eb.y, gb.y, q1.y);
+          q2.x = fmaf(eb.z, gb.x, q2.x); q2.y = fmaf(eb.z, gb.y, q2.y);
+          q3.x = fmaf(eb.w, gb.x, q3.x); q3.y = fmaf(eb.w, gb.y, q3.y);
         }
       };
       // The row is handed to the transform through the group's exchange buffer.  A lane stores 2 x 32 bytes at a
       // 32-byte lane stride: the eight lanes of a ds_write_b128 group would hit four bank groups twice, so the
       // 16-byte chunk c = x / 2 lives at c ^ ((c >> 3) & 1) (chunks 2 xg, 2 xg + 1 of lanes xg and xg + 4 then fall
       // into different halves of the 128-byte bank span); the reader un-swizzles with one precomputed base.
-      auto chunk = [](int c) { return HH_KF_PSWZ ? (c ^ ((c >> 3) & 1)) : c; };
+      auto chunk = [](int c) { return c ^ ((c >> 3) & 1); };
       if constexpr (SPLIT) {
         accumulate(t, t + T);
         // the radix-2 step, then y0 into the row's first half and y1 into its second (chunks 2 t, 2 t + 1 of each)
@@ -1926,10 +1822,10 @@ __global__ __launch_bounds__(N, (N >= 256 ? HH_KF_WPS : 1)) void k_fused_pass(Fu
     group_sync<T>();
     float2 v[8];
     if constexpr (SPLIT) {  // n = tf + 64 m of the wavefront's own half
-      const int ps = HH_KF_PSWZ ? ((((tf >> 1) ^ ((tf >> 4) & 1)) << 1) | (tf & 1)) : tf;
+      const int ps = (((tf >> 1) ^ ((tf >> 4) & 1)) << 1) | (tf & 1);
 #pragma unroll
       for (int m = 0; m < 8; ++m) v[m] = fbuf[ps + m * TF];
-    } else if constexpr (HH_KF_PSWZ && T % 32 == 0) {  // x = t + m T: bit 4 of x is bit 4 of t, one swizzled base serves every m
+    } else if constexpr (T % 32 == 0) {  // x = t + m T: bit 4 of x is bit 4 of t, one swizzled base serves every m
       const int ps = (((t >> 1) ^ ((t >> 4) & 1)) << 1) | (t & 1);
 #pragma unroll
       for (int m = 0; m < 8; ++m) v[m] = buf[ps + m * T];
@@ -1937,22 +1833,17 @@ __global__ __launch_bounds__(N, (N >= 256 ? HH_KF_WPS : 1)) void k_fused_pass(Fu
 #pragma unroll
       for (int m = 0; m < 8; ++m) {
         const int x = t + m * T;
-        v[m] = buf[HH_KF_PSWZ ? ((((x >> 1) ^ ((x >> 4) & 1)) << 1) | (x & 1)) : x];
+        v[m] = buf[(((x >> 1) ^ ((x >> 4) & 1)) << 1) | (x & 1)];
       }
     }
     if constexpr (T > 64 && !SPLIT) __syncthreads();  // both wavefronts of a row have read it before either exchanges in it
-    if (!(HH_ABLATE & 16)) fft_lanes_part<NF, HH_FFT_SWZ != 0, TwRegs, 1, KCUT>(v, twsrc, tf, fbuf);
+    fft_lanes_part<NF, true, TwRegs, 1, 1>(v, twsrc, tf, fbuf);
   };
 
   auto part_b = [&](int cc) {
     const size_t b = (size_t)(cfirst + cc);
     float2 v[8];
-    if (!(HH_ABLATE & 16)) {
-      fft_lanes_part<NF, HH_FFT_SWZ != 0, TwRegs, 2, KCUT>(v, twsrc, tf, fbuf);  // v[m] = C[kx = t + m*T] (SPLIT: kx = 2 (tf + 64 m) + h); the exchanges reuse the row's panel slots
-    } else {
-#pragma unroll
-      for (int m = 0; m < 8; ++m) v[m] = fbuf[tf + m * TF];
-    }
+    fft_lanes_part<NF, true, TwRegs, 2, 1>(v, twsrc, tf, fbuf);  // v[m] = C[kx = t + m*T] (SPLIT: kx = 2 (tf + 64 m) + h); the exchanges reuse the row's panel slots
 
     bool scored = false;
     if (kb == 0 && (gi == 0 || (T > 64 && !SPLIT))) {
@@ -2022,7 +1913,7 @@ __global__ __launch_bounds__(N, (N >= 256 ? HH_KF_WPS : 1)) void k_fused_pass(Fu
       [[maybe_unused]] float qkeep[8];
 #pragma unroll
       for (int m = 0; m < 8; ++m) {
-        const float q = (HH_ABLATE & 32) ? v[m].x + v[m].y : amp_to_q<LOG>(v[m]);
+        const float q = amp_to_q<LOG>(v[m]);
         s1 += w[m].x * q;
         s2 += w[m].x * q * q;
         if constexpr (EPI == EPI_QSTORE) {
@@ -2081,7 +1972,7 @@ __global__ __launch_bounds__(N, (N >= 256 ? HH_KF_WPS : 1)) void k_fused_pass(Fu
     // pass) into the other factor buffer, which nobody reads before the barrier at the end of this round
     // (an explicit s_waitcnt vmcnt(0) ahead of that barrier retires the copies).  One wave-instruction moves
     // 64 x 16 B to a wave-uniform LDS base + lane x 16.
-    const bool more = it + 1 < nc && !(HH_ABLATE & 4096) && !EGLOBAL;
+    const bool more = it + 1 < nc;
     if (more) {
       const size_t bn = (size_t)(cfirst + it + 1);
       const char* const gsrc = reinterpret_cast<const char*>(a.eg + bn * a.kg * N);
@@ -2100,8 +1991,8 @@ __global__ __launch_bounds__(N, (N >= 256 ? HH_KF_WPS : 1)) void k_fused_pass(Fu
     if (!late) part_b(it);
     // The LDS-DMA copies of the next candidate's factors count on vmcnt only; neither the workgroup-scope fence nor
     // s_barrier waits for them, so every wavefront retires its own copies before it arrives at the barrier.
-    if (more && !(HH_ABLATE & 32768)) lds_dma_wait();
-    if (!(HH_ABLATE & 16384) && !EGLOBAL) __syncthreads();  // the next candidate's factors are complete; every group is done reading this one's
+    if (more) lds_dma_wait();
+    __syncthreads();  // the next candidate's factors are complete; every group is done reading this one's
   }
   if (late) part_b(nc - 1);
   if (defer_q) flush_q(nc - 1);
@@ -3106,12 +2997,11 @@ FusedSchedule fused_schedule(int64_t runs, int run_len, int n_kb, int slots) {
   auto groups_of = [&](int cpw) { return (run_len + cpw - 1) / cpw; };   // even groups: ceil(len / ceil(len / g)) <= g
   FusedSchedule best{};
   double best_t = 1e300;
-  const int g_lo = HH_KF_CPW > 0 ? groups_of(HH_KF_CPW) : 1, g_hi = HH_KF_CPW > 0 ? g_lo : gmax;
-  for (int ga = g_lo; ga <= g_hi; ++ga) {
+  for (int ga = 1; ga <= gmax; ++ga) {
     const int cpw_a = cpw_of(ga), ga_e = groups_of(cpw_a);
     const int64_t per_run = (int64_t)ga_e * n_kb;
     const int64_t full = runs * per_run / slots;                          // whole rounds of region A
-    const int64_t runs_a = HH_KF_CPW > 0 ? runs : std::min<int64_t>(runs, full * slots / per_run);
+    const int64_t runs_a = std::min<int64_t>(runs, full * slots / per_run);
     const int64_t runs_b = runs - runs_a;
     const double ta = (double)((runs_a * per_run + slots - 1) / slots) * (cpw_a + setup);
     int gb = ga_e, cpw_b = cpw_a;
@@ -3171,9 +3061,11 @@ int ensure_segment_buffers(hh_ctx* c, int batch) {
 }
 
 // several segments: candidates per launch of the shared-twist pipelines (q of a batch lives in HBM)
+constexpr int64_t SEG_BATCH = 24576;          // most candidates per launch (C5: 11.6 ms at 1024, 9.5 ms at 20k)
+constexpr int64_t SEG_BYTES = 12LL << 30;     // ... shortened so that the batch's masked q (0.5 MB per candidate at N = 512) fits this
 inline int seg_batch(int n) {
   const int64_t per = (int64_t)(n / 2 + 1) * n * (int64_t)sizeof(float);
-  return (int)std::max<int64_t>(1024, std::min<int64_t>(HH_SEG_BATCH, HH_SEG_BYTES / per) / 64 * 64);
+  return (int)std::max<int64_t>(1024, std::min<int64_t>(SEG_BATCH, SEG_BYTES / per) / 64 * 64);
 }
 
 // Candidates [first, first + count) of the list of g (count = whole runs of plan.len).
@@ -3184,7 +3076,9 @@ int sweep_runs(hh_ctx* c, const double* d_params, int64_t g, float* d_scores, co
   const int nky = c->n / 2;
   // The fused pass has no intermediate to hold, so its batches are not tied to max_batch: long
   // launches even out the tail of the grid (C2: 3.2 M candidates/s at 250 per launch, 3.8 M at 4000).
-  const int fused_cap = (int)std::max<int64_t>(1024, std::min<int64_t>(HH_FUSED_BATCH, HH_FUSED_BYTES / ((int64_t)2 * std::max(1, plan.kg) * c->n * 4)));
+  constexpr int64_t FUSED_BATCH = 131072;       // most candidates per launch (whole runs); 6 GB of column factors + moments at N = 512
+  constexpr int64_t FUSED_BYTES = 8LL << 30;    // the launch is shortened so that its column factors (two halves) fit this
+  const int fused_cap = (int)std::max<int64_t>(1024, std::min<int64_t>(FUSED_BATCH, FUSED_BYTES / ((int64_t)2 * std::max(1, plan.kg) * c->n * 4)));
   // (never more than the sweep itself holds: the factor and moment buffers are sized by it and only grow)
   const int bmax = !plan.fused ? c->max_batch
                    : (int)std::min<int64_t>(c->n_segments == 1 ? std::max(c->max_batch, fused_cap) : std::max(c->max_batch, seg_batch(c->n)),
@@ -3853,13 +3747,13 @@ int hh_set_reference(hh_ctx* c, const float* images, int n_segments, const uint8
   // with several segments the centred spectra go to a [Sp][K] matrix for the MFMA contraction
   const bool multi = n_segments > 1;
   const int s_pad = multi ? (n_segments + 63) / 64 * 64 : 0;
-  // several segments: the shared-twist pipelines batch up to HH_SEG_BATCH candidates (q of a batch lives in HBM:
+  // several segments: the shared-twist pipelines batch up to SEG_BATCH candidates (q of a batch lives in HBM:
   // 0.5 MB per candidate at N = 512), the general pipeline max_batch
   std::vector<float2> w2(nh);
   // several segments, N <= 512: q and the centred spectra keep only the bins with weight (a fifth fewer bytes through HBM
   // under the radial band, most of them under a resolution-limited or layer-line mask): row r's bins from roff[r] on, in
   // ascending kx — the order the kernels' ballots give (compact_positions)
-  const bool compact = multi && n <= 512 && std::getenv("HH_Q_FULL") == nullptr;
+  const bool compact = multi && n <= 512;
   std::vector<int> roff((size_t)n / 2 + 2, 0), cpos(compact ? nh : 0, -1);
   size_t q_stride = nh;
   if (compact) {

@@ -792,7 +792,7 @@ __global__ __launch_bounds__(1024) void k_pab_emit(PabEmit a) {
 template <int STEP>
 __global__ __launch_bounds__(256) void k_pab_share_rows(const PabState* __restrict__ st, const int* __restrict__ ray_of_row,
                                                         const uint16_t* __restrict__ map16, int d2p, int l2, int d2, int max_ops,
-                                                        int* __restrict__ first, int* __restrict__ second, int* __restrict__ maprow, int count, int own) {
+                                                        int* __restrict__ first, int* __restrict__ second, int* __restrict__ maprow, int count) {
   const int c = PAB_SLOT, bx = PAB_BLOCK;
   if (c >= count) return;
   const PabState& s = st[c];
@@ -805,10 +805,6 @@ __global__ __launch_bounds__(256) void k_pab_share_rows(const PabState* __restri
   const size_t key = ((size_t)c * max_ops + op) * d2 + j;
   if (STEP == 0) {
     if (sub == 0) atomicMin(&first[key], (int)r);
-    return;
-  }
-  if (own) {   // (HH_PAB_OWN_ROWS: the A/B switch — every row reads its own map)
-    if (STEP == 1 && sub == 0) maprow[row] = (int)row;
     return;
   }
   if (STEP == 2 && maprow[row] >= 0) return;
@@ -2252,7 +2248,7 @@ int hh_pab_create(hh_pab** out, int device, const float* image, int ny, int nx, 
       int f[PAB_FLAG_WORDS];
       PAB_RC(pab_poll(p, f));
       if (f[9]) { p->err = "hh_pab_create: a ray left its slice (internal)"; return bail(HH_ERR_STATE); }
-      // rows of one (operation, image row) read one copy of their map (k_pab_share_rows); HH_PAB_OWN_ROWS: every row its own
+      // rows of one (operation, image row) read one copy of their map (k_pab_share_rows)
       PAB_RC(pab_alloc(p, &p->d_maprow, (size_t)std::max<int64_t>(p->total_rows, 1)));
       int max_ops_used = 0;
       for (int c = 0; c < count; ++c) max_ops_used = std::max(max_ops_used, p->n_ops_used[(size_t)c]);
@@ -2264,10 +2260,9 @@ int hh_pab_create(hh_pab** out, int device, const float* image, int ny, int nx, 
       if (es == hipSuccess) es = hipMemsetAsync(d_second, 0x7f, keys * sizeof(int), p->stream);
       if (es == hipSuccess) {
         const dim3 grid = pab_grid((int)((md * 8 + 255) / 256), count);
-        const bool own = std::getenv("HH_PAB_OWN_ROWS") != nullptr;
-        hipLaunchKernelGGL(k_pab_share_rows<0>, grid, dim3(256), 0, p->stream, p->d_st, p->d_ray_of_row, p->d_map16, p->d2p, l2, d2, max_ops_used, d_first, d_second, p->d_maprow, count, 0);
-        hipLaunchKernelGGL(k_pab_share_rows<1>, grid, dim3(256), 0, p->stream, p->d_st, p->d_ray_of_row, p->d_map16, p->d2p, l2, d2, max_ops_used, d_first, d_second, p->d_maprow, count, own ? 1 : 0);
-        hipLaunchKernelGGL(k_pab_share_rows<2>, grid, dim3(256), 0, p->stream, p->d_st, p->d_ray_of_row, p->d_map16, p->d2p, l2, d2, max_ops_used, d_first, d_second, p->d_maprow, count, own ? 1 : 0);
+        hipLaunchKernelGGL(k_pab_share_rows<0>, grid, dim3(256), 0, p->stream, p->d_st, p->d_ray_of_row, p->d_map16, p->d2p, l2, d2, max_ops_used, d_first, d_second, p->d_maprow, count);
+        hipLaunchKernelGGL(k_pab_share_rows<1>, grid, dim3(256), 0, p->stream, p->d_st, p->d_ray_of_row, p->d_map16, p->d2p, l2, d2, max_ops_used, d_first, d_second, p->d_maprow, count);
+        hipLaunchKernelGGL(k_pab_share_rows<2>, grid, dim3(256), 0, p->stream, p->d_st, p->d_ray_of_row, p->d_map16, p->d2p, l2, d2, max_ops_used, d_first, d_second, p->d_maprow, count);
         es = hipStreamSynchronize(p->stream);
       }
       (void)hipFree(d_first);
@@ -2332,13 +2327,12 @@ int hh_pab_create(hh_pab** out, int device, const float* image, int ny, int nx, 
     if (e != hipSuccess) { p->err = std::string("hh_pab_create: ") + hipGetErrorString(e); return bail(HH_ERR_HIP); }
   }
   lap("transposed lists");
-  if (p->linear && std::getenv("HH_PAB_LINEAR_DIRECT") == nullptr && d2 <= 128) {
+  if (p->linear && d2 <= 128) {
     // ---- the separable form of the trilinear data rows (path_a_factored.inc) ----------------------------------------------------
     // per (candidate, operation, image column): axial data, the hash of its samples' cell decisions, its first row and the
     // image rows that have a ray — computed on the device, grouped into footprint lists and column groups on the host
     // (4k entries per candidate), then the lists' samples are written by the device
     int G = 4;   // (+ 26 KB for the group's list table, sized below)
-    if (const char* ge = std::getenv("HH_PAB_G")) G = std::max(1, std::min(4, std::atoi(ge)));   // (A/B switch)
     while (G > 1 && (size_t)(G + 1) * p->nslice * sizeof(double) > ((size_t)120 << 10)) --G;
     const int ng = std::max(1, (p->mz - 1 + G - 1) / G);
     int max_ops = 0;
@@ -2463,7 +2457,6 @@ int hh_pab_create(hh_pab** out, int device, const float* image, int ny, int nx, 
       int64_t ms_max = 0;
       for (const PabState& st : p->st) ms_max = std::max(ms_max, st.m_sym);
       p->fac_split = std::max(1, std::min(8, (16 + ng - 1) / ng));   // about sixteen workgroups per candidate and product
-      if (const char* sp = std::getenv("HH_PAB_SPLIT")) p->fac_split = std::max(1, std::min(16, std::atoi(sp)));
       p->nb_mv = ng * p->fac_split + (int)((ms_max + 256 * PABF_TAIL_ROWS - 1) / (256 * PABF_TAIL_ROWS));
       p->nb_mva = ng * p->fac_split + (int)((ms_max + p->n + 256 * PABF_TAIL_ROWS - 1) / (256 * PABF_TAIL_ROWS));
       if (p->nb_mva > p->RB) { p->err = "hh_pab_create: more partial sums than planned (internal)"; return bail(HH_ERR_STATE); }

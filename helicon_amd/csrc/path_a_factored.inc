@@ -1,5 +1,5 @@
 // path_a_factored.inc — the trilinear projector of the batched Path-A solver in SEPARABLE form (round 4; included by
-// path_a_batch.inc after path_a_linear.inc, whose direct kernels remain as the A/B reference: HH_PAB_LINEAR_DIRECT=1).
+// path_a_batch.inc after path_a_linear.inc, whose direct kernels remain for lists too long for it: d2 > 128).
 //
 // Reference: webApps/denovo3D/solver_linear_regression.py:1414-1503 (build_A_data_matrix, "linear").
 //
@@ -24,9 +24,6 @@
 // and plane.  About 16 instructions per (sample, row) instead of 150, and the footprint lists (3 MB per candidate) are
 // read once per group instead of the geometry being recomputed per row.
 
-#ifndef HH_PABF_ABLATE
-#define HH_PABF_ABLATE 0   // timing-only builds of the forward product (wrong results): 1 no entry loads, 2 no LDS gathers, 4 no staging
-#endif
 constexpr int PABF_KMAX = 8;   // rows of a column (= lanes per column)
 
 struct PabfEntry {        // one valid sample of a footprint list
@@ -203,7 +200,7 @@ __global__ __launch_bounds__(PABS_THREADS) void k_pabf_matvec(PabView w, int src
     // one box — was 1 % slower at 512 candidates and 7 % slower for a single candidate's product)
     for (int p = 0; p < np; ++p) {
       const int64_t pb = (int64_t)(base_z + p) * w.nslice;
-      for (int v = threadIdx.x; v < ((HH_PABF_ABLATE & 4) ? 0 : w.nslice); v += PABS_THREADS) {
+      for (int v = threadIdx.x; v < w.nslice; v += PABS_THREADS) {
         const int64_t gi = pb + v;
         double xv = x[gi];
         if (MODE == 1) {
@@ -266,16 +263,8 @@ __global__ __launch_bounds__(PABS_THREADS) void k_pabf_matvec(PabView w, int src
           PabfEntry e[8];
 #pragma unroll
           for (int q = 0; q < 8; ++q)
-            if (t0 + q * PABF_KMAX < d2) {
-              if (HH_PABF_ABLATE & 1) {
-                e[q].xf = 0.25 + 0.001 * l; e[q].yf = 0.5; e[q].pad = 0;
-                const unsigned a0 = (unsigned)((col * 67 + (t0 + q * PABF_KMAX) * 131) % (w.nslice - 80));
-                e[q].idx = a0 | ((a0 + 64) << 16);
-              } else {
-                e[q] = en[t0 + q * PABF_KMAX];
-              }
-            }
-          if (t0 == l) n = (HH_PABF_ABLATE & 1) ? 52 : w.fac_count[lj];
+            if (t0 + q * PABF_KMAX < d2) e[q] = en[t0 + q * PABF_KMAX];
+          if (t0 == l) n = w.fac_count[lj];
           if (t0 >= n) break;
 #pragma unroll
           for (int q = 0; q < 8; ++q)
@@ -287,9 +276,8 @@ __global__ __launch_bounds__(PABS_THREADS) void k_pabf_matvec(PabView w, int src
               for (int p = 0; p <= G; ++p)
                 if (p < np) {
                   const double* __restrict__ xp = fac_lds + (size_t)p * w.nslice;
-                  double a, b1, b2, b3;
-                  if (HH_PABF_ABLATE & 2) { a = wt[0] * (double)i0; b1 = (double)(i0 + p); b2 = (double)i1; b3 = (double)(i1 + p); }
-                  else { a = wt[0] * xp[i0]; b1 = xp[i0 + 1]; b2 = xp[i1]; b3 = xp[i1 + 1]; }
+                  double a = wt[0] * xp[i0];
+                  const double b1 = xp[i0 + 1], b2 = xp[i1], b3 = xp[i1 + 1];
                   a += wt[1] * b1;
                   a += wt[2] * b2;
                   a += wt[3] * b3;
@@ -452,10 +440,7 @@ __global__ __launch_bounds__(PABS_THREADS) void k_pabf_scatter(PabView w, int sr
 
 // ---- A x, symmetry rows (16 entries each, gathered from L2) and the augmented rows root[v] x[v] ---------------------------------------
 // 256 threads, PABF_TAIL_ROWS rows per thread; block b of this launch is partial-sum block fac_ng + b of the forward product.
-#ifndef PABF_TAIL_ROWS_N
-#define PABF_TAIL_ROWS_N 4   // (2 -> 4: 4.06 -> 3.98-4.02 s for 512 candidates, back to back; 1: no change)
-#endif
-constexpr int PABF_TAIL_ROWS = PABF_TAIL_ROWS_N;
+constexpr int PABF_TAIL_ROWS = 4;   // (2 -> 4: 4.06 -> 3.98-4.02 s for 512 candidates, back to back; 1: no change)
 template <int MODE, class P>
 __global__ __launch_bounds__(256) void k_pabf_tail(PabView w, int src, int dsc, int rootv, int dst, P pred) {
 #pragma clang fp contract(off)

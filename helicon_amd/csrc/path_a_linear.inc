@@ -327,13 +327,7 @@ __global__ __launch_bounds__(PABS_THREADS) void k_pabl_scatter(PabView w, int sr
 // ---- A^T y, gather half: accumulator -> result (+ symmetry rows, scaling, the LSMR update, |.|^2), accumulator cleared ------------
 // MODE 0: dst = A^T y[:m].  MODE 1 (LSMR): dst = (dst inv_alpha) neg_beta + Op^T (y inv_beta), |dst|^2 -> slot 1.
 // MODE 2 (create): colmax[c] = max of the accumulator (the largest column sum of |A_data|, x 2^20).
-#ifndef PABL_FIN_FOUR
-#define PABL_FIN_FOUR 0   // timing knob: 1 = at most four (entry, gather) pairs in flight in k_pabl_finish
-#endif
-#ifndef PABL_FIN_ELEMS_N
-#define PABL_FIN_ELEMS_N 1
-#endif
-constexpr int PABL_FIN_ELEMS = PABL_FIN_ELEMS_N;   // voxels per thread: a voxel's list is a chain of (entry, gather) pairs — short chains, many threads
+constexpr int PABL_FIN_ELEMS = 1;   // voxels per thread: a voxel's list is a chain of (entry, gather) pairs — short chains, many threads
 template <int MODE, class P>
 __global__ __launch_bounds__(256) void k_pabl_finish(PabView w, int src, int dsc, int rootv, int dst, long long* __restrict__ colmax, P pred) {
 #pragma clang fp contract(off)
@@ -371,7 +365,7 @@ __global__ __launch_bounds__(256) void k_pabl_finish(PabView w, int src, int dsc
     G[v] = 0;
     const int e1 = tp[v + 1];
     int e = tp[v];
-    for (; !(PABL_FIN_FOUR) && e + 8 <= e1; e += 8) {   // eight (entry, gather) pairs in flight (a list is 16 long on average: two rounds of two trips; sixteen in flight: no better); the sum keeps the list's order
+    for (; e + 8 <= e1; e += 8) {   // eight (entry, gather) pairs in flight (a list is 16 long on average: two rounds of two trips; sixteen in flight: no better); the sum keeps the list's order
       int2 nn[8];
       double yy[8];
 #pragma unroll
