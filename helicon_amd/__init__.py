@@ -5,9 +5,10 @@ from .grid import (CandidateGrid, build_grid, layer_line_mask, radial_band_mask,
                    shard_bounds, sweep_axis)
 from .denovo3D import (SweepEngine, SweepResult, apply_helical_symmetry, auto_horizontalize, compute_power_spectra,
                        cosine_similarity, cross_correlation_coefficient, down_scale,
-                       estimate_helix_rotation_center_diameter, is_vertical, low_high_pass_filter, process_one_task,
-                       rotate_shift_image, simulate_helical_projection, sweep, threshold_data, transform_image,
-                       transform_map)
+                       estimate_helix_rotation_center_diameter, generate_xyz_projections, is_vertical, low_high_pass_filter,
+                       low_high_pass_filter_3d, process_one_task,
+                       rotate_shift_image, simulate_helical_projection, sweep, symmetrize_transform_map, threshold_data,
+                       transform_image, transform_map)
 from ._lib import HeliconHipError
 from .solver import lsq_reconstruct, lsq_reconstruct_batch
 

@@ -8,6 +8,8 @@ Same names, argument order and return shapes as the reference callables it stand
 * ``cosine_similarity``             src/helicon/lib/analysis.py:802-821
 * ``process_one_task``              src/helicon/webApps/denovo3D/pipeline.py:85-497 (tuple layout)
 * ``sweep`` / ``SweepEngine``       replace the thread pool of app.py:2455-2523
+* ``symmetrize_transform_map``      src/helicon/webApps/denovo3D/utils.py:346-383 (the 3-D map input)
+* ``generate_xyz_projections``      src/helicon/webApps/denovo3D/utils.py:336-345
 
 All arithmetic happens in libhelicon_hip.so (hand-written gfx950 kernels) through ctypes;
 there is no NumPy/SciPy fallback — without the library or a GPU these functions raise.
@@ -44,6 +46,9 @@ __all__ = [
     "estimate_helix_rotation_center_diameter",
     "auto_horizontalize",
     "transform_map",
+    "low_high_pass_filter_3d",
+    "symmetrize_transform_map",
+    "generate_xyz_projections",
     "is_vertical",
     "units_to_cylindrical",
 ]
@@ -734,6 +739,88 @@ def apply_helical_symmetry(data, apix, twist_degree, rise_angstrom, csym=1, frac
     ms = C.c_double(0.0)
     _lib.check(L.hh_apply_helical_symmetry(*args, _ptr(out, C.c_float), out_shape, C.byref(ms)), None)
     return (out, ms.value) if return_kernel_ms else out
+
+
+_MAP_MIN_SIDE, _MAP_MAX_SIDE = 2, 1024   # the reference divides by n // 2; 1024 bounds the operators and the planes
+
+
+def _map_volume(data, name, min_side=1, max_side=None):
+    d = np.asarray(data)
+    if d.ndim != 3:
+        raise ValueError(f"{name}: data must be a 3D volume (nz, ny, nx); got {d.ndim} dimension(s)")
+    if d.dtype.kind not in "biuf":
+        raise ValueError(f"{name}: data must be real; got dtype {d.dtype}")
+    if min(d.shape) < min_side or (max_side is not None and max(d.shape) > max_side):
+        raise ValueError(f"{name}: every side must lie in [{min_side}, {max_side}]; got {d.shape}")
+    return d
+
+
+def low_high_pass_filter_3d(data, low_pass_fraction=0, high_pass_fraction=0, *, device=0):
+    """The 3-D branch of ``helicon.low_high_pass_filter`` (lib/filters.py:314-372, 3-D case :349-372): the Gaussian low
+    pass exp(-f2 R^2) and / or high pass 1 - exp(-f2 R^2) (f2 = ln 2 / fraction^2, fractions outside (0, 1) ignored)
+    applied in Fourier space, ``Re ifftn(fftn(data) * fftshift(filter))``, on the device (``hh_low_high_pass_filter_3d``:
+    three 1-D circulant operators on the f32 matrix cores, every side in [2, 1024]).  The result has the reference's
+    dtype under NumPy 2: float32 for float32 input, float64 otherwise (computed in float32)."""
+    d = _map_volume(data, "low_high_pass_filter_3d", _MAP_MIN_SIDE, _MAP_MAX_SIDE)
+    vol = np.ascontiguousarray(d, dtype=np.float32)
+    out = np.empty_like(vol)
+    shape = (C.c_int32 * 3)(*vol.shape)
+    _lib.check(_lib.lib().hh_low_high_pass_filter_3d(int(device), _ptr(vol, C.c_float), shape, float(low_pass_fraction),
+                                                     float(high_pass_fraction), _ptr(out, C.c_float)), None)
+    return out if d.dtype == np.float32 else out.astype(np.float64)
+
+
+def symmetrize_transform_map(data, apix, twist_degree, rise_angstrom, csym=1, fraction=1.0, new_size=None, new_apix=None,
+                             axial_rotation=0, tilt=0, *, device=0):
+    """webApps/denovo3D/utils.py:346-383 (same positional signature, no joblib cache): low-pass the map to the output
+    pixel size when that is coarser (``low_high_pass_filter_3d`` with low_pass_fraction = apix / new_apix, :361-366),
+    helically symmetrise and resample it (``apply_helical_symmetry``, :367-377), then rotate it about the helical axis and
+    tilt it (``transform_map``, :378-379).  ``new_size=None`` / ``new_apix=None`` mean "unchanged", as in
+    ``apply_helical_symmetry``.  Every step runs on the device; float32 result."""
+    d = _map_volume(data, "symmetrize_transform_map")
+    if not (float(apix) > 0) or not (float(rise_angstrom) > 0) or int(csym) < 1:
+        raise ValueError("symmetrize_transform_map: apix and rise_angstrom must be > 0 and csym >= 1")
+    if new_apix is not None and not (float(new_apix) > 0):
+        raise ValueError("symmetrize_transform_map: new_apix must be > 0")
+    if new_size is not None and (len(new_size) != 3 or min(int(v) for v in new_size) < 1):
+        raise ValueError(f"symmetrize_transform_map: new_size must be three positive sides; got {new_size}")
+    if new_apix is not None and new_apix > apix:
+        data_work = low_high_pass_filter_3d(d, low_pass_fraction=apix / new_apix, device=device)
+    else:
+        data_work = d
+    m = apply_helical_symmetry(data_work, apix, twist_degree, rise_angstrom, csym=csym, fraction=fraction, new_size=new_size,
+                               new_apix=new_apix, device=device)
+    if axial_rotation or tilt:
+        m = transform_map(m, rot=axial_rotation, tilt=tilt, device=device)
+    return m
+
+
+def _amyloid_slab(nz, apix):
+    """utils.py:340-343: ``map3d[z0 : z0 + nz_center]`` with nz_center = round(4.75 / apix), z0 = nz // 2 - nz_center // 2,
+    resolved as Python resolves the slice (a negative start counts from the end)."""
+    nz_center = int(round(4.75 / apix))
+    z0 = nz // 2 - nz_center // 2
+    start, stop, _ = slice(z0, z0 + nz_center).indices(nz)
+    return start, max(start, stop)
+
+
+def generate_xyz_projections(map3d, is_amyloid=False, apix=None, *, device=0):
+    """webApps/denovo3D/utils.py:336-345: the map's sums along x, y and z (``[map3d.sum(axis=i) for i in [2, 1, 0]]``) —
+    for an amyloid, the last one over the 4.75 Angstrom slab about the centre slice — in one device call
+    (``hh_map_projections``, float64 running sums).  float32 results for float32 input, float64 otherwise."""
+    d = _map_volume(map3d, "generate_xyz_projections", 1, 4096)
+    nz, ny, nx = d.shape
+    slab = (-1, -1)
+    if is_amyloid:
+        if apix is None or not (float(apix) > 0):
+            raise ValueError("generate_xyz_projections: is_amyloid needs apix > 0")
+        slab = _amyloid_slab(nz, float(apix))
+    vol = np.ascontiguousarray(d, dtype=np.float32)
+    px, py, pz = (np.empty((nz, ny), np.float32), np.empty((nz, nx), np.float32), np.empty((ny, nx), np.float32))
+    shape = (C.c_int32 * 3)(*vol.shape)
+    _lib.check(_lib.lib().hh_map_projections(int(device), _ptr(vol, C.c_float), shape, int(slab[0]), int(slab[1]),
+                                             _ptr(px, C.c_float), _ptr(py, C.c_float), _ptr(pz, C.c_float)), None)
+    return [p if d.dtype == np.float32 else p.astype(np.float64) for p in (px, py, pz)]
 
 
 # ------------------------------------------------------------------------------------------

@@ -14,6 +14,15 @@ descending, app.py:2521-2523) this driver reproduces without the Shiny UI.
 ``process_one_task(..., algorithm={"scorer": "lsq"})`` — on the sweep's K best candidates of every image, from a
 thread pool like the app's (app.py:2473-2476), and reports them in the order of that score.
 
+``--from-map TWIST RISE CSYM`` reads ``image`` as a 3-D map instead (``.mrc`` / ``.map`` / ``.npy``, ``--apix`` its voxel
+size) and builds the input image as the app does for a map (app.py:1780-1829): the map is symmetrised with the given
+twist, rise and Csym, resampled to ``--output-size`` at ``--output-apix`` with ``--axial-rotation`` / ``--output-tilt``
+(``symmetrize_transform_map``), projected along x, and ``--noise`` times its foreground standard deviation of Gaussian noise
+is added.  The sweep and ``--rescore`` then run on that image at the output pixel size:
+
+    python -m helicon_amd.denovo3DBatch emd.map --from-map 29.4 4.75 1 --output-apix 5 --twist 28 31 0.2 --rise 4 6 0.1 \
+           --seed 0 --save-projection proj.npy
+
 Images are ``.npy`` arrays or MRC files/stacks (``[ny, nx]`` or ``[S, ny, nx]``, helical axis along x; square
 power-of-two sides 32…1024 run the tuned kernels, any other size in 8…1024 the runtime-sized ones); ``--index``
 picks slices of a stack like ``read_image_2d`` (io_mrc.py:71-100).
@@ -57,11 +66,103 @@ def add_args(parser: argparse.ArgumentParser) -> argparse.ArgumentParser:
     parser.add_argument("--threads", type=int, default=8, help="for --rescore")
     parser.add_argument("--map-out", default=None, help="for --rescore: write the best candidate's helically symmetrised map of every "
                         "image to <map-out>_<image>.mrc (the app's map download, app.py:1267-1287)")
+    g = parser.add_argument_group("map input (app.py:1780-1829)")
+    g.add_argument("--from-map", type=float, nargs=3, metavar=("TWIST", "RISE", "CSYM"), default=None,
+                   help="read IMAGE as a 3-D map (.mrc / .map / .npy) with this helical symmetry and sweep its projection")
+    g.add_argument("--output-apix", type=float, default=5.0, help="pixel size of the projection, Angstrom (app.py:312)")
+    g.add_argument("--output-size", type=int, nargs=2, metavar=("LENGTH", "WIDTH"), default=None,
+                   help="the resampled map is LENGTH x WIDTH x WIDTH voxels (default: the app's rule, app.py:266-273)")
+    g.add_argument("--axial-rotation", type=float, default=0.0, help="degrees, about the helical axis")
+    g.add_argument("--output-tilt", type=float, default=0.0, help="degrees, out of plane")
+    g.add_argument("--noise", type=float, default=1.0,
+                   help="Gaussian noise, in units of the projection's foreground standard deviation (app.py:359, 1818-1821)")
+    g.add_argument("--seed", type=int, default=None, help="seed of NumPy's global generator before the noise is drawn")
+    g.add_argument("--save-projection", default=None, help="write the image that is swept (.npy or .mrc)")
     return parser
 
 
-def run(args) -> dict:
+def default_output_size(nx, apix, output_apix, twist, rise) -> tuple[int, int]:
+    """app.py:266-273 with the output pixel size in place of its literal 5: width = int(nx apix / output_apix) // 4 * 4,
+    length = int(round(0.5 pitch / output_apix)) // 4 * 4 with pitch = 360 rise / |twist| (twice the width when the
+    pitch is undefined, twist = 0)."""
+    width = int(nx * apix / output_apix) // 4 * 4
+    if twist == 0:
+        return width * 2, width
+    pitch = 360.0 * rise / abs(twist)
+    return int(round(0.5 * pitch / output_apix)) // 4 * 4, width
+
+
+def map_to_image(vol, apix, twist, rise, csym, output_apix, output_size, axial_rotation=0.0, tilt=0.0, noise=1.0, device=0):
+    """The app's image of a map (app.py:1780-1829): ``symmetrize_transform_map`` onto LENGTH x WIDTH x WIDTH voxels of
+    output_apix, the sum along x transposed and flipped left-right (``xyz[0].T[:, ::-1]``: rows across the helix, columns
+    along it), then, for noise > 0, N(0, (noise sigma)^2) from NumPy's global generator with sigma the standard deviation of
+    the pixels above 1e-3.  float32."""
+    from .denovo3D import generate_xyz_projections, symmetrize_transform_map
+
+    length, width = (int(v) for v in output_size)
+    if length < 1 or width < 1:
+        raise ValueError(f"the output size must be positive; got length {length}, width {width}")
+    m = symmetrize_transform_map(vol, apix, twist, rise, int(csym), 1.0, (length, width, width), output_apix, axial_rotation,
+                                 tilt, device=device)
+    proj = np.ascontiguousarray(generate_xyz_projections(m, device=device)[0].T[:, ::-1], dtype=np.float32)
+    if noise > 0:
+        fg = proj[proj > 1e-3]
+        if fg.size == 0:
+            raise ValueError("the projection has no pixel above 1e-3: there is no foreground to scale the noise by")
+        proj += np.random.normal(scale=np.std(fg) * noise, size=proj.shape)   # in place on float32, as app.py:1820
+    return proj
+
+
+def _map_input(args):
+    """--from-map: the map, its voxel size and the projection that is swept (args.apix becomes the output pixel size)."""
+    twist, rise, csym = args.from_map
+    if csym != int(csym) or csym < 1:
+        raise SystemExit(f"--from-map: CSYM must be a positive integer; got {csym}")
+    if not rise > 0:
+        raise SystemExit(f"--from-map: RISE must be > 0; got {rise}")
+    if not args.output_apix > 0:
+        raise SystemExit(f"--output-apix must be > 0; got {args.output_apix}")
+    if args.index:
+        raise SystemExit("--index selects slices of a 2-D stack; it does not apply to --from-map")
     if str(args.image).lower().endswith((".mrc", ".mrcs", ".map")):
+        from .mrc import read_mrc
+
+        vol, header_apix = read_mrc(args.image)
+        if args.apix is None:
+            args.apix = header_apix
+    else:
+        vol = np.load(args.image)
+    if vol.ndim != 3:
+        raise SystemExit(f"--from-map needs a 3-D map; {args.image} has shape {vol.shape}")
+    if not args.apix or args.apix <= 0:
+        raise SystemExit("--apix is required (the map carries no voxel size)")
+    size = tuple(args.output_size) if args.output_size else default_output_size(vol.shape[2], args.apix, args.output_apix, twist, rise)
+    if min(size) < 8 or max(size) > 1024:
+        raise SystemExit(f"the output size (length {size[0]}, width {size[1]}) must lie in [8, 1024]: set --output-size")
+    if args.seed is not None:
+        np.random.seed(args.seed)
+    proj = map_to_image(vol, args.apix, twist, rise, int(csym), args.output_apix, size, args.axial_rotation, args.output_tilt,
+                        args.noise, args.device)
+    if args.save_projection:
+        if str(args.save_projection).lower().endswith((".mrc", ".mrcs", ".map")):
+            from .mrc import write_mrc
+
+            write_mrc(args.save_projection, proj, args.output_apix)
+        else:
+            np.save(args.save_projection, proj)
+    info = dict(path=str(args.image), shape=[int(v) for v in vol.shape], apix=float(args.apix), twist=float(twist), rise=float(rise),
+                csym=int(csym), output_apix=float(args.output_apix), output_size=[int(v) for v in size],
+                axial_rotation=float(args.axial_rotation), tilt=float(args.output_tilt), noise=float(args.noise), seed=args.seed,
+                projection_shape=[int(v) for v in proj.shape])
+    args.apix = args.output_apix
+    return proj[None], info
+
+
+def run(args) -> dict:
+    map_info = None
+    if getattr(args, "from_map", None) is not None:
+        images, map_info = _map_input(args)
+    elif str(args.image).lower().endswith((".mrc", ".mrcs", ".map")):
         from .mrc import read_mrc
 
         images, header_apix = read_mrc(args.image)
@@ -73,7 +174,7 @@ def run(args) -> dict:
         raise SystemExit("--apix is required (the input carries no pixel size)")
     if images.ndim == 2:
         images = images[None]
-    if args.index:
+    if args.index and map_info is None:
         images = images[np.asarray(args.index)]
     images = np.ascontiguousarray(images, dtype=np.float32)
     n = images.shape[-2]  # rows: the lattice has to fit across the helical axis (utils.py:88)
@@ -87,6 +188,8 @@ def run(args) -> dict:
         mask=mask, log=not args.no_log, rot=args.rot, tilt=args.tilt, psi=args.psi, dy=args.dy, device=args.device,
     )
     report = {"n_candidates": int(len(res.grid)), "n_skipped": int((~res.grid.valid).sum()), "images": []}
+    if map_info is not None:
+        report["map"] = map_info
     flat = res.scores.reshape(res.scores.shape[0], -1)
     for s in range(flat.shape[0]):
         order = np.argsort(-flat[s], kind="stable")[: args.top]  # score descending, like app.py:2521-2523

@@ -14,6 +14,8 @@
  *   hh_apply_helical_symmetry  lib/transforms.py:58-165       apply_helical_symmetry
  *   hh_affine_transform_2d lib/transforms.py:315-369          rotate_shift_image (its scipy.ndimage.affine_transform call)
  *   hh_transform_map       lib/transforms.py:168-235          transform_map (Euler ZYZ + scipy.ndimage.map_coordinates, cubic)
+ *   hh_low_high_pass_filter_3d  lib/filters.py:349-372        low_high_pass_filter_3d (symmetrize_transform_map's 3-D filter)
+ *   hh_map_projections     webApps/denovo3D/utils.py:336-345  generate_xyz_projections
  *   hh_warp_affine_2d      lib/transforms.py:238-312          transform_image (its skimage.transform.warp call)
  *   hh_rescale_2d          lib/filters.py:375-412             down_scale, and the app's binning (their skimage rescale call)
  *   hh_helix_moments       lib/analysis.py:645-728            estimate_helix_rotation_center_diameter (closing + moments)
@@ -309,6 +311,22 @@ int hh_apply_helical_symmetry(int device, const float* data, const int32_t in_sh
                               double twist_degree, double rise_angstrom, int csym, double fraction,
                               const int32_t new_size[3], double new_apix, float* out, int32_t out_shape[3],
                               double* kernel_ms);
+
+/* The 3-D branch of helicon.low_high_pass_filter (lib/filters.py:349-372), which the app's symmetrize_transform_map runs
+ * on every map it resamples to a coarser pixel (webApps/denovo3D/utils.py:361-366): Re ifftn(fftn(x) * fftshift(filter)),
+ * the Gaussian low pass exp(-f2 R^2) and / or high pass 1 - exp(-f2 R^2), f2 = ln 2 / fraction^2, R on the reference's
+ * centred float32 grid.  Computed as three 1-D circulant operators (one per axis) on the exact-f32 MFMA, for any side.
+ * data / out: host float32 [shape[0]][shape[1]][shape[2]] (z, y, x); every side in [2, 1024]; a fraction outside (0, 1)
+ * is ignored, as in the reference.  Context-free: errors are read with hh_last_error(NULL). */
+int hh_low_high_pass_filter_3d(int device, const float* data, const int32_t shape[3], double low_pass_fraction,
+                               double high_pass_fraction, float* out);
+
+/* The three axis projections of a map (generate_xyz_projections, webApps/denovo3D/utils.py:336-345): out_x[nz][ny] =
+ * sum over x, out_y[nz][nx] = sum over y, out_z[ny][nx] = sum over z, or over the slab z in [slab_begin, slab_end) when
+ * slab_begin >= 0 (the amyloid view; the caller resolves the reference's Python slice).  float64 running sums, float32
+ * results.  Context-free: errors are read with hh_last_error(NULL). */
+int hh_map_projections(int device, const float* data, const int32_t shape[3], int32_t slab_begin, int32_t slab_end, float* out_x,
+                       float* out_y, float* out_z);
 
 int hh_synchronize(hh_ctx* ctx);
 
