@@ -68,7 +68,7 @@ struct alignas(128) PabState {   // one cache line set per candidate: neighbours
   double score;
   // proximal-gradient solver of the scikit-learn models (hh_pab_solve_prox)
   int p_it, p_conv, p_nnz, p_pad;
-  double p_alpha, p_rho, p_L, p_t, p_beta, p_mu_w, p_sum, p_rn2, p_ybar, p_lam, p_obj, p_dw, p_wmax;
+  double p_alpha, p_rho, p_L, p_t, p_beta, p_mu_w, p_sum, p_rn2, p_ybar, p_lam, p_obj, p_dw, p_wmax, p_lam0;
 };
 
 struct PabView {
@@ -3246,7 +3246,9 @@ int hh_pab_rmatvec(hh_pab* p, int c, const double* y, double* g) try {
 // (O'Donoghue & Candes 2015) on the implicit operator, every vector on the device, every candidate of the batch in the same
 // launches; float64 (the reference's solvers run in float32 on its float32 matrix: its results sit 1e-4 from the
 // minimiser and scatter by 1e-5 from run to run; the fixtures G14 record both).  The step 1 / L comes from 40 power
-// iterations on the centred operator.  A candidate stops when max |w_new - w| <= tol max |w_new| (or after max_iter).
+// iterations on the centred operator.  A candidate stops when max |w_new - w| <= tol max |w_new|, or when the prox-gradient
+// mapping at the momentum point v, L max |v - w_new|, is at most 20 tol lambda_max (lambda_max = max |grad| at w = 0, its
+// positive part under positivity), or after max_iter.
 // alpha: [K] (the caller repeats all-zero solutions with alpha / 10 like solver:333-338); ridge_form: alpha is divided by m.
 // info: [K][3] = {iterations, converged, non-zero coefficients}; objective: [K] value of the function above at w (may be NULL).
 int hh_pab_solve_prox(hh_pab* p, const int32_t* positive, const int32_t* clip, const double* alpha, double l1_ratio, int ridge_form,
@@ -3269,7 +3271,7 @@ int hh_pab_solve_prox(hh_pab* p, const int32_t* positive, const int32_t* clip, c
     s.phase = PH_PRE; s.aug = 0; s.start = 0; s.l_on = 0; s.l_skip = 0; s.pend = 0; s.t_on = 0; s.inb = 0; s.rsu_pos = 0; s.bt_on = 0; s.bt_fix = 0;
     s.p_alpha = ridge_form ? alpha[c] / m : alpha[c];
     s.p_rho = l1_ratio;
-    s.p_it = 0; s.p_conv = 0; s.p_nnz = 0; s.p_t = 1.0; s.p_beta = 0; s.p_L = 1; s.p_lam = 0; s.p_obj = 0;
+    s.p_it = 0; s.p_conv = 0; s.p_nnz = 0; s.p_t = 1.0; s.p_beta = 0; s.p_L = 1; s.p_lam = 0; s.p_obj = 0; s.p_lam0 = 0;
     s.fx_scale_r = s.fx_scale; s.fx_inv_r = s.fx_inv;   // |y| <= 1 for the first transposed product below (a vector of ones)
     s.score = 0;
   }
@@ -3353,7 +3355,7 @@ int hh_pab_solve_prox(hh_pab* p, const int32_t* positive, const int32_t* clip, c
     for (int k = 0; k < per_poll && it < max_iter; ++k, ++it) {
       centred_forward(NV_P, true);
       centred_backward();
-      pab_vec<4>(p, CNT_N, pab_red<4>({RED_MAX, RED_MAX, RED_SUM, RED_SUM}, {0, 1, 2, 3}, p->nb_n), run,
+      pab_vec<6>(p, CNT_N, pab_red<6>({RED_MAX, RED_MAX, RED_SUM, RED_SUM, RED_MAX, RED_MAX}, {0, 1, 2, 3, 4, 5}, p->nb_n), run,
                  [] __device__(const PabView& w, int c, int64_t i, const PabState& s, double* acc) {
 #pragma clang fp contract(off)
                    const double v = w.nvec(NV_P, c)[i], wo = w.nvec(NV_X, c)[i];
@@ -3368,16 +3370,24 @@ int hh_pab_solve_prox(hh_pab* p, const int32_t* positive, const int32_t* clip, c
                    acc[1] = fmax(acc[1], fabs(wn));
                    acc[2] += (v - wn) * (wn - wo);
                    acc[3] += wn != 0.0 ? 1.0 : 0.0;
+                   acc[4] = fmax(acc[4], fabs(v - wn));                       // the prox-gradient mapping, / L
+                   acc[5] = fmax(acc[5], s.bounded ? fmax(-g, 0.0) : fabs(g));   // lambda_max at the first step (v = 0)
                  });
-      pab_scalar<4>(p, pab_red<4>({RED_MAX, RED_MAX, RED_SUM, RED_SUM}, {0, 1, 2, 3}, p->nb_n), run, [tol, max_iter] __device__(const PabView&, int, PabState& s, const double* v) {
+      pab_scalar<6>(p, pab_red<6>({RED_MAX, RED_MAX, RED_SUM, RED_SUM, RED_MAX, RED_MAX}, {0, 1, 2, 3, 4, 5}, p->nb_n), run,
+                    [tol, max_iter] __device__(const PabView&, int, PabState& s, const double* v) {
         s.p_dw = v[0]; s.p_wmax = v[1]; s.p_nnz = (int)v[3];
+        if (s.p_it == 0) s.p_lam0 = v[5];
         double t = s.p_t;
         if (v[2] > 0) t = 1.0;                                  // gradient restart: the momentum points uphill
         const double tn = (1 + sqrt(1 + 4 * t * t)) / 2;
         s.p_beta = (t - 1) / tn;
         s.p_t = tn;
         ++s.p_it;
-        if (s.p_dw <= tol * s.p_wmax || s.p_it >= max_iter) s.p_conv = s.p_dw <= tol * s.p_wmax ? 1 : 2;
+        // stop on a small relative step, or on optimality: the subgradient residual at w_new, L |v - w_new| up to the
+        // change of the gradient between v and w_new, at most 20 tol of lambda_max (the case of ill-conditioned fits
+        // without a penalty, whose steps stay large: lreg on the trilinear products)
+        const bool done = s.p_dw <= tol * s.p_wmax || s.p_L * v[4] <= 20 * tol * s.p_lam0;
+        if (done || s.p_it >= max_iter) s.p_conv = done ? 1 : 2;
       });
       pab_vec<0>(p, CNT_N, PabRed<0>{}, run, [] __device__(const PabView& w, int c, int64_t i, const PabState& s, double*) {
 #pragma clang fp contract(off)

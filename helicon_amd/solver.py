@@ -26,6 +26,7 @@ Not provided (``NotImplementedError``): model "ard".  There is no CPU fallback: 
 from __future__ import annotations
 
 import ctypes as C
+import warnings
 
 import numpy as np
 
@@ -612,21 +613,26 @@ def _box(img, reconstruct_diameter_2d_pixel, reconstruct_length_2d_pixel, recons
     return d2, l2, d3, l3, mask, n3, target
 
 
+# FISTA iterations of hh_pab_solve_prox per model.  lreg has no penalty: on the trilinear products its system is ill
+# conditioned, and the solver needs up to ~1e5 iterations to meet its optimality stop there (Path A models)
+PROX_MAX_ITER = {"elasticnet": 5000, "lasso": 5000, "ridge": 5000, "lreg": 200000}
+
+
 def _model_of(algorithm):
-    """algorithm dict of lsq_reconstruct -> None for "lsq", else (alpha, l1_ratio, ridge_form) of the common objective
-    (solver:270-342: the defaults of the reference's constructors)."""
+    """algorithm dict of lsq_reconstruct -> None for "lsq", else (alpha, l1_ratio, ridge_form, max_iter) of the common
+    objective (solver:270-342: the defaults of the reference's constructors) and the solver's iteration budget."""
     algorithm = algorithm or {}
     model = algorithm.get("model", "lsq")
     if model == "lsq":
         return None
     if model == "elasticnet":
-        return float(algorithm.get("alpha", 1e-4)), float(algorithm.get("l1_ratio", 0.5)), False
+        return float(algorithm.get("alpha", 1e-4)), float(algorithm.get("l1_ratio", 0.5)), False, PROX_MAX_ITER[model]
     if model == "lasso":
-        return float(algorithm.get("alpha", 1e-4)), 1.0, False
+        return float(algorithm.get("alpha", 1e-4)), 1.0, False, PROX_MAX_ITER[model]
     if model == "ridge":
-        return float(algorithm.get("alpha", 1)), 0.0, True
+        return float(algorithm.get("alpha", 1)), 0.0, True, PROX_MAX_ITER[model]
     if model == "lreg":
-        return 0.0, 0.0, False
+        return 0.0, 0.0, False, PROX_MAX_ITER[model]
     raise NotImplementedError(f"algorithm model {model!r}: the GPU path has lsq, elasticnet, lasso, ridge and lreg (ard is a dense "
                               "Bayesian fit in the reference)")
 
@@ -659,6 +665,7 @@ def lsq_reconstruct_batch(projection_image, scale2d_to_3d, candidates, tilt_degr
     if interpolation not in ("nn", "linear"):
         raise ValueError("interpolation must be 'nn' or 'linear'")
     model = _model_of(algorithm)
+    lreg = model is not None and algorithm.get("model") == "lreg"
     if model is not None and (tilt_degree != 0 or psi_degree != 0):
         raise NotImplementedError("the scikit-learn models run on the slice-major products: tilt = psi = 0")
 
@@ -721,20 +728,34 @@ def lsq_reconstruct_batch(projection_image, scale2d_to_3d, candidates, tilt_degr
             if model is None:
                 x, scores, info = B.solve(positive, clip, want_x=want_x)
             else:
-                alpha, rho, ridge_form = model
+                alpha, rho, ridge_form, max_iter = model
                 al = np.full(len(params), alpha, dtype=np.float64)
-                x, scores, info3, _ = B.solve_prox(positive, clip, al, rho, ridge_form, want_x=want_x)
+                x, scores, info3, _ = B.solve_prox(positive, clip, al, rho, ridge_form, max_iter=max_iter, want_x=want_x)
                 # solver:331-338: an all-zero solution is refitted with alpha / 10 (elasticnet, lasso, ridge) until it is not
                 for _ in range(12):
                     zero = info3[:, 2] == 0
                     if not zero.any() or alpha == 0:
                         break
                     al = np.where(zero, al * 0.1, al)
-                    x2, s2, i2, _ = B.solve_prox(positive, clip, al, rho, ridge_form, want_x=want_x)
+                    x2, s2, i2, _ = B.solve_prox(positive, clip, al, rho, ridge_form, max_iter=max_iter, want_x=want_x)
                     scores = np.where(zero, s2, scores)
                     info3 = np.where(zero[:, None], i2, info3)
                     if want_x:
                         x = np.where(zero[:, None], x2, x)
+                if lreg:
+                    # solver:330-332: an all-zero LinearRegression fit (lreg only) becomes e_{n//2}; the score is that map's
+                    for c in np.flatnonzero(info3[:, 2] == 0):
+                        e = np.zeros(B.n)
+                        e[B.n // 2] = 1
+                        b_c = B.rhs(c)[0]
+                        pred = B.matvec(c, e)[: len(b_c)]
+                        scores[c] = cosine_similarity(np.clip(pred, 0, None) if clip else pred, b_c)
+                        info3[c, 2] = 1
+                        if want_x:
+                            x[c] = e
+                if (info3[:, 1] != 1).any():
+                    warnings.warn(f"{int((info3[:, 1] != 1).sum())} of {len(params)} {algorithm.get('model')} fits ran out of "
+                                  f"{max_iter} iterations before the solver's stop (stats['info'][:, 0] == 0)", RuntimeWarning)
                 info = np.concatenate([np.where(info3[:, 1:2] == 1, 1, 0), info3[:, :1], np.zeros_like(info3[:, :1]), info3[:, :1],
                                        np.zeros_like(info3[:, :1])], axis=1)   # status, iterations, -, iterations, -
             if two_d:
