@@ -2444,6 +2444,8 @@ struct EventPair {
 #include "general_sizes.inc"  // kernels of the general-size path (any ny x nx) and struct hh_gen
 #include "path_a.inc"         // Path A (sparse least-squares scorer): projector kernels and struct hh_pa
 
+struct hh_zoom;   // zoom_sweep.inc: the sweep on Fourier-zoomed spectra (hh_set_spectrum_zoom)
+
 struct hh_ctx {
   int device = 0;
   int n = 0;                     // side of a square power-of-two context; 0 for a general-size one
@@ -2451,6 +2453,8 @@ struct hh_ctx {
   bool general = false;          // true: every entry point goes through general_sizes.inc / general_host.inc
   void* comm = nullptr;          // ncclComm_t of hh_comm_init (RCCL, loaded on first use)
   hh_gen* gen = nullptr;
+  hh_zoom* zoom = nullptr;
+  double apix = 0;               // hh_set_geometry's pixel size in full precision (the zoomed frequencies use it)
   int max_batch = 0;
   int n_cu = 0;                  // compute units of the device
   int slots = 0;                 // resident k_fused_pass workgroups for the launch shape slots_key (fused_slots)
@@ -2496,7 +2500,7 @@ struct hh_ctx {
   int* d_cgs = nullptr;          // fused pass: [max_batch][N/4]
   size_t cap_eg = 0, cap_cgs = 0;
   int cap_partials = 0;          // candidates per half of d_partials
-  int last_first_pass = 0;       // what the last sweep ran: 0 per-candidate transform, 1 run tables
+  int last_first_pass = 0;       // what the last sweep ran: 0 per-candidate transform, 1 run tables, 2 fused, 3 zoomed spectra
   unsigned long long kb_mask = ~0ull;
   int s_pad = 0, b_pad = 0;
   float2* d_spec = nullptr;      // [N/2+1][N] scratch (grown for S segments)
@@ -2524,6 +2528,12 @@ namespace {
 
 // general-size path (general_host.inc, included at the end of this namespace)
 int gen_sweep(hh_ctx* c, const double* d_params, const double* h_params, int64_t n_cand, float* d_scores, int64_t ld);
+
+// the sweep on Fourier-zoomed spectra (zoom_sweep.inc, included at the end of the file)
+bool zoom_on(const hh_ctx* c);
+void zoom_free(hh_ctx* c);
+int zoom_set_reference(hh_ctx* c, const float* images, int n_segments, const uint8_t* mask, int log_flag);
+int zoom_sweep(hh_ctx* c, const double* d_params, int64_t n_cand, float* d_scores, int64_t ld);
 
 int fail(hh_ctx* c, int code, const std::string& msg) {
   if (c) c->err = msg; else g_create_error = msg;
@@ -3291,6 +3301,7 @@ int sweep_transform(hh_ctx* c, const double* d_params, int64_t g, float* d_score
 // their `g` argument for that addressing, so they are handed ld.
 int sweep_on_device(hh_ctx* c, const double* d_params, const int64_t n_cand, float* d_scores,
                     const double* h_params = nullptr, int64_t ld = 0) {
+  if (zoom_on(c)) return zoom_sweep(c, d_params, n_cand, d_scores, ld);
   if (c->general) return gen_sweep(c, d_params, h_params, n_cand, d_scores, ld);
   RunPlan plan = plan_runs(c, h_params, n_cand);
   c->last_first_pass = plan.ok ? (plan.fused ? 2 : 1) : 0;
@@ -3559,6 +3570,7 @@ void hh_destroy(hh_ctx* c) try {
   (void)hipFree(c->d_spec);
   (void)hipFree(c->d_img);
   gen_free(c);
+  zoom_free(c);
   if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
   delete c;
 } catch (...) {
@@ -3694,7 +3706,9 @@ int hh_set_geometry(hh_ctx* c, const hh_geom* g) try {
   }
   HH_HIP(c, hipMemcpyAsync(c->d_units, units.data(), units.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
   HH_HIP(c, hipStreamSynchronize(c->stream));
+  if (zoom_on(c) && g->apix != c->apix) c->n_segments = 0;   // the zoomed frequencies scale with the pixel size: new reference
   c->geom = d;
+  c->apix = g->apix;
   c->have_geom = true;
   return HH_OK;
 } HH_CATCH_CTX(c, "hh_set_geometry")
@@ -3702,6 +3716,7 @@ int hh_set_geometry(hh_ctx* c, const hh_geom* g) try {
 int hh_set_reference(hh_ctx* c, const float* images, int n_segments, const uint8_t* mask, int log_flag) try {
   if (!c || !images || !mask || n_segments <= 0) return fail(c, HH_ERR_ARG, "hh_set_reference: bad argument");
   HH_HIP(c, hipSetDevice(c->device));
+  if (zoom_on(c)) return zoom_set_reference(c, images, n_segments, mask, log_flag);
   if (c->general) return gen_set_reference(c, images, n_segments, mask, log_flag);
   const int n = c->n;
   const size_t npix = (size_t)n * n, nh = (size_t)(n / 2 + 1) * n;
@@ -4520,6 +4535,7 @@ int hh_profile_get(hh_ctx* c, hh_profile* out) try {
 
 #include "image_prep.inc"    // pre-sweep image preparation that is scikit-image in the reference (warp, rescale, closing + moments)
 #include "fourier_zoom.inc"  // compute_power_spectra with cutoff_res / output_size: direct non-uniform DFT (hh_power_spectrum_zoom)
+#include "zoom_sweep.inc"    // the sweep on those zoomed spectra: factors + complex product on the f32 MFMA + fused moments (hh_set_spectrum_zoom)
 #include "path_a_host.inc"  // Path A: host side and C ABI (hh_pa_*)
 #include "path_a_batch.inc"  // Path A for many candidates at once, device-resident solve (hh_pab_*)
 #include "map_filter.inc"  // the 3-D map input: separable Gaussian filter of a whole map on the f32 MFMA, axis projections

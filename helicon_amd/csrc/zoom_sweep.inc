@@ -1,0 +1,469 @@
+// zoom_sweep.inc — the sweep on Fourier-zoomed spectra: compute_power_spectra(sim, apix, cutoff_res, output_size) of every
+// candidate against the same view of the experimental image (lib/transforms.py:663-713, 771-820), in one batched call.
+//
+// The zoomed transform is the image's Fourier sum at ony x onx frequencies that are no FFT grid (fourier_zoom.inc).  A
+// simulated projection is a sum of truncated Gaussian footprints and every footprint is a product ex_c(x) ey_c(y), so
+//     F[u][v] = sum_c Gy_c[u] Gx_c[v],   Gy_c[u] = sum_y ey_c(y) e^{-2 pi i f_y[u] (y - ny/2)},   Gx_c[v] likewise along x
+// over the lattice centres c whose footprint meets the image: one complex [ony x C] . [C x onx] product per candidate.
+// k_zoom_sweep does all of it for one output tile of one candidate: lattice centres with the sweep's own device code
+// (decode_candidate / centre_position), the raster's window tests, the factors by Horner's rule over a footprint's taps,
+// the product on the exact-f32 MFMA (32x32x2, K staged through LDS: the layout of k_circ_gemm, four real products for
+// the complex one), and the epilogue |F| -> log1p -> masked moments fused, so F never leaves the registers.  The
+// reference side is k_zoom_rows / k_zoom_cols on the device plus k_zoom_weights ({w, w (E - Ebar)} per segment).
+//
+// The whole plane is computed: the zoomed grid is not closed under negation (row ony/2 and column onx/2 of an even side
+// have no Friedel partner on the grid), so there is no half-plane fold here; tiles without a masked bin are skipped.
+
+struct hh_zoom {
+  bool on = false;
+  int ony = 0, onx = 0;
+  double cutoff_y = 0, cutoff_x = 0;
+  double apix_ref = 0;            // pixel size the reference was prepared with (the frequencies depend on it)
+  int tiles_v = 0, n_tiles = 0;   // active output tiles (any masked bin)
+  float* d_img = nullptr;         // [S][ny][nx]
+  double2* d_r = nullptr;         // [ny][onx] row pass of one image
+  float* d_pwr = nullptr;         // [ony][onx] fftshifted spectrum of one image
+  unsigned* d_mm = nullptr;       // k_zoom_cols' min / max slots (unused here: Pearson drops the normalisation)
+  uint8_t* d_mask = nullptr;      // [ony][onx] fftshifted
+  float* d_w = nullptr;           // [ony][onx] unshifted mask weight
+  float* d_wec = nullptr;         // [S][ony][onx] unshifted w (E_s - Ebar_s)
+  RefConsts* d_ref = nullptr;     // [S]
+  int* d_tiles = nullptr;
+  double* d_partials = nullptr;   // [S][batch][n_tiles][3]
+  size_t cap_img = 0, cap_r = 0, cap_pwr = 0, cap_mm = 0, cap_mask = 0, cap_w = 0, cap_wec = 0, cap_ref = 0, cap_tiles = 0,
+         cap_partials = 0;
+  std::vector<RefConsts> ref;
+};
+
+namespace {
+
+constexpr int ZS_TU = 128;     // output tile of a workgroup: 128 rows (u) x 128 columns (v); a wavefront owns 32 x 64
+constexpr int ZS_TV = 128;
+constexpr int ZS_THREADS = 512;
+constexpr int ZS_WAVES = ZS_THREADS / 64;
+constexpr int ZS_K = 32;       // lattice centres per K slice
+constexpr int ZS_CHUNK = ZS_THREADS;  // lattice centres tested per step (one per lane of the workgroup)
+constexpr int ZS_TAPS = 64;    // footprints up to this many pixels keep their profiles in LDS
+constexpr int ZS_LIST = ZS_CHUNK + ZS_K;
+constexpr int64_t ZS_BATCH = 8192;
+
+struct ZoomLds {   // dynamic LDS of k_zoom_sweep
+  float as_re[ZS_TU][ZS_K + 1], as_im[ZS_TU][ZS_K + 1];
+  float bs_re[ZS_K][ZS_TV + 1], bs_im[ZS_K][ZS_TV + 1];
+  float prof_y[ZS_K][ZS_TAPS], prof_x[ZS_K][ZS_TAPS];
+  float yc[ZS_LIST], xc[ZS_LIST];
+  int y0[ZS_LIST], ly[ZS_LIST], x0[ZS_LIST], lx[ZS_LIST];
+  double red[ZS_WAVES][3];
+  int wave_cnt[ZS_WAVES];
+};
+static_assert(offsetof(ZoomLds, prof_y) % 16 == 0 && offsetof(ZoomLds, prof_x) % 16 == 0 && ZS_TAPS % 4 == 0,
+              "the profiles are read four taps at a time");
+
+struct ZoomSweepArgs {
+  const double* params;   // [batch][4]
+  const double* units;
+  const float* w;         // [ony][onx]
+  const float* wec;       // [S][ony][onx]
+  const int* tiles;       // [n_tiles]: tu * tiles_v + tv
+  double* partials;       // [S][batch][n_tiles][3]
+  DevGeom g;
+  ZoomDims d;
+  double apix, cutoff_y, cutoff_x;
+  int tiles_v, n_seg;
+};
+
+// One tap of a footprint's profile along one axis: 2^(-k2 ((p - half) apix - centre)^2), the raster's arithmetic.
+__device__ __forceinline__ float zoom_tap(int p, int half, float apix, float centre, float k2) {
+  const float dq = (float)(p - half) * apix - centre;
+  return __builtin_amdgcn_exp2f(-(dq * dq * k2));
+}
+
+// sum_j e_j e^{-2 pi i f (p0 + j - half)} over the len taps from pixel p0: Horner's rule in w = e^{-2 pi i f} from the
+// last tap, then the phase of the first one (its argument reduced in float64).  An LDS profile is zero past its last tap
+// and is read four taps at a time (the extra steps leave the zero sum as it is: same result as tap by tap).
+template <bool LDSP>
+__device__ __forceinline__ float2 zoom_factor(double f, float2 w, int p0, int len, int half, float centre, float apix, float k2,
+                                              const float* prof) {
+  float sr = 0.f, si = 0.f;
+  auto step = [&](float e) __attribute__((always_inline)) {
+    const float nr = fmaf(sr, w.x, fmaf(-si, w.y, e));
+    si = fmaf(sr, w.y, si * w.x);
+    sr = nr;
+  };
+  if constexpr (LDSP) {
+    const float4* const p4 = reinterpret_cast<const float4*>(prof);
+    for (int q = ((len + 3) >> 2) - 1; q >= 0; --q) {
+      const float4 e = p4[q];
+      step(e.w);
+      step(e.z);
+      step(e.y);
+      step(e.x);
+    }
+  } else {
+    for (int j = len - 1; j >= 0; --j) step(zoom_tap(p0 + j, half, apix, centre, k2));
+  }
+  double t = f * (double)(p0 - half);
+  t -= rint(t);
+  float sn, cs;
+  sincospif(-2.0f * (float)t, &sn, &cs);
+  return make_float2(sr * cs - si * sn, sr * sn + si * cs);
+}
+
+template <int LOG, bool LDSP>
+__global__ __launch_bounds__(ZS_THREADS) void k_zoom_sweep(ZoomSweepArgs a) {
+  extern __shared__ __align__(16) unsigned char zoom_lds_raw[];
+  ZoomLds& L = *reinterpret_cast<ZoomLds*>(zoom_lds_raw);
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int r = lane & 31, h = lane >> 5;
+  const int wu = wave & 3, wv = wave >> 2;   // 4 x 2 wavefronts of 32 x 64
+  const int b = blockIdx.y, n_tiles = gridDim.x, batch = gridDim.y;
+  const int tile = a.tiles[blockIdx.x];
+  const int u0 = (tile / a.tiles_v) * ZS_TU, v0 = (tile % a.tiles_v) * ZS_TV;
+  const DevGeom& g = a.g;
+  const int ny = a.d.ny, nx = a.d.nx, ony = a.d.ony, onx = a.d.onx;
+  const float rp = (float)g.rpx;
+  const float k2 = g.inv_sigma2 * 1.44269504088896341f;
+  const Cand c = decode_candidate(a.params + 4 * (size_t)b, g);
+
+  // the two frequencies this lane builds factors for, and their unit steps w = e^{-2 pi i f}
+  const int ul = tid & (ZS_TU - 1), vl = tid & (ZS_TV - 1);
+  const bool u_ok = u0 + ul < ony, v_ok = v0 + vl < onx;
+  const double fy = u_ok ? zoom_freq(u0 + ul, ony, a.d.sy, a.apix, a.cutoff_y) : 0.0;
+  const double fx = v_ok ? zoom_freq(v0 + vl, onx, a.d.sx, a.apix, a.cutoff_x) : 0.0;
+  float2 wy, wx;
+  {
+    double sn, cs;
+    sincospi(-2.0 * fy, &sn, &cs);
+    wy = make_float2((float)cs, (float)sn);
+    sincospi(-2.0 * fx, &sn, &cs);
+    wx = make_float2((float)cs, (float)sn);
+  }
+
+  f32x16 acc_re[2] = {{0}, {0}}, acc_im[2] = {{0}, {0}};
+
+  // one K slice: list entries [s0, s0 + cnt), cnt <= ZS_K (the rest of the slice is zero)
+  auto slice = [&](int s0, int cnt) __attribute__((always_inline)) {
+    if constexpr (LDSP) {
+      for (int e = tid; e < ZS_K * ZS_TAPS; e += ZS_THREADS) {
+        const int k = e / ZS_TAPS, j = e % ZS_TAPS;
+        if (k < cnt) {
+          L.prof_y[k][j] = j < L.ly[s0 + k] ? zoom_tap(L.y0[s0 + k] + j, ny / 2, g.apix, L.yc[s0 + k], k2) : 0.f;
+          L.prof_x[k][j] = j < L.lx[s0 + k] ? zoom_tap(L.x0[s0 + k] + j, nx / 2, g.apix, L.xc[s0 + k], k2) : 0.f;
+        }
+      }
+      __syncthreads();
+    }
+    for (int k = tid / ZS_TU; k < ZS_K; k += ZS_THREADS / ZS_TU) {
+      float2 v = make_float2(0.f, 0.f);
+      if (k < cnt && u_ok)
+        v = zoom_factor<LDSP>(fy, wy, L.y0[s0 + k], L.ly[s0 + k], ny / 2, L.yc[s0 + k], g.apix, k2, L.prof_y[k]);
+      L.as_re[ul][k] = v.x;
+      L.as_im[ul][k] = v.y;
+    }
+    for (int k = tid / ZS_TV; k < ZS_K; k += ZS_THREADS / ZS_TV) {
+      float2 v = make_float2(0.f, 0.f);
+      if (k < cnt && v_ok)
+        v = zoom_factor<LDSP>(fx, wx, L.x0[s0 + k], L.lx[s0 + k], nx / 2, L.xc[s0 + k], g.apix, k2, L.prof_x[k]);
+      L.bs_re[k][vl] = v.x;
+      L.bs_im[k][vl] = v.y;
+    }
+    __syncthreads();
+#pragma unroll 4
+    for (int kk = 0; kk < ZS_K; kk += 2) {
+      const float ar = L.as_re[wu * 32 + r][kk + h], ai = L.as_im[wu * 32 + r][kk + h];
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        const float br = L.bs_re[kk + h][wv * 64 + t * 32 + r], bi = L.bs_im[kk + h][wv * 64 + t * 32 + r];
+        acc_re[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(ar, br, acc_re[t], 0, 0, 0);
+        acc_re[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(-ai, bi, acc_re[t], 0, 0, 0);
+        acc_im[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(ar, bi, acc_im[t], 0, 0, 0);
+        acc_im[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(ai, br, acc_im[t], 0, 0, 0);
+      }
+    }
+    __syncthreads();
+  };
+
+  // Walk the lattice in chunks of one centre per lane; the centres whose footprint meets the image are appended to the
+  // list in lattice order (ballot + prefix), full K slices are consumed, the remainder waits for the next chunk.
+  int pending = 0;
+  for (int base = 0; base < c.M; base += ZS_CHUNK) {
+    const int ci = base + tid;
+    bool hit = false;
+    float2 p = make_float2(0.f, 0.f);
+    int y0 = 0, y1 = -1, x0 = 0, x1 = -1;
+    if (ci < c.M) {
+      p = centre_position(c, g, a.units, ci);
+      const float cy = p.x * g.inv_apix + (float)(ny / 2), cx = p.y * g.inv_apix + (float)(nx / 2);
+      if (cy >= -rp - 1.f && cy <= (float)ny + rp && cx >= -rp - 1.f && cx <= (float)nx + rp) {
+        y0 = max(0, (int)ceilf(cy - rp));
+        y1 = min(ny - 1, (int)floorf(cy + rp));
+        x0 = max(0, (int)ceilf(cx - rp));
+        x1 = min(nx - 1, (int)floorf(cx + rp));
+        hit = y0 <= y1 && x0 <= x1;
+      }
+    }
+    const unsigned long long bal = __ballot(hit);
+    if (lane == 0) L.wave_cnt[wave] = __popcll(bal);
+    __syncthreads();
+    int off = pending, total = pending;
+    for (int w = 0; w < ZS_WAVES; ++w) {
+      if (w < wave) off += L.wave_cnt[w];
+      total += L.wave_cnt[w];
+    }
+    if (hit) {
+      const int at = off + __popcll(bal & ((1ull << lane) - 1ull));
+      L.yc[at] = p.x;
+      L.xc[at] = p.y;
+      L.y0[at] = y0;
+      L.ly[at] = y1 - y0 + 1;
+      L.x0[at] = x0;
+      L.lx[at] = x1 - x0 + 1;
+    }
+    __syncthreads();
+    const bool last = base + ZS_CHUNK >= c.M;   // the last chunk also consumes the partial slice
+    int s0 = 0;
+    for (; total - s0 >= ZS_K || (last && s0 < total); s0 += ZS_K) slice(s0, min(ZS_K, total - s0));
+    pending = max(0, total - s0);
+    if (s0 > 0 && pending > 0) {   // move the remainder (< ZS_K entries) to the front
+      float ryc = 0.f, rxc = 0.f;
+      int ry0 = 0, rly = 0, rx0 = 0, rlx = 0;
+      if (tid < pending) {
+        ryc = L.yc[s0 + tid]; rxc = L.xc[s0 + tid];
+        ry0 = L.y0[s0 + tid]; rly = L.ly[s0 + tid]; rx0 = L.x0[s0 + tid]; rlx = L.lx[s0 + tid];
+      }
+      __syncthreads();
+      if (tid < pending) {
+        L.yc[tid] = ryc; L.xc[tid] = rxc;
+        L.y0[tid] = ry0; L.ly[tid] = rly; L.x0[tid] = rx0; L.lx[tid] = rlx;
+      }
+    }
+    __syncthreads();
+  }
+
+  // epilogue: q = log1p|F| (or |F|) and the three masked moments of this tile, per segment
+  const size_t plane = (size_t)ony * onx;
+  for (int s = 0; s < a.n_seg; ++s) {
+    const float* const wec = a.wec + (size_t)s * plane;
+    float f1 = 0.f, f2 = 0.f, f3 = 0.f;
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+      for (int i = 0; i < 16; ++i) {
+        const int u = u0 + wu * 32 + (i & 3) + 8 * (i >> 2) + 4 * h;   // 32x32 C/D map: column = lane & 31
+        const int v = v0 + wv * 64 + t * 32 + r;
+        if (u < ony && v < onx) {
+          const size_t at = (size_t)u * onx + v;
+          const float wt = a.w[at];
+          if (wt != 0.f) {
+            const float q = amp_to_q<LOG>(make_float2(acc_re[t][i], acc_im[t][i]));
+            f1 = fmaf(wt, q, f1);
+            f2 = fmaf(wt * q, q, f2);
+            f3 = fmaf(wec[at], q, f3);
+          }
+        }
+      }
+    double s1 = f1, s2 = f2, s3 = f3;
+    for (int o = 32; o > 0; o >>= 1) {
+      s1 += __shfl_down(s1, o, 64);
+      s2 += __shfl_down(s2, o, 64);
+      s3 += __shfl_down(s3, o, 64);
+    }
+    if (lane == 0) {
+      L.red[wave][0] = s1;
+      L.red[wave][1] = s2;
+      L.red[wave][2] = s3;
+    }
+    __syncthreads();
+    if (tid < 3) {
+      double* const out = a.partials + (((size_t)s * batch + b) * n_tiles + blockIdx.x) * 3;
+      double sum = 0;
+      for (int w = 0; w < ZS_WAVES; ++w) sum += L.red[w][tid];   // fixed order
+      out[tid] = sum;
+    }
+    __syncthreads();
+  }
+}
+
+// {w, w (E - Ebar)} of one segment from its fftshifted spectrum and the fftshifted mask, on the unshifted plane the
+// sweep kernel indexes; the reference's three constants.  One workgroup: a once-per-reference step.
+__global__ __launch_bounds__(1024) void k_zoom_weights(const float* __restrict__ pwr, const uint8_t* __restrict__ mask, int ony,
+                                                       int onx, float* __restrict__ w, float* __restrict__ wec,
+                                                       RefConsts* __restrict__ ref) {
+  __shared__ double red[16][2];
+  __shared__ double tot[2];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int n = ony * onx;
+  auto block_sum2 = [&](double x, double y) {
+    for (int o = 32; o > 0; o >>= 1) {
+      x += __shfl_down(x, o, 64);
+      y += __shfl_down(y, o, 64);
+    }
+    if (lane == 0) { red[wave][0] = x; red[wave][1] = y; }
+    __syncthreads();
+    if (tid == 0) {
+      double sx = 0, sy = 0;
+      for (int k = 0; k < 16; ++k) { sx += red[k][0]; sy += red[k][1]; }
+      tot[0] = sx; tot[1] = sy;
+    }
+    __syncthreads();
+  };
+  double sw = 0, se = 0;
+  for (int i = tid; i < n; i += 1024)
+    if (mask[i]) { sw += 1.0; se += (double)pwr[i]; }
+  block_sum2(sw, se);
+  sw = tot[0];
+  const double ebar = sw > 0 ? tot[1] / sw : 0.0;
+  __syncthreads();
+  double swec = 0, var_e = 0;
+  for (int i = tid; i < n; i += 1024) {
+    const int su = i / onx, sv = i % onx;
+    const int u = (su + ony - ony / 2) % ony, v = (sv + onx - onx / 2) % onx;   // np.fft.fftshift moved u to (u + n/2) mod n
+    const double m = mask[i] ? 1.0 : 0.0, dc = (double)pwr[i] - ebar;
+    const float x = (float)(m * dc);
+    w[(size_t)u * onx + v] = (float)m;
+    wec[(size_t)u * onx + v] = x;
+    swec += (double)x;
+    var_e += m * dc * dc;
+  }
+  block_sum2(swec, var_e);
+  if (tid == 0) *ref = RefConsts{sw, tot[0], tot[1]};
+}
+
+void zoom_free(hh_ctx* c) {
+  hh_zoom* z = c->zoom;
+  if (!z) return;
+  (void)hipFree(z->d_img); (void)hipFree(z->d_r); (void)hipFree(z->d_pwr); (void)hipFree(z->d_mm); (void)hipFree(z->d_mask);
+  (void)hipFree(z->d_w); (void)hipFree(z->d_wec); (void)hipFree(z->d_ref); (void)hipFree(z->d_tiles); (void)hipFree(z->d_partials);
+  delete z;
+  c->zoom = nullptr;
+}
+
+bool zoom_on(const hh_ctx* c) { return c->zoom && c->zoom->on; }
+
+// hh_set_reference with a zoom set: images [S][ny][nx] (host), mask [ony][onx] bytes on the fftshifted zoomed plane.
+int zoom_set_reference(hh_ctx* c, const float* images, int n_segments, const uint8_t* mask, int log_flag) {
+  hh_zoom* z = c->zoom;
+  if (!c->have_geom) return fail(c, HH_ERR_STATE, "hh_set_reference: a spectrum zoom needs the pixel size; call hh_set_geometry first");
+  const int ny = c->ny, nx = c->nx, ony = z->ony, onx = z->onx;
+  const size_t plane = (size_t)ony * onx, npix = (size_t)ny * nx;
+  // active tiles, from the mask alone (unshifted index u sits at fftshifted row (u + ony/2) mod ony)
+  const int tiles_u = (ony + ZS_TU - 1) / ZS_TU, tiles_v = (onx + ZS_TV - 1) / ZS_TV;
+  std::vector<int> tiles;
+  for (int tu = 0; tu < tiles_u; ++tu)
+    for (int tv = 0; tv < tiles_v; ++tv) {
+      bool any = false;
+      for (int u = tu * ZS_TU; u < std::min(ony, (tu + 1) * ZS_TU) && !any; ++u)
+        for (int v = tv * ZS_TV; v < std::min(onx, (tv + 1) * ZS_TV) && !any; ++v)
+          any = mask[(size_t)((u + ony / 2) % ony) * onx + (v + onx / 2) % onx] != 0;
+      if (any) tiles.push_back(tu * tiles_v + tv);
+    }
+  if (tiles.empty()) return fail(c, HH_ERR_ARG, "hh_set_reference: the mask selects no Fourier bin");
+  c->n_segments = 0;   // from here on the old reference is gone
+  int rc;
+  if ((rc = ensure_bytes(c, (void**)&z->d_img, &z->cap_img, (size_t)n_segments * npix * sizeof(float)))) return rc;
+  if ((rc = ensure_bytes(c, (void**)&z->d_r, &z->cap_r, (size_t)ny * onx * sizeof(double2)))) return rc;
+  if ((rc = ensure_bytes(c, (void**)&z->d_pwr, &z->cap_pwr, plane * sizeof(float)))) return rc;
+  if ((rc = ensure_bytes(c, (void**)&z->d_mm, &z->cap_mm, 2 * sizeof(unsigned)))) return rc;
+  if ((rc = ensure_bytes(c, (void**)&z->d_mask, &z->cap_mask, plane))) return rc;
+  if ((rc = ensure_bytes(c, (void**)&z->d_w, &z->cap_w, plane * sizeof(float)))) return rc;
+  if ((rc = ensure_bytes(c, (void**)&z->d_wec, &z->cap_wec, (size_t)n_segments * plane * sizeof(float)))) return rc;
+  if ((rc = ensure_bytes(c, (void**)&z->d_ref, &z->cap_ref, (size_t)n_segments * sizeof(RefConsts)))) return rc;
+  if ((rc = ensure_bytes(c, (void**)&z->d_tiles, &z->cap_tiles, (size_t)tiles_u * tiles_v * sizeof(int)))) return rc;
+  const unsigned init[2] = {0x7f800000u, 0u};
+  HH_HIP(c, hipMemcpyAsync(z->d_img, images, (size_t)n_segments * npix * sizeof(float), hipMemcpyHostToDevice, c->stream));
+  HH_HIP(c, hipMemcpyAsync(z->d_mask, mask, plane, hipMemcpyHostToDevice, c->stream));
+  HH_HIP(c, hipMemcpyAsync(z->d_mm, init, sizeof(init), hipMemcpyHostToDevice, c->stream));
+  HH_HIP(c, hipMemcpyAsync(z->d_tiles, tiles.data(), tiles.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  const double apix = c->apix;
+  const ZoomDims d{ny, nx, ony, onx, 2 * apix / z->cutoff_y, 2 * apix / z->cutoff_x};
+  for (int s = 0; s < n_segments; ++s) {
+    hipLaunchKernelGGL(k_zoom_rows, dim3((onx + 127) / 128, ny), dim3(128), 0, c->stream, z->d_img + (size_t)s * npix, d, apix,
+                       z->cutoff_x, z->d_r);
+    hipLaunchKernelGGL(k_zoom_cols, dim3((onx + 127) / 128, ony), dim3(128), 0, c->stream, z->d_r, d, apix, z->cutoff_y,
+                       log_flag ? 1 : 0, z->d_pwr, (float*)nullptr, z->d_mm);
+    hipLaunchKernelGGL(k_zoom_weights, dim3(1), dim3(1024), 0, c->stream, z->d_pwr, z->d_mask, ony, onx, z->d_w,
+                       z->d_wec + (size_t)s * plane, z->d_ref + s);
+    HH_HIP(c, hipGetLastError());
+  }
+  z->ref.assign(n_segments, RefConsts{});
+  HH_HIP(c, hipMemcpyAsync(z->ref.data(), z->d_ref, (size_t)n_segments * sizeof(RefConsts), hipMemcpyDeviceToHost, c->stream));
+  HH_HIP(c, hipStreamSynchronize(c->stream));   // (images, mask, init and tiles are the caller's / locals)
+  z->tiles_v = tiles_v;
+  z->n_tiles = (int)tiles.size();
+  z->apix_ref = apix;
+  c->n_segments = n_segments;
+  c->log_flag = log_flag ? 1 : 0;
+  return HH_OK;
+}
+
+template <int LOG, bool LDSP>
+int launch_zoom(hh_ctx* c, const ZoomSweepArgs& a, int batch) {
+  if (int rc = ensure_lds_attr(c, reinterpret_cast<const void*>(&k_zoom_sweep<LOG, LDSP>), (int)sizeof(ZoomLds))) return rc;
+  hipLaunchKernelGGL((k_zoom_sweep<LOG, LDSP>), dim3(c->zoom->n_tiles, batch), dim3(ZS_THREADS), sizeof(ZoomLds), c->stream, a);
+  HH_HIP(c, hipGetLastError());
+  return HH_OK;
+}
+
+// Every hh_sweep* entry point with a zoom set.  ld: row stride of d_scores (0: n_cand).
+int zoom_sweep(hh_ctx* c, const double* d_params, int64_t n_cand, float* d_scores, int64_t ld) {
+  hh_zoom* z = c->zoom;
+  const int64_t stride = ld > 0 ? ld : n_cand;
+  const int S = c->n_segments, npart = z->n_tiles;
+  const int64_t cap = std::min<int64_t>(n_cand, ZS_BATCH);
+  if (int rc = ensure_bytes(c, (void**)&z->d_partials, &z->cap_partials, (size_t)S * cap * npart * 3 * sizeof(double))) return rc;
+  const bool ldsp = 2 * c->geom.rpx + 1 <= ZS_TAPS;
+  c->last_first_pass = 3;
+  for (int64_t b0 = 0; b0 < n_cand; b0 += cap) {
+    const int nb = (int)std::min<int64_t>(cap, n_cand - b0);
+    ZoomSweepArgs a{};
+    a.params = d_params + 4 * b0;
+    a.units = c->d_units;
+    a.w = z->d_w;
+    a.wec = z->d_wec;
+    a.tiles = z->d_tiles;
+    a.partials = z->d_partials;
+    a.g = c->geom;
+    a.d = ZoomDims{c->ny, c->nx, z->ony, z->onx, 2 * z->apix_ref / z->cutoff_y, 2 * z->apix_ref / z->cutoff_x};
+    a.apix = z->apix_ref;
+    a.cutoff_y = z->cutoff_y;
+    a.cutoff_x = z->cutoff_x;
+    a.tiles_v = z->tiles_v;
+    a.n_seg = S;
+    int rc;
+    if (c->log_flag) rc = ldsp ? launch_zoom<1, true>(c, a, nb) : launch_zoom<1, false>(c, a, nb);
+    else rc = ldsp ? launch_zoom<0, true>(c, a, nb) : launch_zoom<0, false>(c, a, nb);
+    if (rc) return rc;
+    for (int s = 0; s < S; ++s) {
+      hipLaunchKernelGGL(k_finalize, dim3(std::min(1024, (nb + 3) / 4)), dim3(256), 0, c->stream,
+                         z->d_partials + (size_t)s * nb * npart * 3, npart, (int64_t)nb, z->ref[s], d_scores + (size_t)s * stride + b0);
+      HH_HIP(c, hipGetLastError());
+    }
+  }
+  return HH_OK;
+}
+
+}  // namespace
+
+extern "C" int hh_set_spectrum_zoom(hh_ctx* c, int ony, int onx, double cutoff_y, double cutoff_x) try {
+  if (!c) return HH_ERR_ARG;
+  if (ony == 0 && onx == 0 && cutoff_y == 0.0 && cutoff_x == 0.0) {   // back to the default sampling
+    if (zoom_on(c)) {
+      c->zoom->on = false;
+      c->n_segments = 0;   // the reference was prepared for the zoomed plane: hh_set_reference comes next
+    }
+    return HH_OK;
+  }
+  if (ony < 8 || onx < 8 || ony > 1024 || onx > 1024)
+    return fail(c, HH_ERR_ARG, "hh_set_spectrum_zoom: the spectrum's sides must lie in [8, 1024]");
+  if (!(cutoff_y > 0) || !(cutoff_x > 0) || !std::isfinite(cutoff_y) || !std::isfinite(cutoff_x))
+    return fail(c, HH_ERR_ARG, "hh_set_spectrum_zoom: the cutoff resolutions must be positive and finite");
+  if (!c->zoom) c->zoom = new hh_zoom();
+  hh_zoom* z = c->zoom;
+  z->on = true;
+  z->ony = ony;
+  z->onx = onx;
+  z->cutoff_y = cutoff_y;
+  z->cutoff_x = cutoff_x;
+  c->n_segments = 0;   // any earlier reference belongs to another sampling
+  return HH_OK;
+} HH_CATCH_CTX(c, "hh_set_spectrum_zoom")

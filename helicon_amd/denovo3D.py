@@ -24,7 +24,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib
-from .grid import CandidateGrid, build_grid, radial_band_mask, set_to_periodic_range
+from .grid import CandidateGrid, build_grid, radial_band_mask, set_to_periodic_range, zoom_spec
 
 __all__ = [
     "SweepEngine",
@@ -116,6 +116,8 @@ class SweepEngine:
         self.n_segments = 0
         self._geom_key = None
         self._ref_key = None
+        self._apix = None
+        self._zoom = None          # (ony, onx, cutoff_y, cutoff_x) while the engine scores on zoomed spectra
 
     @contextlib.contextmanager
     def session(self):
@@ -178,6 +180,36 @@ class SweepEngine:
             self._geom_key = None
             self._check(self._L.hh_set_geometry(self._ctx, C.byref(g)))
             self._geom_key = key
+            if self._zoom is not None and self._apix != float(apix):   # the library dropped the zoomed reference
+                self.n_segments, self._ref_key = 0, None
+            self._apix = float(apix)
+
+    @property
+    def spectrum_shape(self) -> tuple[int, int]:
+        """Shape of the plane the mask lives on: the zoomed spectrum's with a zoom set, else the image's."""
+        return (self._zoom[0], self._zoom[1]) if self._zoom is not None else (self.ny, self.nx)
+
+    def set_zoom(self, cutoff_res=None, output_size=None):
+        """Score on the Fourier-zoomed spectrum ``compute_power_spectra(img, apix, cutoff_res, output_size)`` instead of
+        the default sampling (``hh_set_spectrum_zoom``); call it after ``set_geometry`` (the pixel size decides what the
+        arguments mean) and before ``set_reference``, whose mask then has the shape ``output_size``.  Arguments that
+        describe the default sampling (``grid.zoom_spec`` returns ``None``) clear a zoom and otherwise change nothing.
+        A change of sampling drops the reference.  The zoom belongs to the engine, so ``ShardedSweep`` and every
+        ``sweep_device`` caller score on it without further arguments."""
+        with self._lock:
+            if cutoff_res is None and output_size is None and self._zoom is None:
+                return
+            if self._apix is None:
+                raise RuntimeError("set_geometry comes first: the pixel size decides what cutoff_res means")
+            spec = zoom_spec((self.ny, self.nx), self._apix, cutoff_res, output_size)
+            if spec == self._zoom:
+                return
+            if spec is None:
+                self._check(self._L.hh_set_spectrum_zoom(self._ctx, 0, 0, 0.0, 0.0))
+            else:
+                self._check(self._L.hh_set_spectrum_zoom(self._ctx, spec[0], spec[1], spec[2], spec[3]))
+            self._zoom = spec
+            self.n_segments, self._ref_key = 0, None
 
     def set_reference(self, images, mask=None, log=True, key=None):
         """``key``: an optional hashable identity of (images, mask, log); when it equals the key of the
@@ -191,11 +223,13 @@ class SweepEngine:
             imgs = imgs[None]
         if imgs.ndim != 3 or imgs.shape[1:] != (self.ny, self.nx):
             raise ValueError(f"images must be [S, {self.ny}, {self.nx}], got {imgs.shape}")
+        my, mx = self.spectrum_shape
         if mask is None:
-            mask = radial_band_mask(self.ny, self.nx)
+            mask = radial_band_mask(my, mx)
         m = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8)
-        if m.shape != (self.ny, self.nx):
-            raise ValueError(f"mask must be [{self.ny}, {self.nx}] on the fftshifted plane")
+        if m.shape != (my, mx):
+            raise ValueError(f"mask must be [{my}, {mx}] on the fftshifted plane" +
+                             (" of the zoomed spectrum (output_size)" if self._zoom is not None else ""))
         with self._lock:
             try:
                 self._check(self._L.hh_set_reference(self._ctx, _ptr(imgs, C.c_float), imgs.shape[0],
@@ -292,8 +326,9 @@ class SweepEngine:
     @property
     def last_first_pass(self) -> str:
         """Pipeline of the last sweep: "transform" (raster + column transform per candidate),
-        "run_tables" (shared-twist tables + second pass) or "fused" (shared-twist, no intermediate)."""
-        return {1: "run_tables", 2: "fused"}.get(self._L.hh_last_first_pass(self._ctx), "transform")
+        "run_tables" (shared-twist tables + second pass), "fused" (shared-twist, no intermediate) or "zoom"
+        (Fourier-zoomed spectra, ``set_zoom``)."""
+        return {1: "run_tables", 2: "fused", 3: "zoom"}.get(self._L.hh_last_first_pass(self._ctx), "transform")
 
     def synchronize(self):
         with self._lock:
@@ -855,9 +890,15 @@ def finish_sweep(scores: np.ndarray, grid: CandidateGrid) -> SweepResult:
 
 
 def sweep(images, twists, rises, csyms=(1,), *, apix, helical_diameter, ball_radius, mask=None, log=True,
-          rot=0.0, tilt=0.0, psi=0.0, dy=0.0, device=0, engine: SweepEngine | None = None) -> SweepResult:
+          rot=0.0, tilt=0.0, psi=0.0, dy=0.0, device=0, engine: SweepEngine | None = None,
+          cutoff_res=None, output_size=None) -> SweepResult:
     """Score every (csym, twist, rise) candidate against the experimental image(s) on one GPU.
-    For several GPUs see ``helicon_amd.distributed.sweep_distributed``."""
+    For several GPUs see ``helicon_amd.distributed.sweep_distributed``.
+
+    ``cutoff_res`` (Angstrom, (y, x)) / ``output_size`` ((ony, onx)): score on the Fourier-zoomed spectrum
+    ``compute_power_spectra(img, apix, cutoff_res, output_size)`` of the image and of every candidate; the mask (default
+    ``radial_band_mask(ony, onx)``) then lives on that plane.  Arguments that describe the default sampling
+    (``grid.zoom_spec``) leave the sweep exactly as it is without them."""
     imgs = np.asarray(images)
     ny, nx = _image_shape(*imgs.shape[-2:])
     eng = engine or _engine((ny, nx), device)
@@ -869,8 +910,13 @@ def sweep(images, twists, rises, csyms=(1,), *, apix, helical_diameter, ball_rad
     with eng.session():
         eng.set_geometry(apix=apix, helical_diameter=helical_diameter, ball_radius=ball_radius,
                          tilt=tilt, psi=psi, dy=dy)
-        eng.set_reference(imgs, mask, log=log)
-        scores = eng.sweep(params)
+        eng.set_zoom(cutoff_res, output_size)
+        try:
+            eng.set_reference(imgs, mask, log=log)
+            scores = eng.sweep(params)
+        finally:
+            if engine is None:   # the module's shared engines serve other callers too: they keep the default sampling
+                eng.set_zoom()
     return finish_sweep(scores, grid)
 
 

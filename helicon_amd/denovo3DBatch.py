@@ -8,11 +8,18 @@ descending, app.py:2521-2523) this driver reproduces without the Shiny UI.
 
     python -m helicon_amd.denovo3DBatch image.npy --apix 2.0 --twist 25 33 0.2 --rise 8 13 0.2 \\
            --csym 1 --out scores.npz [--mask mask.npy] [--no-log] [--device 0] [--top 10] \
+           [--cutoff-res 10 10 --spectrum-size 256 256] \
            [--rescore 20 --tube-diameter 120 --interpolation linear]
 
 ``--rescore K`` runs the reference's own scorer — the sparse least-squares reconstruction of pipeline.py:84-496,
 ``process_one_task(..., algorithm={"scorer": "lsq"})`` — on the sweep's K best candidates of every image, from a
 thread pool like the app's (app.py:2473-2476), and reports them in the order of that score.
+
+``--cutoff-res Y X`` (Angstrom) and ``--spectrum-size NY NX`` score on the Fourier-zoomed power spectrum
+``compute_power_spectra(image, apix, cutoff_res=(Y, X), output_size=(NY, NX))`` (transforms.py:663-713, 771-820) of the
+image and of every candidate: the spectrum stops at that resolution instead of Nyquist and NY x NX samples cover it.  A
+``--mask`` file then has the shape NY x NX.  Either flag may be given alone (the other keeps its default: Nyquist, the
+image's shape).
 
 ``--from-map TWIST RISE CSYM`` reads ``image`` as a 3-D map instead (``.mrc`` / ``.map`` / ``.npy``, ``--apix`` its voxel
 size) and builds the input image as the app does for a map (app.py:1780-1829): the map is symmetrised with the given
@@ -36,7 +43,7 @@ import sys
 import numpy as np
 
 from .denovo3D import sweep
-from .grid import sweep_axis
+from .grid import sweep_axis, zoom_spec
 
 
 def add_args(parser: argparse.ArgumentParser) -> argparse.ArgumentParser:
@@ -54,6 +61,10 @@ def add_args(parser: argparse.ArgumentParser) -> argparse.ArgumentParser:
     parser.add_argument("--dy", type=float, default=0.0)
     parser.add_argument("--mask", default=None, help=".npy boolean mask on the fftshifted plane (default: radial band)")
     parser.add_argument("--no-log", action="store_true", help="correlate |F| instead of log1p|F|")
+    parser.add_argument("--cutoff-res", type=float, nargs=2, metavar=("Y", "X"), default=None,
+                        help="score on spectra that stop at this resolution (Angstrom) instead of Nyquist (compute_power_spectra's cutoff_res)")
+    parser.add_argument("--spectrum-size", type=int, nargs=2, metavar=("NY", "NX"), default=None,
+                        help="samples of the scored spectrum (compute_power_spectra's output_size; default: the image's shape)")
     parser.add_argument("--device", type=int, default=0)
     parser.add_argument("--top", type=int, default=10, help="how many best candidates to print per image")
     parser.add_argument("--out", default=None, help=".npz with scores[S, C, T, R], twists, rises, csyms")
@@ -202,13 +213,27 @@ def run(args) -> dict:
     twists = sweep_axis(*args.twist)
     rises = sweep_axis(*args.rise)
     mask = np.load(args.mask) if args.mask else None
+    cutoff_res = tuple(args.cutoff_res) if getattr(args, "cutoff_res", None) else None
+    spectrum_size = tuple(args.spectrum_size) if getattr(args, "spectrum_size", None) else None
+    try:
+        zoom = zoom_spec(images.shape[-2:], args.apix, cutoff_res, spectrum_size)
+    except ValueError as e:
+        raise SystemExit(f"--cutoff-res / --spectrum-size: {e}")
+    plane = (zoom[0], zoom[1]) if zoom else tuple(int(v) for v in images.shape[-2:])
+    if mask is not None and tuple(mask.shape) != plane:
+        raise SystemExit(f"--mask {args.mask} has shape {tuple(mask.shape)}; the scored spectrum is {plane[0]} x {plane[1]}" +
+                         (" (--spectrum-size / --cutoff-res)" if zoom else " (the image's shape)"))
     res = sweep(
         images, twists, rises, tuple(args.csym), apix=args.apix,
         helical_diameter=args.helical_diameter if args.helical_diameter is not None else 0.4 * n * args.apix,
         ball_radius=args.ball_radius if args.ball_radius is not None else 2.0 * args.apix,
         mask=mask, log=not args.no_log, rot=args.rot, tilt=args.tilt, psi=args.psi, dy=args.dy, device=args.device,
+        cutoff_res=cutoff_res, output_size=spectrum_size,
     )
     report = {"n_candidates": int(len(res.grid)), "n_skipped": int((~res.grid.valid).sum()), "images": []}
+    # the sampling that was scored (the defaults written out: Nyquist, the image's shape)
+    report["cutoff_res"] = [float(zoom[2]), float(zoom[3])] if zoom else [2.0 * args.apix, 2.0 * args.apix]
+    report["spectrum_size"] = [int(plane[0]), int(plane[1])]
     if map_info is not None:
         report["map"] = map_info
     flat = res.scores.reshape(res.scores.shape[0], -1)
@@ -240,7 +265,8 @@ def run(args) -> dict:
                                                 np.nan if r["lsq_score"] is None else r["lsq_score"]]
                                                for r in im.get("rescored", [])] for im in report["images"]], dtype=np.float64))
         np.savez_compressed(args.out, scores=res.scores, twists=twists, rises=rises, csyms=np.asarray(args.csym),
-                            params=res.grid.params, valid=res.grid.valid, **extra)
+                            params=res.grid.params, valid=res.grid.valid, cutoff_res=np.asarray(report["cutoff_res"]),
+                            spectrum_size=np.asarray(report["spectrum_size"]), **extra)
     return report
 
 

@@ -22,6 +22,7 @@ __all__ = [
     "radial_band_mask",
     "layer_line_mask",
     "shard_bounds",
+    "zoom_spec",
 ]
 
 
@@ -118,3 +119,41 @@ def shard_bounds(n_items: int, rank: int, world: int, align: int = 1) -> tuple[i
     lo = min(n_items, rank * per)
     hi = min(n_items, lo + per)
     return lo, hi, per
+
+
+_ZOOM_MIN_SIDE, _ZOOM_MAX_SIDE = 8, 1024
+
+
+def zoom_spec(shape, apix, cutoff_res=None, output_size=None):
+    """The Fourier sampling that ``compute_power_spectra(img, apix, cutoff_res, output_size)`` asks of the sweep
+    (transforms.py:663-713): ``None`` for the default sampling, ``(ony, onx, cutoff_y, cutoff_x)`` for a zoom.
+
+    The default sampling is ``cutoff_res`` ``None`` or ``(2 apix, 2 apix)`` together with ``output_size`` ``None`` or the
+    image's own shape (on an odd side the reference's transform differs from the FFT by a phase only, and the sweep reads
+    amplitudes): such arguments take the sweep's standard pipelines unchanged.  ``ValueError`` on a spectrum side outside
+    [8, 1024] or a cutoff that is not a positive finite number."""
+    ny, nx = (int(v) for v in shape)
+    if not apix > 0:
+        raise ValueError(f"apix must be positive; got {apix}")
+    if cutoff_res is None:
+        cy = cx = 2.0 * float(apix)
+    else:
+        if np.size(cutoff_res) != 2:
+            raise ValueError(f"cutoff_res must be (cutoff_y, cutoff_x) in Angstrom; got {cutoff_res!r}")
+        cy, cx = (float(v) for v in cutoff_res)
+    if not (cy > 0 and cx > 0 and math.isfinite(cy) and math.isfinite(cx)):
+        raise ValueError(f"cutoff_res must be positive and finite; got ({cy}, {cx})")
+    if output_size is None:
+        ony, onx = ny, nx
+    else:
+        if np.size(output_size) != 2:
+            raise ValueError(f"output_size must be (ony, onx); got {output_size!r}")
+        oy, ox = output_size
+        if oy != int(oy) or ox != int(ox):
+            raise ValueError(f"output_size must be whole numbers; got {output_size!r}")
+        ony, onx = int(oy), int(ox)
+    if not (_ZOOM_MIN_SIDE <= ony <= _ZOOM_MAX_SIDE and _ZOOM_MIN_SIDE <= onx <= _ZOOM_MAX_SIDE):
+        raise ValueError(f"output_size must lie in [{_ZOOM_MIN_SIDE}, {_ZOOM_MAX_SIDE}] per side; got ({ony}, {onx})")
+    if (cy, cx) == (2.0 * float(apix), 2.0 * float(apix)) and (ony, onx) == (ny, nx):
+        return None
+    return ony, onx, cy, cx

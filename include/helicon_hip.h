@@ -146,6 +146,16 @@ int hh_use_own_stream(hh_ctx* ctx);
 
 int hh_set_geometry(hh_ctx* ctx, const hh_geom* geom);
 
+/* Score on Fourier-zoomed spectra: compute_power_spectra(..., cutoff_res = (cutoff_y, cutoff_x) Angstrom, output_size =
+ * (ony, onx)) of lib/transforms.py:663-713, 771-820 for the experimental image(s) and for every candidate of a sweep.
+ * Call it between hh_set_geometry and hh_set_reference: hh_set_reference then takes a mask of ony x onx bytes on the
+ * fftshifted zoomed plane (the images keep the context's ny x nx) and every hh_sweep* entry point scores on the zoomed
+ * spectrum (any candidate list, tilt / psi / dy included).  ony, onx in [8, 1024], cutoffs > 0; all four arguments zero
+ * return the context to the default sampling.  A call that changes the sampling drops the reference (the next sweep
+ * reports HH_ERR_STATE until hh_set_reference is called), and so does a later hh_set_geometry with another apix.  Bad
+ * arguments return HH_ERR_ARG and change nothing; nothing here touches the device. */
+int hh_set_spectrum_zoom(hh_ctx* ctx, int ony, int onx, double cutoff_y, double cutoff_x);
+
 /* Experimental image(s) and mask.  images: host, S x N x N float32; mask: host, N x N bytes on
  * the fftshifted plane (DC at [N/2][N/2]), non-zero = bin takes part in the correlation;
  * log_flag selects log1p(|F|) (transforms.py:807-810).  The library transforms the images on
@@ -181,7 +191,7 @@ int hh_sweep_device_strided(hh_ctx* ctx, const double* d_params, const double* h
                             float* d_scores, int64_t ld_scores);
 int hh_set_table_path(hh_ctx* ctx, int mode);
 /* Which pipeline the last sweep of this context ran: 0 = per-candidate raster + column transform +
- * second pass, 1 = run tables + second pass, 2 = fused. */
+ * second pass, 1 = run tables + second pass, 2 = fused, 3 = zoomed spectra (hh_set_spectrum_zoom). */
 int hh_last_first_pass(const hh_ctx* ctx);
 
 /* Pre-sweep image preparation on the device.
