@@ -2,7 +2,7 @@
 Python signatures.  Hand-written gfx950 kernels in ``csrc/``, reached through the C ABI of
 ``include/helicon_hip.h``; importing this package does not touch the GPU."""
 from .grid import (CandidateGrid, build_grid, layer_line_mask, radial_band_mask, set_to_periodic_range,
-                   shard_bounds, sweep_axis, zoom_spec)
+                   shard_bounds, sweep_axis, zoom_spec, filter_spec)
 from .denovo3D import (SweepEngine, SweepResult, apply_helical_symmetry, auto_horizontalize, compute_power_spectra,
                        cosine_similarity, cross_correlation_coefficient, down_scale,
                        estimate_helix_rotation_center_diameter, generate_xyz_projections, is_vertical, low_high_pass_filter,

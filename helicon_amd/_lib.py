@@ -79,6 +79,7 @@ EXPORTS = {
     "hh_use_own_stream": (C.c_int, [_ctx]),
     "hh_set_geometry": (C.c_int, [_ctx, C.POINTER(hh_geom)]),
     "hh_set_spectrum_zoom": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_double, C.c_double]),
+    "hh_set_spectrum_filter": (C.c_int, [_ctx, C.c_double, C.c_double]),
     "hh_set_reference": (C.c_int, [_ctx, _f32p, C.c_int, C.POINTER(C.c_uint8), C.c_int]),
     "hh_sweep": (C.c_int, [_ctx, _f64p, C.c_int64, _f32p]),
     "hh_sweep_device": (C.c_int, [_ctx, C.c_void_p, C.c_int64, C.c_void_p]),

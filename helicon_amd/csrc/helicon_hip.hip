@@ -2500,7 +2500,7 @@ struct hh_ctx {
   int* d_cgs = nullptr;          // fused pass: [max_batch][N/4]
   size_t cap_eg = 0, cap_cgs = 0;
   int cap_partials = 0;          // candidates per half of d_partials
-  int last_first_pass = 0;       // what the last sweep ran: 0 per-candidate transform, 1 run tables, 2 fused, 3 zoomed spectra
+  int last_first_pass = 0;       // what the last sweep ran: 0 per-candidate transform, 1 run tables, 2 fused, 3 zoomed spectra, 4 filtered spectra
   unsigned long long kb_mask = ~0ull;
   int s_pad = 0, b_pad = 0;
   float2* d_spec = nullptr;      // [N/2+1][N] scratch (grown for S segments)
@@ -2534,6 +2534,7 @@ bool zoom_on(const hh_ctx* c);
 void zoom_free(hh_ctx* c);
 int zoom_set_reference(hh_ctx* c, const float* images, int n_segments, const uint8_t* mask, int log_flag);
 int zoom_sweep(hh_ctx* c, const double* d_params, int64_t n_cand, float* d_scores, int64_t ld);
+int64_t zoom_filter_bytes(const hh_ctx* c);   // device bytes of the spectrum filter's buffers (hh_set_spectrum_filter)
 
 int fail(hh_ctx* c, int code, const std::string& msg) {
   if (c) c->err = msg; else g_create_error = msg;
@@ -3605,6 +3606,7 @@ int64_t hh_memory_bytes(const hh_ctx* c, int64_t out[5]) try {
                           (const void*)g->d_layers, (const void*)g->d_partials, (const void*)g->d_r, (const void*)g->d_f, (const void*)g->d_cent})
       part[4] += size_of(p);
   }
+  part[4] += zoom_filter_bytes(c);
   int64_t total = 0;
   for (int k = 0; k < 5; ++k) { total += part[k]; if (out) out[k] = part[k]; }
   return total;
@@ -4539,3 +4541,4 @@ int hh_profile_get(hh_ctx* c, hh_profile* out) try {
 #include "path_a_host.inc"  // Path A: host side and C ABI (hh_pa_*)
 #include "path_a_batch.inc"  // Path A for many candidates at once, device-resident solve (hh_pab_*)
 #include "map_filter.inc"  // the 3-D map input: separable Gaussian filter of a whole map on the f32 MFMA, axis projections
+#include "filtered_sweep.inc"  // the sweep on low / high-pass filtered spectra (hh_set_spectrum_filter): y pass + fused x pass / moments

@@ -10,6 +10,8 @@
 // the product on the exact-f32 MFMA (32x32x2, K staged through LDS: the layout of k_circ_gemm, four real products for
 // the complex one), and the epilogue |F| -> log1p -> masked moments fused, so F never leaves the registers.  The
 // reference side is k_zoom_rows / k_zoom_cols on the device plus k_zoom_weights ({w, w (E - Ebar)} per segment).
+// With a spectrum filter set (hh_set_spectrum_filter, at the end of this file) the kernel's other epilogue stores q instead
+// and filtered_sweep.inc takes it from there; without a zoom that runs at the identity zoom (the image's shape and Nyquist).
 //
 // The whole plane is computed: the zoomed grid is not closed under negation (row ony/2 and column onx/2 of an even side
 // have no Friedel partner on the grid), so there is no half-plane fold here; tiles without a masked bin are skipped.
@@ -33,6 +35,26 @@ struct hh_zoom {
   size_t cap_img = 0, cap_r = 0, cap_pwr = 0, cap_mm = 0, cap_mask = 0, cap_w = 0, cap_wec = 0, cap_ref = 0, cap_tiles = 0,
          cap_partials = 0;
   std::vector<RefConsts> ref;
+  // the view the reference was prepared on: the zoom's, or the identity zoom (the image's own shape and Nyquist) when only
+  // a spectrum filter is set
+  int r_ony = 0, r_onx = 0;
+  double r_cy = 0, r_cx = 0;
+  // the spectrum filter (hh_set_spectrum_filter; kernels and host side in filtered_sweep.inc)
+  bool f_on = false;
+  double f_lp = 0, f_hp = 0;      // fractions inside (0, 1), or 0 = that pass is off
+  bool f_ref = false;             // the reference was prepared with the filter
+  int f_terms = 0;                // separable terms J of the operator: L q = c0 q + sum_j Ay_j q Ax_j^T
+  float f_c0 = 0.f;
+  int f_tiles_v = 0, f_n_tiles = 0;
+  float* d_ay = nullptr;          // [J][ony][ony]
+  float* d_ax = nullptr;          // [J][onx][onx], the term's sign folded in
+  float* d_fq = nullptr;          // [B][ony][onx] q of one batch (also: the filtered spectrum of a reference image)
+  float* d_ft = nullptr;          // [J][B][ony][onx] y pass of one batch
+  int* d_tiles_all = nullptr;     // every tile of k_zoom_sweep (the filter needs the whole plane)
+  int* d_ftiles = nullptr;        // x-pass tiles with a masked bin; behind them, at f_all_off, every x-pass tile
+  int f_all_off = 0, f_all_tiles = 0;
+  double* d_fpart = nullptr;      // [S][B][f_n_tiles][3]
+  size_t cap_ay = 0, cap_ax = 0, cap_fq = 0, cap_ft = 0, cap_tiles_all = 0, cap_ftiles = 0, cap_fpart = 0;
 };
 
 namespace {
@@ -70,6 +92,7 @@ struct ZoomSweepArgs {
   ZoomDims d;
   double apix, cutoff_y, cutoff_x;
   int tiles_v, n_seg;
+  float* q_out;           // [batch][ony][onx]: the q-storing epilogue's plane (the filtered sweep), else unused
 };
 
 // One tap of a footprint's profile along one axis: 2^(-k2 ((p - half) apix - centre)^2), the raster's arithmetic.
@@ -109,7 +132,7 @@ __device__ __forceinline__ float2 zoom_factor(double f, float2 w, int p0, int le
   return make_float2(sr * cs - si * sn, sr * sn + si * cs);
 }
 
-template <int LOG, bool LDSP>
+template <int LOG, bool LDSP, bool QS>
 __global__ __launch_bounds__(ZS_THREADS) void k_zoom_sweep(ZoomSweepArgs a) {
   extern __shared__ __align__(16) unsigned char zoom_lds_raw[];
   ZoomLds& L = *reinterpret_cast<ZoomLds*>(zoom_lds_raw);
@@ -240,8 +263,20 @@ __global__ __launch_bounds__(ZS_THREADS) void k_zoom_sweep(ZoomSweepArgs a) {
     __syncthreads();
   }
 
-  // epilogue: q = log1p|F| (or |F|) and the three masked moments of this tile, per segment
   const size_t plane = (size_t)ony * onx;
+  if constexpr (QS) {   // the q-storing epilogue: the tile of q itself, for the filter passes (filtered_sweep.inc)
+    float* const qb = a.q_out + (size_t)b * plane;
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+      for (int i = 0; i < 16; ++i) {
+        const int u = u0 + wu * 32 + (i & 3) + 8 * (i >> 2) + 4 * h;
+        const int v = v0 + wv * 64 + t * 32 + r;
+        if (u < ony && v < onx) qb[(size_t)u * onx + v] = amp_to_q<LOG>(make_float2(acc_re[t][i], acc_im[t][i]));
+      }
+    return;
+  }
+  // epilogue: q = log1p|F| (or |F|) and the three masked moments of this tile, per segment
   for (int s = 0; s < a.n_seg; ++s) {
     const float* const wec = a.wec + (size_t)s * plane;
     float f1 = 0.f, f2 = 0.f, f3 = 0.f;
@@ -334,17 +369,39 @@ void zoom_free(hh_ctx* c) {
   if (!z) return;
   (void)hipFree(z->d_img); (void)hipFree(z->d_r); (void)hipFree(z->d_pwr); (void)hipFree(z->d_mm); (void)hipFree(z->d_mask);
   (void)hipFree(z->d_w); (void)hipFree(z->d_wec); (void)hipFree(z->d_ref); (void)hipFree(z->d_tiles); (void)hipFree(z->d_partials);
+  (void)hipFree(z->d_ay); (void)hipFree(z->d_ax); (void)hipFree(z->d_fq); (void)hipFree(z->d_ft); (void)hipFree(z->d_tiles_all);
+  (void)hipFree(z->d_ftiles); (void)hipFree(z->d_fpart);
   delete z;
   c->zoom = nullptr;
 }
 
-bool zoom_on(const hh_ctx* c) { return c->zoom && c->zoom->on; }
+// true when the sweep scores through the product kernel: a zoom, or a spectrum filter (then at the identity zoom)
+bool zoom_on(const hh_ctx* c) { return c->zoom && (c->zoom->on || c->zoom->f_on); }
+
+int64_t zoom_filter_bytes(const hh_ctx* c) {
+  const hh_zoom* z = c->zoom;
+  if (!z) return 0;
+  int64_t total = 0;
+  for (const void* p : {(const void*)z->d_ay, (const void*)z->d_ax, (const void*)z->d_fq, (const void*)z->d_ft, (const void*)z->d_tiles_all,
+                        (const void*)z->d_ftiles, (const void*)z->d_fpart}) {
+    size_t n = 0;
+    if (p && hipMemPtrGetInfo(const_cast<void*>(p), &n) == hipSuccess) total += (int64_t)n;
+  }
+  return total;
+}
+
+// filtered_sweep.inc
+int filt_prepare(hh_ctx* c, const uint8_t* mask);
+int filt_reference_plane(hh_ctx* c, const float** pwr);
+int filt_sweep(hh_ctx* c, const double* d_params, int64_t n_cand, float* d_scores, int64_t ld);
 
 // hh_set_reference with a zoom set: images [S][ny][nx] (host), mask [ony][onx] bytes on the fftshifted zoomed plane.
 int zoom_set_reference(hh_ctx* c, const float* images, int n_segments, const uint8_t* mask, int log_flag) {
   hh_zoom* z = c->zoom;
   if (!c->have_geom) return fail(c, HH_ERR_STATE, "hh_set_reference: a spectrum zoom needs the pixel size; call hh_set_geometry first");
-  const int ny = c->ny, nx = c->nx, ony = z->ony, onx = z->onx;
+  const double apix = c->apix;
+  const int ny = c->ny, nx = c->nx, ony = z->on ? z->ony : ny, onx = z->on ? z->onx : nx;
+  const double cutoff_y = z->on ? z->cutoff_y : 2 * apix, cutoff_x = z->on ? z->cutoff_x : 2 * apix;
   const size_t plane = (size_t)ony * onx, npix = (size_t)ny * nx;
   // active tiles, from the mask alone (unshifted index u sits at fftshifted row (u + ony/2) mod ony)
   const int tiles_u = (ony + ZS_TU - 1) / ZS_TU, tiles_v = (onx + ZS_TV - 1) / ZS_TV;
@@ -369,19 +426,26 @@ int zoom_set_reference(hh_ctx* c, const float* images, int n_segments, const uin
   if ((rc = ensure_bytes(c, (void**)&z->d_wec, &z->cap_wec, (size_t)n_segments * plane * sizeof(float)))) return rc;
   if ((rc = ensure_bytes(c, (void**)&z->d_ref, &z->cap_ref, (size_t)n_segments * sizeof(RefConsts)))) return rc;
   if ((rc = ensure_bytes(c, (void**)&z->d_tiles, &z->cap_tiles, (size_t)tiles_u * tiles_v * sizeof(int)))) return rc;
+  z->r_ony = ony;
+  z->r_onx = onx;
+  z->r_cy = cutoff_y;
+  z->r_cx = cutoff_x;
+  z->f_ref = false;
+  if (z->f_on && (rc = filt_prepare(c, mask))) return rc;
   const unsigned init[2] = {0x7f800000u, 0u};
   HH_HIP(c, hipMemcpyAsync(z->d_img, images, (size_t)n_segments * npix * sizeof(float), hipMemcpyHostToDevice, c->stream));
   HH_HIP(c, hipMemcpyAsync(z->d_mask, mask, plane, hipMemcpyHostToDevice, c->stream));
   HH_HIP(c, hipMemcpyAsync(z->d_mm, init, sizeof(init), hipMemcpyHostToDevice, c->stream));
   HH_HIP(c, hipMemcpyAsync(z->d_tiles, tiles.data(), tiles.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
-  const double apix = c->apix;
-  const ZoomDims d{ny, nx, ony, onx, 2 * apix / z->cutoff_y, 2 * apix / z->cutoff_x};
+  const ZoomDims d{ny, nx, ony, onx, 2 * apix / cutoff_y, 2 * apix / cutoff_x};
   for (int s = 0; s < n_segments; ++s) {
     hipLaunchKernelGGL(k_zoom_rows, dim3((onx + 127) / 128, ny), dim3(128), 0, c->stream, z->d_img + (size_t)s * npix, d, apix,
-                       z->cutoff_x, z->d_r);
-    hipLaunchKernelGGL(k_zoom_cols, dim3((onx + 127) / 128, ony), dim3(128), 0, c->stream, z->d_r, d, apix, z->cutoff_y,
+                       cutoff_x, z->d_r);
+    hipLaunchKernelGGL(k_zoom_cols, dim3((onx + 127) / 128, ony), dim3(128), 0, c->stream, z->d_r, d, apix, cutoff_y,
                        log_flag ? 1 : 0, z->d_pwr, (float*)nullptr, z->d_mm);
-    hipLaunchKernelGGL(k_zoom_weights, dim3(1), dim3(1024), 0, c->stream, z->d_pwr, z->d_mask, ony, onx, z->d_w,
+    const float* pwr = z->d_pwr;
+    if (z->f_on && (rc = filt_reference_plane(c, &pwr))) return rc;   // the same filter as every candidate's spectrum
+    hipLaunchKernelGGL(k_zoom_weights, dim3(1), dim3(1024), 0, c->stream, pwr, z->d_mask, ony, onx, z->d_w,
                        z->d_wec + (size_t)s * plane, z->d_ref + s);
     HH_HIP(c, hipGetLastError());
   }
@@ -391,48 +455,60 @@ int zoom_set_reference(hh_ctx* c, const float* images, int n_segments, const uin
   z->tiles_v = tiles_v;
   z->n_tiles = (int)tiles.size();
   z->apix_ref = apix;
+  z->f_ref = z->f_on;
   c->n_segments = n_segments;
   c->log_flag = log_flag ? 1 : 0;
   return HH_OK;
 }
 
-template <int LOG, bool LDSP>
-int launch_zoom(hh_ctx* c, const ZoomSweepArgs& a, int batch) {
-  if (int rc = ensure_lds_attr(c, reinterpret_cast<const void*>(&k_zoom_sweep<LOG, LDSP>), (int)sizeof(ZoomLds))) return rc;
-  hipLaunchKernelGGL((k_zoom_sweep<LOG, LDSP>), dim3(c->zoom->n_tiles, batch), dim3(ZS_THREADS), sizeof(ZoomLds), c->stream, a);
+template <int LOG, bool LDSP, bool QS>
+int launch_zoom(hh_ctx* c, const ZoomSweepArgs& a, int n_tiles, int batch) {
+  if (int rc = ensure_lds_attr(c, reinterpret_cast<const void*>(&k_zoom_sweep<LOG, LDSP, QS>), (int)sizeof(ZoomLds))) return rc;
+  hipLaunchKernelGGL((k_zoom_sweep<LOG, LDSP, QS>), dim3(n_tiles, batch), dim3(ZS_THREADS), sizeof(ZoomLds), c->stream, a);
   HH_HIP(c, hipGetLastError());
   return HH_OK;
+}
+
+template <bool QS>
+int launch_zoom_any(hh_ctx* c, const ZoomSweepArgs& a, int n_tiles, int batch) {
+  const bool ldsp = 2 * c->geom.rpx + 1 <= ZS_TAPS;
+  if (c->log_flag) return ldsp ? launch_zoom<1, true, QS>(c, a, n_tiles, batch) : launch_zoom<1, false, QS>(c, a, n_tiles, batch);
+  return ldsp ? launch_zoom<0, true, QS>(c, a, n_tiles, batch) : launch_zoom<0, false, QS>(c, a, n_tiles, batch);
+}
+
+// the arguments every launch of k_zoom_sweep shares (params, tiles, partials / q_out: the caller's)
+ZoomSweepArgs zoom_args(const hh_ctx* c) {
+  const hh_zoom* z = c->zoom;
+  ZoomSweepArgs a{};
+  a.units = c->d_units;
+  a.w = z->d_w;
+  a.wec = z->d_wec;
+  a.g = c->geom;
+  a.d = ZoomDims{c->ny, c->nx, z->r_ony, z->r_onx, 2 * z->apix_ref / z->r_cy, 2 * z->apix_ref / z->r_cx};
+  a.apix = z->apix_ref;
+  a.cutoff_y = z->r_cy;
+  a.cutoff_x = z->r_cx;
+  a.tiles_v = z->tiles_v;
+  a.n_seg = c->n_segments;
+  return a;
 }
 
 // Every hh_sweep* entry point with a zoom set.  ld: row stride of d_scores (0: n_cand).
 int zoom_sweep(hh_ctx* c, const double* d_params, int64_t n_cand, float* d_scores, int64_t ld) {
   hh_zoom* z = c->zoom;
+  if (z->f_ref) return filt_sweep(c, d_params, n_cand, d_scores, ld);
   const int64_t stride = ld > 0 ? ld : n_cand;
   const int S = c->n_segments, npart = z->n_tiles;
   const int64_t cap = std::min<int64_t>(n_cand, ZS_BATCH);
   if (int rc = ensure_bytes(c, (void**)&z->d_partials, &z->cap_partials, (size_t)S * cap * npart * 3 * sizeof(double))) return rc;
-  const bool ldsp = 2 * c->geom.rpx + 1 <= ZS_TAPS;
   c->last_first_pass = 3;
   for (int64_t b0 = 0; b0 < n_cand; b0 += cap) {
     const int nb = (int)std::min<int64_t>(cap, n_cand - b0);
-    ZoomSweepArgs a{};
+    ZoomSweepArgs a = zoom_args(c);
     a.params = d_params + 4 * b0;
-    a.units = c->d_units;
-    a.w = z->d_w;
-    a.wec = z->d_wec;
     a.tiles = z->d_tiles;
     a.partials = z->d_partials;
-    a.g = c->geom;
-    a.d = ZoomDims{c->ny, c->nx, z->ony, z->onx, 2 * z->apix_ref / z->cutoff_y, 2 * z->apix_ref / z->cutoff_x};
-    a.apix = z->apix_ref;
-    a.cutoff_y = z->cutoff_y;
-    a.cutoff_x = z->cutoff_x;
-    a.tiles_v = z->tiles_v;
-    a.n_seg = S;
-    int rc;
-    if (c->log_flag) rc = ldsp ? launch_zoom<1, true>(c, a, nb) : launch_zoom<1, false>(c, a, nb);
-    else rc = ldsp ? launch_zoom<0, true>(c, a, nb) : launch_zoom<0, false>(c, a, nb);
-    if (rc) return rc;
+    if (int rc = launch_zoom_any<false>(c, a, npart, nb)) return rc;
     for (int s = 0; s < S; ++s) {
       hipLaunchKernelGGL(k_finalize, dim3(std::min(1024, (nb + 3) / 4)), dim3(256), 0, c->stream,
                          z->d_partials + (size_t)s * nb * npart * 3, npart, (int64_t)nb, z->ref[s], d_scores + (size_t)s * stride + b0);
@@ -447,7 +523,7 @@ int zoom_sweep(hh_ctx* c, const double* d_params, int64_t n_cand, float* d_score
 extern "C" int hh_set_spectrum_zoom(hh_ctx* c, int ony, int onx, double cutoff_y, double cutoff_x) try {
   if (!c) return HH_ERR_ARG;
   if (ony == 0 && onx == 0 && cutoff_y == 0.0 && cutoff_x == 0.0) {   // back to the default sampling
-    if (zoom_on(c)) {
+    if (c->zoom && c->zoom->on) {
       c->zoom->on = false;
       c->n_segments = 0;   // the reference was prepared for the zoomed plane: hh_set_reference comes next
     }
@@ -467,3 +543,23 @@ extern "C" int hh_set_spectrum_zoom(hh_ctx* c, int ony, int onx, double cutoff_y
   c->n_segments = 0;   // any earlier reference belongs to another sampling
   return HH_OK;
 } HH_CATCH_CTX(c, "hh_set_spectrum_zoom")
+
+extern "C" int hh_set_spectrum_filter(hh_ctx* c, double low_pass_fraction, double high_pass_fraction) try {
+  if (!c) return HH_ERR_ARG;
+  if (std::isnan(low_pass_fraction) || std::isnan(high_pass_fraction))
+    return fail(c, HH_ERR_ARG, "hh_set_spectrum_filter: a fraction is NaN");
+  // filters.py:363-370: a fraction outside (0, 1) is ignored
+  const double lp = low_pass_fraction > 0 && low_pass_fraction < 1 ? low_pass_fraction : 0.0;
+  const double hp = high_pass_fraction > 0 && high_pass_fraction < 1 ? high_pass_fraction : 0.0;
+  if (!c->zoom) {
+    if (lp == 0.0 && hp == 0.0) return HH_OK;
+    c->zoom = new hh_zoom();
+  }
+  hh_zoom* z = c->zoom;
+  if (lp == z->f_lp && hp == z->f_hp) return HH_OK;
+  z->f_lp = lp;
+  z->f_hp = hp;
+  z->f_on = lp != 0.0 || hp != 0.0;
+  c->n_segments = 0;   // the reference was prepared for another filter: hh_set_reference comes next
+  return HH_OK;
+} HH_CATCH_CTX(c, "hh_set_spectrum_filter")

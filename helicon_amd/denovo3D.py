@@ -24,7 +24,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib
-from .grid import CandidateGrid, build_grid, radial_band_mask, set_to_periodic_range, zoom_spec
+from .grid import CandidateGrid, build_grid, filter_spec, radial_band_mask, set_to_periodic_range, zoom_spec
 
 __all__ = [
     "SweepEngine",
@@ -118,6 +118,7 @@ class SweepEngine:
         self._ref_key = None
         self._apix = None
         self._zoom = None          # (ony, onx, cutoff_y, cutoff_x) while the engine scores on zoomed spectra
+        self._filter = None        # (low_pass_fraction, high_pass_fraction) while the engine scores on filtered spectra
 
     @contextlib.contextmanager
     def session(self):
@@ -180,7 +181,7 @@ class SweepEngine:
             self._geom_key = None
             self._check(self._L.hh_set_geometry(self._ctx, C.byref(g)))
             self._geom_key = key
-            if self._zoom is not None and self._apix != float(apix):   # the library dropped the zoomed reference
+            if (self._zoom is not None or self._filter is not None) and self._apix != float(apix):   # the library dropped the reference
                 self.n_segments, self._ref_key = 0, None
             self._apix = float(apix)
 
@@ -209,6 +210,21 @@ class SweepEngine:
             else:
                 self._check(self._L.hh_set_spectrum_zoom(self._ctx, spec[0], spec[1], spec[2], spec[3]))
             self._zoom = spec
+            self.n_segments, self._ref_key = 0, None
+
+    def set_filter(self, low_pass_fraction=0, high_pass_fraction=0):
+        """Score on the filtered spectrum ``compute_power_spectra(img, apix, ..., low_pass_fraction, high_pass_fraction)``:
+        ``low_high_pass_filter`` of the spectrum image of the experimental image(s) and of every candidate
+        (``hh_set_spectrum_filter``); call it before ``set_reference``.  A fraction outside (0, 1) is off
+        (``grid.filter_spec``); both off clear the filter and otherwise change nothing.  It combines with ``set_zoom``;
+        without a zoom the mask keeps the image's shape.  A change of filter drops the reference.  The filter belongs to
+        the engine, so ``ShardedSweep`` and every ``sweep_device`` caller score on it without further arguments."""
+        with self._lock:
+            spec = filter_spec(low_pass_fraction, high_pass_fraction)
+            if spec == self._filter:
+                return
+            self._check(self._L.hh_set_spectrum_filter(self._ctx, *(spec or (0.0, 0.0))))
+            self._filter = spec
             self.n_segments, self._ref_key = 0, None
 
     def set_reference(self, images, mask=None, log=True, key=None):
@@ -326,9 +342,9 @@ class SweepEngine:
     @property
     def last_first_pass(self) -> str:
         """Pipeline of the last sweep: "transform" (raster + column transform per candidate),
-        "run_tables" (shared-twist tables + second pass), "fused" (shared-twist, no intermediate) or "zoom"
-        (Fourier-zoomed spectra, ``set_zoom``)."""
-        return {1: "run_tables", 2: "fused", 3: "zoom"}.get(self._L.hh_last_first_pass(self._ctx), "transform")
+        "run_tables" (shared-twist tables + second pass), "fused" (shared-twist, no intermediate), "zoom"
+        (Fourier-zoomed spectra, ``set_zoom``) or "filtered" (low / high-pass filtered spectra, ``set_filter``)."""
+        return {1: "run_tables", 2: "fused", 3: "zoom", 4: "filtered"}.get(self._L.hh_last_first_pass(self._ctx), "transform")
 
     def synchronize(self):
         with self._lock:
@@ -891,14 +907,19 @@ def finish_sweep(scores: np.ndarray, grid: CandidateGrid) -> SweepResult:
 
 def sweep(images, twists, rises, csyms=(1,), *, apix, helical_diameter, ball_radius, mask=None, log=True,
           rot=0.0, tilt=0.0, psi=0.0, dy=0.0, device=0, engine: SweepEngine | None = None,
-          cutoff_res=None, output_size=None) -> SweepResult:
+          cutoff_res=None, output_size=None, low_pass_fraction=0, high_pass_fraction=0) -> SweepResult:
     """Score every (csym, twist, rise) candidate against the experimental image(s) on one GPU.
     For several GPUs see ``helicon_amd.distributed.sweep_distributed``.
 
     ``cutoff_res`` (Angstrom, (y, x)) / ``output_size`` ((ony, onx)): score on the Fourier-zoomed spectrum
     ``compute_power_spectra(img, apix, cutoff_res, output_size)`` of the image and of every candidate; the mask (default
     ``radial_band_mask(ony, onx)``) then lives on that plane.  Arguments that describe the default sampling
-    (``grid.zoom_spec``) leave the sweep exactly as it is without them."""
+    (``grid.zoom_spec``) leave the sweep exactly as it is without them.
+
+    ``low_pass_fraction`` / ``high_pass_fraction``: score on ``compute_power_spectra(..., low_pass_fraction,
+    high_pass_fraction)``, the Gaussian low / high pass of the spectrum image (a high pass removes its smooth radial
+    fall-off, so the layer lines decide the score).  Fractions outside (0, 1) are off (``grid.filter_spec``) and leave the
+    sweep exactly as it is without them."""
     imgs = np.asarray(images)
     ny, nx = _image_shape(*imgs.shape[-2:])
     eng = engine or _engine((ny, nx), device)
@@ -911,12 +932,17 @@ def sweep(images, twists, rises, csyms=(1,), *, apix, helical_diameter, ball_rad
         eng.set_geometry(apix=apix, helical_diameter=helical_diameter, ball_radius=ball_radius,
                          tilt=tilt, psi=psi, dy=dy)
         eng.set_zoom(cutoff_res, output_size)
+        filt = filter_spec(low_pass_fraction, high_pass_fraction)
+        if filt is not None or getattr(eng, "_filter", None) is not None:   # (off and never set: the engine is not asked)
+            eng.set_filter(low_pass_fraction, high_pass_fraction)
         try:
             eng.set_reference(imgs, mask, log=log)
             scores = eng.sweep(params)
         finally:
             if engine is None:   # the module's shared engines serve other callers too: they keep the default sampling
                 eng.set_zoom()
+                if filt is not None:
+                    eng.set_filter()
     return finish_sweep(scores, grid)
 
 

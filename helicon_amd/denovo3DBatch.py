@@ -8,7 +8,7 @@ descending, app.py:2521-2523) this driver reproduces without the Shiny UI.
 
     python -m helicon_amd.denovo3DBatch image.npy --apix 2.0 --twist 25 33 0.2 --rise 8 13 0.2 \\
            --csym 1 --out scores.npz [--mask mask.npy] [--no-log] [--device 0] [--top 10] \
-           [--cutoff-res 10 10 --spectrum-size 256 256] \
+           [--cutoff-res 10 10 --spectrum-size 256 256] [--spectrum-high-pass 0.05] [--spectrum-low-pass 0.3] \
            [--rescore 20 --tube-diameter 120 --interpolation linear]
 
 ``--rescore K`` runs the reference's own scorer — the sparse least-squares reconstruction of pipeline.py:84-496,
@@ -20,6 +20,11 @@ thread pool like the app's (app.py:2473-2476), and reports them in the order of 
 image and of every candidate: the spectrum stops at that resolution instead of Nyquist and NY x NX samples cover it.  A
 ``--mask`` file then has the shape NY x NX.  Either flag may be given alone (the other keeps its default: Nyquist, the
 image's shape).
+
+``--spectrum-low-pass F`` / ``--spectrum-high-pass F`` score on the filtered spectrum ``compute_power_spectra(...,
+low_pass_fraction=F, high_pass_fraction=F)`` (transforms.py:811-816): the Gaussian low / high pass of the spectrum image, as
+fractions of its Nyquist radius; a high pass removes the spectrum's smooth radial fall-off.  A fraction outside (0, 1) is
+off.  They combine with the zoom flags and with ``--mask``, which keeps the shape of the scored spectrum.
 
 ``--from-map TWIST RISE CSYM`` reads ``image`` as a 3-D map instead (``.mrc`` / ``.map`` / ``.npy``, ``--apix`` its voxel
 size) and builds the input image as the app does for a map (app.py:1780-1829): the map is symmetrised with the given
@@ -43,7 +48,7 @@ import sys
 import numpy as np
 
 from .denovo3D import sweep
-from .grid import sweep_axis, zoom_spec
+from .grid import filter_spec, sweep_axis, zoom_spec
 
 
 def add_args(parser: argparse.ArgumentParser) -> argparse.ArgumentParser:
@@ -65,6 +70,10 @@ def add_args(parser: argparse.ArgumentParser) -> argparse.ArgumentParser:
                         help="score on spectra that stop at this resolution (Angstrom) instead of Nyquist (compute_power_spectra's cutoff_res)")
     parser.add_argument("--spectrum-size", type=int, nargs=2, metavar=("NY", "NX"), default=None,
                         help="samples of the scored spectrum (compute_power_spectra's output_size; default: the image's shape)")
+    parser.add_argument("--spectrum-low-pass", type=float, default=0.0, metavar="F",
+                        help="Gaussian low pass of the scored spectrum image (compute_power_spectra's low_pass_fraction; outside (0, 1): off)")
+    parser.add_argument("--spectrum-high-pass", type=float, default=0.0, metavar="F",
+                        help="Gaussian high pass of the scored spectrum image (compute_power_spectra's high_pass_fraction; outside (0, 1): off)")
     parser.add_argument("--device", type=int, default=0)
     parser.add_argument("--top", type=int, default=10, help="how many best candidates to print per image")
     parser.add_argument("--out", default=None, help=".npz with scores[S, C, T, R], twists, rises, csyms")
@@ -223,17 +232,23 @@ def run(args) -> dict:
     if mask is not None and tuple(mask.shape) != plane:
         raise SystemExit(f"--mask {args.mask} has shape {tuple(mask.shape)}; the scored spectrum is {plane[0]} x {plane[1]}" +
                          (" (--spectrum-size / --cutoff-res)" if zoom else " (the image's shape)"))
+    try:
+        filt = filter_spec(getattr(args, "spectrum_low_pass", 0.0), getattr(args, "spectrum_high_pass", 0.0))
+    except ValueError as e:
+        raise SystemExit(f"--spectrum-low-pass / --spectrum-high-pass: {e}")
+    filter_kw = dict(low_pass_fraction=filt[0], high_pass_fraction=filt[1]) if filt else {}   # off: sweep() is called as without the flags
     res = sweep(
         images, twists, rises, tuple(args.csym), apix=args.apix,
         helical_diameter=args.helical_diameter if args.helical_diameter is not None else 0.4 * n * args.apix,
         ball_radius=args.ball_radius if args.ball_radius is not None else 2.0 * args.apix,
         mask=mask, log=not args.no_log, rot=args.rot, tilt=args.tilt, psi=args.psi, dy=args.dy, device=args.device,
-        cutoff_res=cutoff_res, output_size=spectrum_size,
+        cutoff_res=cutoff_res, output_size=spectrum_size, **filter_kw,
     )
     report = {"n_candidates": int(len(res.grid)), "n_skipped": int((~res.grid.valid).sum()), "images": []}
     # the sampling that was scored (the defaults written out: Nyquist, the image's shape)
     report["cutoff_res"] = [float(zoom[2]), float(zoom[3])] if zoom else [2.0 * args.apix, 2.0 * args.apix]
     report["spectrum_size"] = [int(plane[0]), int(plane[1])]
+    report["spectrum_filter"] = [float(filt[0]), float(filt[1])] if filt else [0.0, 0.0]   # (low pass, high pass); 0 = off
     if map_info is not None:
         report["map"] = map_info
     flat = res.scores.reshape(res.scores.shape[0], -1)
@@ -266,7 +281,7 @@ def run(args) -> dict:
                                                for r in im.get("rescored", [])] for im in report["images"]], dtype=np.float64))
         np.savez_compressed(args.out, scores=res.scores, twists=twists, rises=rises, csyms=np.asarray(args.csym),
                             params=res.grid.params, valid=res.grid.valid, cutoff_res=np.asarray(report["cutoff_res"]),
-                            spectrum_size=np.asarray(report["spectrum_size"]), **extra)
+                            spectrum_size=np.asarray(report["spectrum_size"]), spectrum_filter=np.asarray(report["spectrum_filter"]), **extra)
     return report
 
 

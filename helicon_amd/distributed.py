@@ -82,7 +82,8 @@ class ShardedSweep:
     engine : a configured ``SweepEngine`` (geometry and reference set); its stream is bound to torch's
              current stream of the device so the collective is ordered behind the sweep without events.
              A Fourier zoom (``SweepEngine.set_zoom``) belongs to the engine, so a zoomed engine is sharded
-             like any other: every rank sets the same zoom before its reference.
+             like any other: every rank sets the same zoom before its reference.  The same holds for a spectrum filter
+             (``SweepEngine.set_filter``).
     params : the full [G, 4] list (identical on every rank).
     align  : shard granularity in candidates (the number of rises: shards are whole twists).
     device : torch device of the buffers (default: the engine's GPU).  With a ``gloo`` group the

@@ -23,6 +23,7 @@ __all__ = [
     "layer_line_mask",
     "shard_bounds",
     "zoom_spec",
+    "filter_spec",
 ]
 
 
@@ -157,3 +158,17 @@ def zoom_spec(shape, apix, cutoff_res=None, output_size=None):
     if (cy, cx) == (2.0 * float(apix), 2.0 * float(apix)) and (ony, onx) == (ny, nx):
         return None
     return ony, onx, cy, cx
+
+
+def filter_spec(low_pass_fraction=0, high_pass_fraction=0):
+    """The spectrum filter that ``compute_power_spectra(..., low_pass_fraction, high_pass_fraction)`` asks of the sweep
+    (transforms.py:811-816): ``None`` when both passes are off, else ``(low_pass_fraction, high_pass_fraction)`` with 0.0
+    for a pass that is off.  A fraction outside (0, 1) is off, the reference's own rule (filters.py:363-370); ``None``
+    counts as 0.  ``ValueError`` on NaN."""
+    out = []
+    for name, f in (("low_pass_fraction", low_pass_fraction), ("high_pass_fraction", high_pass_fraction)):
+        f = 0.0 if f is None else float(f)
+        if math.isnan(f):
+            raise ValueError(f"{name} is NaN")
+        out.append(f if 0.0 < f < 1.0 else 0.0)
+    return None if out == [0.0, 0.0] else (out[0], out[1])

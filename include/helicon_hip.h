@@ -120,7 +120,8 @@ int hh_max_batch(const hh_ctx* ctx);
 /* Device memory the context holds right now (bytes; its buffers grow with the sweeps it has run and stay until
  * hh_destroy).  parts (may be NULL): {run tables, column factors, two-pass intermediate, several-segment buffers,
  * everything else}.  Typical: C2 (512^2, one 100k launch) 0.21 + 2.9 + 0.27 GB; C4 (1024^2) ~7 GB; C5 (64 segments x
- * 20k candidates) ~12 GB of masked spectra. */
+ * 20k candidates) ~12 GB of masked spectra.  A spectrum filter (hh_set_spectrum_filter) adds its operators and one
+ * batch of candidate planes (at most 128 MB, while a batch holds more than one candidate) to "everything else". */
 int64_t hh_memory_bytes(const hh_ctx* ctx, int64_t parts[5]);
 /* How hh_sweep cuts a launch of the fused pipeline into workgroups: `runs` runs of `run_len`
  * candidates, `n_kb` ky blocks, `slots` workgroups resident on the device at a time.  The first runs_a runs are cut into
@@ -155,6 +156,15 @@ int hh_set_geometry(hh_ctx* ctx, const hh_geom* geom);
  * reports HH_ERR_STATE until hh_set_reference is called), and so does a later hh_set_geometry with another apix.  Bad
  * arguments return HH_ERR_ARG and change nothing; nothing here touches the device. */
 int hh_set_spectrum_zoom(hh_ctx* ctx, int ony, int onx, double cutoff_y, double cutoff_x);
+
+/* Score on low / high-pass filtered spectra: compute_power_spectra(..., low_pass_fraction, high_pass_fraction) of
+ * lib/transforms.py:771-820 — low_high_pass_filter (lib/filters.py:314-372) of the spectrum image log1p|F| (or |F|) — for
+ * the experimental image(s) and for every candidate of a sweep.  Call it between hh_set_geometry and hh_set_reference.  A
+ * fraction outside (0, 1) means that pass is off (the reference's own rule); both off clears the filter.  It combines with
+ * hh_set_spectrum_zoom; without a zoom the sweep runs the zoom's product kernel at the identity zoom (the image's own shape
+ * and Nyquist), the mask keeps the image's shape.  A call that changes the filter drops the reference (HH_ERR_STATE until
+ * the next hh_set_reference).  NaN returns HH_ERR_ARG and changes nothing; nothing here touches the device. */
+int hh_set_spectrum_filter(hh_ctx* ctx, double low_pass_fraction, double high_pass_fraction);
 
 /* Experimental image(s) and mask.  images: host, S x N x N float32; mask: host, N x N bytes on
  * the fftshifted plane (DC at [N/2][N/2]), non-zero = bin takes part in the correlation;
@@ -191,7 +201,8 @@ int hh_sweep_device_strided(hh_ctx* ctx, const double* d_params, const double* h
                             float* d_scores, int64_t ld_scores);
 int hh_set_table_path(hh_ctx* ctx, int mode);
 /* Which pipeline the last sweep of this context ran: 0 = per-candidate raster + column transform +
- * second pass, 1 = run tables + second pass, 2 = fused, 3 = zoomed spectra (hh_set_spectrum_zoom). */
+ * second pass, 1 = run tables + second pass, 2 = fused, 3 = zoomed spectra (hh_set_spectrum_zoom),
+ * 4 = filtered spectra (hh_set_spectrum_filter, with or without a zoom). */
 int hh_last_first_pass(const hh_ctx* ctx);
 
 /* Pre-sweep image preparation on the device.
