@@ -11,5 +11,6 @@ from .denovo3D import (SweepEngine, SweepResult, apply_helical_symmetry, auto_ho
                        transform_image, transform_map)
 from ._lib import HeliconHipError
 from .solver import lsq_reconstruct, lsq_reconstruct_batch
+from .symmetry_search import SymmetrySearch, helical_symmetry_search
 
 __version__ = "0.1.0"

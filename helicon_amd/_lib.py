@@ -153,6 +153,15 @@ EXPORTS = {
     "hh_pab_solve_prox": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _f64p, C.c_double, C.c_int, C.c_double, C.c_int,
                                     _f32p, _f64p, C.POINTER(C.c_int32), _f64p]),
     "hh_pab_counters": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
+    # helical symmetry search of a 3-D map (helicon_amd/symmetry_search.py)
+    "hh_hs_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, _f32p, C.POINTER(C.c_int32), C.c_double, C.c_double]),
+    "hh_hs_set_region": (C.c_int, [C.c_void_p, C.c_double, C.c_double, C.c_double]),
+    "hh_hs_set_budget": (C.c_int, [C.c_void_p, C.c_int64]),
+    "hh_hs_search": (C.c_int, [C.c_void_p, _f64p, C.c_int64, _f32p]),
+    "hh_hs_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "hh_hs_kernel_ms": (C.c_int, [C.c_void_p, _f64p]),
+    "hh_hs_destroy": (None, [C.c_void_p]),
+    "hh_hs_last_error": (C.c_char_p, [C.c_void_p]),
 }
 
 _lib = None

@@ -4542,3 +4542,4 @@ int hh_profile_get(hh_ctx* c, hh_profile* out) try {
 #include "path_a_batch.inc"  // Path A for many candidates at once, device-resident solve (hh_pab_*)
 #include "map_filter.inc"  // the 3-D map input: separable Gaussian filter of a whole map on the f32 MFMA, axis projections
 #include "filtered_sweep.inc"  // the sweep on low / high-pass filtered spectra (hh_set_spectrum_filter): y pass + fused x pass / moments
+#include "symmetry_search.inc"  // helical symmetry search of a 3-D map: batched (twist, rise, Csym) scores of a device-resident map (hh_hs_*)

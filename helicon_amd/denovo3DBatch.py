@@ -30,7 +30,8 @@ off.  They combine with the zoom flags and with ``--mask``, which keeps the shap
 size) and builds the input image as the app does for a map (app.py:1780-1829): the map is symmetrised with the given
 twist, rise and Csym, resampled to ``--output-size`` at ``--output-apix`` with ``--axial-rotation`` / ``--output-tilt``
 (``symmetrize_transform_map``), projected along x, and ``--noise`` times its foreground standard deviation of Gaussian noise
-is added.  The sweep and ``--rescore`` then run on that image at the output pixel size:
+is added.  The sweep and ``--rescore`` then run on that image at the output pixel size (for a map whose symmetry is not
+known, ``python -m helicon_amd.symmetry_search`` finds it: its report's ``best`` is what TWIST RISE CSYM take):
 
     python -m helicon_amd.denovo3DBatch emd.map --from-map 29.4 4.75 1 --output-apix 5 --twist 28 31 0.2 --rise 4 6 0.1 \
            --seed 0 --save-projection proj.npy

@@ -482,6 +482,38 @@ int hh_pab_solve_prox(hh_pab* pab, const int32_t* positive, const int32_t* clip,
  * solver's self-check (every workgroup of a launch saw the per-candidate state the previous launch wrote; must be 0)} */
 int hh_pab_counters(const hh_pab* pab, int64_t out[4]);
 
+/* ---------------------------------------------------------------------------------------------
+ * Helical symmetry search of a 3-D map (csrc/symmetry_search.inc): for every candidate (twist, rise, Csym)
+ *     S = apply_helical_symmetry(V, apix, twist, rise, csym, fraction, new_size = V.shape, new_apix = apix)   (transforms.py:58-165)
+ *     score = cross_correlation_coefficient(V[M], S[M])      Pearson; 0 where either side has no variance
+ * over the region M = { (k, j, i) : rmin^2 <= (j - ny/2)^2 + (i - nx/2)^2 < rmax^2 and -h <= k - nz/2 < h } (integer
+ * centres; h = max(1, int(nz z_fraction + 0.5) / 2), every plane when z_fraction >= 1).  An hh_hs keeps the map (host
+ * float32 [shape[0]][shape[1]][shape[2]] = z, y, x, every side in [2, 1024]) on the device; a search uploads the list,
+ * computes S on the voxels of M only without storing it, and returns one float32 score per candidate.  A score depends on
+ * the candidate and the region alone: not on the list around it, nor on how the list is cut into launches.
+ * hh_hs_create sets the default region rmin = 0, rmax = min(ny, nx) / 2 - 1, z_fraction = 0.5 (a map too small to have
+ * one is created without and needs hh_hs_set_region).  Errors of a handle are read with hh_hs_last_error(handle), those of
+ * hh_hs_create with hh_hs_last_error(NULL). */
+typedef struct hh_hs hh_hs;
+int hh_hs_create(hh_hs** out, int device, const float* map, const int32_t shape[3], double apix, double fraction);
+/* rmax_px < 0: no outer limit.  A region without voxels is HH_ERR_ARG (and the handle is left without a region). */
+int hh_hs_set_region(hh_hs* hs, double rmin_px, double rmax_px, double z_fraction);
+/* Device bytes the per-workgroup partial sums of ONE launch may take (default 64 MiB, or the environment's
+ * HELICON_HS_PARTIAL_BYTES when the handle is created): a list that needs more is cut into several launches of at
+ * least one candidate each.  The scores do not depend on it. */
+int hh_hs_set_budget(hh_hs* hs, int64_t partial_bytes);
+/* params: [g][3] host float64 = twist (degrees), rise (Angstrom), csym; scores: [g] host float32.  rise <= 0 or not
+ * finite, a twist that is not finite, or csym not a whole number in [1, 4096] is HH_ERR_ARG with the candidate's index in
+ * the message; nothing is computed then. */
+int hh_hs_search(hh_hs* hs, const double* params, int64_t g, float* scores);
+/* z_range = the source planes [z0, z1) the operator reads (the 1 % profile rule and `fraction`), region_voxels = |M|,
+ * launches = scoring launches since the handle was created; any of them may be NULL */
+int hh_hs_info(const hh_hs* hs, int32_t z_range[2], int64_t* region_voxels, int64_t* launches);
+/* device time of the last search's kernels (scoring + finalising, all launches), from events on the handle's stream */
+int hh_hs_kernel_ms(const hh_hs* hs, double* ms);
+void hh_hs_destroy(hh_hs* hs);
+const char* hh_hs_last_error(const hh_hs* hs);
+
 #ifdef __cplusplus
 }
 #endif
