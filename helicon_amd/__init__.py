@@ -12,5 +12,7 @@ from .denovo3D import (SweepEngine, SweepResult, apply_helical_symmetry, auto_ho
 from ._lib import HeliconHipError
 from .solver import lsq_reconstruct, lsq_reconstruct_batch
 from .symmetry_search import SymmetrySearch, helical_symmetry_search
+from .fsc import (calc_frc_2d, calc_fsc, calc_fsc_batch, calc_fsc_per_shell, frc_score, fsc_resolution, half_map_fsc,
+                  half_map_fsc_batch)
 
 __version__ = "0.1.0"

@@ -162,6 +162,9 @@ EXPORTS = {
     "hh_hs_kernel_ms": (C.c_int, [C.c_void_p, _f64p]),
     "hh_hs_destroy": (None, [C.c_void_p]),
     "hh_hs_last_error": (C.c_char_p, [C.c_void_p]),
+    # Fourier shell / ring correlation (helicon_amd/fsc.py)
+    "hh_fsc_3d": (C.c_int, [C.c_int, _f32p, _f32p, C.c_int32, C.c_int32, C.c_int, _f64p, _f64p]),
+    "hh_frc_2d": (C.c_int, [C.c_int, _f32p, _f32p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int32, _f64p, _f64p]),
 }
 
 _lib = None

@@ -1,0 +1,349 @@
+// fourier_correlation.inc — Fourier shell correlation of two cubic maps and Fourier ring correlation of two images
+// (lib/analysis.py:116-356: calc_fsc, calc_fsc_per_shell, calc_frc_2d), for a batch of pairs in one call.
+//
+// For every pair and every shell s the three sums
+//     num[s] = sum w Re(F1 conj F2),   den1[s] = sum w |F1|^2,   den2[s] = sum w |F2|^2      over the bins of shell s
+// are returned (the ratio and the `denominator > 0` rule stay on the host).  The transforms are per-axis matrix products
+// on the exact-f32 MFMA, like the map filter's circulant passes (k_circ_gemm, map_filter.inc): a DFT along one axis is the
+// product with [cos | -sin] blocks built in float64 on the host and rounded to float32, so any side works (odd and prime
+// included) and there is no FFT plan.
+//     3-D, F(kz, ky, kx):  z pass on the real input (Re = C x, Im = -S x), y pass on the complex planes
+//                          (Re = [C | S][re; im], Im = [-S | C][re; im]), both through k_circ_gemm;
+//     2-D, F(ky, kx):      y pass on the real input;
+//     last (x) pass:       k_fc_xpass, only the columns that are needed (n / 2 + 1 in 3-D, all nx in 2-D), for both members
+//                          of the pair in one workgroup, which forms the three products from its accumulator registers
+//                          and adds them to the shell sums.  The spectrum of the last pass is never stored.
+// Shell of a 3-D bin: round(sqrt(m)), m = kz^2 + ky^2 + kx^2 in integers, decided without a square root's rounding
+// (shell = k iff k (k - 1) < m <= k (k + 1); sqrt(m) is never k + 1/2), clipped to n / 2.  A 2-D bin reads the host's table
+// (ties are real there and follow NumPy's float64 expression).  Weight: 1, or — the full spectrum seen from its half —
+// 2 off the planes kx = 0 and kx = n / 2 (even n).
+// The sums are bit-identical from run to run and do not depend on the batch: every product is formed in float64, scaled
+// by a power of two chosen per pair and per sum from max |map| alone (sum w |F|^2 <= (voxels max|x|)^2), rounded to a 64-bit
+// integer and added with integer atomics (LDS first, then global), whose result does not depend on the order.  The total
+// stays below 2^62; one unit is 2^-61 of that bound or finer.  k_fc_finish converts back to float64.
+
+namespace {
+
+constexpr int FC_T = 64;          // tile of a workgroup: 64 rows of the planes x 64 output columns
+constexpr int FC_K = 32;          // slice of the x axis staged through LDS per step
+constexpr int FC_MAX_SHELLS = 513;    // LDS shell sums of one workgroup: 3-D n / 2 + 1 <= 257, 2-D min(ny, nx) / 2 + 1 <= 513
+
+struct FcXPass {
+  const float* re;         // [2 B][rows][nx] real plane after the earlier passes: maps 0 .. B-1 are the first members
+  const float* im;         // the imaginary plane
+  const float* cs;         // [nx][ncol] cos(2 pi x k / nx)
+  const float* sn;         // [nx][ncol] sin(2 pi x k / nx)
+  const int32_t* shell;    // 2-D: [rows][ncol] host table; 3-D: null
+  const double* scale;     // [B][3] power-of-two scales of num, den1, den2
+  long long* acc;          // [B][nshell][3] fixed-point sums
+  int batch, rows, nx, ncol, n, nshell, weighted;
+};
+
+// max |x| of every map, as the bit pattern of a non-negative float (ordered like the value; NaN sorts above infinity)
+__global__ __launch_bounds__(256) void k_fc_absmax(const float* __restrict__ v, int64_t per_map, unsigned* __restrict__ amax) {
+  const float* s = v + (int64_t)blockIdx.y * per_map;
+  unsigned m = 0;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < per_map; i += (int64_t)gridDim.x * 256)
+    m = max(m, __float_as_uint(s[i]) & 0x7fffffffu);
+  for (int off = 32; off > 0; off >>= 1) m = max(m, (unsigned)__shfl_down((int)m, off, 64));
+  if ((threadIdx.x & 63) == 0 && m != 0) atomicMax(amax + blockIdx.y, m);
+}
+
+// scale[b][q] = 2^(61 - ilogb(bound)), bound = 2 (voxels)^2 max|a| max|b| >= sum w |products| of the pair; 0 when the
+// bound is 0 (every product is 0 then), NaN when a map holds a NaN or an infinity (the sums come back as NaN)
+__global__ void k_fc_scales(const unsigned* __restrict__ amax, int batch, double voxels, double* __restrict__ scale) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= batch) return;
+  const double a1 = (double)__uint_as_float(amax[b]), a2 = (double)__uint_as_float(amax[batch + b]);
+  const double pr[3] = {a1 * a2, a1 * a1, a2 * a2};
+  for (int q = 0; q < 3; ++q) {
+    const double bound = 2.0 * voxels * voxels * pr[q];
+    double s;
+    if (!(bound == bound) || bound > 1.7e308) s = __longlong_as_double(0x7ff8000000000000ll);
+    else if (bound == 0.0) s = 0.0;
+    else s = ldexp(1.0, 61 - ilogb(bound));
+    scale[b * 3 + q] = s;
+  }
+}
+
+__device__ __forceinline__ int fc_shell_3d(int kz, int ky, int kx, int n) {
+  const int h = n / 2;
+  const int fz = kz <= h ? kz : n - kz, fy = ky <= h ? ky : n - ky, fx = kx <= h ? kx : n - kx;
+  const int m = fz * fz + fy * fy + fx * fx;
+  int k = (int)sqrtf((float)m);
+  while (k * (k + 1) < m) ++k;
+  while (k > 0 && k * (k - 1) >= m) --k;
+  return k < h ? k : h;
+}
+
+// One workgroup: 64 rows x 64 columns of F1 and of F2 (4 wavefronts in 2 x 2, each four 32 x 32 accumulators: Re and Im of
+// both members), then the products of the tile into the shell sums.
+__global__ __launch_bounds__(256) void k_fc_xpass(FcXPass g) {
+  __shared__ float as[4][FC_T][FC_K + 1];   // re1, im1, re2, im2
+  __shared__ float os[2][FC_K][FC_T + 1];   // cos, sin
+  __shared__ unsigned long long sh[FC_MAX_SHELLS * 3];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int r = lane & 31, h = lane >> 5;
+  const int row0 = blockIdx.x * FC_T, col0 = blockIdx.y * FC_T, b = blockIdx.z;
+  const int wm = (wave >> 1) * 32, wp = (wave & 1) * 32;
+  const int64_t plane = (int64_t)g.rows * g.nx;
+  const float* src[4] = {g.re + (int64_t)b * plane, g.im + (int64_t)b * plane, g.re + (int64_t)(g.batch + b) * plane,
+                         g.im + (int64_t)(g.batch + b) * plane};
+  for (int e = tid; e < g.nshell * 3; e += 256) sh[e] = 0ull;
+  const bool active = col0 + wp < g.ncol && row0 + wm < g.rows;   // wavefront-uniform: a sub-tile wholly outside does no product
+  f32x16 re1 = {0}, im1 = {0}, re2 = {0}, im2 = {0};
+  for (int k0 = 0; k0 < g.nx; k0 += FC_K) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+      for (int e = tid; e < FC_T * FC_K; e += 256) {
+        const int mm = e / FC_K, kk = e % FC_K, row = row0 + mm, k = k0 + kk;   // lanes along x: contiguous in memory
+        as[q][mm][kk] = (row < g.rows && k < g.nx) ? src[q][(int64_t)row * g.nx + k] : 0.f;
+      }
+    for (int e = tid; e < FC_K * FC_T; e += 256) {
+      const int kk = e / FC_T, cc = e % FC_T, k = k0 + kk, col = col0 + cc;
+      const bool in = k < g.nx && col < g.ncol;
+      os[0][kk][cc] = in ? g.cs[(int64_t)k * g.ncol + col] : 0.f;
+      os[1][kk][cc] = in ? g.sn[(int64_t)k * g.ncol + col] : 0.f;
+    }
+    __syncthreads();
+    if (active) {
+#pragma unroll
+      for (int kk = 0; kk < FC_K; kk += 2) {
+        const float c = os[0][kk + h][wp + r], s = os[1][kk + h][wp + r];
+        const float a1 = as[0][wm + r][kk + h], b1 = as[1][wm + r][kk + h];
+        const float a2 = as[2][wm + r][kk + h], b2 = as[3][wm + r][kk + h];
+        // (a + i b)(c - i s) = (a c + b s) + i (b c - a s)
+        re1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, c, re1, 0, 0, 0);
+        re1 = __builtin_amdgcn_mfma_f32_32x32x2f32(b1, s, re1, 0, 0, 0);
+        im1 = __builtin_amdgcn_mfma_f32_32x32x2f32(b1, c, im1, 0, 0, 0);
+        im1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, -s, im1, 0, 0, 0);
+        re2 = __builtin_amdgcn_mfma_f32_32x32x2f32(a2, c, re2, 0, 0, 0);
+        re2 = __builtin_amdgcn_mfma_f32_32x32x2f32(b2, s, re2, 0, 0, 0);
+        im2 = __builtin_amdgcn_mfma_f32_32x32x2f32(b2, c, im2, 0, 0, 0);
+        im2 = __builtin_amdgcn_mfma_f32_32x32x2f32(a2, -s, im2, 0, 0, 0);
+      }
+    }
+    __syncthreads();
+  }
+  const double s_num = g.scale[b * 3 + 0], s_d1 = g.scale[b * 3 + 1], s_d2 = g.scale[b * 3 + 2];
+  if (active) {
+    const int col = col0 + wp + r;   // 32x32 C/D map: column = lane & 31
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      const int row = row0 + wm + (i & 3) + 8 * (i >> 2) + 4 * h;
+      if (row >= g.rows || col >= g.ncol) continue;
+      int s;
+      double w = 1.0;
+      if (g.shell) {
+        s = g.shell[(int64_t)row * g.ncol + col];
+        s = s < 0 ? 0 : (s >= g.nshell ? g.nshell - 1 : s);
+      } else {
+        s = fc_shell_3d(row / g.n, row % g.n, col, g.n);
+        if (g.weighted && col != 0 && 2 * col != g.n) w = 2.0;
+      }
+      const double x1 = re1[i], y1 = im1[i], x2 = re2[i], y2 = im2[i];
+      const long long qn = __double2ll_rn(w * (x1 * x2 + y1 * y2) * s_num);
+      const long long q1 = __double2ll_rn(w * (x1 * x1 + y1 * y1) * s_d1);
+      const long long q2 = __double2ll_rn(w * (x2 * x2 + y2 * y2) * s_d2);
+      if (qn != 0) atomicAdd(&sh[s * 3 + 0], (unsigned long long)qn);
+      if (q1 != 0) atomicAdd(&sh[s * 3 + 1], (unsigned long long)q1);
+      if (q2 != 0) atomicAdd(&sh[s * 3 + 2], (unsigned long long)q2);
+    }
+  }
+  __syncthreads();
+  unsigned long long* const G = reinterpret_cast<unsigned long long*>(g.acc + (int64_t)b * g.nshell * 3);
+  for (int e = tid; e < g.nshell * 3; e += 256) {
+    const unsigned long long v = sh[e];
+    if (v != 0ull) atomicAdd(G + e, v);
+  }
+}
+
+__global__ __launch_bounds__(256) void k_fc_finish(const long long* __restrict__ acc, const double* __restrict__ scale, int nshell,
+                                                   int64_t total, double* __restrict__ sums) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= total) return;
+  const int64_t b = i / ((int64_t)nshell * 3);
+  const double s = scale[b * 3 + i % 3];
+  sums[i] = s == 0.0 ? 0.0 : (double)acc[i] / s;   // a NaN scale (a map that is not finite) gives NaN
+}
+
+// C[j][k] = cos(2 pi j k / n), S = sin, float64 tables indexed by j k mod n
+void fc_trig(int n, std::vector<double>& c, std::vector<double>& s) {
+  c.resize(n);
+  s.resize(n);
+  for (int t = 0; t < n; ++t) {
+    c[t] = std::cos(2.0 * M_PI * t / n);
+    s[t] = std::sin(2.0 * M_PI * t / n);
+  }
+}
+
+// Row-major n x ka operator block [sp p | sq q] (q only when ka = 2 n) of the pass along one axis, appended to `mats`
+size_t fc_operator(std::vector<float>& mats, int n, const std::vector<double>& p, double sp, const std::vector<double>* q, double sq) {
+  const size_t off = mats.size();
+  const int ka = q ? 2 * n : n;
+  mats.resize(off + (size_t)n * ka);
+  for (int i = 0; i < n; ++i)
+    for (int j = 0; j < n; ++j) {
+      const int t = (int)(((int64_t)i * j) % n);
+      mats[off + (size_t)i * ka + j] = (float)(sp * p[t]);
+      if (q) mats[off + (size_t)i * ka + n + j] = (float)(sq * (*q)[t]);
+    }
+  return off;
+}
+
+// the x pass's tables: [n][ncol]
+size_t fc_xtable(std::vector<float>& mats, int n, int ncol, const std::vector<double>& p) {
+  const size_t off = mats.size();
+  mats.resize(off + (size_t)n * ncol);
+  for (int x = 0; x < n; ++x)
+    for (int k = 0; k < ncol; ++k) mats[off + (size_t)x * ncol + k] = (float)p[(int)(((int64_t)x * k) % n)];
+  return off;
+}
+
+constexpr int64_t FC_SCRATCH_BYTES = (int64_t)8 << 30;   // device planes of one chunk of the batch
+
+struct FcBuffers {
+  float *in = nullptr, *p1 = nullptr, *p2 = nullptr, *mats = nullptr;   // p1 / p2: [re | im] plane pairs
+  int32_t* shell = nullptr;
+  unsigned* amax = nullptr;
+  double *scale = nullptr, *sums = nullptr;
+  long long* acc = nullptr;
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  ~FcBuffers() {
+    (void)hipFree(in); (void)hipFree(p1); (void)hipFree(p2); (void)hipFree(mats); (void)hipFree(shell); (void)hipFree(amax);
+    (void)hipFree(scale); (void)hipFree(sums); (void)hipFree(acc);
+    if (ev0) (void)hipEventDestroy(ev0);
+    if (ev1) (void)hipEventDestroy(ev1);
+  }
+};
+
+// nz == 0: images [ny][nx] with the host's shell table; else cubes of side nz = ny = nx
+int fc_run(const char* name, int device, const float* a, const float* b, int64_t batch, int nz, int ny, int nx, const int32_t* shell,
+           int nshell, bool weighted, double* sums, double* kernel_ms) {
+  const bool cube = nz > 0;
+  const int ncol = cube ? nx / 2 + 1 : nx;
+  const int rows = cube ? nz * ny : ny;
+  const int64_t per_map = (int64_t)rows * nx;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
+    return fail(nullptr, HH_ERR_HIP, std::string(name) + ": no such HIP device (there is no CPU fallback)");
+  HH_HIP(nullptr, hipSetDevice(device));
+  // operators: first pass on the real input, (3-D) second pass on the complex planes, the x pass's tables
+  std::vector<float> mats;
+  std::vector<double> c, s;
+  fc_trig(cube ? nz : ny, c, s);
+  const int n1 = cube ? nz : ny;
+  const size_t o_c = fc_operator(mats, n1, c, 1.0, nullptr, 0.0), o_ms = fc_operator(mats, n1, s, -1.0, nullptr, 0.0);
+  size_t o_re = 0, o_im = 0;
+  if (cube) {
+    fc_trig(ny, c, s);
+    o_re = fc_operator(mats, ny, c, 1.0, &s, 1.0);
+    o_im = fc_operator(mats, ny, s, -1.0, &c, 1.0);
+  }
+  fc_trig(nx, c, s);
+  const size_t o_xc = fc_xtable(mats, nx, ncol, c), o_xs = fc_xtable(mats, nx, ncol, s);
+  // chunk of the batch: input + one or two plane pairs within the scratch cap, and the y pass's grid.z = 2 chunk nz <= 65535
+  const int64_t bytes_per_pair = (int64_t)(cube ? 10 : 6) * per_map * (int64_t)sizeof(float);
+  int64_t chunk = std::max<int64_t>(1, FC_SCRATCH_BYTES / bytes_per_pair);
+  chunk = std::min<int64_t>(chunk, cube ? 65535 / (2 * nz) : 32767);
+  chunk = std::min<int64_t>(chunk, batch);
+  FcBuffers d;
+  const size_t map_bytes = (size_t)per_map * sizeof(float);
+  HH_HIP(nullptr, hipMalloc(&d.in, 2 * (size_t)chunk * map_bytes));
+  HH_HIP(nullptr, hipMalloc(&d.p1, 4 * (size_t)chunk * map_bytes));
+  if (cube) HH_HIP(nullptr, hipMalloc(&d.p2, 4 * (size_t)chunk * map_bytes));
+  HH_HIP(nullptr, hipMalloc(&d.mats, mats.size() * sizeof(float)));
+  HH_HIP(nullptr, hipMemcpy(d.mats, mats.data(), mats.size() * sizeof(float), hipMemcpyHostToDevice));
+  if (!cube) {
+    HH_HIP(nullptr, hipMalloc(&d.shell, (size_t)per_map * sizeof(int32_t)));
+    HH_HIP(nullptr, hipMemcpy(d.shell, shell, (size_t)per_map * sizeof(int32_t), hipMemcpyHostToDevice));
+  }
+  const size_t n_sums = (size_t)chunk * nshell * 3;
+  HH_HIP(nullptr, hipMalloc(&d.amax, 2 * (size_t)chunk * sizeof(unsigned)));
+  HH_HIP(nullptr, hipMalloc(&d.scale, (size_t)chunk * 3 * sizeof(double)));
+  HH_HIP(nullptr, hipMalloc(&d.acc, n_sums * sizeof(long long)));
+  HH_HIP(nullptr, hipMalloc(&d.sums, n_sums * sizeof(double)));
+  HH_HIP(nullptr, hipEventCreate(&d.ev0));
+  HH_HIP(nullptr, hipEventCreate(&d.ev1));
+  double ms_total = 0.0;
+  for (int64_t b0 = 0; b0 < batch; b0 += chunk) {
+    const int64_t nb = std::min(chunk, batch - b0);
+    const int64_t maps = 2 * nb;
+    float* const re1 = d.p1;
+    float* const im1 = d.p1 + maps * per_map;
+    HH_HIP(nullptr, hipMemcpy(d.in, a + b0 * per_map, (size_t)nb * map_bytes, hipMemcpyHostToDevice));
+    HH_HIP(nullptr, hipMemcpy(d.in + nb * per_map, b + b0 * per_map, (size_t)nb * map_bytes, hipMemcpyHostToDevice));
+    HH_HIP(nullptr, hipMemsetAsync(d.amax, 0, (size_t)maps * sizeof(unsigned), nullptr));
+    HH_HIP(nullptr, hipMemsetAsync(d.acc, 0, (size_t)nb * nshell * 3 * sizeof(long long), nullptr));
+    HH_HIP(nullptr, hipEventRecord(d.ev0, nullptr));
+    hipLaunchKernelGGL(k_fc_absmax, dim3((unsigned)std::min<int64_t>((per_map + 255) / 256, 256), (unsigned)maps), dim3(256), 0, nullptr,
+                       d.in, per_map, d.amax);
+    hipLaunchKernelGGL(k_fc_scales, dim3((unsigned)((nb + 63) / 64)), dim3(64), 0, nullptr, d.amax, (int)nb, (double)per_map, d.scale);
+    // first pass: the real input along z (cubes: P = ny nx, one map per grid.z) or along y (images: P = nx)
+    for (int part = 0; part < 2; ++part) {
+      CircPass g{};
+      g.a = d.mats + (part == 0 ? o_c : o_ms);
+      g.b0 = d.in; g.b1 = nullptr;
+      g.y = part == 0 ? re1 : im1;
+      g.n = n1; g.ka = n1;
+      g.np = cube ? (int64_t)ny * nx : nx; g.sk = g.np; g.sp = 1; g.sb = per_map;
+      hipLaunchKernelGGL(k_circ_gemm<false>, dim3((unsigned)((g.np + MF_T - 1) / MF_T), (unsigned)((n1 + MF_T - 1) / MF_T), (unsigned)maps),
+                         dim3(256), 0, nullptr, g);
+    }
+    const float *xre = re1, *xim = im1;
+    if (cube) {   // second pass along y: one z slice of one map per grid.z, K = 2 ny over the [re; im] planes
+      float* const re2 = d.p2;
+      float* const im2 = d.p2 + maps * per_map;
+      for (int part = 0; part < 2; ++part) {
+        CircPass g{};
+        g.a = d.mats + (part == 0 ? o_re : o_im);
+        g.b0 = re1; g.b1 = im1;
+        g.y = part == 0 ? re2 : im2;
+        g.n = ny; g.ka = 2 * ny;
+        g.np = nx; g.sk = nx; g.sp = 1; g.sb = (int64_t)ny * nx;
+        hipLaunchKernelGGL(k_circ_gemm<false>, dim3((unsigned)((nx + MF_T - 1) / MF_T), (unsigned)((ny + MF_T - 1) / MF_T), (unsigned)(maps * nz)),
+                           dim3(256), 0, nullptr, g);
+      }
+      xre = re2; xim = im2;
+    }
+    FcXPass x{};
+    x.re = xre; x.im = xim;
+    x.cs = d.mats + o_xc; x.sn = d.mats + o_xs;
+    x.shell = cube ? nullptr : d.shell;
+    x.scale = d.scale; x.acc = d.acc;
+    x.batch = (int)nb; x.rows = rows; x.nx = nx; x.ncol = ncol; x.n = nx; x.nshell = nshell; x.weighted = weighted ? 1 : 0;
+    hipLaunchKernelGGL(k_fc_xpass, dim3((unsigned)((rows + FC_T - 1) / FC_T), (unsigned)((ncol + FC_T - 1) / FC_T), (unsigned)nb), dim3(256), 0,
+                       nullptr, x);
+    const int64_t total = nb * nshell * 3;
+    hipLaunchKernelGGL(k_fc_finish, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, nullptr, d.acc, d.scale, nshell, total, d.sums);
+    HH_HIP(nullptr, hipGetLastError());
+    HH_HIP(nullptr, hipEventRecord(d.ev1, nullptr));
+    HH_HIP(nullptr, hipMemcpy(sums + b0 * nshell * 3, d.sums, (size_t)total * sizeof(double), hipMemcpyDeviceToHost));
+    float ms = 0.f;
+    HH_HIP(nullptr, hipEventElapsedTime(&ms, d.ev0, d.ev1));
+    ms_total += ms;
+  }
+  if (kernel_ms) *kernel_ms = ms_total;
+  return HH_OK;
+}
+
+}  // namespace
+
+extern "C" int hh_fsc_3d(int device, const float* maps1, const float* maps2, int32_t batch, int32_t n, int full_spectrum, double* sums,
+                         double* kernel_ms) try {
+  if (!maps1 || !maps2 || !sums) return fail(nullptr, HH_ERR_ARG, "hh_fsc_3d: NULL argument");
+  if (batch < 1) return fail(nullptr, HH_ERR_ARG, "hh_fsc_3d: batch must be >= 1");
+  if (n < 8 || n > 512) return fail(nullptr, HH_ERR_ARG, "hh_fsc_3d: the side of the cubes must lie in [8, 512]");
+  return fc_run("hh_fsc_3d", device, maps1, maps2, batch, n, n, n, nullptr, n / 2 + 1, full_spectrum != 0, sums, kernel_ms);
+} HH_CATCH_CTX(nullptr, "hh_fsc_3d")
+
+extern "C" int hh_frc_2d(int device, const float* imgs1, const float* imgs2, int32_t batch, int32_t ny, int32_t nx, const int32_t* shell,
+                         int32_t n_shells, double* sums, double* kernel_ms) try {
+  if (!imgs1 || !imgs2 || !shell || !sums) return fail(nullptr, HH_ERR_ARG, "hh_frc_2d: NULL argument");
+  if (batch < 1) return fail(nullptr, HH_ERR_ARG, "hh_frc_2d: batch must be >= 1");
+  if (ny < 8 || ny > 1024 || nx < 8 || nx > 1024) return fail(nullptr, HH_ERR_ARG, "hh_frc_2d: both sides of the images must lie in [8, 1024]");
+  if (n_shells < 0 || n_shells + 1 > FC_MAX_SHELLS) return fail(nullptr, HH_ERR_ARG, "hh_frc_2d: n_shells must lie in [0, 512]");
+  for (int64_t i = 0; i < (int64_t)ny * nx; ++i)
+    if (shell[i] < 0 || shell[i] > n_shells) return fail(nullptr, HH_ERR_ARG, "hh_frc_2d: a shell index lies outside [0, n_shells]");
+  return fc_run("hh_frc_2d", device, imgs1, imgs2, batch, 0, ny, nx, shell, n_shells + 1, false, sums, kernel_ms);
+} HH_CATCH_CTX(nullptr, "hh_frc_2d")

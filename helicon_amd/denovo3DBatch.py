@@ -9,11 +9,16 @@ descending, app.py:2521-2523) this driver reproduces without the Shiny UI.
     python -m helicon_amd.denovo3DBatch image.npy --apix 2.0 --twist 25 33 0.2 --rise 8 13 0.2 \\
            --csym 1 --out scores.npz [--mask mask.npy] [--no-log] [--device 0] [--top 10] \
            [--cutoff-res 10 10 --spectrum-size 256 256] [--spectrum-high-pass 0.05] [--spectrum-low-pass 0.3] \
-           [--rescore 20 --tube-diameter 120 --interpolation linear]
+           [--rescore 20 --tube-diameter 120 --interpolation linear [--half-map-fsc 1]]
 
 ``--rescore K`` runs the reference's own scorer — the sparse least-squares reconstruction of pipeline.py:84-496,
 ``process_one_task(..., algorithm={"scorer": "lsq"})`` — on the sweep's K best candidates of every image, from a
 thread pool like the app's (app.py:2473-2476), and reports them in the order of that score.
+
+``--rescore K --half-map-fsc {1,2}`` also solves the two half-data problems of every rescored candidate (the scorer's
+``fsc_test``: 1 = random halves of the pixels, 2 = even / odd), symmetrises both half maps onto a cube and adds their Fourier
+shell correlation to the record (``fsc``, ``fsc_resolution_0143``, ``fsc_resolution_05``; ``helicon_amd.fsc.half_map_fsc``,
+all candidates of a box group in one batched call) and ``rescored_fsc`` to ``--out``.  It needs ``--tilt 0 --psi 0``.
 
 ``--cutoff-res Y X`` (Angstrom) and ``--spectrum-size NY NX`` score on the Fourier-zoomed power spectrum
 ``compute_power_spectra(image, apix, cutoff_res=(Y, X), output_size=(NY, NX))`` (transforms.py:663-713, 771-820) of the
@@ -92,6 +97,9 @@ def add_args(parser: argparse.ArgumentParser) -> argparse.ArgumentParser:
     parser.add_argument("--alpha", type=float, default=None, help="for --rescore with a model: its regularisation strength "
                         "(default: the model's own — 1e-4 for elasticnet and lasso, 1 for ridge)")
     parser.add_argument("--threads", type=int, default=8, help="for --rescore")
+    parser.add_argument("--half-map-fsc", type=int, choices=(1, 2), default=0, metavar="{1,2}",
+                        help="for --rescore: also solve the two half-data problems (the scorer's fsc_test: 1 random halves, 2 even / odd "
+                             "pixels) and report the Fourier shell correlation of the symmetrised half maps; needs --tilt 0 --psi 0")
     parser.add_argument("--map-out", default=None, help="for --rescore: write the best candidate's helically symmetrised map of every "
                         "image to <map-out>_<image>.mrc (the app's map download, app.py:1267-1287)")
     g = parser.add_argument_group("map input (app.py:1780-1829)")
@@ -201,6 +209,10 @@ def run(args) -> dict:
     if getattr(args, "model", "lsq") != "lsq" and (args.tilt != 0 or args.psi != 0):
         raise SystemExit(f"--model {args.model} needs --tilt 0 --psi 0: the scikit-learn models run in the group solver, "
                          "whose products have no tilted form")
+    half_fsc = int(getattr(args, "half_map_fsc", 0) or 0)
+    if half_fsc and args.rescore > 0 and (args.tilt != 0 or args.psi != 0):
+        raise SystemExit("--half-map-fsc needs --tilt 0 --psi 0: with a tilt the rescoring goes through process_one_task one "
+                         "candidate at a time, which returns no half maps")
     map_info = None
     if getattr(args, "from_map", None) is not None:
         images, map_info = _map_input(args)
@@ -280,6 +292,10 @@ def run(args) -> dict:
                          rescored=np.asarray([[[r["twist"], r["rise"], r["csym"], r["sweep_score"],
                                                 np.nan if r["lsq_score"] is None else r["lsq_score"]]
                                                for r in im.get("rescored", [])] for im in report["images"]], dtype=np.float64))
+            if half_fsc and all("fsc" in r for im in report["images"] for r in im.get("rescored", [])):   # [image][rescored candidate][shell][saxis, fsc] and the two resolutions, in the order of `rescored`
+                extra["rescored_fsc"] = np.asarray([[r["fsc"] for r in im.get("rescored", [])] for im in report["images"]], dtype=np.float64)
+                extra["rescored_fsc_resolution"] = np.asarray([[[r["fsc_resolution_0143"], r["fsc_resolution_05"]]
+                                                                for r in im.get("rescored", [])] for im in report["images"]], dtype=np.float64)
         np.savez_compressed(args.out, scores=res.scores, twists=twists, rises=rises, csyms=np.asarray(args.csym),
                             params=res.grid.params, valid=res.grid.valid, cutoff_res=np.asarray(report["cutoff_res"]),
                             spectrum_size=np.asarray(report["spectrum_size"]), spectrum_filter=np.asarray(report["spectrum_filter"]), **extra)
@@ -317,17 +333,27 @@ def rescore(image, candidates, args) -> list:
             box = lsq_box(ny, nx, args.apix, c["rise"], (c["rise"], c["rise"]), (0, 0), args.apix, -1, tube_d, 0, -1, 1, 0)
             groups.setdefault(box, []).append(k)
         scores = [None] * len(candidates)
+        half_fsc = int(getattr(args, "half_map_fsc", 0) or 0)
+        fsc_of = [None] * len(candidates)
         for (a3, d2, l2, d3, d3_inner, l3, oversample), members in groups.items():
             res = lsq_reconstruct_batch(img, args.apix / a3, [(candidates[k]["twist"], candidates[k]["rise"] / a3, candidates[k]["csym"])
                                                              for k in members],
                                         reconstruct_diameter_3d_inner_pixel=d3_inner, reconstruct_diameter_2d_pixel=d2,
                                         reconstruct_diameter_3d_pixel=d3, reconstruct_length_2d_pixel=l2, reconstruct_length_3d_pixel=l3,
-                                        sym_oversample=oversample, return_3d=False, device=args.device, streams=max(1, args.threads),
-                                        interpolation=args.interpolation, algorithm=rescore_algorithm(args))
+                                        sym_oversample=oversample, fsc_test=half_fsc, return_3d=bool(half_fsc), device=args.device,
+                                        streams=max(1, args.threads), interpolation=args.interpolation, algorithm=rescore_algorithm(args))
             for k, (_, sc) in zip(members, res):
                 scores[k] = sc
+            if half_fsc:   # every half map of the group symmetrised onto its cube, then one batched correlation
+                from .fsc import half_map_fsc_batch
+
+                curves = half_map_fsc_batch([maps[1] for maps, _ in res], [maps[2] for maps, _ in res], a3,
+                                            [(candidates[k]["twist"], candidates[k]["rise"], candidates[k]["csym"]) for k in members],
+                                            device=args.device)
+                for k, (curve, resolution) in zip(members, curves):
+                    fsc_of[k] = dict(fsc_resolution_0143=resolution["0.143"], fsc_resolution_05=resolution["0.5"], fsc=curve.tolist())
         got = [dict(twist=c["twist"], rise=c["rise"], csym=c["csym"], sweep_score=c["score"], lsq_score=float(scores[k]),
-                    interpolation=args.interpolation) for k, c in enumerate(candidates)]
+                    interpolation=args.interpolation, **(fsc_of[k] or {})) for k, c in enumerate(candidates)]
         return sorted(got, key=lambda r: -r["lsq_score"])
 
     from concurrent.futures import ThreadPoolExecutor

@@ -514,6 +514,23 @@ int hh_hs_kernel_ms(const hh_hs* hs, double* ms);
 void hh_hs_destroy(hh_hs* hs);
 const char* hh_hs_last_error(const hh_hs* hs);
 
+/* ---------------------------------------------------------------------------------------------
+ * Fourier shell / ring correlation (csrc/fourier_correlation.inc; lib/analysis.py:116-356 calc_fsc, calc_fsc_per_shell,
+ * calc_frc_2d).  `batch` pairs of equal size in one call (host float32, contiguous); per pair and shell the three sums
+ *     num = sum w Re(F1 conj F2),   den1 = sum w |F1|^2,   den2 = sum w |F2|^2
+ * come back as host float64 [batch][shells][3]; the ratio and its `denominator > 0` rule are the caller's.  float32
+ * transforms, float64 products, sums that are bit-identical from run to run and do not depend on the batch.  Errors are
+ * read with hh_last_error(NULL).  kernel_ms (may be NULL): device time of the kernels.
+ * hh_fsc_3d: cubes of side n in [8, 512]; shells n / 2 + 1; shell = clip(round(sqrt(kz^2 + ky^2 + kx^2)), 0, n / 2) over
+ * the half spectrum kx <= n / 2, every bin once (full_spectrum = 0: calc_fsc) or with the Hermitian weight, which equals
+ * the sums over the full spectrum (full_spectrum = 1: calc_fsc_per_shell). */
+int hh_fsc_3d(int device, const float* maps1, const float* maps2, int32_t batch, int32_t n, int full_spectrum, double* sums,
+              double* kernel_ms);
+/* images [ny][nx], both sides in [8, 1024], full spectrum; shell: host table [ny][nx] with entries in [0, n_shells]
+ * (n_shells <= 512), sums: [batch][n_shells + 1][3] */
+int hh_frc_2d(int device, const float* imgs1, const float* imgs2, int32_t batch, int32_t ny, int32_t nx, const int32_t* shell,
+              int32_t n_shells, double* sums, double* kernel_ms);
+
 #ifdef __cplusplus
 }
 #endif
