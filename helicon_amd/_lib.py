@@ -87,6 +87,7 @@ EXPORTS = {
     "hh_sweep_device_strided": (C.c_int, [_ctx, C.c_void_p, _f64p, C.c_int64, C.c_void_p, C.c_int64]),
     "hh_set_table_path": (C.c_int, [_ctx, C.c_int]),
     "hh_last_first_pass": (C.c_int, [_ctx]),
+    "hh_last_row_kernel": (C.c_int, [_ctx, C.POINTER(C.c_int32)]),
     "hh_low_high_pass_filter": (C.c_int, [_ctx, _f32p, C.c_double, C.c_double, _f32p]),
     "hh_threshold_data": (C.c_int, [_ctx, _f32p, C.c_int64, C.c_int, C.c_double, _f32p]),
     "hh_argmax": (C.c_int, [_f32p, C.c_int64, C.POINTER(C.c_int64)]),

@@ -47,7 +47,9 @@ int gen_create(hh_ctx* c, int ny, int nx) {
   c->gen = g;
   g->d = GenDims{ny, nx, ny / 2 + 1, (nx + 3) / 4 * 4};
   // a row length with a prime factor above 31 (37, 74, 127 ...) has no row-transform plan: its sweeps take the direct
-  // path (gen_sweep_direct: float64 transforms per candidate) — every (ny, nx) in [8, 1024]^2 is served, those slowly
+  // path (gen_sweep_direct: float64 transforms per candidate), and so does a list whose Stockham launch would need more
+  // than the CU's 160 KB of LDS (gen_sweep) — every (ny, nx) in [8, 1024]^2 is served, those slowly.  What stays refused:
+  // a rise so small that one column group reaches more than 32 table rows (kg > 32, gen_sweep).
   g->direct_only = !gen_factor(nx, g->plan);
   std::vector<float2> tw;
   for (int pass = 0; pass < 2; ++pass) {
@@ -204,7 +206,7 @@ constexpr int64_t GEN_SEG_BYTES = (int64_t)8 << 30;   // several segments: most 
 // (ny, nx) with any tilt / psi, utils.py:31-47, 166-170): the shared-twist tables need tilt = psi = 0, so these go the
 // direct way, candidate by candidate — the lattice's centres and the pixel raster of hh_simulate, the float64 direct
 // transforms of the reference image's own spectrum, Pearson from float64 moments — in batches of as many images as
-// 512 MB of scratch hold.  Exact and slow (tens of thousands of candidates per second at 200 x 200): the path for the few
+// 512 MB of scratch hold (and one launch's gridDim.z, 65,535, allows).  Exact and slow (tens of thousands of candidates per second at 200 x 200): the path for the few
 // candidates a tilt / psi refinement looks at, not for a grid.
 int gen_sweep_direct(hh_ctx* c, const double* d_params, const double* h_params, int64_t n_cand, float* d_scores, int64_t ld) {
   hh_gen* g = c->gen;
@@ -218,7 +220,8 @@ int gen_sweep_direct(hh_ctx* c, const double* d_params, const double* h_params, 
     HH_HIP(c, hipStreamSynchronize(c->stream));
     h_params = hp.data();
   }
-  const int64_t batch = std::max<int64_t>(1, std::min<int64_t>(n_cand, ((int64_t)512 << 20) / (int64_t)(npix * 20 + nh * 16)));
+  int64_t batch = std::max<int64_t>(1, std::min<int64_t>(n_cand, ((int64_t)512 << 20) / (int64_t)(npix * 20 + nh * 16)));
+  batch = std::min<int64_t>(batch, 65535);   // a batch is the z extent of the transform launches
   size_t cap_img_b = (size_t)c->cap_img * sizeof(float);
   int rc = ensure_bytes(c, (void**)&c->d_img, &cap_img_b, (size_t)batch * npix * sizeof(float));
   c->cap_img = (int64_t)(cap_img_b / sizeof(float));
@@ -252,6 +255,7 @@ int gen_sweep_direct(hh_ctx* c, const double* d_params, const double* h_params, 
     HH_HIP(c, hipGetLastError());
   }
   c->last_first_pass = 0;
+  g->last_row_kernel[0] = g->last_row_kernel[1] = g->last_row_kernel[2] = 0;
   return HH_OK;
 }
 
@@ -362,7 +366,9 @@ int gen_sweep(hh_ctx* c, const double* d_params, const double* h_params, int64_t
         g->slots_two_step = true;
       }
     } else {
-      if (lds > 160 * 1024) return fail(c, HH_ERR_ARG, "image too wide / rise too small for the general-size path (LDS)");
+      // a row too wide (or a table slice too tall) for the Stockham kernel's LDS: the whole list goes the direct way, as
+      // the lengths without a plan do (batches already launched are scored again: same values, stream-ordered)
+      if (lds > 160 * 1024) { g->plan_valid = false; return gen_sweep_direct(c, d_params, h_params, n_cand, d_scores, ld); }
       if ((rc = ensure_lds_attr(c, reinterpret_cast<const void*>(fused_kernel), 160 * 1024))) return rc;
       if (g->slots == 0 || g->slots_lds != lds || g->slots_two_step) {
         int per_cu = 0;
@@ -410,6 +416,9 @@ int gen_sweep(hh_ctx* c, const double* d_params, const double* h_params, int64_t
     const size_t lds = bp.lds;
     const bool two_step = bp.two_step;
     const GenRowsPlan rp = bp.rp;
+    g->last_row_kernel[0] = two_step ? rp.r1 : 0;
+    g->last_row_kernel[1] = two_step ? rp.r2 : 0;
+    g->last_row_kernel[2] = (int32_t)(two_step ? rp.lds : lds);
     void (*const fused_kernel)(GenFusedArgs) = d.nx <= 256 ? k_gen_fused<4> : d.nx <= 512 ? k_gen_fused<8> : k_gen_fused<16>;
     int* const d_first = g->d_runs;
     int* const d_imax = g->d_runs + 2 * runs;

@@ -659,6 +659,7 @@ struct hh_gen {
   size_t cap_psum = 0;
   RefConsts* d_ref = nullptr;
   size_t cap_ref = 0;
+  int32_t last_row_kernel[3] = {0, 0, 0};   // the last sweep's row kernel: {R1, R2, LDS bytes}, {0, 0, LDS} Stockham, all zero direct
   bool direct_only = false;       // nx without a row-transform plan (a prime factor above 31): every sweep is gen_sweep_direct
   int s_pad = 0, b_pad = 0;
   size_t kp = 0;

@@ -3892,6 +3892,11 @@ int hh_sweep_device_strided(hh_ctx* c, const double* d_params, const double* h_p
 } HH_CATCH_CTX(c, "hh_sweep_device_strided")
 
 int hh_last_first_pass(const hh_ctx* c) { return c ? c->last_first_pass : HH_ERR_ARG; }
+int hh_last_row_kernel(const hh_ctx* c, int32_t out[3]) try {
+  if (!c || !out) return HH_ERR_ARG;
+  for (int k = 0; k < 3; ++k) out[k] = c->gen ? c->gen->last_row_kernel[k] : 0;
+  return HH_OK;
+} HH_CATCH_CTX(nullptr, "hh_last_row_kernel")
 
 int hh_set_table_path(hh_ctx* c, int mode) try {
   if (!c) return HH_ERR_ARG;

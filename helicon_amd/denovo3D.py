@@ -261,7 +261,12 @@ class SweepEngine:
 
     # -- the hot path -----------------------------------------------------------------------
     def sweep(self, params) -> np.ndarray:
-        """params [G, 4] float64 (twist, rise, csym, rot) -> scores [S, G] float32 (host in, host out)."""
+        """params [G, 4] float64 (twist, rise, csym, rot) -> scores [S, G] float32 (host in, host out).
+
+        On a general image size a list that no row kernel can hold — a row length with a prime factor above 31, or a
+        wide row (from about 890 points) without a two-step pair, or whose pair is declined, whose Stockham launch would
+        need more than 160 KB of LDS — is swept candidate by candidate on the float64 direct path: exact, and orders of
+        magnitude slower.  Nothing is raised; ``last_row_kernel == (0, 0, 0)`` (``last_first_pass == "transform"``) tells."""
         p = np.ascontiguousarray(params, dtype=np.float64).reshape(-1, 4)
         out = np.empty((max(self.n_segments, 1), len(p)), dtype=np.float32)
         with self._lock:
@@ -345,6 +350,15 @@ class SweepEngine:
         "run_tables" (shared-twist tables + second pass), "fused" (shared-twist, no intermediate), "zoom"
         (Fourier-zoomed spectra, ``set_zoom``) or "filtered" (low / high-pass filtered spectra, ``set_filter``)."""
         return {1: "run_tables", 2: "fused", 3: "zoom", 4: "filtered"}.get(self._L.hh_last_first_pass(self._ctx), "transform")
+
+    @property
+    def last_row_kernel(self) -> tuple[int, int, int]:
+        """Row kernel of the last sweep on a general image size (``hh_last_row_kernel``): ``(R1, R2, LDS bytes)`` for the
+        two-step kernel of the pair nx = R1 R2, ``(0, 0, LDS bytes)`` for the Stockham kernel, ``(0, 0, 0)`` for the
+        float64 direct path (and on the tuned power-of-two squares)."""
+        out = (C.c_int32 * 3)()
+        self._check(self._L.hh_last_row_kernel(self._ctx, out))
+        return int(out[0]), int(out[1]), int(out[2])
 
     def synchronize(self):
         with self._lock:

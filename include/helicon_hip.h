@@ -204,6 +204,11 @@ int hh_set_table_path(hh_ctx* ctx, int mode);
  * second pass, 1 = run tables + second pass, 2 = fused, 3 = zoomed spectra (hh_set_spectrum_zoom),
  * 4 = filtered spectra (hh_set_spectrum_filter, with or without a zoom). */
 int hh_last_first_pass(const hh_ctx* ctx);
+/* Which row kernel the last sweep of a general-size context (hh_create2, not a power-of-two square) ran, read-only:
+ * out = {R1, R2, dynamic LDS bytes} for the two-step kernel of the pair nx = R1 R2, {0, 0, LDS bytes} for the Stockham
+ * kernel, {0, 0, 0} for the float64 direct path (a row length with a prime factor above 31, tilt / psi, a launch that
+ * does not fit the LDS) and for any other context.  A list swept in several batches reports its last batch. */
+int hh_last_row_kernel(const hh_ctx* ctx, int32_t out[3]);
 
 /* Pre-sweep image preparation on the device.
  * hh_low_high_pass_filter: helicon.low_high_pass_filter (lib/filters.py:314-372) for one N x N float32 image

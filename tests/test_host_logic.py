@@ -76,6 +76,12 @@ def test_header_symbols_all_exported_and_bound():
     for name in declared:
         assert hasattr(L, name)
     assert L.hh_abi_version() == 1
+    # the read-only query of the general sweep's row kernel: declared, bound, and a NULL context or buffer is an argument error
+    import ctypes as C
+    assert "hh_last_row_kernel" in declared and "int hh_last_row_kernel(const hh_ctx* ctx, int32_t out[3]);" in hdr
+    out = (C.c_int32 * 3)(7, 7, 7)
+    assert L.hh_last_row_kernel(None, out) == -1 and tuple(out) == (7, 7, 7)
+    assert isinstance(H.SweepEngine.last_row_kernel, property)
     assert L.hh_algorithmic_bytes(512) == 3153920
     assert L.hh_algorithmic_bytes(256) == 790528
     assert L.hh_algorithmic_bytes(1024) == 12599296

@@ -1,0 +1,59 @@
+#!/usr/bin/env python3
+"""The band-mask probe of tests/spectrum_bands.py over every row length 8 ... 1024 (CPU only, the reference alone): per
+length the smallest change of a band's oracle score over all adjacent-column swaps, the same for a kx <-> -kx mirror, the
+float32 floor of the reference pipeline and the tolerance that follows from it, for both experimental images of the probe
+(each with the candidate it was made from); prints the worst of each (DESIGN.md,
+"Row-length census").
+    python tools/band_probe_census.py [--jobs 8] [--lo 8] [--hi 1024]"""
+import argparse
+import sys
+from concurrent.futures import ProcessPoolExecutor
+from pathlib import Path
+
+import numpy as np
+
+ROOT = Path(__file__).resolve().parent.parent
+sys.path[:0] = [str(ROOT), str(ROOT / "tests")]
+import spectrum_bands as SB  # noqa: E402
+
+
+def one(nx):
+    probe = SB.probe_for_length(nx)
+    rows = []
+    for log, second in ((True, False), (False, False), (True, True), (False, True)):
+        o = SB.OracleSide(probe, log, image=probe.image2 if second else None)
+        cand = probe.cand2 if second else 0
+        swap, mirror = o.swap_sensitivity(cand), o.mirror_sensitivity(cand)
+        band, k = SB.band_of_frequency(nx), np.abs(np.arange(nx) - nx // 2)
+        paired = [b for b in range(len(mirror)) if np.any((band == b) & (k > 0) & (2 * k != nx))]   # more than self-mirrored columns
+        rows.append((nx, (log, second), len(probe.units), float(swap.min()), float(mirror[paired].min()), float(o.floor.max()), float(o.tol.max()),
+                     float((swap / o.tol).min())))
+    return rows
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--jobs", type=int, default=8)
+    ap.add_argument("--lo", type=int, default=8)
+    ap.add_argument("--hi", type=int, default=1024)
+    a = ap.parse_args()
+    two, stockham, direct = SB.census()
+    family = {**{n: "two-step" for n in two}, **{n: "stockham" for n in stockham}, **{n: "direct" for n in direct}}
+    with ProcessPoolExecutor(a.jobs) as ex:
+        rows = [r for rs in ex.map(one, range(a.lo, a.hi + 1), chunksize=8) for r in rs]
+    for fam in ("two-step", "stockham", "direct"):
+        for log in ((True, False), (False, False), (True, True), (False, True)):
+            sel = [r for r in rows if family[r[0]] == fam and r[1] == log]
+            if not sel:
+                continue
+            w = min(sel, key=lambda r: r[7])
+            print(f"{fam:9s} log={int(log[0])} image {2 if log[1] else 1}: {len(sel)} lengths; smallest swap change {min(r[3] for r in sel):.2e}, smallest mirror change "
+                  f"{min(r[4] for r in sel):.2e}, largest float32 floor {max(r[5] for r in sel):.2e}, largest tolerance {max(r[6] for r in sel):.2e}, "
+                  f"smallest swap / tolerance {w[7]:.0f} (nx = {w[0]}, {w[2]} subunits)")
+    bad = [r for r in rows if r[7] < SB.MARGIN]
+    print(f"{len(rows) // 4} lengths, {len(bad)} (length, spectrum) cases below {SB.MARGIN:.0f} x tolerance" + (f": {bad}" if bad else ""))
+    return 1 if bad else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

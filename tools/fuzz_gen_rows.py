@@ -1,53 +1,52 @@
 #!/usr/bin/env python3
-"""Every row length the two-step row kernel is instantiated for (gen_rows.hip: nx = R1 R2, 109 pairs) against the NumPy
-oracle on a small grid, and against the Stockham kernel where that one fits (run on the GPU box):
-    python tools/fuzz_gen_rows.py [ny]"""
-import ctypes as C
+"""Every row length the row-transform kernels serve (109 two-step pairs of gen_rows.hip, 326 Stockham-only lengths)
+against the NumPy oracle under the kx-band masks of tests/spectrum_bands.py — masks that together see every spectrum
+column, on the probe geometry whose spectrum has no empty column — and against the other device paths (run on the GPU
+box; the suite's own census is tests/test_gpu_row_lengths.py, this prints the figures per length):
+    python tools/fuzz_gen_rows.py [two-step|stockham|all] [ny]"""
 import os
 import sys
 from pathlib import Path
 
 import numpy as np
 
-sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
+ROOT = Path(__file__).resolve().parent.parent
+sys.path[:0] = [str(ROOT), str(ROOT / "tests")]
 import helicon_amd as H  # noqa: E402
-from helicon_amd import _lib  # noqa: E402
-from helicon_amd.grid import build_grid  # noqa: E402
-from oracle import path_b as O  # noqa: E402
+import spectrum_bands as SB  # noqa: E402
 
-ny = int(sys.argv[1]) if len(sys.argv) > 1 else 24
-L = _lib.lib()
-sizes = []
-for nx in range(32, 1025):
-    out = (C.c_int64 * 6)()
-    assert L.hh_general_plan(nx, 2 * (nx // 8) + 1, 7, out) == 0
-    if out[0] and not (nx & (nx - 1) == 0 and nx == ny):
-        sizes.append((nx, int(out[0]), int(out[1])))
+family = sys.argv[1] if len(sys.argv) > 1 else "two-step"
+ny = int(sys.argv[2]) if len(sys.argv) > 2 else SB.NY
+two, stockham, _ = SB.census()
+sizes = sorted(two) * (family in ("two-step", "all")) + stockham * (family in ("stockham", "all"))
 print(f"{len(sizes)} row lengths, ny = {ny}", flush=True)
+
+
+def swept(eng, probe, masks, log, switch=None):
+    if switch:
+        os.environ[switch] = "1"
+    try:
+        got, kernel = SB.device_scores(eng, probe, masks, log)
+        return got[:, 0], kernel
+    finally:
+        if switch:
+            del os.environ[switch]
+
+
 worst, worst_vs = 0.0, 0.0
-for nx, r1, r2 in sizes:
-    apix, tw0, rs0 = 2.0, 31.0, 9.0
-    d, br = 0.4 * ny * apix, 2 * apix
-    clean = O.simulate_helical_projection(1, tw0, rs0, 1, d, br, 0, 0, ny, nx, apix)
-    img = (clean + np.random.default_rng(nx).normal(0, 0.5 * clean.std(), clean.shape)).astype(np.float32)
-    grid = build_grid(tw0 + np.array([-0.6, 0.0]), rs0 + np.array([-0.2, 0.0, 0.3]), (1,), tube_length=nx * apix)
-    mask = O.radial_band_mask(ny, nx)
+for nx in sorted(sizes):
+    probe = SB.probe_for_length(nx, ny)
     with H.SweepEngine((ny, nx)) as eng:
-        eng.set_geometry(apix=apix, helical_diameter=d, ball_radius=br)
-        eng.set_reference(img, mask)
-        got = eng.sweep(grid.params)[0]
-        vs = None
-        if nx <= 600:
-            os.environ["HH_GEN_STOCKHAM"] = "1"
-            try:
-                vs = float(np.abs(eng.sweep(grid.params)[0] - got).max())
-            finally:
-                del os.environ["HH_GEN_STOCKHAM"]
-    ref = O.sweep_cpu(img, grid.params[:, :3], mask, apix=apix, helical_diameter=d, ball_radius=br)
-    err = float(np.abs(got - ref).max())
-    worst = max(worst, err)
-    if vs is not None:
-        worst_vs = max(worst_vs, vs)
-    flag = "" if err < 2e-5 and (vs is None or vs < 5e-6) else "   <-- CHECK"
-    print(f"nx {nx:4d} = {r1:2d} x {r2:2d}: |score - oracle| {err:.2e}" + (f", |two-step - Stockham| {vs:.2e}" if vs is not None else "") + flag, flush=True)
-print(f"done: {len(sizes)} sizes, worst against the oracle {worst:.2e}, against the Stockham kernel {worst_vs:.2e}")
+        eng.set_geometry(**probe.geometry())
+        for log in (True, False):
+            o = SB.OracleSide(probe, log)
+            got, kernel = swept(eng, probe, o.masks, log)
+            err = np.abs(got - o.scores).max(axis=1)
+            vs = float(np.abs(swept(eng, probe, o.masks, log, "HH_GEN_DIRECT")[0] - got).max())
+            if kernel[0] and probe.stockham_lds() <= SB.LDS_LIMIT:
+                vs = max(vs, float(np.abs(swept(eng, probe, o.masks, log, "HH_GEN_STOCKHAM")[0] - got).max()))
+            worst, worst_vs = max(worst, float(err.max())), max(worst_vs, vs)
+            flag = "" if (err <= o.tol).all() and vs <= SB.PATHS_TOL else "   <-- CHECK"
+            print(f"nx {nx:4d} kernel {kernel} log {int(log)}: |score - oracle| {err.max():.2e} (band {int(err.argmax())} of {len(err)}, "
+                  f"tolerance {o.tol[int(err.argmax())]:.1e}), between device paths {vs:.2e}{flag}", flush=True)
+print(f"done: {len(sizes)} sizes, worst against the oracle {worst:.2e}, between device paths {worst_vs:.2e}")
