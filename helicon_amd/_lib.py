@@ -166,6 +166,12 @@ EXPORTS = {
     # Fourier shell / ring correlation (helicon_amd/fsc.py)
     "hh_fsc_3d": (C.c_int, [C.c_int, _f32p, _f32p, C.c_int32, C.c_int32, C.c_int, _f64p, _f64p]),
     "hh_frc_2d": (C.c_int, [C.c_int, _f32p, _f32p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int32, _f64p, _f64p]),
+    # phase-randomised true FSC on a resident context (helicon_amd/true_fsc.py)
+    "hh_tfsc_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, _f32p, _f32p, C.c_int32, C.c_int64, _f64p, _f64p, C.c_uint64]),
+    "hh_tfsc_curves": (C.c_int, [C.c_void_p, _f64p]),
+    "hh_tfsc_download": (C.c_int, [C.c_void_p, C.c_int, _f32p, _f32p]),
+    "hh_tfsc_masked": (C.c_int, [C.c_void_p, _f32p, _f32p, C.c_int32, C.c_int, _f64p, _f64p]),
+    "hh_tfsc_destroy": (C.c_int, [C.c_void_p]),
 }
 
 _lib = None

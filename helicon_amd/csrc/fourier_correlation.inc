@@ -217,43 +217,124 @@ struct FcBuffers {
   }
 };
 
+// The operators of one shape, built in float64 on the host: first pass on the real input, (3-D) second pass on the complex
+// planes, the x pass's tables.  nz == 0: images [ny][nx]; else cubes of side nz = ny = nx.
+struct FcPlan {
+  bool cube = false;
+  int nz = 0, ny = 0, nx = 0, ncol = 0, rows = 0, n1 = 0;
+  int64_t per_map = 0;
+  size_t o_c = 0, o_ms = 0, o_re = 0, o_im = 0, o_xc = 0, o_xs = 0;
+  std::vector<float> mats;
+};
+
+void fc_plan(FcPlan& p, int nz, int ny, int nx) {
+  p.cube = nz > 0;
+  p.nz = nz; p.ny = ny; p.nx = nx;
+  p.ncol = p.cube ? nx / 2 + 1 : nx;
+  p.rows = p.cube ? nz * ny : ny;
+  p.per_map = (int64_t)p.rows * nx;
+  p.n1 = p.cube ? nz : ny;
+  std::vector<double> c, s;
+  fc_trig(p.n1, c, s);
+  p.o_c = fc_operator(p.mats, p.n1, c, 1.0, nullptr, 0.0);
+  p.o_ms = fc_operator(p.mats, p.n1, s, -1.0, nullptr, 0.0);
+  if (p.cube) {
+    fc_trig(ny, c, s);
+    p.o_re = fc_operator(p.mats, ny, c, 1.0, &s, 1.0);
+    p.o_im = fc_operator(p.mats, ny, s, -1.0, &c, 1.0);
+  }
+  fc_trig(nx, c, s);
+  p.o_xc = fc_xtable(p.mats, nx, p.ncol, c);
+  p.o_xs = fc_xtable(p.mats, nx, p.ncol, s);
+}
+
+// The passes before the last one on device-resident input: `in` holds 2 nb real maps (the first members, then the second
+// members), p1 / p2 are [re | im] plane pairs of 4 nb maps each (p2: cubes only), mats the plan's operators on the device.
+// Also max |x| of every map and the pairs' scales.  The planes the x pass reads come back in xre / xim.
+void fc_passes(const FcPlan& p, const float* in, float* p1, float* p2, const float* mats, unsigned* amax, double* scale, int64_t nb,
+               const float** xre, const float** xim) {
+  const int64_t maps = 2 * nb, per_map = p.per_map;
+  const int nx = p.nx, ny = p.ny, nz = p.nz, n1 = p.n1;
+  float* const re1 = p1;
+  float* const im1 = p1 + maps * per_map;
+  hipLaunchKernelGGL(k_fc_absmax, dim3((unsigned)std::min<int64_t>((per_map + 255) / 256, 256), (unsigned)maps), dim3(256), 0, nullptr,
+                     in, per_map, amax);
+  hipLaunchKernelGGL(k_fc_scales, dim3((unsigned)((nb + 63) / 64)), dim3(64), 0, nullptr, amax, (int)nb, (double)per_map, scale);
+  // first pass: the real input along z (cubes: P = ny nx, one map per grid.z) or along y (images: P = nx)
+  for (int part = 0; part < 2; ++part) {
+    CircPass g{};
+    g.a = mats + (part == 0 ? p.o_c : p.o_ms);
+    g.b0 = in; g.b1 = nullptr;
+    g.y = part == 0 ? re1 : im1;
+    g.n = n1; g.ka = n1;
+    g.np = p.cube ? (int64_t)ny * nx : nx; g.sk = g.np; g.sp = 1; g.sb = per_map;
+    hipLaunchKernelGGL(k_circ_gemm<false>, dim3((unsigned)((g.np + MF_T - 1) / MF_T), (unsigned)((n1 + MF_T - 1) / MF_T), (unsigned)maps),
+                       dim3(256), 0, nullptr, g);
+  }
+  *xre = re1; *xim = im1;
+  if (p.cube) {   // second pass along y: one z slice of one map per grid.z, K = 2 ny over the [re; im] planes
+    float* const re2 = p2;
+    float* const im2 = p2 + maps * per_map;
+    for (int part = 0; part < 2; ++part) {
+      CircPass g{};
+      g.a = mats + (part == 0 ? p.o_re : p.o_im);
+      g.b0 = re1; g.b1 = im1;
+      g.y = part == 0 ? re2 : im2;
+      g.n = ny; g.ka = 2 * ny;
+      g.np = nx; g.sk = nx; g.sp = 1; g.sb = (int64_t)ny * nx;
+      hipLaunchKernelGGL(k_circ_gemm<false>, dim3((unsigned)((nx + MF_T - 1) / MF_T), (unsigned)((ny + MF_T - 1) / MF_T), (unsigned)(maps * nz)),
+                         dim3(256), 0, nullptr, g);
+    }
+    *xre = re2; *xim = im2;
+  }
+}
+
+// All passes of nb pairs on device-resident input, down to the float64 sums [nb][nshell][3] on the device (acc: zeroed here)
+void fc_device(const FcPlan& p, const float* in, float* p1, float* p2, const float* mats, const int32_t* shell, unsigned* amax, double* scale,
+               long long* acc, double* sums, int64_t nb, int nshell, bool weighted) {
+  (void)hipMemsetAsync(amax, 0, (size_t)(2 * nb) * sizeof(unsigned), nullptr);
+  (void)hipMemsetAsync(acc, 0, (size_t)nb * nshell * 3 * sizeof(long long), nullptr);
+  const float *xre = nullptr, *xim = nullptr;
+  fc_passes(p, in, p1, p2, mats, amax, scale, nb, &xre, &xim);
+  FcXPass x{};
+  x.re = xre; x.im = xim;
+  x.cs = mats + p.o_xc; x.sn = mats + p.o_xs;
+  x.shell = p.cube ? nullptr : shell;
+  x.scale = scale; x.acc = acc;
+  x.batch = (int)nb; x.rows = p.rows; x.nx = p.nx; x.ncol = p.ncol; x.n = p.nx; x.nshell = nshell; x.weighted = weighted ? 1 : 0;
+  hipLaunchKernelGGL(k_fc_xpass, dim3((unsigned)((p.rows + FC_T - 1) / FC_T), (unsigned)((p.ncol + FC_T - 1) / FC_T), (unsigned)nb), dim3(256), 0,
+                     nullptr, x);
+  const int64_t total = nb * nshell * 3;
+  hipLaunchKernelGGL(k_fc_finish, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, nullptr, acc, scale, nshell, total, sums);
+}
+
+// chunk of a batch of pairs: input + one or two plane pairs within the scratch cap, and the y pass's grid.z = 2 chunk nz <= 65535
+int64_t fc_chunk(const FcPlan& p, int64_t batch) {
+  const int64_t bytes_per_pair = (int64_t)(p.cube ? 10 : 6) * p.per_map * (int64_t)sizeof(float);
+  int64_t chunk = std::max<int64_t>(1, FC_SCRATCH_BYTES / bytes_per_pair);
+  chunk = std::min<int64_t>(chunk, p.cube ? 65535 / (2 * p.nz) : 32767);
+  return std::min<int64_t>(chunk, batch);
+}
+
 // nz == 0: images [ny][nx] with the host's shell table; else cubes of side nz = ny = nx
 int fc_run(const char* name, int device, const float* a, const float* b, int64_t batch, int nz, int ny, int nx, const int32_t* shell,
            int nshell, bool weighted, double* sums, double* kernel_ms) {
-  const bool cube = nz > 0;
-  const int ncol = cube ? nx / 2 + 1 : nx;
-  const int rows = cube ? nz * ny : ny;
-  const int64_t per_map = (int64_t)rows * nx;
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
     return fail(nullptr, HH_ERR_HIP, std::string(name) + ": no such HIP device (there is no CPU fallback)");
   HH_HIP(nullptr, hipSetDevice(device));
-  // operators: first pass on the real input, (3-D) second pass on the complex planes, the x pass's tables
-  std::vector<float> mats;
-  std::vector<double> c, s;
-  fc_trig(cube ? nz : ny, c, s);
-  const int n1 = cube ? nz : ny;
-  const size_t o_c = fc_operator(mats, n1, c, 1.0, nullptr, 0.0), o_ms = fc_operator(mats, n1, s, -1.0, nullptr, 0.0);
-  size_t o_re = 0, o_im = 0;
-  if (cube) {
-    fc_trig(ny, c, s);
-    o_re = fc_operator(mats, ny, c, 1.0, &s, 1.0);
-    o_im = fc_operator(mats, ny, s, -1.0, &c, 1.0);
-  }
-  fc_trig(nx, c, s);
-  const size_t o_xc = fc_xtable(mats, nx, ncol, c), o_xs = fc_xtable(mats, nx, ncol, s);
-  // chunk of the batch: input + one or two plane pairs within the scratch cap, and the y pass's grid.z = 2 chunk nz <= 65535
-  const int64_t bytes_per_pair = (int64_t)(cube ? 10 : 6) * per_map * (int64_t)sizeof(float);
-  int64_t chunk = std::max<int64_t>(1, FC_SCRATCH_BYTES / bytes_per_pair);
-  chunk = std::min<int64_t>(chunk, cube ? 65535 / (2 * nz) : 32767);
-  chunk = std::min<int64_t>(chunk, batch);
+  FcPlan p;
+  fc_plan(p, nz, ny, nx);
+  const bool cube = p.cube;
+  const int64_t per_map = p.per_map;
+  const int64_t chunk = fc_chunk(p, batch);
   FcBuffers d;
   const size_t map_bytes = (size_t)per_map * sizeof(float);
   HH_HIP(nullptr, hipMalloc(&d.in, 2 * (size_t)chunk * map_bytes));
   HH_HIP(nullptr, hipMalloc(&d.p1, 4 * (size_t)chunk * map_bytes));
   if (cube) HH_HIP(nullptr, hipMalloc(&d.p2, 4 * (size_t)chunk * map_bytes));
-  HH_HIP(nullptr, hipMalloc(&d.mats, mats.size() * sizeof(float)));
-  HH_HIP(nullptr, hipMemcpy(d.mats, mats.data(), mats.size() * sizeof(float), hipMemcpyHostToDevice));
+  HH_HIP(nullptr, hipMalloc(&d.mats, p.mats.size() * sizeof(float)));
+  HH_HIP(nullptr, hipMemcpy(d.mats, p.mats.data(), p.mats.size() * sizeof(float), hipMemcpyHostToDevice));
   if (!cube) {
     HH_HIP(nullptr, hipMalloc(&d.shell, (size_t)per_map * sizeof(int32_t)));
     HH_HIP(nullptr, hipMemcpy(d.shell, shell, (size_t)per_map * sizeof(int32_t), hipMemcpyHostToDevice));
@@ -268,57 +349,13 @@ int fc_run(const char* name, int device, const float* a, const float* b, int64_t
   double ms_total = 0.0;
   for (int64_t b0 = 0; b0 < batch; b0 += chunk) {
     const int64_t nb = std::min(chunk, batch - b0);
-    const int64_t maps = 2 * nb;
-    float* const re1 = d.p1;
-    float* const im1 = d.p1 + maps * per_map;
     HH_HIP(nullptr, hipMemcpy(d.in, a + b0 * per_map, (size_t)nb * map_bytes, hipMemcpyHostToDevice));
     HH_HIP(nullptr, hipMemcpy(d.in + nb * per_map, b + b0 * per_map, (size_t)nb * map_bytes, hipMemcpyHostToDevice));
-    HH_HIP(nullptr, hipMemsetAsync(d.amax, 0, (size_t)maps * sizeof(unsigned), nullptr));
-    HH_HIP(nullptr, hipMemsetAsync(d.acc, 0, (size_t)nb * nshell * 3 * sizeof(long long), nullptr));
     HH_HIP(nullptr, hipEventRecord(d.ev0, nullptr));
-    hipLaunchKernelGGL(k_fc_absmax, dim3((unsigned)std::min<int64_t>((per_map + 255) / 256, 256), (unsigned)maps), dim3(256), 0, nullptr,
-                       d.in, per_map, d.amax);
-    hipLaunchKernelGGL(k_fc_scales, dim3((unsigned)((nb + 63) / 64)), dim3(64), 0, nullptr, d.amax, (int)nb, (double)per_map, d.scale);
-    // first pass: the real input along z (cubes: P = ny nx, one map per grid.z) or along y (images: P = nx)
-    for (int part = 0; part < 2; ++part) {
-      CircPass g{};
-      g.a = d.mats + (part == 0 ? o_c : o_ms);
-      g.b0 = d.in; g.b1 = nullptr;
-      g.y = part == 0 ? re1 : im1;
-      g.n = n1; g.ka = n1;
-      g.np = cube ? (int64_t)ny * nx : nx; g.sk = g.np; g.sp = 1; g.sb = per_map;
-      hipLaunchKernelGGL(k_circ_gemm<false>, dim3((unsigned)((g.np + MF_T - 1) / MF_T), (unsigned)((n1 + MF_T - 1) / MF_T), (unsigned)maps),
-                         dim3(256), 0, nullptr, g);
-    }
-    const float *xre = re1, *xim = im1;
-    if (cube) {   // second pass along y: one z slice of one map per grid.z, K = 2 ny over the [re; im] planes
-      float* const re2 = d.p2;
-      float* const im2 = d.p2 + maps * per_map;
-      for (int part = 0; part < 2; ++part) {
-        CircPass g{};
-        g.a = d.mats + (part == 0 ? o_re : o_im);
-        g.b0 = re1; g.b1 = im1;
-        g.y = part == 0 ? re2 : im2;
-        g.n = ny; g.ka = 2 * ny;
-        g.np = nx; g.sk = nx; g.sp = 1; g.sb = (int64_t)ny * nx;
-        hipLaunchKernelGGL(k_circ_gemm<false>, dim3((unsigned)((nx + MF_T - 1) / MF_T), (unsigned)((ny + MF_T - 1) / MF_T), (unsigned)(maps * nz)),
-                           dim3(256), 0, nullptr, g);
-      }
-      xre = re2; xim = im2;
-    }
-    FcXPass x{};
-    x.re = xre; x.im = xim;
-    x.cs = d.mats + o_xc; x.sn = d.mats + o_xs;
-    x.shell = cube ? nullptr : d.shell;
-    x.scale = d.scale; x.acc = d.acc;
-    x.batch = (int)nb; x.rows = rows; x.nx = nx; x.ncol = ncol; x.n = nx; x.nshell = nshell; x.weighted = weighted ? 1 : 0;
-    hipLaunchKernelGGL(k_fc_xpass, dim3((unsigned)((rows + FC_T - 1) / FC_T), (unsigned)((ncol + FC_T - 1) / FC_T), (unsigned)nb), dim3(256), 0,
-                       nullptr, x);
-    const int64_t total = nb * nshell * 3;
-    hipLaunchKernelGGL(k_fc_finish, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, nullptr, d.acc, d.scale, nshell, total, d.sums);
+    fc_device(p, d.in, d.p1, d.p2, d.mats, d.shell, d.amax, d.scale, d.acc, d.sums, nb, nshell, weighted);
     HH_HIP(nullptr, hipGetLastError());
     HH_HIP(nullptr, hipEventRecord(d.ev1, nullptr));
-    HH_HIP(nullptr, hipMemcpy(sums + b0 * nshell * 3, d.sums, (size_t)total * sizeof(double), hipMemcpyDeviceToHost));
+    HH_HIP(nullptr, hipMemcpy(sums + b0 * nshell * 3, d.sums, (size_t)nb * nshell * 3 * sizeof(double), hipMemcpyDeviceToHost));
     float ms = 0.f;
     HH_HIP(nullptr, hipEventElapsedTime(&ms, d.ev0, d.ev1));
     ms_total += ms;

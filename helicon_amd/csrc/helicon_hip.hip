@@ -4549,3 +4549,4 @@ int hh_profile_get(hh_ctx* c, hh_profile* out) try {
 #include "filtered_sweep.inc"  // the sweep on low / high-pass filtered spectra (hh_set_spectrum_filter): y pass + fused x pass / moments
 #include "symmetry_search.inc"  // helical symmetry search of a 3-D map: batched (twist, rise, Csym) scores of a device-resident map (hh_hs_*)
 #include "fourier_correlation.inc"  // Fourier shell / ring correlation of batches of map or image pairs: DFT passes on the f32 MFMA, fused last pass (hh_fsc_3d, hh_frc_2d)
+#include "true_fsc.inc"  // phase-randomised (noise-substituted) true FSC of two half maps on a resident context: stored spectrum, inverse passes, masked curves (hh_tfsc_*)

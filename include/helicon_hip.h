@@ -536,6 +536,29 @@ int hh_fsc_3d(int device, const float* maps1, const float* maps2, int32_t batch,
 int hh_frc_2d(int device, const float* imgs1, const float* imgs2, int32_t batch, int32_t ny, int32_t nx, const int32_t* shell,
               int32_t n_shells, double* sums, double* kernel_ms);
 
+/* ---------------------------------------------------------------------------------------------
+ * Phase-randomised ("true") FSC of two half maps (csrc/true_fsc.inc; commands/trueFSC.py, lib/filters.py:469-520
+ * randomize_phases_lowpass).  A context keeps one pair of cubic maps of EVEN side n in [8, 512] on the device, together with
+ * their phase-randomised versions: every bin of the rfftn half spectrum with kz^2 + ky^2 + kx^2 >= m_cut (folded integer
+ * frequencies) becomes |F| e^{i theta}, the bins below stay as they are; the maps come back through the inverse transform
+ * with irfftn's semantics.  theta: phases1 / phases2 (host float64 [n][n][n / 2 + 1], radians; both or neither), or, when they
+ * are NULL, a Philox4x32-10 draw with key = seed and counter = (bin index, map index).  Errors: hh_last_error(NULL). */
+typedef struct hh_tfsc hh_tfsc;
+int hh_tfsc_create(hh_tfsc** out, int device, const float* map1, const float* map2, int32_t n, int64_t m_cut,
+                   const double* phases1, const double* phases2, uint64_t seed);
+/* sums: [2][n / 2 + 1][3] num, den1, den2 of the unmasked curve and of the randomised-unmasked curve (every bin of the half
+ * spectrum once, as calc_fsc counts them); the first equals hh_fsc_3d(full_spectrum = 0) bit for bit */
+int hh_tfsc_curves(hh_tfsc* ctx, double* sums);
+/* which = 0 / 1: the randomised map [n][n][n] (map_out, may be NULL) and / or its stored half spectrum, interleaved
+ * complex64 [n][n][n / 2 + 1][2] (spec_out, may be NULL) */
+int hh_tfsc_download(hh_tfsc* ctx, int which, float* map_out, float* spec_out);
+/* masks1 (and masks2, or NULL: one mask for both members): host float32 [batch][n][n][n].  sums: [batch][2][n / 2 + 1][3] of
+ * the pairs (map1 m1, map2 m2) and (map1r m1, map2r m2), with hh_fsc_3d's meaning of full_spectrum and its guarantees:
+ * bit-identical from run to run, independent of the batch and of a mask's place in it.  Only the masks are uploaded. */
+int hh_tfsc_masked(hh_tfsc* ctx, const float* masks1, const float* masks2, int32_t batch, int full_spectrum, double* sums,
+                   double* kernel_ms);
+int hh_tfsc_destroy(hh_tfsc* ctx);
+
 #ifdef __cplusplus
 }
 #endif

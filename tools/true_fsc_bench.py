@@ -1,0 +1,184 @@
+#!/usr/bin/env python3
+"""Times of the phase-randomised true FSC on the device (helicon_amd/true_fsc.py, csrc/true_fsc.inc).
+
+    python tools/true_fsc_bench.py [--out profiles/true_fsc.json] [--sizes 64 128 256] [--repeats 5] [--accuracy LOG]
+
+Per size, one pair of n^3 maps (a blob plus noise, so that the adaptive mask has something to find), after a warm-up of every
+call that is timed; medians of REPEATS:
+
+* ``create``: ``TrueFSC(map1, map2, apix, cutoff, seed=1)`` — upload of two maps, forward passes, substitution, inverse
+  passes; wall (host clock; the call ends in a device synchronise) only;
+* ``masked``: one ``.masked(mask, per_shell=True)`` on the resident context — wall, and ``kernel_ms`` from device events;
+* ``masked_batch_8``: one ``.masked_batch`` of 8 masks — the same two numbers, also per mask;
+* ``parent_one_mask``: what the parent commit offers for one mask: four host multiplies and two ``calc_fsc_per_shell`` calls
+  (the randomised maps taken from the context beforehand, outside the timing) — wall;
+* ``host_composition``: ``scipy.fft.rfftn`` / ``irfftn`` / ``fftn(workers=16)`` + ``bincount`` for the whole method with one
+  mask on the host — wall;
+* ``refine``: a whole ``true_fsc(one_mask=True, refine_mask=True, seed=1)`` run — wall, the seconds of it spent in the host's
+  mask helpers (``host_mask_s``), the number of ``.masked`` evaluations, one run.
+
+THE GATE: at 128^3 and 256^3 ``masked.wall_ms`` must not exceed ``parent_one_mask.wall_ms`` of the same run (same kernels,
+one mask uploaded instead of four maps): both are printed, and the tool exits 1 if it is missed.  With ``--accuracy LOG`` the
+TFSC_FIGURE lines of a ``pytest tests/test_gpu_true_fsc.py -s`` log are parsed into the ``accuracy`` section.  A run without
+a GPU fails: there is nothing to time.
+"""
+import argparse
+import importlib
+import json
+import re
+import sys
+import time
+from pathlib import Path
+
+import numpy as np
+
+ROOT = Path(__file__).resolve().parents[1]
+sys.path.insert(0, str(ROOT))
+sys.path.insert(0, str(ROOT / "tests"))
+
+
+def median_wall(fn, repeats):
+    walls = []
+    for _ in range(repeats):
+        t = time.perf_counter()
+        fn()
+        walls.append((time.perf_counter() - t) * 1e3)
+    return float(np.median(walls))
+
+
+def parse_figures(path):
+    out = {}
+    keys = ("n", "map", "per_shell")
+    for line in Path(path).read_text().splitlines():
+        m = re.search(r"TFSC_FIGURE (.*)$", line)
+        if not m:
+            continue
+        words = m.group(1).split()
+        name = " ".join(w for w in words if "=" not in w or w.split("=")[0] in keys)
+        out[name] = {w.split("=")[0]: w.split("=", 1)[1] for w in words if "=" in w and w.split("=")[0] not in keys}
+    return out
+
+
+def host_composition(a, b, mask, m_sel, shell_full, angles):
+    """The whole method with one mask on the host: 2 rfftn, substitution, 2 irfftn, 4 multiplies, 4 fftn, 2 x 3 bincounts."""
+    from scipy.fft import fftn, irfftn, rfftn
+
+    out = []
+    maps = []
+    for x, th in zip((a, b), angles):
+        F = rfftn(x, workers=16)
+        F[m_sel] = np.abs(F[m_sel]) * np.exp(1j * th[m_sel])
+        maps.append(irfftn(F, workers=16))
+    nb = a.shape[0] // 2 + 1
+    s = shell_full.ravel()
+    for p, q in ((a, b), maps):
+        f1, f2 = fftn(p * mask, workers=16), fftn(q * mask, workers=16)
+        out.append(np.stack([np.bincount(s, weights=np.real(f1 * np.conj(f2)).ravel(), minlength=nb),
+                             np.bincount(s, weights=(np.abs(f1) ** 2).ravel(), minlength=nb),
+                             np.bincount(s, weights=(np.abs(f2) ** 2).ravel(), minlength=nb)], axis=1))
+    return out
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--sizes", type=int, nargs="*", default=[64, 128, 256])
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--accuracy", default=None, help="log of `pytest tests/test_gpu_true_fsc.py -s` to take the measured errors from")
+    ap.add_argument("--no-refine", action="store_true", help="leave the whole-run timing out")
+    args = ap.parse_args(argv)
+
+    import fsc_oracle as O
+    import true_fsc_oracle as TO
+    import helicon_amd as H
+
+    T = importlib.import_module("helicon_amd.true_fsc")
+    apix = 2.0
+    result = {"repeats": args.repeats, "cases": [], "gate": {}}
+    missed = False
+    for n in args.sizes:
+        a, b = O.make_map_pair(n, 500 + n, dc="auto")
+        g = np.arange(n) - n // 2
+        blob = 6.0 * np.exp(-(g[:, None, None] ** 2 + g[None, :, None] ** 2 + g[None, None, :] ** 2) / (2.0 * (n / 6.0) ** 2))
+        a, b = (a + blob).astype(np.float32), (b + blob).astype(np.float32)
+        cutoff = apix * n / (n / 4 + 0.5)
+        masks = np.stack([TO.sphere_mask(n, (0.2 + 0.02 * j) * n, 4.0) for j in range(8)]).astype(np.float32)
+        mask = masks[5]
+        case = {"case": f"1 x {n}^3", "n": n}
+
+        def create():
+            H.TrueFSC(a, b, apix, cutoff, seed=1).close()
+
+        create()
+        case["create"] = {"wall_ms": median_wall(create, args.repeats)}
+        with H.TrueFSC(a, b, apix, cutoff, seed=1) as ctx:
+            ar, br = ctx.randomized_map(0), ctx.randomized_map(1)
+
+            def parent():
+                t = H.calc_fsc_per_shell(a * mask, b * mask, apix)
+                nz = H.calc_fsc_per_shell(ar * mask, br * mask, apix)
+                return t, nz
+
+            # alternate the two sides of the gate: other work shares the host
+            ctx.masked(mask, per_shell=True)
+            parent()
+            w_dev, w_par, k_dev = [], [], []
+            for _ in range(args.repeats):
+                t0 = time.perf_counter()
+                got = ctx.masked(mask, per_shell=True)
+                w_dev.append((time.perf_counter() - t0) * 1e3)
+                k_dev.append(ctx.kernel_ms)
+                t0 = time.perf_counter()
+                want = parent()
+                w_par.append((time.perf_counter() - t0) * 1e3)
+            case["masked"] = {"wall_ms": float(np.median(w_dev)), "kernel_ms": float(np.median(k_dev))}
+            case["parent_one_mask"] = {"wall_ms": float(np.median(w_par))}
+            case["masked_equals_parent_bitwise"] = bool(np.array_equal(got[0], want[0]) and np.array_equal(got[1], want[1]))
+            ctx.masked_batch(masks, per_shell=True)
+            k8 = []
+
+            def batch8():
+                ctx.masked_batch(masks, per_shell=True)
+                k8.append(ctx.kernel_ms)
+
+            w8 = median_wall(batch8, args.repeats)
+            case["masked_batch_8"] = {"wall_ms": w8, "kernel_ms": float(np.median(k8)), "wall_ms_per_mask": w8 / 8,
+                                      "kernel_ms_per_mask": float(np.median(k8)) / 8}
+        m_sel = TO.m_half(n) >= T.cutoff_m(n, apix, cutoff)
+        shell_full = O.shell_3d_full(n)
+        rng = np.random.RandomState(1)
+        angles = [rng.uniform(0, 2 * np.pi, size=m_sel.shape) for _ in range(2)]
+        host_composition(a, b, mask, m_sel, shell_full, angles)
+        case["host_composition"] = {"wall_ms": median_wall(lambda: host_composition(a, b, mask, m_sel, shell_full, angles), max(1, args.repeats // 2))}
+        if not args.no_refine:
+            calls = [0]
+
+            class Counting(H.TrueFSC):
+                def masked(self, *p, **k):
+                    calls[0] += 1
+                    return super().masked(*p, **k)
+
+            t0 = time.perf_counter()
+            out = T.true_fsc(a, b, apix, cutoff_res=cutoff, one_mask=True, refine_mask=True, seed=1, context=Counting)
+            wall = time.perf_counter() - t0
+            case["refine"] = {"wall_s": wall, "host_mask_s": out["host_mask_s"], "device_and_rest_s": wall - out["host_mask_s"],
+                              "masked_calls": calls[0], "mask_soft_px": out["mask_soft_px"], "resolution": out["resolution"]}
+        if n >= 128:
+            ok = case["masked"]["wall_ms"] <= case["parent_one_mask"]["wall_ms"]
+            result["gate"][str(n)] = {"masked_wall_ms": case["masked"]["wall_ms"], "parent_wall_ms": case["parent_one_mask"]["wall_ms"],
+                                      "passed": bool(ok)}
+            print(f"GATE n={n}: masked {case['masked']['wall_ms']:.3f} ms, parent {case['parent_one_mask']['wall_ms']:.3f} ms: "
+                  f"{'ok' if ok else 'MISSED'}", flush=True)
+            missed = missed or not ok
+        result["cases"].append(case)
+        print(json.dumps(case), flush=True)
+    if args.accuracy:
+        result["accuracy"] = parse_figures(args.accuracy)
+    if args.out:
+        Path(args.out).parent.mkdir(parents=True, exist_ok=True)
+        Path(args.out).write_text(json.dumps(result, indent=1) + "\n")
+    return 1 if missed else 0
+
+
+if __name__ == "__main__":
+    raise SystemExit(main())
