@@ -2,8 +2,9 @@
 Python signatures.  Hand-written gfx950 kernels in ``csrc/``, reached through the C ABI of
 ``include/helicon_hip.h``; importing this package does not touch the GPU."""
 from .grid import (CandidateGrid, build_grid, layer_line_mask, radial_band_mask, set_to_periodic_range,
-                   shard_bounds, sweep_axis, zoom_spec, filter_spec)
-from .denovo3D import (SweepEngine, SweepResult, apply_helical_symmetry, auto_horizontalize, compute_power_spectra,
+                   shard_bounds, sweep_axis, zoom_spec, filter_spec, phase_spec)
+from .denovo3D import (SweepEngine, SweepResult, apply_helical_symmetry, auto_horizontalize,
+                       compute_phase_difference_across_meridian, compute_power_spectra,
                        cosine_similarity, cross_correlation_coefficient, down_scale,
                        estimate_helix_rotation_center_diameter, generate_xyz_projections, is_vertical, low_high_pass_filter,
                        low_high_pass_filter_3d, process_one_task,

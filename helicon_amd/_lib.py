@@ -80,11 +80,14 @@ EXPORTS = {
     "hh_set_geometry": (C.c_int, [_ctx, C.POINTER(hh_geom)]),
     "hh_set_spectrum_zoom": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_double, C.c_double]),
     "hh_set_spectrum_filter": (C.c_int, [_ctx, C.c_double, C.c_double]),
+    "hh_set_spectrum_phase": (C.c_int, [_ctx, C.c_double]),
     "hh_set_reference": (C.c_int, [_ctx, _f32p, C.c_int, C.POINTER(C.c_uint8), C.c_int]),
     "hh_sweep": (C.c_int, [_ctx, _f64p, C.c_int64, _f32p]),
     "hh_sweep_device": (C.c_int, [_ctx, C.c_void_p, C.c_int64, C.c_void_p]),
     "hh_sweep_device_mirrored": (C.c_int, [_ctx, C.c_void_p, _f64p, C.c_int64, C.c_void_p]),
     "hh_sweep_device_strided": (C.c_int, [_ctx, C.c_void_p, _f64p, C.c_int64, C.c_void_p, C.c_int64]),
+    "hh_sweep_parts": (C.c_int, [_ctx, _f64p, C.c_int64, _f32p, _f32p, _f32p]),
+    "hh_phase_map": (C.c_int, [_ctx, _f32p, C.c_int, _f32p, _f32p]),
     "hh_set_table_path": (C.c_int, [_ctx, C.c_int]),
     "hh_last_first_pass": (C.c_int, [_ctx]),
     "hh_last_row_kernel": (C.c_int, [_ctx, C.POINTER(C.c_int32)]),

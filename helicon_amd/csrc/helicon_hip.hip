@@ -2445,6 +2445,7 @@ struct EventPair {
 #include "path_a.inc"         // Path A (sparse least-squares scorer): projector kernels and struct hh_pa
 
 struct hh_zoom;   // zoom_sweep.inc: the sweep on Fourier-zoomed spectra (hh_set_spectrum_zoom)
+struct hh_phase;  // phase_sweep.inc: the sweep's phase score across the meridian (hh_set_spectrum_phase)
 
 struct hh_ctx {
   int device = 0;
@@ -2454,6 +2455,7 @@ struct hh_ctx {
   void* comm = nullptr;          // ncclComm_t of hh_comm_init (RCCL, loaded on first use)
   hh_gen* gen = nullptr;
   hh_zoom* zoom = nullptr;
+  hh_phase* phase = nullptr;
   double apix = 0;               // hh_set_geometry's pixel size in full precision (the zoomed frequencies use it)
   int max_batch = 0;
   int n_cu = 0;                  // compute units of the device
@@ -2500,7 +2502,7 @@ struct hh_ctx {
   int* d_cgs = nullptr;          // fused pass: [max_batch][N/4]
   size_t cap_eg = 0, cap_cgs = 0;
   int cap_partials = 0;          // candidates per half of d_partials
-  int last_first_pass = 0;       // what the last sweep ran: 0 per-candidate transform, 1 run tables, 2 fused, 3 zoomed spectra, 4 filtered spectra
+  int last_first_pass = 0;       // what the last sweep ran: 0 per-candidate transform, 1 run tables, 2 fused, 3 zoomed spectra, 4 filtered spectra, 5 phase score
   unsigned long long kb_mask = ~0ull;
   int s_pad = 0, b_pad = 0;
   float2* d_spec = nullptr;      // [N/2+1][N] scratch (grown for S segments)
@@ -2535,6 +2537,13 @@ void zoom_free(hh_ctx* c);
 int zoom_set_reference(hh_ctx* c, const float* images, int n_segments, const uint8_t* mask, int log_flag);
 int zoom_sweep(hh_ctx* c, const double* d_params, int64_t n_cand, float* d_scores, int64_t ld);
 int64_t zoom_filter_bytes(const hh_ctx* c);   // device bytes of the spectrum filter's buffers (hh_set_spectrum_filter)
+
+// the phase score across the meridian (phase_sweep.inc, included at the end of the file); it scores through the zoom's
+// reference side, at the identity zoom when no zoom is set
+bool phase_on(const hh_ctx* c);
+void phase_free(hh_ctx* c);
+int phase_sweep(hh_ctx* c, const double* d_params, int64_t n_cand, float* d_scores, int64_t ld, float* d_amp = nullptr,
+                float* d_phase = nullptr);
 
 int fail(hh_ctx* c, int code, const std::string& msg) {
   if (c) c->err = msg; else g_create_error = msg;
@@ -3302,6 +3311,7 @@ int sweep_transform(hh_ctx* c, const double* d_params, int64_t g, float* d_score
 // their `g` argument for that addressing, so they are handed ld.
 int sweep_on_device(hh_ctx* c, const double* d_params, const int64_t n_cand, float* d_scores,
                     const double* h_params = nullptr, int64_t ld = 0) {
+  if (phase_on(c)) return phase_sweep(c, d_params, n_cand, d_scores, ld);
   if (zoom_on(c)) return zoom_sweep(c, d_params, n_cand, d_scores, ld);
   if (c->general) return gen_sweep(c, d_params, h_params, n_cand, d_scores, ld);
   RunPlan plan = plan_runs(c, h_params, n_cand);
@@ -3571,6 +3581,7 @@ void hh_destroy(hh_ctx* c) try {
   (void)hipFree(c->d_spec);
   (void)hipFree(c->d_img);
   gen_free(c);
+  phase_free(c);
   zoom_free(c);
   if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
   delete c;
@@ -3708,7 +3719,7 @@ int hh_set_geometry(hh_ctx* c, const hh_geom* g) try {
   }
   HH_HIP(c, hipMemcpyAsync(c->d_units, units.data(), units.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
   HH_HIP(c, hipStreamSynchronize(c->stream));
-  if (zoom_on(c) && g->apix != c->apix) c->n_segments = 0;   // the zoomed frequencies scale with the pixel size: new reference
+  if ((zoom_on(c) || phase_on(c)) && g->apix != c->apix) c->n_segments = 0;   // the zoomed frequencies scale with the pixel size: new reference
   c->geom = d;
   c->apix = g->apix;
   c->have_geom = true;
@@ -3718,7 +3729,7 @@ int hh_set_geometry(hh_ctx* c, const hh_geom* g) try {
 int hh_set_reference(hh_ctx* c, const float* images, int n_segments, const uint8_t* mask, int log_flag) try {
   if (!c || !images || !mask || n_segments <= 0) return fail(c, HH_ERR_ARG, "hh_set_reference: bad argument");
   HH_HIP(c, hipSetDevice(c->device));
-  if (zoom_on(c)) return zoom_set_reference(c, images, n_segments, mask, log_flag);
+  if (zoom_on(c) || phase_on(c)) return zoom_set_reference(c, images, n_segments, mask, log_flag);
   if (c->general) return gen_set_reference(c, images, n_segments, mask, log_flag);
   const int n = c->n;
   const size_t npix = (size_t)n * n, nh = (size_t)(n / 2 + 1) * n;
@@ -4547,6 +4558,7 @@ int hh_profile_get(hh_ctx* c, hh_profile* out) try {
 #include "path_a_batch.inc"  // Path A for many candidates at once, device-resident solve (hh_pab_*)
 #include "map_filter.inc"  // the 3-D map input: separable Gaussian filter of a whole map on the f32 MFMA, axis projections
 #include "filtered_sweep.inc"  // the sweep on low / high-pass filtered spectra (hh_set_spectrum_filter): y pass + fused x pass / moments
+#include "phase_sweep.inc"  // the sweep's phase score across the meridian (hh_set_spectrum_phase): four real products kept apart, F and its partner at -f_y from the same MFMAs
 #include "symmetry_search.inc"  // helical symmetry search of a 3-D map: batched (twist, rise, Csym) scores of a device-resident map (hh_hs_*)
 #include "fourier_correlation.inc"  // Fourier shell / ring correlation of batches of map or image pairs: DFT passes on the f32 MFMA, fused last pass (hh_fsc_3d, hh_frc_2d)
 #include "true_fsc.inc"  // phase-randomised (noise-substituted) true FSC of two half maps on a resident context: stored spectrum, inverse passes, masked curves (hh_tfsc_*)

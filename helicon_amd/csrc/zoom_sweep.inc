@@ -395,6 +395,10 @@ int filt_prepare(hh_ctx* c, const uint8_t* mask);
 int filt_reference_plane(hh_ctx* c, const float** pwr);
 int filt_sweep(hh_ctx* c, const double* d_params, int64_t n_cand, float* d_scores, int64_t ld);
 
+// phase_sweep.inc: the reference side of the phase score (w M_exp per segment and its norm), prepared with the spectra
+int phase_prepare(hh_ctx* c, int n_segments, size_t plane);
+int phase_reference_plane(hh_ctx* c, int s, const ZoomDims& d, double cutoff_y, int log_flag);
+
 // hh_set_reference with a zoom set: images [S][ny][nx] (host), mask [ony][onx] bytes on the fftshifted zoomed plane.
 int zoom_set_reference(hh_ctx* c, const float* images, int n_segments, const uint8_t* mask, int log_flag) {
   hh_zoom* z = c->zoom;
@@ -432,6 +436,7 @@ int zoom_set_reference(hh_ctx* c, const float* images, int n_segments, const uin
   z->r_cx = cutoff_x;
   z->f_ref = false;
   if (z->f_on && (rc = filt_prepare(c, mask))) return rc;
+  if (phase_on(c) && (rc = phase_prepare(c, n_segments, plane))) return rc;
   const unsigned init[2] = {0x7f800000u, 0u};
   HH_HIP(c, hipMemcpyAsync(z->d_img, images, (size_t)n_segments * npix * sizeof(float), hipMemcpyHostToDevice, c->stream));
   HH_HIP(c, hipMemcpyAsync(z->d_mask, mask, plane, hipMemcpyHostToDevice, c->stream));
@@ -443,6 +448,7 @@ int zoom_set_reference(hh_ctx* c, const float* images, int n_segments, const uin
                        cutoff_x, z->d_r);
     hipLaunchKernelGGL(k_zoom_cols, dim3((onx + 127) / 128, ony), dim3(128), 0, c->stream, z->d_r, d, apix, cutoff_y,
                        log_flag ? 1 : 0, z->d_pwr, (float*)nullptr, z->d_mm);
+    if (phase_on(c) && (rc = phase_reference_plane(c, s, d, cutoff_y, log_flag))) return rc;
     const float* pwr = z->d_pwr;
     if (z->f_on && (rc = filt_reference_plane(c, &pwr))) return rc;   // the same filter as every candidate's spectrum
     hipLaunchKernelGGL(k_zoom_weights, dim3(1), dim3(1024), 0, c->stream, pwr, z->d_mask, ony, onx, z->d_w,
@@ -557,6 +563,8 @@ extern "C" int hh_set_spectrum_filter(hh_ctx* c, double low_pass_fraction, doubl
   }
   hh_zoom* z = c->zoom;
   if (lp == z->f_lp && hp == z->f_hp) return HH_OK;
+  if ((lp != 0.0 || hp != 0.0) && phase_on(c))
+    return fail(c, HH_ERR_ARG, "hh_set_spectrum_filter: the phase score (hh_set_spectrum_phase) reads the unfiltered transform; clear it first");
   z->f_lp = lp;
   z->f_hp = hp;
   z->f_on = lp != 0.0 || hp != 0.0;

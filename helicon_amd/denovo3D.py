@@ -24,7 +24,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib
-from .grid import CandidateGrid, build_grid, filter_spec, radial_band_mask, set_to_periodic_range, zoom_spec
+from .grid import CandidateGrid, build_grid, filter_spec, phase_spec, radial_band_mask, set_to_periodic_range, zoom_spec
 
 __all__ = [
     "SweepEngine",
@@ -32,6 +32,7 @@ __all__ = [
     "sweep",
     "simulate_helical_projection",
     "compute_power_spectra",
+    "compute_phase_difference_across_meridian",
     "cross_correlation_coefficient",
     "cosine_similarity",
     "process_one_task",
@@ -119,6 +120,7 @@ class SweepEngine:
         self._apix = None
         self._zoom = None          # (ony, onx, cutoff_y, cutoff_x) while the engine scores on zoomed spectra
         self._filter = None        # (low_pass_fraction, high_pass_fraction) while the engine scores on filtered spectra
+        self._phase = None         # weight of the phase score across the meridian while the engine mixes it in
 
     @contextlib.contextmanager
     def session(self):
@@ -181,7 +183,7 @@ class SweepEngine:
             self._geom_key = None
             self._check(self._L.hh_set_geometry(self._ctx, C.byref(g)))
             self._geom_key = key
-            if (self._zoom is not None or self._filter is not None) and self._apix != float(apix):   # the library dropped the reference
+            if (self._zoom is not None or self._filter is not None or self._phase is not None) and self._apix != float(apix):   # the library dropped the reference
                 self.n_segments, self._ref_key = 0, None
             self._apix = float(apix)
 
@@ -226,6 +228,24 @@ class SweepEngine:
             self._check(self._L.hh_set_spectrum_filter(self._ctx, *(spec or (0.0, 0.0))))
             self._filter = spec
             self.n_segments, self._ref_key = 0, None
+
+    def set_phase_score(self, weight=0):
+        """Score ``(1 - weight) * amplitude Pearson + weight * phase score``, the phase score being the cosine similarity of
+        the masked "meridian phase maps" ``M = q cos(phase difference across the meridian)`` of the experimental image and
+        of the candidate (``hh_set_spectrum_phase``; ``compute_phase_difference_across_meridian`` is the reference's tool
+        for the even / odd Bessel order that amplitudes cannot tell).  The helix must be centred on row ``ny // 2`` (or
+        ``dy`` must say where it is).  Call it before ``set_reference``.  ``weight`` in (0, 1] turns the mode on, 0 (or
+        ``None``) off (``grid.phase_spec``).  It combines with ``set_zoom`` and not with ``set_filter`` (``ValueError``).
+        Switching it on or off drops the reference; changing only the weight does not.  The setting belongs to the
+        engine, so ``ShardedSweep`` and every ``sweep_device`` caller score with it without further arguments."""
+        with self._lock:
+            spec = phase_spec(weight)
+            if spec == self._phase:
+                return
+            self._check(self._L.hh_set_spectrum_phase(self._ctx, spec or 0.0))
+            if (spec is None) != (self._phase is None):
+                self.n_segments, self._ref_key = 0, None
+            self._phase = spec
 
     def set_reference(self, images, mask=None, log=True, key=None):
         """``key``: an optional hashable identity of (images, mask, log); when it equals the key of the
@@ -272,6 +292,15 @@ class SweepEngine:
         with self._lock:
             self._check(self._L.hh_sweep(self._ctx, _ptr(p, C.c_double), len(p), _ptr(out, C.c_float)))
         return out
+
+    def sweep_parts(self, params):
+        """``sweep`` with the phase score on (``set_phase_score``): ``(scores, amplitude, phase)``, [S, G] float32 each — the
+        combined score ``sweep`` returns, the amplitude Pearson coefficient and the phase score (``hh_sweep_parts``)."""
+        p = np.ascontiguousarray(params, dtype=np.float64).reshape(-1, 4)
+        out = [np.empty((max(self.n_segments, 1), len(p)), dtype=np.float32) for _ in range(3)]
+        with self._lock:
+            self._check(self._L.hh_sweep_parts(self._ctx, _ptr(p, C.c_double), len(p), *(_ptr(o, C.c_float) for o in out)))
+        return tuple(out)
 
     def sweep_device(self, d_params: int, n_candidates: int, d_scores: int, host_params=None, ld_scores: int = 0):
         """Device pointers (ints): params [G, 4] float64, scores [S, G] float32; asynchronous on
@@ -348,8 +377,9 @@ class SweepEngine:
     def last_first_pass(self) -> str:
         """Pipeline of the last sweep: "transform" (raster + column transform per candidate),
         "run_tables" (shared-twist tables + second pass), "fused" (shared-twist, no intermediate), "zoom"
-        (Fourier-zoomed spectra, ``set_zoom``) or "filtered" (low / high-pass filtered spectra, ``set_filter``)."""
-        return {1: "run_tables", 2: "fused", 3: "zoom", 4: "filtered"}.get(self._L.hh_last_first_pass(self._ctx), "transform")
+        (Fourier-zoomed spectra, ``set_zoom``), "filtered" (low / high-pass filtered spectra, ``set_filter``) or "phase"
+        (amplitude and phase score, ``set_phase_score``)."""
+        return {1: "run_tables", 2: "fused", 3: "zoom", 4: "filtered", 5: "phase"}.get(self._L.hh_last_first_pass(self._ctx), "transform")
 
     @property
     def last_row_kernel(self) -> tuple[int, int, int]:
@@ -383,6 +413,19 @@ class SweepEngine:
                                                   _ptr(pwr, C.c_float),
                                                   _ptr(phase, C.c_float) if want_phase else None))
         return pwr, phase
+
+    def phase_map(self, image, log=True):
+        """``(M, c)`` of one image on the fftshifted scored plane (``spectrum_shape``): ``c`` the cosine of the phase
+        difference across the meridian, ``M = log1p|F| c`` (``|F| c`` with ``log=False``) the map the phase score compares
+        (``hh_phase_map``; float64 on the device).  Needs ``set_geometry``, not the mode."""
+        img = _f32(image)
+        if img.shape != (self.ny, self.nx):
+            raise ValueError(f"image must be [{self.ny}, {self.nx}]")
+        m = np.empty(self.spectrum_shape, dtype=np.float32)
+        c = np.empty(self.spectrum_shape, dtype=np.float32)
+        with self._lock:
+            self._check(self._L.hh_phase_map(self._ctx, _ptr(img, C.c_float), 1 if log else 0, _ptr(m, C.c_float), _ptr(c, C.c_float)))
+        return m, c
 
     def low_high_pass_filter(self, image, low_pass_fraction=0.0, high_pass_fraction=0.0) -> np.ndarray:
         img = _f32(image)
@@ -555,6 +598,18 @@ def compute_power_spectra(data, apix, cutoff_res=None, output_size=None, log=Tru
             vmin, vmax = float(f.min()), float(f.max())
             pwr = (f - vmin) / (vmax - vmin) if vmax != vmin else f  # filters.py:276-280
     return pwr.astype(np.float64), phase.astype(np.float64)
+
+
+def compute_phase_difference_across_meridian(phase):
+    """``helicon.compute_phase_difference_across_meridian`` (lib/transforms.py:823-842): the phase array of
+    ``compute_power_spectra`` minus its mirror image along the last axis, in degrees folded into [0, 180] — 0 for an even
+    Bessel order on a layer line, 180 for an odd one.  Index 0 of the last axis (the unpaired frequency of an even side)
+    keeps a difference of 0; indices 1... pair with their mirror image, also on an odd length.  Any dimension; NumPy on the
+    host (no device is needed)."""
+    p = np.asarray(phase)
+    diff = p * 0
+    diff[..., 1:] = p[..., 1:] - p[..., :0:-1]
+    return np.rad2deg(np.arccos(np.cos(diff)))
 
 
 def cross_correlation_coefficient(a, b, *, device=0):
@@ -921,7 +976,7 @@ def finish_sweep(scores: np.ndarray, grid: CandidateGrid) -> SweepResult:
 
 def sweep(images, twists, rises, csyms=(1,), *, apix, helical_diameter, ball_radius, mask=None, log=True,
           rot=0.0, tilt=0.0, psi=0.0, dy=0.0, device=0, engine: SweepEngine | None = None,
-          cutoff_res=None, output_size=None, low_pass_fraction=0, high_pass_fraction=0) -> SweepResult:
+          cutoff_res=None, output_size=None, low_pass_fraction=0, high_pass_fraction=0, phase_weight=0.0) -> SweepResult:
     """Score every (csym, twist, rise) candidate against the experimental image(s) on one GPU.
     For several GPUs see ``helicon_amd.distributed.sweep_distributed``.
 
@@ -933,7 +988,11 @@ def sweep(images, twists, rises, csyms=(1,), *, apix, helical_diameter, ball_rad
     ``low_pass_fraction`` / ``high_pass_fraction``: score on ``compute_power_spectra(..., low_pass_fraction,
     high_pass_fraction)``, the Gaussian low / high pass of the spectrum image (a high pass removes its smooth radial
     fall-off, so the layer lines decide the score).  Fractions outside (0, 1) are off (``grid.filter_spec``) and leave the
-    sweep exactly as it is without them."""
+    sweep exactly as it is without them.
+
+    ``phase_weight``: score ``(1 - phase_weight) * amplitude Pearson + phase_weight * phase score``
+    (``SweepEngine.set_phase_score``: the phase difference across the meridian, which tells an even Bessel order from an odd
+    one where amplitudes cannot).  0 leaves the sweep exactly as it is without it; not together with a spectrum filter."""
     imgs = np.asarray(images)
     ny, nx = _image_shape(*imgs.shape[-2:])
     eng = engine or _engine((ny, nx), device)
@@ -942,13 +1001,19 @@ def sweep(images, twists, rises, csyms=(1,), *, apix, helical_diameter, ball_rad
 
     params = grid.params.copy()
     params[~grid.valid, 1] = harmless_rise(grid)  # skipped pairs still occupy a slot
+    filt, phase = filter_spec(low_pass_fraction, high_pass_fraction), phase_spec(phase_weight)
+    if filt is not None and phase is not None:
+        raise ValueError("phase_weight does not combine with a spectrum filter: the phase score reads the unfiltered transform")
     with eng.session():
         eng.set_geometry(apix=apix, helical_diameter=helical_diameter, ball_radius=ball_radius,
                          tilt=tilt, psi=psi, dy=dy)
         eng.set_zoom(cutoff_res, output_size)
-        filt = filter_spec(low_pass_fraction, high_pass_fraction)
+        if phase is None and getattr(eng, "_phase", None) is not None:   # (off and never set: the engine is not asked)
+            eng.set_phase_score()
         if filt is not None or getattr(eng, "_filter", None) is not None:   # (off and never set: the engine is not asked)
             eng.set_filter(low_pass_fraction, high_pass_fraction)
+        if phase is not None:
+            eng.set_phase_score(phase_weight)
         try:
             eng.set_reference(imgs, mask, log=log)
             scores = eng.sweep(params)
@@ -957,6 +1022,8 @@ def sweep(images, twists, rises, csyms=(1,), *, apix, helical_diameter, ball_rad
                 eng.set_zoom()
                 if filt is not None:
                     eng.set_filter()
+                if phase is not None:
+                    eng.set_phase_score()
     return finish_sweep(scores, grid)
 
 

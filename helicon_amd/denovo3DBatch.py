@@ -8,7 +8,7 @@ descending, app.py:2521-2523) this driver reproduces without the Shiny UI.
 
     python -m helicon_amd.denovo3DBatch image.npy --apix 2.0 --twist 25 33 0.2 --rise 8 13 0.2 \\
            --csym 1 --out scores.npz [--mask mask.npy] [--no-log] [--device 0] [--top 10] \
-           [--cutoff-res 10 10 --spectrum-size 256 256] [--spectrum-high-pass 0.05] [--spectrum-low-pass 0.3] \
+           [--cutoff-res 10 10 --spectrum-size 256 256] [--spectrum-high-pass 0.05] [--spectrum-low-pass 0.3] [--phase-weight 0.5] \
            [--rescore 20 --tube-diameter 120 --interpolation linear [--half-map-fsc 1]]
 
 ``--rescore K`` runs the reference's own scorer — the sparse least-squares reconstruction of pipeline.py:84-496,
@@ -30,6 +30,12 @@ image's shape).
 low_pass_fraction=F, high_pass_fraction=F)`` (transforms.py:811-816): the Gaussian low / high pass of the spectrum image, as
 fractions of its Nyquist radius; a high pass removes the spectrum's smooth radial fall-off.  A fraction outside (0, 1) is
 off.  They combine with the zoom flags and with ``--mask``, which keeps the shape of the scored spectrum.
+
+``--phase-weight W`` scores ``(1 - W) * amplitude Pearson + W * phase score``: the phase score compares the phase difference
+across the meridian (``compute_phase_difference_across_meridian``, transforms.py:823-842) of the image and of every
+candidate, which tells an even Bessel order from an odd one where the amplitudes cannot.  The helix must be centred on the
+image's middle row (or ``--dy`` must say where it is).  W in (0, 1]; 0 is off.  It combines with the zoom flags and is
+refused together with the spectrum filter flags.  With the flag on, the report and ``--out`` record ``phase_weight``.
 
 ``--from-map TWIST RISE CSYM`` reads ``image`` as a 3-D map instead (``.mrc`` / ``.map`` / ``.npy``, ``--apix`` its voxel
 size) and builds the input image as the app does for a map (app.py:1780-1829): the map is symmetrised with the given
@@ -54,7 +60,7 @@ import sys
 import numpy as np
 
 from .denovo3D import sweep
-from .grid import filter_spec, sweep_axis, zoom_spec
+from .grid import filter_spec, phase_spec, sweep_axis, zoom_spec
 
 
 def add_args(parser: argparse.ArgumentParser) -> argparse.ArgumentParser:
@@ -80,6 +86,8 @@ def add_args(parser: argparse.ArgumentParser) -> argparse.ArgumentParser:
                         help="Gaussian low pass of the scored spectrum image (compute_power_spectra's low_pass_fraction; outside (0, 1): off)")
     parser.add_argument("--spectrum-high-pass", type=float, default=0.0, metavar="F",
                         help="Gaussian high pass of the scored spectrum image (compute_power_spectra's high_pass_fraction; outside (0, 1): off)")
+    parser.add_argument("--phase-weight", type=float, default=0.0, metavar="W",
+                        help="weight in [0, 1] of the phase score across the meridian in the score (0: amplitudes alone); not with the spectrum filter flags")
     parser.add_argument("--device", type=int, default=0)
     parser.add_argument("--top", type=int, default=10, help="how many best candidates to print per image")
     parser.add_argument("--out", default=None, help=".npz with scores[S, C, T, R], twists, rises, csyms")
@@ -250,6 +258,14 @@ def run(args) -> dict:
     except ValueError as e:
         raise SystemExit(f"--spectrum-low-pass / --spectrum-high-pass: {e}")
     filter_kw = dict(low_pass_fraction=filt[0], high_pass_fraction=filt[1]) if filt else {}   # off: sweep() is called as without the flags
+    try:
+        phase = phase_spec(getattr(args, "phase_weight", 0.0))
+    except ValueError as e:
+        raise SystemExit(f"--phase-weight: {e}")
+    if phase is not None and filt:
+        raise SystemExit("--phase-weight does not combine with --spectrum-low-pass / --spectrum-high-pass: the phase score reads the unfiltered transform")
+    if phase is not None:
+        filter_kw["phase_weight"] = phase
     res = sweep(
         images, twists, rises, tuple(args.csym), apix=args.apix,
         helical_diameter=args.helical_diameter if args.helical_diameter is not None else 0.4 * n * args.apix,
@@ -262,6 +278,8 @@ def run(args) -> dict:
     report["cutoff_res"] = [float(zoom[2]), float(zoom[3])] if zoom else [2.0 * args.apix, 2.0 * args.apix]
     report["spectrum_size"] = [int(plane[0]), int(plane[1])]
     report["spectrum_filter"] = [float(filt[0]), float(filt[1])] if filt else [0.0, 0.0]   # (low pass, high pass); 0 = off
+    if phase is not None:   # (off: the report and the file are what they are without the flag)
+        report["phase_weight"] = float(phase)
     if map_info is not None:
         report["map"] = map_info
     flat = res.scores.reshape(res.scores.shape[0], -1)
@@ -296,6 +314,8 @@ def run(args) -> dict:
                 extra["rescored_fsc"] = np.asarray([[r["fsc"] for r in im.get("rescored", [])] for im in report["images"]], dtype=np.float64)
                 extra["rescored_fsc_resolution"] = np.asarray([[[r["fsc_resolution_0143"], r["fsc_resolution_05"]]
                                                                 for r in im.get("rescored", [])] for im in report["images"]], dtype=np.float64)
+        if "phase_weight" in report:
+            extra["phase_weight"] = np.asarray(report["phase_weight"])
         np.savez_compressed(args.out, scores=res.scores, twists=twists, rises=rises, csyms=np.asarray(args.csym),
                             params=res.grid.params, valid=res.grid.valid, cutoff_res=np.asarray(report["cutoff_res"]),
                             spectrum_size=np.asarray(report["spectrum_size"]), spectrum_filter=np.asarray(report["spectrum_filter"]), **extra)

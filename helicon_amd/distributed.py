@@ -83,7 +83,8 @@ class ShardedSweep:
              current stream of the device so the collective is ordered behind the sweep without events.
              A Fourier zoom (``SweepEngine.set_zoom``) belongs to the engine, so a zoomed engine is sharded
              like any other: every rank sets the same zoom before its reference.  The same holds for a spectrum filter
-             (``SweepEngine.set_filter``).
+             (``SweepEngine.set_filter``) and for the phase score (``SweepEngine.set_phase_score``: the gathered scores
+             are then the combined ones).
     params : the full [G, 4] list (identical on every rank).
     align  : shard granularity in candidates (the number of rises: shards are whole twists).
     device : torch device of the buffers (default: the engine's GPU).  With a ``gloo`` group the

@@ -24,6 +24,7 @@ __all__ = [
     "shard_bounds",
     "zoom_spec",
     "filter_spec",
+    "phase_spec",
 ]
 
 
@@ -172,3 +173,13 @@ def filter_spec(low_pass_fraction=0, high_pass_fraction=0):
             raise ValueError(f"{name} is NaN")
         out.append(f if 0.0 < f < 1.0 else 0.0)
     return None if out == [0.0, 0.0] else (out[0], out[1])
+
+
+def phase_spec(weight=0):
+    """The weight of the phase score across the meridian in the sweep's score, ``(1 - weight) * amplitude Pearson + weight *
+    phase score``: ``None`` when it is off (0 or ``None``), else the weight as a float in (0, 1].  ``ValueError`` on NaN or a
+    value outside [0, 1]."""
+    w = 0.0 if weight is None else float(weight)
+    if math.isnan(w) or not 0.0 <= w <= 1.0:
+        raise ValueError(f"phase_weight must lie in [0, 1]; got {weight!r}")
+    return None if w == 0.0 else w

@@ -166,6 +166,26 @@ int hh_set_spectrum_zoom(hh_ctx* ctx, int ony, int onx, double cutoff_y, double 
  * the next hh_set_reference).  NaN returns HH_ERR_ARG and changes nothing; nothing here touches the device. */
 int hh_set_spectrum_filter(hh_ctx* ctx, double low_pass_fraction, double high_pass_fraction);
 
+/* Score on the phase difference across the meridian as well (lib/transforms.py:823-842, "0 -> even order, 180 -> odd
+ * order"): with centre-origin transforms on the scored plane (the zoom's, or the image's shape and Nyquist), F~(u, v) the
+ * transform at (-f_y[u], f_x[v]), c = Re(F conj F~) / (|F| |F~|) (0 where that is 0 / 0), q = log1p|F| or |F| and M = q c,
+ *     phase score = cosine_similarity(M_exp[mask], M_cand[mask])      (analysis.py:802-821; 0 when a norm is 0)
+ *     score       = (1 - weight) * amplitude Pearson + weight * phase score
+ * and every hh_sweep* entry point writes that score.  The helix must be centred on row ny / 2 (or hh_geom.dy must say
+ * where it is); the subunit's azimuth and an axial shift cancel.  weight in (0, 1] turns the mode on, 0 turns it off; NaN
+ * or a value outside [0, 1] returns HH_ERR_ARG and changes nothing.  Call it between hh_set_geometry and hh_set_reference.
+ * It combines with hh_set_spectrum_zoom and not with hh_set_spectrum_filter: whichever of the two is set second returns
+ * HH_ERR_ARG.  Switching the mode on or off drops the reference (HH_ERR_STATE until the next hh_set_reference); changing
+ * only the weight does not.  Nothing here touches the device. */
+int hh_set_spectrum_phase(hh_ctx* ctx, double weight);
+/* hh_sweep with the phase score on (else HH_ERR_STATE): the combined score, the amplitude Pearson coefficient and the
+ * phase score of every candidate, host pointers, [S][g] each; any output may be NULL. */
+int hh_sweep_parts(hh_ctx* ctx, const double* params, int64_t g, float* scores, float* amplitude, float* phase);
+/* M = q c (map_out) and c (cos_out) of one ny x nx host image on the fftshifted scored plane (the zoom's shape with a
+ * zoom set), float64 on the device: the reference side of the phase score.  Either output may be NULL.  Needs
+ * hh_set_geometry (the pixel size), not the mode. */
+int hh_phase_map(hh_ctx* ctx, const float* image, int log_flag, float* map_out, float* cos_out);
+
 /* Experimental image(s) and mask.  images: host, S x N x N float32; mask: host, N x N bytes on
  * the fftshifted plane (DC at [N/2][N/2]), non-zero = bin takes part in the correlation;
  * log_flag selects log1p(|F|) (transforms.py:807-810).  The library transforms the images on
@@ -202,7 +222,8 @@ int hh_sweep_device_strided(hh_ctx* ctx, const double* d_params, const double* h
 int hh_set_table_path(hh_ctx* ctx, int mode);
 /* Which pipeline the last sweep of this context ran: 0 = per-candidate raster + column transform +
  * second pass, 1 = run tables + second pass, 2 = fused, 3 = zoomed spectra (hh_set_spectrum_zoom),
- * 4 = filtered spectra (hh_set_spectrum_filter, with or without a zoom). */
+ * 4 = filtered spectra (hh_set_spectrum_filter, with or without a zoom), 5 = amplitude and phase score
+ * (hh_set_spectrum_phase, with or without a zoom). */
 int hh_last_first_pass(const hh_ctx* ctx);
 /* Which row kernel the last sweep of a general-size context (hh_create2, not a power-of-two square) ran, read-only:
  * out = {R1, R2, dynamic LDS bytes} for the two-step kernel of the pair nx = R1 R2, {0, 0, LDS bytes} for the Stockham
