@@ -22,7 +22,7 @@ namespace {
 constexpr int FS_T = 64;    // x-pass output tile of a workgroup: 64 rows (u) x 64 columns (v), four wavefronts of 32 x 32
 constexpr int FS_K = 32;    // K slice staged through LDS
 constexpr int64_t FS_BYTES = (int64_t)128 << 20;   // q and T of one batch stay below this
-constexpr int64_t FS_BATCH = 1024;
+constexpr int64_t FS_BATCH = 1024;   // both pinned by tests/test_launch_cuts_host.py, crossed by tests/test_gpu_launch_cuts.py
 
 struct FiltArgs {
   const float* t;       // [J][batch][ony][onx] y passes

@@ -309,6 +309,7 @@ void fc_device(const FcPlan& p, const float* in, float* p1, float* p2, const flo
 }
 
 // chunk of a batch of pairs: input + one or two plane pairs within the scratch cap, and the y pass's grid.z = 2 chunk nz <= 65535
+// (both caps pinned by tests/test_launch_cuts_host.py, crossed by tests/test_gpu_launch_cuts.py)
 int64_t fc_chunk(const FcPlan& p, int64_t batch) {
   const int64_t bytes_per_pair = (int64_t)(p.cube ? 10 : 6) * p.per_map * (int64_t)sizeof(float);
   int64_t chunk = std::max<int64_t>(1, FC_SCRATCH_BYTES / bytes_per_pair);

@@ -461,6 +461,7 @@ int hh_hs_search(hh_hs* p, const double* params, int64_t g, float* scores) try {
   HS_HIP(p, hipSetDevice(p->device));
   const size_t n_part = (size_t)p->nplanes * p->ntiles;
   const size_t per_cand = n_part * 3 * sizeof(double);
+  // 65535: the grid.z limit (pinned by tests/test_launch_cuts_host.py, crossed by tests/test_gpu_launch_cuts.py)
   const size_t per_launch = (size_t)std::max<int64_t>(1, std::min<int64_t>({(int64_t)(p->budget / (int64_t)per_cand), g, 65535}));
   if (per_launch > p->part_cap) {
     (void)hipFree(p->d_part); p->d_part = nullptr; p->part_cap = 0;

@@ -440,6 +440,7 @@ extern "C" int hh_tfsc_masked(hh_tfsc* ctx, const float* masks1, const float* ma
   const int64_t per_map = c->per_map;
   const int nshell = c->nshell;
   // masks per chunk: two pairs each within fc_run's scratch cap, and the y pass's grid.z = 4 chunk n <= 65535
+  // (pinned by tests/test_launch_cuts_host.py, crossed by tests/test_gpu_launch_cuts.py)
   int64_t chunk = std::max<int64_t>(1, FC_SCRATCH_BYTES / (20 * per_map * (int64_t)sizeof(float)));
   chunk = std::min<int64_t>(chunk, 65535 / (4 * c->n));
   chunk = std::min<int64_t>(chunk, batch);

@@ -67,7 +67,7 @@ constexpr int ZS_K = 32;       // lattice centres per K slice
 constexpr int ZS_CHUNK = ZS_THREADS;  // lattice centres tested per step (one per lane of the workgroup)
 constexpr int ZS_TAPS = 64;    // footprints up to this many pixels keep their profiles in LDS
 constexpr int ZS_LIST = ZS_CHUNK + ZS_K;
-constexpr int64_t ZS_BATCH = 8192;
+constexpr int64_t ZS_BATCH = 8192;   // pinned by tests/test_launch_cuts_host.py, crossed by tests/test_gpu_launch_cuts.py
 
 struct ZoomLds {   // dynamic LDS of k_zoom_sweep
   float as_re[ZS_TU][ZS_K + 1], as_im[ZS_TU][ZS_K + 1];
