@@ -90,6 +90,7 @@ EXPORTS = {
     "hh_phase_map": (C.c_int, [_ctx, _f32p, C.c_int, _f32p, _f32p]),
     "hh_set_table_path": (C.c_int, [_ctx, C.c_int]),
     "hh_last_first_pass": (C.c_int, [_ctx]),
+    "hh_last_factor_sets": (C.c_int64, [_ctx]),
     "hh_last_row_kernel": (C.c_int, [_ctx, C.POINTER(C.c_int32)]),
     "hh_low_high_pass_filter": (C.c_int, [_ctx, _f32p, C.c_double, C.c_double, _f32p]),
     "hh_threshold_data": (C.c_int, [_ctx, _f32p, C.c_int64, C.c_int, C.c_double, _f32p]),
@@ -109,6 +110,8 @@ EXPORTS = {
     "hh_cosine_similarity_f64": (C.c_int, [_ctx, _f64p, _f64p, C.c_int64, _f64p]),
     "hh_fused_schedule": (C.c_int, [C.c_int64, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32)]),
     "hh_general_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
+    "hh_rise_columns_shared": (C.c_int, [_f64p, C.c_int64, C.c_int64]),
+    "hh_table_extent": (C.c_int64, [C.c_int, C.c_double, C.c_int, C.c_double, C.c_double]),
     "hh_affine_transform_2d": (C.c_int, [C.c_int, _f32p, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), _f32p]),
     "hh_affine_transform_2d_cubic": (C.c_int, [C.c_int, _f32p, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), _f32p]),
     "hh_warp_affine_2d": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_int, C.c_double, C.c_int,

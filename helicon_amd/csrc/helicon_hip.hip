@@ -973,8 +973,9 @@ __global__ __launch_bounds__(256) void k_first_pass_table(TableArgs a) {
     const float inv_rise = 1.0f / (float)c.rise;
     const float i0 = ((float)(x0 - N / 2) * g.apix - rp * g.apix - g.slack) * inv_rise;
     const float i1 = ((float)(x0 + K::COLS - 1 - N / 2) * g.apix + rp * g.apix + g.slack) * inv_rise;
-    ilo = max(-c.imax, (int)floorf(fmaxf(i0, -2.0e9f)));
-    const int ihi = min(c.imax, (int)ceilf(fminf(i1, 2.0e9f)));
+    const int ilim = min(c.imax, imax_t);  // the table stops where no row can reach the image (plan_runs)
+    ilo = max(-ilim, (int)floorf(fmaxf(i0, -2.0e9f)));
+    const int ihi = min(ilim, (int)ceilf(fminf(i1, 2.0e9f)));
     rows = ihi < ilo ? 0 : min(a.rows_lds, (ihi - ilo + 1) * g.n_units);
   }
   // stage the rows: all of a thread's loads are issued before the first LDS write waits for one
@@ -1416,7 +1417,8 @@ __global__ __launch_bounds__(KB<N>::THREADS, (N >= 256 ? KB<N>::WAVES_PER_SIMD :
 // CPW candidates of one run: it keeps the table slice in LDS (transposed, [ky][row]), builds each
 // candidate's 8 x N panel of H straight into the row transforms' exchange buffers, and runs
 // k_second_pass's transform + moments on it.  HBM sees the parameters, the column factors
-// (k_column_factors: KG x N floats per candidate, written once, read from L2) and the scores.
+// (k_column_factors: KG x N floats per rise when every run carries the same rises, else per candidate;
+// written once, read from L2) and the scores.
 // ------------------------------------------------------------------------------------------
 struct FactorArgs {
   const double* params;   // [B][4]
@@ -1519,8 +1521,8 @@ struct FusedArgs {
   const float2* twtab;
   const float2* table;    // [runs][cap][N/2]
   const int* run_imax;    // [runs]
-  const float* eg;        // [B][kg][N]
-  const int* cgs;         // [B][N/4 + 4]
+  const float* eg;        // [B][kg][N], or [run_len][kg][N] shared by every run (factor_stride = 0)
+  const int* cgs;         // [B][N/4 + 4], or [run_len][N/4 + 4]
   const float2* w2;
   double* partials;
   float* q_out;           // EPI_QSTORE (layout: SecondArgs)
@@ -1530,6 +1532,7 @@ struct FusedArgs {
   int n_kb;
   int batch;              // candidates in this launch
   int run_len;            // candidates per run inside this batch
+  int factor_stride;      // factor sets from one run to the next: run_len, or 0 when all runs share run 0's (same rise column)
   // work layers: the first runs_a runs are cut into groups_a layers of cpw_a candidates each, the remaining runs
   // into groups_b layers of cpw_b (shorter workgroups for the launch's last, partly filled round: fused_schedule)
   int runs_a, groups_a, cpw_a, groups_b, cpw_b;
@@ -1638,6 +1641,7 @@ __global__ __launch_bounds__(N, (N >= 256 ? KF<N>::WPS : 1)) void k_fused_pass(F
   const int cfirst = run * a.run_len + off;
   const int nc = min(cpw, min(a.run_len - off, a.batch - cfirst));
   if (nc <= 0) return;
+  const int ffirst = run * a.factor_stride + off;  // the first candidate's factor set (the factors do not depend on the twist)
 
   // N = 1024 (SPLIT): a row belongs to two wavefronts (h = 0, 1).  A lane's build already owns columns n and n + N/2
   // (its two groups of four), so the first radix-2 step of the row transform needs no exchange:
@@ -1716,7 +1720,7 @@ __global__ __launch_bounds__(N, (N >= 256 ? KF<N>::WPS : 1)) void k_fused_pass(F
     for (int e = tid; e < n_e4; e += K::THREADS) reinterpret_cast<float4*>(eg)[e] = src[e];
     if (tid < CGS) cgs[tid] = a.cgs[(size_t)b * CGS + tid];
   };
-  stage_factors(cfirst);  // buffer 0
+  stage_factors(ffirst);  // buffer 0
   // Every load issued so far (twiddles, weights, slice, factors) is retired HERE, explicitly: the barrier's fence only
   // waits for LDS traffic, and with register loads still pending at the loop's entry the compiler guards their first
   // uses INSIDE the loop with counted waits — the last of them a vmcnt(0) in the middle of part B, which in every later
@@ -1974,7 +1978,7 @@ __global__ __launch_bounds__(N, (N >= 256 ? KF<N>::WPS : 1)) void k_fused_pass(F
     // 64 x 16 B to a wave-uniform LDS base + lane x 16.
     const bool more = it + 1 < nc;
     if (more) {
-      const size_t bn = (size_t)(cfirst + it + 1);
+      const size_t bn = (size_t)(ffirst + it + 1);
       const char* const gsrc = reinterpret_cast<const char*>(a.eg + bn * a.kg * N);
       char* const ldst = reinterpret_cast<char*>(eg + (size_t)((it & 1) ^ 1) * a.kg * N);
       const int lane = tid & 63, wave = tid >> 6;
@@ -2498,9 +2502,10 @@ struct hh_ctx {
   std::vector<int> h_run_imax;
   int table_path = 1;            // 0: never take the shared-twist first pass
   int fused_path = 1;            // 0: shared-twist runs go through the two-pass pipeline (k_first_pass_table + k_second_pass)
-  float* d_eg = nullptr;         // fused pass: [max_batch][kg][N] column factors
-  int* d_cgs = nullptr;          // fused pass: [max_batch][N/4]
-  size_t cap_eg = 0, cap_cgs = 0;
+  float* d_eg = nullptr;         // fused pass: column factors, [run_len][kg][N] shared by all runs or [2][batch][kg][N]
+  int* d_cgs = nullptr;          // fused pass: [sets][N/4 + 4]
+  size_t cap_eg = 0, cap_cgs = 0;  // bytes; factor sets
+  int64_t last_factor_sets = 0;  // factor sets the last fused sweep computed (0: another pipeline)
   int cap_partials = 0;          // candidates per half of d_partials
   int last_first_pass = 0;       // what the last sweep ran: 0 per-candidate transform, 1 run tables, 2 fused, 3 zoomed spectra, 4 filtered spectra, 5 phase score
   unsigned long long kb_mask = ~0ull;
@@ -2795,7 +2800,7 @@ int dispatch_first_table(hh_ctx* c, const TableArgs& a, int batch) {
 
 // A candidate list the shared-twist first pass can take: runs of `len` consecutive candidates with
 // identical (twist, csym, rot) and positive finite rises; h_run_imax[r] = the subunit index range
-// of run r (from its smallest rise).
+// run r's table covers (table_extent of its smallest rise).
 struct RunPlan {
   bool ok = false;
   int64_t len = 0;
@@ -2804,6 +2809,7 @@ struct RunPlan {
   bool fused = false;  // the fused pass fits: whole table slice + column factors in LDS
   int kg = 0;          // fused: table rows per group of four columns
   int rows_f = 0;      // fused: table rows staged per ky
+  bool shared_factors = false;  // every run carries run 0's rise column (a twist-major grid): one set of column factors per rise
 };
 
 constexpr int64_t HH_MIN_RUN = 8;              // shorter runs do not amortise their table and workgroup granularity
@@ -2831,6 +2837,30 @@ int table_cols(int n) {
   }
 }
 
+// Whether every run of `len` candidates carries run 0's rise column, value for value (at least two runs).  The column
+// factors depend on the rise alone (column_factors_of reads neither twist, csym nor rot), so such a list needs one set
+// per rise, not one per candidate.  The driver's itertools.product(twists, rises) grid is of this shape.
+bool rise_columns_shared(const double* hp, int64_t g, int64_t len) {
+  if (!hp || len < 1 || g < 2 * len || g % len) return false;
+  for (int64_t i = len; i < g; ++i)
+    if (!(hp[4 * i + 1] == hp[4 * (i % len) + 1])) return false;
+  return true;
+}
+
+// Largest |i| a run's table has to cover.  The lattice of utils.py:153 spans ceil(height / rise) indices either side,
+// twice what the image holds; a row enters a column's sum only through the window test |x - cx| <= rpx with
+// cx = xc inv_apix + N/2 and xc = z_u + i rise, so for x in [0, N - 1] it needs |xc| <= (N/2 + rpx) apix and with it
+// |i| rise <= reach = (N/2 + rpx) apix + slack (slack >= |z_u|).  The device evaluates xc and cx in float32: the
+// product i rise, the sum with z_u, the product with inv_apix (itself a rounded reciprocal) and the sum with N/2 are
+// each off by at most 2^-24 of a magnitude below 2 reach, under 1e-6 reach together.  The bound allows 1e-5 reach and
+// one whole index more, so it also holds where reach / rise is an integer or one ulp from it.
+int64_t table_extent(int nx, double apix, int rpx, double slack, double height, double rise) {
+  const double full = std::ceil(height / rise);
+  const double reach = ((double)(nx / 2) + (double)rpx) * apix + slack;
+  const double cap = std::floor(reach * (1.0 + 1e-5) / rise) + 1.0;
+  return (int64_t)std::min(std::min(full, cap), 1048576.0);
+}
+
 RunPlan plan_runs(hh_ctx* c, const double* hp, int64_t g) {
   RunPlan plan;
   if (!hp || !c->table_path || c->geom.has_rot || g < HH_MIN_RUN) return plan;
@@ -2852,8 +2882,9 @@ RunPlan plan_runs(hh_ctx* c, const double* hp, int64_t g) {
     }
     const double im = std::ceil(c->geom.height / rise_min);
     if (im > 1048576.0) return plan;
-    c->h_run_imax[(size_t)r] = (int)im;
-    imax_all = std::max(imax_all, (int)im);
+    const int ext = (int)table_extent(c->n, (double)c->geom.apix, c->geom.rpx, (double)c->geom.slack, c->geom.height, rise_min);
+    c->h_run_imax[(size_t)r] = ext;
+    imax_all = std::max(imax_all, ext);
     rise_all = std::min(rise_all, rise_min);
   }
   // k_first_pass_table: rows = ceil(i1) - floor(i0) + 1 <= (i1 - i0) + 3 with
@@ -2876,6 +2907,10 @@ RunPlan plan_runs(hh_ctx* c, const double* hp, int64_t g) {
     }
   }
   if (!plan.fused && plan.rows_lds == 0) return plan;
+  plan.shared_factors = plan.fused && rise_columns_shared(hp, g, len);
+  if (plan.shared_factors)  // equal columns have equal smallest rises: the shared cgs index ONE table geometry
+    for (int64_t r = 1; r < runs; ++r)
+      if (c->h_run_imax[(size_t)r] != c->h_run_imax[0]) throw std::logic_error("plan_runs: equal rise columns with unequal table extents");
   plan.len = len;
   plan.ok = true;
   return plan;
@@ -3097,12 +3132,24 @@ int sweep_runs(hh_ctx* c, const double* d_params, int64_t g, float* d_scores, co
   // The fused pass has no intermediate to hold, so its batches are not tied to max_batch: long
   // launches even out the tail of the grid (C2: 3.2 M candidates/s at 250 per launch, 3.8 M at 4000).
   constexpr int64_t FUSED_BATCH = 131072;       // most candidates per launch (whole runs); 6 GB of column factors + moments at N = 512
-  constexpr int64_t FUSED_BYTES = 8LL << 30;    // the launch is shortened so that its column factors (two halves) fit this
-  const int fused_cap = (int)std::max<int64_t>(1024, std::min<int64_t>(FUSED_BATCH, FUSED_BYTES / ((int64_t)2 * std::max(1, plan.kg) * c->n * 4)));
+  constexpr int64_t FUSED_BYTES = 8LL << 30;    // the launch is shortened so that its per-candidate column factors (two halves) fit this
   // (never more than the sweep itself holds: the factor and moment buffers are sized by it and only grow)
-  const int bmax = !plan.fused ? c->max_batch
-                   : (int)std::min<int64_t>(c->n_segments == 1 ? std::max(c->max_batch, fused_cap) : std::max(c->max_batch, seg_batch(c->n)),
-                                            std::max<int64_t>(count_cand, 16));
+  auto bmax_of = [&](bool shared_sets) {
+    // one factor set per rise does not grow with the launch: only FUSED_BATCH and the moments bound it then
+    const int fused_cap = shared_sets ? (int)FUSED_BATCH
+                                      : (int)std::max<int64_t>(1024, std::min<int64_t>(FUSED_BATCH, FUSED_BYTES / ((int64_t)2 * std::max(1, plan.kg) * c->n * 4)));
+    return !plan.fused ? c->max_batch
+                       : (int)std::min<int64_t>(c->n_segments == 1 ? std::max(c->max_batch, fused_cap) : std::max(c->max_batch, seg_batch(c->n)),
+                                                std::max<int64_t>(count_cand, 16));
+  };
+  // One set of column factors per rise, computed once for the whole sweep, when every run carries the same rise column
+  // and a launch holds whole runs; a run cut into several launches keeps per-launch, per-candidate factors.
+  bool shared = plan.fused && plan.shared_factors && runs >= 2;
+  int bmax = bmax_of(shared);
+  if (shared && plan.len > bmax) {
+    shared = false;
+    bmax = bmax_of(false);
+  }
   if (c->n_segments > 1) {
     const int rcs = ensure_segment_buffers(c, bmax);
     if (rcs) return rcs;
@@ -3121,7 +3168,9 @@ int sweep_runs(hh_ctx* c, const double* d_params, int64_t g, float* d_scores, co
     c->cap_table = need;
   }
   if (plan.fused) {
-    const size_t need_eg = (size_t)2 * bmax * plan.kg * c->n * sizeof(float);  // two halves, alternating
+    // shared: one set per rise; else two halves of a launch's candidates, alternating
+    const size_t sets = shared ? (size_t)plan.len : (size_t)2 * bmax;
+    const size_t need_eg = sets * plan.kg * c->n * sizeof(float);
     if (need_eg > c->cap_eg) {
       if (c->d_eg) HH_HIP(c, hipFree(c->d_eg));
       c->d_eg = nullptr;
@@ -3129,13 +3178,14 @@ int sweep_runs(hh_ctx* c, const double* d_params, int64_t g, float* d_scores, co
       HH_HIP(c, hipMalloc(&c->d_eg, need_eg));
       c->cap_eg = need_eg;
     }
-    if ((size_t)bmax > c->cap_cgs) {
+    if (sets > c->cap_cgs) {
       if (c->d_cgs) HH_HIP(c, hipFree(c->d_cgs));
       c->d_cgs = nullptr;
       c->cap_cgs = 0;
-      HH_HIP(c, hipMalloc(&c->d_cgs, (size_t)2 * bmax * (c->n / 4 + 4) * sizeof(int)));
-      c->cap_cgs = (size_t)bmax;
+      HH_HIP(c, hipMalloc(&c->d_cgs, sets * (c->n / 4 + 4) * sizeof(int)));
+      c->cap_cgs = sets;
     }
+    c->last_factor_sets = shared ? plan.len : count_cand;
     const int rc = ensure_partials(c, bmax);
     if (rc) return rc;
   }
@@ -3223,7 +3273,9 @@ int sweep_runs(hh_ctx* c, const double* d_params, int64_t g, float* d_scores, co
       // computed by leading layers of the previous batch's launch (its own launch for the first).
       const int half = (int)(bi & 1);
       if (bi == 0) {
-        rc = dispatch_factors(c, factor_args(bt, half), bt.nb);
+        FactorArgs fa = factor_args(bt, half);  // shared: bt is at run 0, whose candidates give the sweep's one set per rise
+        if (shared) fa.run_len = fa.count = (int)plan.len;
+        rc = dispatch_factors(c, fa, fa.count);
         if (rc) return rc;
       }
       FusedArgs fu{};
@@ -3231,8 +3283,8 @@ int sweep_runs(hh_ctx* c, const double* d_params, int64_t g, float* d_scores, co
       fu.twtab = c->d_tw;
       fu.table = ta.table;
       fu.run_imax = ta.run_imax;
-      fu.eg = c->d_eg + half * eg_half;
-      fu.cgs = c->d_cgs + half * cg_half;
+      fu.eg = shared ? c->d_eg : c->d_eg + half * eg_half;
+      fu.cgs = shared ? c->d_cgs : c->d_cgs + half * cg_half;
       fu.w2 = c->d_w2;
       double* const part = c->d_partials + (size_t)half * bmax * npart_for(c->n) * 3;
       fu.partials = part;
@@ -3243,6 +3295,7 @@ int sweep_runs(hh_ctx* c, const double* d_params, int64_t g, float* d_scores, co
       fu.n_kb = c->n_kb;
       fu.batch = bt.nb;
       fu.run_len = bt.run_len;
+      fu.factor_stride = shared ? 0 : bt.run_len;
       fu.cap = plan.rows;
       fu.rows_lds = plan.rows_f;
       fu.kg = plan.kg;
@@ -3259,7 +3312,7 @@ int sweep_runs(hh_ctx* c, const double* d_params, int64_t g, float* d_scores, co
       }
       fu.n_units = c->geom.n_units;
       fu.fin = pending;
-      if (bi + 1 < batches.size()) {
+      if (!shared && bi + 1 < batches.size()) {
         fu.next = factor_args(batches[bi + 1], half ^ 1);
         fu.factor_layers = (fu.next.count + c->n_kb - 1) / c->n_kb;
       }
@@ -3311,6 +3364,7 @@ int sweep_transform(hh_ctx* c, const double* d_params, int64_t g, float* d_score
 // their `g` argument for that addressing, so they are handed ld.
 int sweep_on_device(hh_ctx* c, const double* d_params, const int64_t n_cand, float* d_scores,
                     const double* h_params = nullptr, int64_t ld = 0) {
+  c->last_factor_sets = 0;
   if (phase_on(c)) return phase_sweep(c, d_params, n_cand, d_scores, ld);
   if (zoom_on(c)) return zoom_sweep(c, d_params, n_cand, d_scores, ld);
   if (c->general) return gen_sweep(c, d_params, h_params, n_cand, d_scores, ld);
@@ -3645,6 +3699,18 @@ int hh_fused_schedule(int64_t runs, int run_len, int n_kb, int slots, int32_t ou
   return HH_OK;
 } HH_CATCH_CTX(nullptr, "hh_fused_schedule")
 
+// Host-only: does a candidate list of runs of `run_len` carry one rise column in every run (plan_runs' test)?
+int hh_rise_columns_shared(const double* params, int64_t n, int64_t run_len) try {
+  if (!params || n < 1 || run_len < 1) return HH_ERR_ARG;
+  return rise_columns_shared(params, n, run_len) ? 1 : 0;
+} HH_CATCH_CTX(nullptr, "hh_rise_columns_shared")
+
+// Host-only: the subunit index range a run's table covers (plan_runs' extent) for a run whose smallest rise is `rise`.
+int64_t hh_table_extent(int nx, double apix, int rpx, double slack, double rise) try {
+  if (nx < 1 || !(apix > 0) || rpx < 0 || !(slack >= 0) || !(rise > 0) || !(rise < INFINITY)) return HH_ERR_ARG;
+  return table_extent(nx, (double)(float)apix, rpx, (double)(float)slack, (double)nx * apix, rise);
+} HH_CATCH_CTX(nullptr, "hh_table_extent")
+
 int hh_set_stream(hh_ctx* c, void* hip_stream) try {
   if (!c) return HH_ERR_ARG;
   HH_HIP(c, hipSetDevice(c->device));
@@ -3903,6 +3969,7 @@ int hh_sweep_device_strided(hh_ctx* c, const double* d_params, const double* h_p
 } HH_CATCH_CTX(c, "hh_sweep_device_strided")
 
 int hh_last_first_pass(const hh_ctx* c) { return c ? c->last_first_pass : HH_ERR_ARG; }
+int64_t hh_last_factor_sets(const hh_ctx* c) { return c ? c->last_factor_sets : HH_ERR_ARG; }
 int hh_last_row_kernel(const hh_ctx* c, int32_t out[3]) try {
   if (!c || !out) return HH_ERR_ARG;
   for (int k = 0; k < 3; ++k) out[k] = c->gen ? c->gen->last_row_kernel[k] : 0;

@@ -382,6 +382,13 @@ class SweepEngine:
         return {1: "run_tables", 2: "fused", 3: "zoom", 4: "filtered", 5: "phase"}.get(self._L.hh_last_first_pass(self._ctx), "transform")
 
     @property
+    def last_factor_sets(self) -> int:
+        """Sets of column factors the last sweep computed on the fused pipeline (``hh_last_factor_sets``): the run length
+        when every run of the list carries the same rise column, the number of fused candidates otherwise, 0 when the
+        sweep ran another pipeline."""
+        return int(self._L.hh_last_factor_sets(self._ctx))
+
+    @property
     def last_row_kernel(self) -> tuple[int, int, int]:
         """Row kernel of the last sweep on a general image size (``hh_last_row_kernel``): ``(R1, R2, LDS bytes)`` for the
         two-step kernel of the pair nx = R1 R2, ``(0, 0, LDS bytes)`` for the Stockham kernel, ``(0, 0, 0)`` for the

@@ -119,7 +119,8 @@ void hh_destroy(hh_ctx* ctx);
 int hh_max_batch(const hh_ctx* ctx);
 /* Device memory the context holds right now (bytes; its buffers grow with the sweeps it has run and stay until
  * hh_destroy).  parts (may be NULL): {run tables, column factors, two-pass intermediate, several-segment buffers,
- * everything else}.  Typical: C2 (512^2, one 100k launch) 0.21 + 2.9 + 0.27 GB; C4 (1024^2) ~7 GB; C5 (64 segments x
+ * everything else}.  Typical: C2 (512^2, one 100k launch) 0.11 + 0.004 + 0.27 GB (a list whose runs do not share one
+ * rise column: 2.9 GB of column factors); C4 (1024^2) ~7 GB; C5 (64 segments x
  * 20k candidates) ~12 GB of masked spectra.  A spectrum filter (hh_set_spectrum_filter) adds its operators and one
  * batch of candidate planes (at most 128 MB, while a batch holds more than one candidate) to "everything else". */
 int64_t hh_memory_bytes(const hh_ctx* ctx, int64_t parts[5]);
@@ -129,6 +130,16 @@ int64_t hh_memory_bytes(const hh_ctx* ctx, int64_t parts[5]);
  * groups_b, cpw_b, layers}.  Pure host arithmetic (the reference has no counterpart: its pool takes one task per candidate,
  * app.py:2473-2476); exported so the plan can be inspected and tested without a device. */
 int hh_fused_schedule(int64_t runs, int run_len, int n_kb, int slots, int32_t out[6]);
+/* Whether the fused pipeline computes one set of column factors per rise for this list: params = n x 4 float64 in runs of
+ * run_len candidates; 1 when there are at least two runs and every run carries run 0's rises, value for value and in the
+ * same order (the twist-major grid of itertools.product(twists, rises), csym-major lists of such grids included), else 0.
+ * The column factors depend on the rise alone, so such a list needs run_len sets, not n.  Pure host arithmetic. */
+int hh_rise_columns_shared(const double* params, int64_t n, int64_t run_len);
+/* Subunit index range [-extent, extent] a run's table covers when `rise` is the run's smallest: the largest |i| whose
+ * row can pass the window test of any image column (|i| rise <= (nx / 2 + rpx) apix + slack, plus a margin for the
+ * device's float32 roundings), never more than the lattice's own ceil(nx apix / rise).  rpx = truncation half-window in
+ * pixels, slack = largest |axial offset| of a unit + 1e-3 Angstrom (hh_set_geometry's values).  Pure host arithmetic. */
+int64_t hh_table_extent(int nx, double apix, int rpx, double slack, double rise);
 /* Which row kernel hh_sweep takes for an image that is not a power-of-two square, and its launch shape: nx = row length
  * (helical axis), rows_lds = table rows a run keeps in LDS ((2 ceil(nx apix / rise_min) + 1) n_units), kg = table rows
  * one column group may reach (<= 32).  out = {r1, r2, spectrum rows per workgroup, threads per workgroup, LDS buffers
@@ -225,6 +236,10 @@ int hh_set_table_path(hh_ctx* ctx, int mode);
  * 4 = filtered spectra (hh_set_spectrum_filter, with or without a zoom), 5 = amplitude and phase score
  * (hh_set_spectrum_phase, with or without a zoom). */
 int hh_last_first_pass(const hh_ctx* ctx);
+/* How many sets of column factors the last sweep of this context computed on the fused pipeline: the run length when
+ * every run shares one rise column (hh_rise_columns_shared) and a launch holds whole runs, the number of candidates
+ * swept by the fused pipeline otherwise, 0 when the sweep ran another pipeline. */
+int64_t hh_last_factor_sets(const hh_ctx* ctx);
 /* Which row kernel the last sweep of a general-size context (hh_create2, not a power-of-two square) ran, read-only:
  * out = {R1, R2, dynamic LDS bytes} for the two-step kernel of the pair nx = R1 R2, {0, 0, LDS bytes} for the Stockham
  * kernel, {0, 0, 0} for the float64 direct path (a row length with a prime factor above 31, tilt / psi, a launch that
