@@ -91,6 +91,12 @@ EXPORTS = {
     "hh_set_table_path": (C.c_int, [_ctx, C.c_int]),
     "hh_last_first_pass": (C.c_int, [_ctx]),
     "hh_last_factor_sets": (C.c_int64, [_ctx]),
+    "hh_set_fused_walk": (C.c_int, [_ctx, C.c_int]),
+    "hh_last_fused_walk": (C.c_int, [_ctx]),
+    "hh_set_fused_piece": (C.c_int, [_ctx, C.c_int]),
+    "hh_fused_lds_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "hh_fused_walk_choice": (C.c_int, [C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
+    "hh_fused_walk_footprint": (C.c_int, [_ctx, C.c_double, C.POINTER(C.c_int64)]),
     "hh_last_row_kernel": (C.c_int, [_ctx, C.POINTER(C.c_int32)]),
     "hh_low_high_pass_filter": (C.c_int, [_ctx, _f32p, C.c_double, C.c_double, _f32p]),
     "hh_threshold_data": (C.c_int, [_ctx, _f32p, C.c_int64, C.c_int, C.c_double, _f32p]),

@@ -825,7 +825,10 @@ struct TableArgs {
   const double* params;   // [B][4]: the batch's candidates (runs of run_len share twist, csym, rot)
   const double* units;
   const float2* twtab;    // [N] exp(-2 pi i k / N)
-  float2* table;          // [runs][cap][N/2]: G rows, slot ky = 0 packs (G[0], G[N/2]) — both real
+  float2* table;          // [runs][cap][N/2]: G rows, slot ky = 0 packs (G[0], G[N/2]) — both real (nullptr: not wanted)
+  float2* table_ky;       // the same values ky-major, [runs][N/2][rows_pad], zero past a run's rows (the fused pass's twist
+                          // walk: a wavefront's ky row of one run is contiguous); nullptr: not wanted
+  int rows_pad;           // multiple of SUB (4), >= every run's rows
   const int* run_imax;    // [runs] subunit index range [-imax, imax] a run's table covers
   float2* inter;
   FinArgs fin;
@@ -874,7 +877,15 @@ __global__ __launch_bounds__(256) void k_run_table(TableArgs a) {
   const float k2 = g.inv_sigma2 * 1.44269504088896341f;
   const int row0 = blockIdx.x * K::SUB;
   const int nrow = min(K::SUB, rows - row0);
-  if (nrow <= 0) return;
+  if (nrow <= 0) {
+    // ky-major form: the launch covers rows_pad table rows; those past the run's own are the zeros the row build reads
+    if (a.table_ky && row0 < a.rows_pad)
+      for (int ky = threadIdx.x; ky < K::NKY; ky += 256) {
+        float4* const dst = reinterpret_cast<float4*>(a.table_ky + ((size_t)run * K::NKY + ky) * a.rows_pad + row0);
+        dst[0] = dst[1] = make_float4(0.f, 0.f, 0.f, 0.f);
+      }
+    return;
+  }
   float2 acc[K::SUB][(K::NKY + 255) / 256];
   float alt[K::SUB];  // ky = N/2: sum ey (-1)^y (thread 0 only needs it)
 #pragma unroll
@@ -918,16 +929,35 @@ __global__ __launch_bounds__(256) void k_run_table(TableArgs a) {
       }
     }
   }
+  if (a.table) {
 #pragma unroll
-  for (int r = 0; r < K::SUB; ++r) {
-    if (r >= nrow) break;
+    for (int r = 0; r < K::SUB; ++r) {
+      if (r >= nrow) break;
+#pragma unroll
+      for (int q = 0; q < (K::NKY + 255) / 256; ++q) {
+        const int ky = threadIdx.x + 256 * q;
+        if (ky >= K::NKY) continue;
+        float2 o = acc[r][q];
+        if (ky == 0) o.y = alt[r];
+        tab[(size_t)(row0 + r) * K::NKY + ky] = o;
+      }
+    }
+  }
+  if (a.table_ky) {  // the workgroup's SUB rows of one ky are 32 contiguous bytes here (rows_pad is a multiple of SUB)
+    static_assert(K::SUB == 4, "two 16-byte stores per ky");
 #pragma unroll
     for (int q = 0; q < (K::NKY + 255) / 256; ++q) {
       const int ky = threadIdx.x + 256 * q;
       if (ky >= K::NKY) continue;
-      float2 o = acc[r][q];
-      if (ky == 0) o.y = alt[r];
-      tab[(size_t)(row0 + r) * K::NKY + ky] = o;
+      float2 o[K::SUB];
+#pragma unroll
+      for (int r = 0; r < K::SUB; ++r) {
+        o[r] = r < nrow ? acc[r][q] : make_float2(0.f, 0.f);
+        if (ky == 0 && r < nrow) o[r].y = alt[r];
+      }
+      float4* const dst = reinterpret_cast<float4*>(a.table_ky + ((size_t)run * K::NKY + ky) * a.rows_pad + row0);
+      dst[0] = make_float4(o[0].x, o[0].y, o[1].x, o[1].y);
+      dst[1] = make_float4(o[2].x, o[2].y, o[3].x, o[3].y);
     }
   }
 }
@@ -1520,6 +1550,7 @@ struct FusedArgs {
   const double* params;
   const float2* twtab;
   const float2* table;    // [runs][cap][N/2]
+  const float2* table_ky; // twist walk: [runs][N/2][rows_lds], zero past a run's rows (k_run_table)
   const int* run_imax;    // [runs]
   const float* eg;        // [B][kg][N], or [run_len][kg][N] shared by every run (factor_stride = 0)
   const int* cgs;         // [B][N/4 + 4], or [run_len][N/4 + 4]
@@ -1534,8 +1565,10 @@ struct FusedArgs {
   int run_len;            // candidates per run inside this batch
   int factor_stride;      // factor sets from one run to the next: run_len, or 0 when all runs share run 0's (same rise column)
   // work layers: the first runs_a runs are cut into groups_a layers of cpw_a candidates each, the remaining runs
-  // into groups_b layers of cpw_b (shorter workgroups for the launch's last, partly filled round: fused_schedule)
+  // into groups_b layers of cpw_b (shorter workgroups for the launch's last, partly filled round: fused_schedule).
+  // Twist walk: the same plan with the roles swapped — the first runs_a RISES in groups_a layers of cpw_a runs each.
   int runs_a, groups_a, cpw_a, groups_b, cpw_b;
+  int n_runs;             // twist walk: runs of this launch (batch = n_runs * run_len)
   int cap;                // table rows reserved per run
   int rows_lds;           // table rows staged per ky (>= every run's row count, >= kg)
   int kg;                 // table rows per group of four columns
@@ -1578,21 +1611,31 @@ struct KF {
   static constexpr int BROW = N + 4;               // complex slots per panel row (+32 B against bank conflicts)
   static constexpr size_t LDS_BUF = (size_t)8 * BROW * sizeof(float2);
   static constexpr size_t LDS_R2 = N == 1024 ? (size_t)(N / 2) * sizeof(float2) : 0;  // W_N^n, n < N/2 (k_fused_pass's SPLIT)
-  static size_t lds(int rows_lds, int kg) {
-    return LDS_BUF + (size_t)8 * rows_lds * sizeof(float2) + 2 * ((size_t)kg * N * sizeof(float) + (size_t)cgs_stride<N>() * sizeof(int)) + LDS_R2;
+  // rise walk: one table slice, two factor sets (double-buffered); twist walk: two table slices, one factor set
+  static size_t lds(int rows_lds, int kg, bool twists = false) {
+    const size_t slice = (size_t)8 * rows_lds * sizeof(float2), set = (size_t)kg * N * sizeof(float) + (size_t)cgs_stride<N>() * sizeof(int);
+    return LDS_BUF + (twists ? 2 * slice + set : slice + 2 * set) + LDS_R2;
   }
 };
+constexpr int WALK_RISES = 0, WALK_TWISTS = 1;  // k_fused_pass's candidate loop
 
-template <int N, int EPI, int LOG>
+// WALK_RISES: a workgroup owns (run, ky block) and walks rises — the table slice stays, the factor set changes per
+// candidate (shared by the eight rows: one workgroup barrier per candidate).  WALK_TWISTS (factor_stride = 0, N <= 512):
+// a workgroup owns (rise, ky block) and walks RUNS — the factor set stays, and per candidate each wavefront fetches its
+// own ky row(s) of the next run's table into a buffer nobody else reads: no workgroup barrier in the loop.
+template <int N, int EPI, int LOG, int WALK>
 __global__ __launch_bounds__(N, (N >= 256 ? KF<N>::WPS : 1)) void k_fused_pass(FusedArgs a) {
   using K = KF<N>;
   using KP = KB<N>;  // the partial-moment layout is k_second_pass's
   constexpr int T = K::T, TL = T < 64 ? T : 64, NKY = N / 2;
+  constexpr bool TW = WALK == WALK_TWISTS;
+  static_assert(!TW || N <= 512, "the twist walk has no SPLIT form");
+  constexpr int GBUF = TW ? 2 : 1, FBUF = TW ? 1 : 2;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   float2* const bufs = reinterpret_cast<float2*>(smem);
-  float2* const gs = reinterpret_cast<float2*>(smem + K::LDS_BUF);                       // [8][rows_lds]
-  float* const eg = reinterpret_cast<float*>(smem + K::LDS_BUF + (size_t)8 * a.rows_lds * sizeof(float2));  // [2][kg][N]
-  int* const cgs = reinterpret_cast<int*>(eg + (size_t)2 * a.kg * N);                    // [2][N/4 + 4]
+  float2* const gs = reinterpret_cast<float2*>(smem + K::LDS_BUF);                       // [8][rows_lds]; twist walk: [2][8][rows_lds]
+  float* const eg = reinterpret_cast<float*>(smem + K::LDS_BUF + (size_t)GBUF * 8 * a.rows_lds * sizeof(float2));  // [2][kg][N]; twist walk: [kg][N]
+  int* const cgs = reinterpret_cast<int*>(eg + (size_t)FBUF * a.kg * N);                 // [2][N/4 + 4]; twist walk: [N/4 + 4]
   constexpr int CGS = cgs_stride<N>();
   const int tid = threadIdx.x;
   // leading grid layers: the next batch's column factors (so that batch needs no launch of its own),
@@ -1612,9 +1655,22 @@ __global__ __launch_bounds__(N, (N >= 256 ? KF<N>::WPS : 1)) void k_fused_pass(F
   // order, so ids that are equal mod 8 share an L2.  Every ky block of one layer reads the same column factors and
   // neighbouring 64-byte pieces of the same table rows; mapping a layer's blocks to ids of ONE residue class lets the
   // XCD's L2 fetch them once instead of all eight L2s once each (placement is a speed matter only).
+  // Twist walk: what workgroups share is the table rows of one ky block and one piece of runs, whatever their rise.
+  // The first region's layers (whole multiples of 8) are dealt so that XCD x gets the x-th eighth of them in ky-block-major
+  // order: the workgroups resident on an XCD at one time are then consecutive rises of ONE ky block, walking the same
+  // table rows at about the same pace.  The last region (the short workgroups that fill the launch's tail) keeps the
+  // dispatch order, so it still runs last.
   int gy = blockIdx.y - a.factor_layers - (a.fin.n > 0 ? 1 : 0);
   int kbi = blockIdx.x;
-  {
+  if constexpr (TW) {
+    const int nkb = gridDim.x, la8 = (a.runs_a * a.groups_a) & ~7;
+    const int lw = gy * nkb + kbi;
+    if (lw < la8 * nkb) {
+      const int j = (lw & 7) * (la8 / 8 * nkb) + (lw >> 3);
+      kbi = j / la8;
+      gy = j % la8;
+    }
+  } else {
     const int nkb = gridDim.x, work_layers = gridDim.y - a.factor_layers - (a.fin.n > 0 ? 1 : 0);
     const int lw = gy * nkb + kbi;
     if (lw < (work_layers & ~7) * nkb) {
@@ -1638,10 +1694,13 @@ __global__ __launch_bounds__(N, (N >= 256 ? KF<N>::WPS : 1)) void k_fused_pass(F
       cpw = a.cpw_b;
     }
   }
-  const int cfirst = run * a.run_len + off;
-  const int nc = min(cpw, min(a.run_len - off, a.batch - cfirst));
+  // twist walk: `run` is the workgroup's rise, `off` its first run and cpw the runs of its piece
+  const int cfirst = TW ? off * a.run_len + run : run * a.run_len + off;
+  const int nc = TW ? (run < a.run_len ? min(cpw, a.n_runs - off) : 0) : min(cpw, min(a.run_len - off, a.batch - cfirst));
   if (nc <= 0) return;
-  const int ffirst = run * a.factor_stride + off;  // the first candidate's factor set (the factors do not depend on the twist)
+  const int ffirst = TW ? run : run * a.factor_stride + off;  // the first candidate's factor set (the factors do not depend on the twist)
+  // the workgroup's candidate number cc -> its place in the launch
+  auto cand_of = [&](int cc) { return TW ? (size_t)cfirst + (size_t)cc * a.run_len : (size_t)(cfirst + cc); };
 
   // N = 1024 (SPLIT): a row belongs to two wavefronts (h = 0, 1).  A lane's build already owns columns n and n + N/2
   // (its two groups of four), so the first radix-2 step of the row transform needs no exchange:
@@ -1700,9 +1759,25 @@ __global__ __launch_bounds__(N, (N >= 256 ? KF<N>::WPS : 1)) void k_fused_pass(F
     }
   };
 
+  // Twist walk: the wavefront's own ky row(s) of run off + r, copied by the load unit into slice buffer `half`.  A
+  // wavefront owns RPW consecutive rows of the block, which are RPW * rows_lds contiguous complex words both in the
+  // ky-major table and in the slice; nobody else reads or writes them, so the wavefront alone orders the copy
+  // (lds_dma_wait before its next build).
+  [[maybe_unused]] auto stage_rows = [&](int r, int half) {
+    constexpr int WAVES = N >= 64 ? N / 64 : 1, RPW = 8 / WAVES, LANES = N >= 64 ? 64 : N;
+    const int lane = tid & 63, wave = tid >> 6;
+    const int pieces = RPW * a.rows_lds / 2;   // 16-byte pieces (rows_lds is even)
+    const char* const gsrc = reinterpret_cast<const char*>(a.table_ky + ((size_t)(off + r) * NKY + 8 * kb + wave * RPW) * a.rows_lds);
+    const char* const ldst = reinterpret_cast<const char*>(gs + (size_t)(half * 8 + wave * RPW) * a.rows_lds);
+    for (int p0 = 0; p0 < pieces; p0 += LANES)
+      if (p0 + lane < pieces) lds_dma16(gsrc + (size_t)(p0 + lane) * 16, lds_offset_of(ldst + (size_t)p0 * 16));
+  };
   // the run's table slice of this ky block, transposed to [ky in block][table row]; rows past the
   // run's own count are zero
-  {
+  if constexpr (TW) {
+    stage_rows(0, 0);
+    if (nc > 1) stage_rows(1, 1);
+  } else {
     const int rows = (2 * a.run_imax[run] + 1) * a.n_units;
     const float2* const tab = a.table + (size_t)run * a.cap * NKY + 8 * kb;
     for (int e = tid; e < a.rows_lds * 4; e += K::THREADS) {
@@ -1730,6 +1805,14 @@ __global__ __launch_bounds__(N, (N >= 256 ? KF<N>::WPS : 1)) void k_fused_pass(F
 
   const int wave_in_row = T > 64 ? (t >> 6) : 0;
   const bool writer = (t & (TL - 1)) == group_sum_lane<TL>();
+  // twist walk: what the build needs of the factor set is the same for every candidate of the workgroup — the first
+  // table rows of the lane's two column groups and the row count
+  [[maybe_unused]] int tw_cg0 = 0, tw_cg1 = 0, tw_kgn = 1;
+  if constexpr (TW) {
+    tw_cg0 = cgs[t];
+    tw_cg1 = cgs[t + T];
+    tw_kgn = max(1, min(a.kg, __builtin_amdgcn_readfirstlane(cgs[N / 4])));
+  }
 
   // One candidate = part A (build the row from the table slice and the candidate's factors, first butterflies, data
   // left in the group's exchange buffer) + part B (rest of the transform, amplitudes, moments).  A is LDS-heavy, B is
@@ -1740,7 +1823,7 @@ __global__ __launch_bounds__(N, (N >= 256 ? KF<N>::WPS : 1)) void k_fused_pass(F
   // registers between A and B, and the factor buffers are used exactly as without the stagger: A(it) reads buffer
   // it & 1 in round it, the copies for it + 1 go to the other buffer, one workgroup barrier closes the round.
   // A ends at the exchange after the transform's first stage.
-  constexpr bool STAGGER = T == 64;
+  constexpr bool STAGGER = T == 64 && !TW;   // (twist walk: no barrier holds the wavefronts to a common round)
   const bool late = STAGGER && __builtin_amdgcn_readfirstlane(tid >> 6) >= (N / 64) / 2;
 
   // (see flush_q) — not for the packed row's group (its two rows are un-packed through the exchange buffer)
@@ -1748,8 +1831,9 @@ __global__ __launch_bounds__(N, (N >= 256 ? KF<N>::WPS : 1)) void k_fused_pass(F
 
   auto part_a = [&](int cc) {
     const int cur = cc & 1;
-    const float* const egc = eg + (size_t)cur * a.kg * N;
-    const int* const cgc = cgs + cur * CGS;
+    const float* const egc = TW ? eg : eg + (size_t)cur * a.kg * N;
+    [[maybe_unused]] const int* const cgc = cgs + cur * CGS;
+    const float2* const gsc = TW ? gs + (size_t)cur * 8 * a.rows_lds : gs;   // twist walk: the candidate's slice buffer
     // ---- this group's row of H, built by the group itself into its own exchange buffer (no workgroup barrier).
     // A lane owns two groups of four consecutive columns (x = 4 t + c and 4 (t + T) + c): two independent
     // accumulation chains, and the operands of the next table row are in flight while this row's FMAs issue.
@@ -1758,14 +1842,14 @@ __global__ __launch_bounds__(N, (N >= 256 ? KF<N>::WPS : 1)) void k_fused_pass(F
       // (clamped to the buffer's kg: whatever the word holds, the walk is bounded)
       // (at least one: a candidate that reaches no column has a first factor row of zeros, so the sums need no
       // separate zero fill)
-      const int kgn = max(1, min(a.kg, __builtin_amdgcn_readfirstlane(cgc[N / 4])));
+      const int kgn = TW ? tw_kgn : max(1, min(a.kg, __builtin_amdgcn_readfirstlane(cgc[N / 4])));
       // sums of the two column groups xg0, xg1 (four columns each).  The first table row initialises the sums (no zero
       // fill), the others accumulate; the operand addresses are base + k x constant, so the unrolled loop addresses
       // them with instruction offsets.
       float2 p0, p1, p2, p3, q0, q1, q2, q3;
       auto accumulate = [&](int xg0, int xg1) {
-        const float2* const grow0 = gs + gi * a.rows_lds + cgc[xg0];
-        const float2* const grow1 = gs + gi * a.rows_lds + cgc[xg1];
+        const float2* const grow0 = gsc + gi * a.rows_lds + (TW ? tw_cg0 : cgc[xg0]);
+        const float2* const grow1 = gsc + gi * a.rows_lds + (TW ? tw_cg1 : cgc[xg1]);
         const float* const erow0 = egc + 4 * xg0;
         const float* const erow1 = egc + 4 * xg1;
         {
@@ -1845,7 +1929,7 @@ __global__ __launch_bounds__(N, (N >= 256 ? KF<N>::WPS : 1)) void k_fused_pass(F
   };
 
   auto part_b = [&](int cc) {
-    const size_t b = (size_t)(cfirst + cc);
+    const size_t b = cand_of(cc);
     float2 v[8];
     fft_lanes_part<NF, true, TwRegs, 2, 1>(v, twsrc, tf, fbuf);  // v[m] = C[kx = t + m*T] (SPLIT: kx = 2 (tf + 64 m) + h); the exchanges reuse the row's panel slots
 
@@ -1955,7 +2039,7 @@ __global__ __launch_bounds__(N, (N >= 256 ? KF<N>::WPS : 1)) void k_fused_pass(F
   // stores have a round to land; the late wavefronts (B of the previous candidate first) had that order already.
   auto flush_q = [&](int cc) {
     if constexpr (EPI == EPI_QSTORE) {
-      const size_t b = (size_t)(cfirst + cc);
+      const size_t b = cand_of(cc);
       const float4* const st = reinterpret_cast<const float4*>(fbuf) + 2 * tf;
       const float4 q0 = st[0], q1 = st[1];
       const float qv[8] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w};
@@ -1969,6 +2053,21 @@ __global__ __launch_bounds__(N, (N >= 256 ? KF<N>::WPS : 1)) void k_fused_pass(F
     }
   };
 
+  if constexpr (TW) {
+    // Candidate it = run off + it.  Its rows were copied a whole candidate ago: the copy for it + 2 goes into the buffer
+    // build(it) has just finished with, right after the wait that retires the copy for it + 1 — which has been flying
+    // since build(it - 1), and behind which the only stores (B(it - 1)'s moments and q) are a build old, so the wait does not
+    // sit on their latency (the flush_q lesson; q is stored directly here).  No workgroup barrier: rows and panel are
+    // the wavefront's own, the factor set never changes.
+#pragma unroll 1
+    for (int it = 0; it < nc; ++it) {
+      part_a(it);
+      if (it + 1 < nc) lds_dma_wait();
+      if (it + 2 < nc) stage_rows(it + 2, it & 1);
+      part_b(it);
+    }
+    return;
+  }
 #pragma unroll 1
   for (int it = 0; it < nc; ++it) {
     if (defer_q && it > 0) flush_q(it - 1);
@@ -2464,6 +2563,8 @@ struct hh_ctx {
   int max_batch = 0;
   int n_cu = 0;                  // compute units of the device
   int slots = 0;                 // resident k_fused_pass workgroups for the launch shape slots_key (fused_slots)
+  int slots_tw = 0;              // ... of the twist walk, for slots_key_tw
+  size_t slots_key_tw = 0;
   size_t slots_key = 0;
   hipStream_t own_stream = nullptr;
   hipStream_t stream = nullptr;
@@ -2497,6 +2598,11 @@ struct hh_ctx {
   int n_kb = 0;
   float2* d_table = nullptr;     // shared-twist first pass: [runs per batch][rows][N/2] column-transform table
   size_t cap_table = 0;          // bytes
+  float2* d_table_ky = nullptr;  // the same tables ky-major, [runs][N/2][rows_f], for the fused pass's twist walk
+  size_t cap_table_ky = 0;       // bytes
+  int fused_walk = 0;            // hh_set_fused_walk: 0 auto, 1 rises, 2 twists
+  int last_fused_walk = 0;       // hh_last_fused_walk
+  int fused_piece = 0;           // hh_set_fused_piece: runs per workgroup of the twist walk (0: fused_schedule's own cut)
   int* d_run_imax = nullptr;     // [runs of the sweep]
   int64_t cap_runs = 0;
   std::vector<int> h_run_imax;
@@ -2768,7 +2874,9 @@ template <int N>
 int launch_run_table(hh_ctx* c, const TableArgs& a, int runs, int rows) {
   using K = KT<N>;
   ProfScope ps(c, 3);
-  hipLaunchKernelGGL((k_run_table<N>), dim3((rows + K::SUB - 1) / K::SUB, runs), dim3(256), 0, c->stream, a);
+  // (the ky-major form is written out to rows_pad: the workgroups past the last table row zero its padding)
+  const int rows_out = a.table_ky ? std::max(rows, a.rows_pad) : rows;
+  hipLaunchKernelGGL((k_run_table<N>), dim3((rows_out + K::SUB - 1) / K::SUB, runs), dim3(256), 0, c->stream, a);
   HH_HIP(c, hipGetLastError());
   return HH_OK;
 }
@@ -2815,15 +2923,29 @@ struct RunPlan {
 constexpr int64_t HH_MIN_RUN = 8;              // shorter runs do not amortise their table and workgroup granularity
 constexpr size_t HH_TABLE_BYTES_MAX = 1ull << 30;
 
-size_t fused_lds(int n, int rows_lds, int kg) {
+size_t fused_lds(int n, int rows_lds, int kg, bool twists = false) {
   switch (n) {
-    case 32: return KF<32>::lds(rows_lds, kg);
-    case 64: return KF<64>::lds(rows_lds, kg);
-    case 128: return KF<128>::lds(rows_lds, kg);
-    case 256: return KF<256>::lds(rows_lds, kg);
-    case 512: return KF<512>::lds(rows_lds, kg);
-    default: return KF<1024>::lds(rows_lds, kg);
+    case 32: return KF<32>::lds(rows_lds, kg, twists);
+    case 64: return KF<64>::lds(rows_lds, kg, twists);
+    case 128: return KF<128>::lds(rows_lds, kg, twists);
+    case 256: return KF<256>::lds(rows_lds, kg, twists);
+    case 512: return KF<512>::lds(rows_lds, kg, twists);
+    default: return KF<1024>::lds(rows_lds, kg, twists);
   }
+}
+
+// The fused pass's shape for a sweep whose smallest rise is rise_all and whose largest table has `rows` rows: table rows
+// per group of four columns (subunit indices i with lo <= i rise <= hi, hi - lo = (3 + 2 rpx) apix + 2 slack) and table
+// rows staged per ky.  False: the pass does not fit (more than 16 rows per group, or more LDS than a compute unit has).
+bool fused_shape(const hh_ctx* c, double rise_all, int rows, int* kg_out, int* rows_f_out) {
+  const double span4 = (3.0 + 2.0 * c->geom.rpx) * c->geom.apix + 2.0 * c->geom.slack;
+  const double kg = (std::floor(span4 / (double)(float)rise_all) + 2.0) * c->geom.n_units;
+  int rows_f = std::max(rows, (int)std::min(kg, 1.0e6));
+  rows_f += (4 - rows_f % 8 + 8) % 8;  // = 4 (mod 8): the eight ky rows of the slice start in different banks
+  if (!(kg <= 16.0 && fused_lds(c->n, rows_f, (int)kg) <= 160 * 1024 - 1024)) return false;
+  *kg_out = (int)kg;
+  *rows_f_out = rows_f;
+  return true;
 }
 
 int table_cols(int n) {
@@ -2894,18 +3016,7 @@ RunPlan plan_runs(hh_ctx* c, const double* hp, int64_t g) {
   plan.rows_lds = need <= 64.0 ? (int)need : 0;  // KT<N>::ROWS_MAX: one lane per staged row
   plan.rows = (2 * imax_all + 1) * c->geom.n_units;
   if ((size_t)plan.rows * (c->n / 2) * sizeof(float2) > HH_TABLE_BYTES_MAX) return plan;
-  // fused pass: subunit indices i with lo <= i rise <= hi for four columns, hi - lo = (3 + 2 rpx) apix + 2 slack
-  if (c->fused_path) {
-    const double span4 = (3.0 + 2.0 * c->geom.rpx) * c->geom.apix + 2.0 * c->geom.slack;
-    const double kg = (std::floor(span4 / (double)(float)rise_all) + 2.0) * c->geom.n_units;
-    int rows_f = std::max(plan.rows, (int)std::min(kg, 1.0e6));
-    rows_f += (4 - rows_f % 8 + 8) % 8;  // = 4 (mod 8): the eight ky rows of the slice start in different banks
-    if (kg <= 16.0 && fused_lds(c->n, rows_f, (int)kg) <= 160 * 1024 - 1024) {
-      plan.fused = true;
-      plan.kg = (int)kg;
-      plan.rows_f = rows_f;
-    }
-  }
+  if (c->fused_path) plan.fused = fused_shape(c, rise_all, plan.rows, &plan.kg, &plan.rows_f);
   if (!plan.fused && plan.rows_lds == 0) return plan;
   plan.shared_factors = plan.fused && rise_columns_shared(hp, g, len);
   if (plan.shared_factors)  // equal columns have equal smallest rises: the shared cgs index ONE table geometry
@@ -2987,13 +3098,28 @@ int launch_factors(hh_ctx* c, const FactorArgs& a, int batch) {
   return HH_OK;
 }
 
+// Sizes whose k_fused_pass has a twist-walking candidate loop (N = 1024 keeps the rise walk: its rows are split over
+// two wavefronts, which meet at a workgroup barrier per candidate either way).
+constexpr bool twist_walk_built(int n) { return n <= 512; }
+
 template <int N, int EPI, int LOG>
-int launch_fused(hh_ctx* c, const FusedArgs& a, int layers) {
+int launch_fused(hh_ctx* c, const FusedArgs& a, int layers, bool twists) {
   using K = KF<N>;
-  if (int rc = ensure_lds_attr(c, reinterpret_cast<const void*>(&k_fused_pass<N, EPI, LOG>), 160 * 1024)) return rc;
+  const dim3 grid(a.n_kb, a.factor_layers + layers + (a.fin.n > 0 ? 1 : 0));
+  if (twists) {
+    if constexpr (twist_walk_built(N)) {
+      if (int rc = ensure_lds_attr(c, reinterpret_cast<const void*>(&k_fused_pass<N, EPI, LOG, WALK_TWISTS>), 160 * 1024)) return rc;
+      ProfScope ps(c, 1);
+      hipLaunchKernelGGL((k_fused_pass<N, EPI, LOG, WALK_TWISTS>), grid, dim3(K::THREADS), K::lds(a.rows_lds, a.kg, true), c->stream, a);
+      HH_HIP(c, hipGetLastError());
+      return HH_OK;
+    } else {
+      return fail(c, HH_ERR_STATE, "k_fused_pass has no twist walk at this size");
+    }
+  }
+  if (int rc = ensure_lds_attr(c, reinterpret_cast<const void*>(&k_fused_pass<N, EPI, LOG, WALK_RISES>), 160 * 1024)) return rc;
   ProfScope ps(c, 1);
-  hipLaunchKernelGGL((k_fused_pass<N, EPI, LOG>), dim3(a.n_kb, a.factor_layers + layers + (a.fin.n > 0 ? 1 : 0)),
-                     dim3(K::THREADS), K::lds(a.rows_lds, a.kg), c->stream, a);
+  hipLaunchKernelGGL((k_fused_pass<N, EPI, LOG, WALK_RISES>), grid, dim3(K::THREADS), K::lds(a.rows_lds, a.kg), c->stream, a);
   HH_HIP(c, hipGetLastError());
   return HH_OK;
 }
@@ -3005,35 +3131,49 @@ int dispatch_factors(hh_ctx* c, const FactorArgs& a, int batch) {
 }
 
 template <int EPI, int LOG>
-int dispatch_fused_n(hh_ctx* c, const FusedArgs& a, int layers) {
-#define HH_CALL(NN) launch_fused<NN, EPI, LOG>(c, a, layers)
+int dispatch_fused_n(hh_ctx* c, const FusedArgs& a, int layers, bool twists) {
+#define HH_CALL(NN) launch_fused<NN, EPI, LOG>(c, a, layers, twists)
   HH_SWITCH_N(c, HH_CALL);
 #undef HH_CALL
 }
 
 // Workgroups of k_fused_pass the device holds at once (occupancy x compute units), for the launch shape in `a`.
+// (twists: of the twist walk; 0 workgroups where the size has none or its slices do not fit the compute unit's LDS)
 template <int N, int EPI, int LOG>
-int slots_fused(hh_ctx* c, const FusedArgs& a, int* out) {
+int slots_fused(hh_ctx* c, const FusedArgs& a, bool twists, int* out) {
   using K = KF<N>;
-  if (int rc = ensure_lds_attr(c, reinterpret_cast<const void*>(&k_fused_pass<N, EPI, LOG>), 160 * 1024)) return rc;
   int per_cu = 0;
-  HH_HIP(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_fused_pass<N, EPI, LOG>, K::THREADS, K::lds(a.rows_lds, a.kg)));
+  if (twists) {
+    if constexpr (twist_walk_built(N)) {
+      if (K::lds(a.rows_lds, a.kg, true) > (size_t)160 * 1024) { *out = 0; return HH_OK; }
+      if (int rc = ensure_lds_attr(c, reinterpret_cast<const void*>(&k_fused_pass<N, EPI, LOG, WALK_TWISTS>), 160 * 1024)) return rc;
+      HH_HIP(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_fused_pass<N, EPI, LOG, WALK_TWISTS>, K::THREADS, K::lds(a.rows_lds, a.kg, true)));
+      *out = std::max(0, per_cu) * std::max(1, c->n_cu);
+    } else {
+      *out = 0;
+    }
+    return HH_OK;
+  }
+  if (int rc = ensure_lds_attr(c, reinterpret_cast<const void*>(&k_fused_pass<N, EPI, LOG, WALK_RISES>), 160 * 1024)) return rc;
+  HH_HIP(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_fused_pass<N, EPI, LOG, WALK_RISES>, K::THREADS, K::lds(a.rows_lds, a.kg)));
   *out = std::max(1, per_cu) * std::max(1, c->n_cu);
   return HH_OK;
 }
 template <int EPI, int LOG>
-int slots_fused_n(hh_ctx* c, const FusedArgs& a, int* out) {
-#define HH_CALL(NN) slots_fused<NN, EPI, LOG>(c, a, out)
+int slots_fused_n(hh_ctx* c, const FusedArgs& a, bool twists, int* out) {
+#define HH_CALL(NN) slots_fused<NN, EPI, LOG>(c, a, twists, out)
   HH_SWITCH_N(c, HH_CALL);
 #undef HH_CALL
 }
-int fused_slots(hh_ctx* c, const FusedArgs& a, int* out) {
-  const size_t key = ((size_t)a.rows_lds << 20) ^ ((size_t)a.kg << 8) ^ (size_t)(c->n_segments > 1) ^ ((size_t)c->log_flag << 1);
-  if (c->slots_key == key && c->slots > 0) { *out = c->slots; return HH_OK; }
+int fused_slots(hh_ctx* c, const FusedArgs& a, int* out, bool twists = false) {
+  const size_t key = ((size_t)a.rows_lds << 20) ^ ((size_t)a.kg << 8) ^ (size_t)(c->n_segments > 1) ^ ((size_t)c->log_flag << 1) ^ ((size_t)1 << 40);
+  int& cached = twists ? c->slots_tw : c->slots;
+  size_t& cached_key = twists ? c->slots_key_tw : c->slots_key;
+  if (cached_key == key) { *out = cached; return HH_OK; }
   int rc;
-  if (c->n_segments == 1) rc = c->log_flag ? slots_fused_n<EPI_SCORE, 1>(c, a, out) : slots_fused_n<EPI_SCORE, 0>(c, a, out);
-  else rc = c->log_flag ? slots_fused_n<EPI_QSTORE, 1>(c, a, out) : slots_fused_n<EPI_QSTORE, 0>(c, a, out);
-  if (rc == HH_OK) { c->slots = *out; c->slots_key = key; }
+  if (c->n_segments == 1) rc = c->log_flag ? slots_fused_n<EPI_SCORE, 1>(c, a, twists, out) : slots_fused_n<EPI_SCORE, 0>(c, a, twists, out);
+  else rc = c->log_flag ? slots_fused_n<EPI_QSTORE, 1>(c, a, twists, out) : slots_fused_n<EPI_QSTORE, 0>(c, a, twists, out);
+  if (rc == HH_OK) { cached = *out; cached_key = key; }
   return rc;
 }
 
@@ -3045,7 +3185,7 @@ int fused_slots(hh_ctx* c, const FusedArgs& a, int* out) {
 // (`groups_b`), so that round is short.  C2 in one launch (400 runs of 250, 32 ky blocks, 512 slots) is exactly 25
 // rounds of whole runs; an eighth of it (50 runs) is 3 rounds of whole runs + 2 runs in 8 pieces each, 798 units
 // instead of 4 x 254.
-struct FusedSchedule { int runs_a, groups_a, cpw_a, groups_b, cpw_b, layers; };
+struct FusedSchedule { int runs_a, groups_a, cpw_a, groups_b, cpw_b, layers; double cost; };  // cost: the model's launch length, in candidates
 FusedSchedule fused_schedule(int64_t runs, int run_len, int n_kb, int slots) {
   const int setup = 4, min_cpw = 16, gmax = std::max(1, run_len / min_cpw);
   auto cpw_of = [&](int g) { return (run_len + g - 1) / g; };
@@ -3071,15 +3211,32 @@ FusedSchedule fused_schedule(int64_t runs, int run_len, int n_kb, int slots) {
     }
     if (ta + tb < best_t * 0.995) {  // (near-ties go to the fewer, longer workgroups)
       best_t = ta + tb;
-      best = FusedSchedule{(int)runs_a, ga_e, cpw_a, gb, cpw_b, (int)(runs_a * ga_e + runs_b * gb)};
+      best = FusedSchedule{(int)runs_a, ga_e, cpw_a, gb, cpw_b, (int)(runs_a * ga_e + runs_b * gb), ta + tb};
     }
   }
   return best;
 }
 
-int dispatch_fused(hh_ctx* c, const FusedArgs& a, int layers) {
-  if (c->n_segments == 1) return c->log_flag ? dispatch_fused_n<EPI_SCORE, 1>(c, a, layers) : dispatch_fused_n<EPI_SCORE, 0>(c, a, layers);
-  return c->log_flag ? dispatch_fused_n<EPI_QSTORE, 1>(c, a, layers) : dispatch_fused_n<EPI_QSTORE, 0>(c, a, layers);
+int dispatch_fused(hh_ctx* c, const FusedArgs& a, int layers, bool twists) {
+  if (c->n_segments == 1) return c->log_flag ? dispatch_fused_n<EPI_SCORE, 1>(c, a, layers, twists) : dispatch_fused_n<EPI_SCORE, 0>(c, a, layers, twists);
+  return c->log_flag ? dispatch_fused_n<EPI_QSTORE, 1>(c, a, layers, twists) : dispatch_fused_n<EPI_QSTORE, 0>(c, a, layers, twists);
+}
+
+// Which candidate loop a launch of `runs` whole runs of `run_len` candidates takes when every run shares one rise
+// column: the twist walk (workgroups own a rise and walk the runs; fused_schedule with the roles swapped) needs the
+// compute unit to hold as many of its workgroups as of the rise walk's (its table rows are double-buffered), and under
+// "auto" a schedule whose modelled length is not above the rise walk's — a grid of two or three twists would pay a
+// set-up per two or three candidates.  mode: hh_set_fused_walk.  Returns WALK_RISES or WALK_TWISTS.
+struct WalkChoice { int walk; FusedSchedule rises, twists; };
+WalkChoice choose_walk(int64_t runs, int run_len, int n_kb, int slots_rises, int slots_twists, int mode) {
+  WalkChoice w{};
+  w.walk = WALK_RISES;
+  w.rises = fused_schedule(runs, run_len, n_kb, slots_rises);
+  if (slots_twists <= 0 || runs < 2 || runs > (int64_t)1 << 30) { w.twists = FusedSchedule{}; return w; }
+  w.twists = fused_schedule(run_len, (int)runs, n_kb, slots_twists);
+  if (mode == 1 || slots_twists < slots_rises) return w;
+  if (mode == 2 || w.twists.cost <= w.rises.cost) w.walk = WALK_TWISTS;
+  return w;
 }
 
 // The sweep with the shared-twist first pass (plan.ok): batches are whole runs (or pieces of one
@@ -3159,14 +3316,6 @@ int sweep_runs(hh_ctx* c, const double* d_params, int64_t g, float* d_scores, co
   int64_t per_group = std::max<int64_t>(1, (int64_t)(HH_TABLE_BYTES_MAX / run_bytes));
   per_group = std::min<int64_t>(std::min<int64_t>(per_group, runs), 65535);
   if (per_group > per_batch) per_group -= per_group % per_batch;
-  const size_t need = (size_t)per_group * run_bytes;
-  if (need > c->cap_table) {
-    if (c->d_table) HH_HIP(c, hipFree(c->d_table));
-    c->d_table = nullptr;
-    c->cap_table = 0;
-    HH_HIP(c, hipMalloc(&c->d_table, need));
-    c->cap_table = need;
-  }
   if (plan.fused) {
     // shared: one set per rise; else two halves of a launch's candidates, alternating
     const size_t sets = shared ? (size_t)plan.len : (size_t)2 * bmax;
@@ -3218,6 +3367,54 @@ int sweep_runs(hh_ctx* c, const double* d_params, int64_t g, float* d_scores, co
       }
     }
   }
+  // The candidate loop of every fused launch (choose_walk): with one factor set per rise a launch holds whole runs whose
+  // tables lie in one table group, so a workgroup can own a rise and walk the runs.
+  std::vector<WalkChoice> walks(batches.size());
+  bool any_twists = false, any_rises = false;
+  if (plan.fused) {
+    FusedArgs shape{};
+    shape.rows_lds = plan.rows_f;
+    shape.kg = plan.kg;
+    int slots_r = 0, slots_t = 0;
+    int rc = fused_slots(c, shape, &slots_r);
+    if (rc) return rc;
+    // Several segments: "auto" keeps the rise walk: the twist walk was measured slower there (C5: 8.04 -> 8.18 ms per
+    // step).  The reading that fits: the q of a candidate (0.4 MB at N = 512) is written by the 32 ky blocks' workgroups,
+    // which the rise walk places on one XCD and runs in step, and there the stores, not the factor copies, set the pace.
+    const int walk_mode = c->fused_walk == 0 && c->n_segments > 1 ? 1 : c->fused_walk;
+    if (shared && walk_mode != 1) {
+      rc = fused_slots(c, shape, &slots_t, true);
+      if (rc) return rc;
+    }
+    for (size_t bi = 0; bi < batches.size(); ++bi) {
+      const Batch& bt = batches[bi];
+      const int len = std::min(bt.run_len, bt.nb);
+      const int64_t runs_b = (bt.nb + bt.run_len - 1) / bt.run_len;
+      const bool whole = shared && bt.run_len == plan.len && bt.nb % bt.run_len == 0;
+      walks[bi] = choose_walk(runs_b, len, c->n_kb, slots_r, whole ? slots_t : 0, walk_mode);
+      (walks[bi].walk == WALK_TWISTS ? any_twists : any_rises) = true;
+    }
+    c->last_fused_walk = any_rises ? 1 : 2;
+  }
+  // each table layout is allocated (and built, below) only where a launch reads it
+  const size_t need = (size_t)per_group * run_bytes;
+  if ((!plan.fused || any_rises) && need > c->cap_table) {
+    if (c->d_table) HH_HIP(c, hipFree(c->d_table));
+    c->d_table = nullptr;
+    c->cap_table = 0;
+    HH_HIP(c, hipMalloc(&c->d_table, need));
+    c->cap_table = need;
+  }
+  if (any_twists) {
+    const size_t need_ky = (size_t)per_group * nky * plan.rows_f * sizeof(float2);
+    if (need_ky > c->cap_table_ky) {
+      if (c->d_table_ky) HH_HIP(c, hipFree(c->d_table_ky));
+      c->d_table_ky = nullptr;
+      c->cap_table_ky = 0;
+      HH_HIP(c, hipMalloc(&c->d_table_ky, need_ky));
+      c->cap_table_ky = need_ky;
+    }
+  }
   const size_t eg_half = (size_t)bmax * plan.kg * c->n;
   const size_t cg_half = (size_t)bmax * (c->n / 4 + 4);  // cgs_stride<N>()
   auto factor_args = [&](const Batch& bt, int half) {
@@ -3252,7 +3449,13 @@ int sweep_runs(hh_ctx* c, const double* d_params, int64_t g, float* d_scores, co
       const int nq = (int)std::min<int64_t>(per_group, runs - bt.q0);
       c->prof_now = c->profiling > 0;
       ta.params = d_params + 4 * bt.q0 * plan.len;
-      ta.table = c->d_table;
+      // each layout only where a launch of this group reads it
+      bool rows_major = !plan.fused, ky_major = false;
+      for (size_t bj = bi; bj < batches.size() && batches[bj].q0 == bt.q0; ++bj)
+        (plan.fused && walks[bj].walk == WALK_TWISTS ? ky_major : rows_major) = true;
+      ta.table = rows_major ? c->d_table : nullptr;
+      ta.table_ky = ky_major ? c->d_table_ky : nullptr;
+      ta.rows_pad = plan.rows_f;
       ta.run_imax = c->d_run_imax + bt.q0;
       ta.run_len = (int)std::min<int64_t>(plan.len, 1 << 30);
       ta.fin = FinArgs{};
@@ -3263,7 +3466,8 @@ int sweep_runs(hh_ctx* c, const double* d_params, int64_t g, float* d_scores, co
     }
     c->prof_now = c->profiling > 0 && ((int64_t)bi % c->profiling) == 0;
     if (c->prof_now) c->prof_candidates += bt.nb;
-    ta.table = c->d_table + (size_t)(bt.r0 - bt.q0) * plan.rows * nky;
+    ta.table = c->d_table ? c->d_table + (size_t)(bt.r0 - bt.q0) * plan.rows * nky : nullptr;
+    ta.table_ky = nullptr;
     ta.run_imax = c->d_run_imax + bt.r0;
     ta.run_len = plan.len <= bmax ? (int)plan.len : bmax + 1;
     ta.params = d_params + 4 * bt.g0;
@@ -3281,7 +3485,9 @@ int sweep_runs(hh_ctx* c, const double* d_params, int64_t g, float* d_scores, co
       FusedArgs fu{};
       fu.params = ta.params;
       fu.twtab = c->d_tw;
+      const bool twists = walks[bi].walk == WALK_TWISTS;
       fu.table = ta.table;
+      fu.table_ky = twists ? c->d_table_ky + (size_t)(bt.r0 - bt.q0) * nky * plan.rows_f : nullptr;
       fu.run_imax = ta.run_imax;
       fu.eg = shared ? c->d_eg : c->d_eg + half * eg_half;
       fu.cgs = shared ? c->d_cgs : c->d_cgs + half * cg_half;
@@ -3301,13 +3507,13 @@ int sweep_runs(hh_ctx* c, const double* d_params, int64_t g, float* d_scores, co
       fu.kg = plan.kg;
       int work_layers = 0;
       {
-        const int64_t runs_b = (bt.nb + fu.run_len - 1) / fu.run_len;
-        const int len = std::min(fu.run_len, bt.nb);
-        int slots = 0;
-        rc = fused_slots(c, fu, &slots);
-        if (rc) return rc;
-        const FusedSchedule fs = fused_schedule(runs_b, len, c->n_kb, slots);
+        FusedSchedule fs = twists ? walks[bi].twists : walks[bi].rises;
+        if (twists && c->fused_piece > 0) {  // every rise's runs in pieces of fused_piece (the last piece: what is left)
+          const int runs_b = bt.nb / fu.run_len, g = (runs_b + c->fused_piece - 1) / c->fused_piece;
+          fs = FusedSchedule{fu.run_len, g, c->fused_piece, g, c->fused_piece, fu.run_len * g, 0.0};
+        }
         fu.runs_a = fs.runs_a; fu.groups_a = fs.groups_a; fu.cpw_a = fs.cpw_a; fu.groups_b = fs.groups_b; fu.cpw_b = fs.cpw_b;
+        fu.n_runs = (int)((bt.nb + fu.run_len - 1) / fu.run_len);
         work_layers = fs.layers;
       }
       fu.n_units = c->geom.n_units;
@@ -3316,7 +3522,7 @@ int sweep_runs(hh_ctx* c, const double* d_params, int64_t g, float* d_scores, co
         fu.next = factor_args(batches[bi + 1], half ^ 1);
         fu.factor_layers = (fu.next.count + c->n_kb - 1) / c->n_kb;
       }
-      rc = dispatch_fused(c, fu, work_layers);
+      rc = dispatch_fused(c, fu, work_layers, twists);
       if (rc) return rc;
       pending = FinArgs{};
       rc = scores_tail(c, g, first_cand + bt.g0, bt.nb, bi + 1 == batches.size(), d_scores, pending, part);
@@ -3365,6 +3571,7 @@ int sweep_transform(hh_ctx* c, const double* d_params, int64_t g, float* d_score
 int sweep_on_device(hh_ctx* c, const double* d_params, const int64_t n_cand, float* d_scores,
                     const double* h_params = nullptr, int64_t ld = 0) {
   c->last_factor_sets = 0;
+  c->last_fused_walk = 0;
   if (phase_on(c)) return phase_sweep(c, d_params, n_cand, d_scores, ld);
   if (zoom_on(c)) return zoom_sweep(c, d_params, n_cand, d_scores, ld);
   if (c->general) return gen_sweep(c, d_params, h_params, n_cand, d_scores, ld);
@@ -3627,6 +3834,7 @@ void hh_destroy(hh_ctx* c) try {
   (void)hipFree(c->d_seg_rows);
   (void)hipFree(c->d_q_roff);
   (void)hipFree(c->d_table);
+  (void)hipFree(c->d_table_ky);
   (void)hipFree(c->d_eg);
   (void)hipFree(c->d_cgs);
   (void)hipFree(c->d_run_imax);
@@ -3655,7 +3863,7 @@ int64_t hh_memory_bytes(const hh_ctx* c, int64_t out[5]) try {
     return (p && hipMemPtrGetInfo(const_cast<void*>(p), &n) == hipSuccess) ? (int64_t)n : 0;
   };
   int64_t part[5] = {0, 0, 0, 0, 0};
-  part[0] = size_of(c->d_table);
+  part[0] = size_of(c->d_table) + size_of(c->d_table_ky);
   part[1] = size_of(c->d_eg) + size_of(c->d_cgs);
   part[2] = size_of(c->d_inter);
   part[3] = size_of(c->d_q) + size_of(c->d_cpart) + size_of(c->d_wec) + size_of(c->d_psum);
@@ -3970,6 +4178,60 @@ int hh_sweep_device_strided(hh_ctx* c, const double* d_params, const double* h_p
 
 int hh_last_first_pass(const hh_ctx* c) { return c ? c->last_first_pass : HH_ERR_ARG; }
 int64_t hh_last_factor_sets(const hh_ctx* c) { return c ? c->last_factor_sets : HH_ERR_ARG; }
+int hh_set_fused_walk(hh_ctx* c, int mode) try {
+  if (!c) return HH_ERR_ARG;
+  if (mode < 0 || mode > 2) return fail(c, HH_ERR_ARG, "hh_set_fused_walk: mode is 0 (auto), 1 (rises) or 2 (twists)");
+  c->fused_walk = mode;
+  return HH_OK;
+} HH_CATCH_CTX(c, "hh_set_fused_walk")
+int hh_last_fused_walk(const hh_ctx* c) { return c ? c->last_fused_walk : HH_ERR_ARG; }
+int hh_set_fused_piece(hh_ctx* c, int runs_per_workgroup) try {
+  if (!c) return HH_ERR_ARG;
+  if (runs_per_workgroup < 0) return fail(c, HH_ERR_ARG, "hh_set_fused_piece: runs per workgroup >= 0");
+  c->fused_piece = runs_per_workgroup;
+  return HH_OK;
+} HH_CATCH_CTX(c, "hh_set_fused_piece")
+int64_t hh_fused_lds_bytes(int n, int rows_lds, int kg, int walk) try {
+  if (!(n == 32 || n == 64 || n == 128 || n == 256 || n == 512 || n == 1024) || rows_lds < 1 || kg < 1 || walk < 1 || walk > 2) return HH_ERR_ARG;
+  if (walk == 2 && !twist_walk_built(n)) return 0;
+  return (int64_t)fused_lds(n, rows_lds, kg, walk == 2);
+} HH_CATCH_CTX(nullptr, "hh_fused_lds_bytes")
+int hh_fused_walk_choice(int64_t runs, int run_len, int n_kb, int slots_rises, int slots_twists, int mode, int64_t out[15]) try {
+  if (runs < 1 || run_len < 1 || n_kb < 1 || slots_rises < 1 || slots_twists < 0 || mode < 0 || mode > 2 || !out) return HH_ERR_ARG;
+  const WalkChoice w = choose_walk(runs, run_len, n_kb, slots_rises, slots_twists, mode);
+  const FusedSchedule* const fs[2] = {&w.rises, &w.twists};
+  out[0] = w.walk == WALK_TWISTS ? 2 : 1;
+  for (int k = 0; k < 2; ++k) {
+    const int32_t v[6] = {fs[k]->runs_a, fs[k]->groups_a, fs[k]->cpw_a, fs[k]->groups_b, fs[k]->cpw_b, fs[k]->layers};
+    out[1 + 7 * k] = (int64_t)fs[k]->cost;
+    for (int j = 0; j < 6; ++j) out[2 + 7 * k + j] = v[j];
+  }
+  return HH_OK;
+} HH_CATCH_CTX(nullptr, "hh_fused_walk_choice")
+int hh_fused_walk_footprint(hh_ctx* c, double rise_min, int64_t out[8]) try {
+  if (!c || !out || !(rise_min > 0.0) || c->general) return HH_ERR_ARG;
+  if (int rc = check_ready(c, true)) return rc;
+  HH_HIP(c, hipSetDevice(c->device));
+  for (int k = 0; k < 6; ++k) out[k] = 0;
+  out[6] = c->n_cu;
+  out[7] = c->n_kb;
+  const int ext = (int)table_extent(c->n, (double)c->geom.apix, c->geom.rpx, (double)c->geom.slack, c->geom.height, rise_min);
+  int kg = 0, rows_f = 0;
+  if (!fused_shape(c, rise_min, (2 * ext + 1) * c->geom.n_units, &kg, &rows_f)) return HH_OK;
+  FusedArgs shape{};
+  shape.rows_lds = rows_f;
+  shape.kg = kg;
+  int slots_r = 0, slots_t = 0;
+  if (int rc = fused_slots(c, shape, &slots_r)) return rc;
+  if (int rc = fused_slots(c, shape, &slots_t, true)) return rc;
+  out[0] = rows_f;
+  out[1] = kg;
+  out[2] = (int64_t)fused_lds(c->n, rows_f, kg, false);
+  out[3] = twist_walk_built(c->n) ? (int64_t)fused_lds(c->n, rows_f, kg, true) : 0;
+  out[4] = slots_r / std::max(1, c->n_cu);
+  out[5] = slots_t / std::max(1, c->n_cu);
+  return HH_OK;
+} HH_CATCH_CTX(c, "hh_fused_walk_footprint")
 int hh_last_row_kernel(const hh_ctx* c, int32_t out[3]) try {
   if (!c || !out) return HH_ERR_ARG;
   for (int k = 0; k < 3; ++k) out[k] = c->gen ? c->gen->last_row_kernel[k] : 0;

@@ -388,6 +388,36 @@ class SweepEngine:
         sweep ran another pipeline."""
         return int(self._L.hh_last_factor_sets(self._ctx))
 
+    def set_fused_walk(self, mode="auto"):
+        """How the fused pipeline walks a list with one set of column factors per rise (``hh_set_fused_walk``): "rises" — a
+        workgroup keeps a run's table slice and fetches a factor set per candidate; "twists" — it keeps a rise's factor
+        set and its wavefronts fetch their own table rows per candidate; "auto" (default) — twists where they can run and
+        are not estimated slower.  A forced "twists" that cannot run falls back to "rises".  Scores are the same bits."""
+        mode = {"auto": 0, "rises": 1, "twists": 2}.get(mode, mode)
+        with self._lock:
+            self._check(self._L.hh_set_fused_walk(self._ctx, int(mode)))
+
+    def set_fused_piece(self, runs_per_workgroup=0):
+        """Test and tuning hook (``hh_set_fused_piece``): runs per workgroup of the twist walk; 0 = the schedule's own cut."""
+        with self._lock:
+            self._check(self._L.hh_set_fused_piece(self._ctx, int(runs_per_workgroup)))
+
+    @property
+    def last_fused_walk(self) -> str:
+        """Candidate loop of the last sweep's fused launches (``hh_last_fused_walk``): "twists" when all of them walked
+        twists, "rises" when one of them walked rises, "none" when the sweep ran another pipeline."""
+        return {1: "rises", 2: "twists"}.get(self._L.hh_last_fused_walk(self._ctx), "none")
+
+    def fused_walk_footprint(self, rise_min: float) -> dict:
+        """The fused pass's shape for a sweep whose smallest rise is ``rise_min`` (``hh_fused_walk_footprint``): table rows
+        staged per ky, rows per group of four columns, LDS bytes and resident workgroups per compute unit of both walks
+        (zero when the fused pass does not fit), the device's compute units and the ky blocks the mask touches."""
+        out = (C.c_int64 * 8)()
+        with self._lock:
+            self._check(self._L.hh_fused_walk_footprint(self._ctx, float(rise_min), out))
+        keys = ("rows", "kg", "lds_rises", "lds_twists", "per_cu_rises", "per_cu_twists", "compute_units", "ky_blocks")
+        return dict(zip(keys, (int(v) for v in out)))
+
     @property
     def last_row_kernel(self) -> tuple[int, int, int]:
         """Row kernel of the last sweep on a general image size (``hh_last_row_kernel``): ``(R1, R2, LDS bytes)`` for the

@@ -240,6 +240,38 @@ int hh_last_first_pass(const hh_ctx* ctx);
  * every run shares one rise column (hh_rise_columns_shared) and a launch holds whole runs, the number of candidates
  * swept by the fused pipeline otherwise, 0 when the sweep ran another pipeline. */
 int64_t hh_last_factor_sets(const hh_ctx* ctx);
+/* How the fused pipeline walks a list that has one set of column factors per rise.  1 = rises: a
+ * workgroup owns (run, ky block), keeps the run's table slice and fetches a factor set per candidate.  2 = twists: a
+ * workgroup owns (rise, ky block), keeps the rise's factor set, and each wavefront fetches its own ky row of the next
+ * run's table per candidate (no workgroup barrier in the candidate loop; sizes up to 512).  0 = auto (default): twists
+ * where a launch holds whole runs, the compute unit holds as many twist-walking workgroups as rise-walking ones (the
+ * table rows are double-buffered: 16 bytes per table row and ky instead of 8) and the schedule's estimate is not above
+ * the rise walk's; rises otherwise, and always with several segments (their q stores were measured slower on the twist
+ * walk).  A forced 2 that cannot run (per-candidate factors, N = 1024, the footprint) falls
+ * back to 1.  Scores do not depend on the walk, bit for bit.
+ * hh_last_fused_walk: 2 when every fused launch of the last sweep walked twists, 1 when one of them walked rises, 0 when
+ * the sweep ran another pipeline. */
+int hh_set_fused_walk(hh_ctx* ctx, int mode);
+int hh_last_fused_walk(const hh_ctx* ctx);
+/* Test and tuning hook: the twist walk cuts every rise's runs into workgroups of runs_per_workgroup runs (the last one
+ * takes what is left) instead of the cut of hh_fused_walk_choice; 0 (default) = the schedule's own cut.  The choice of
+ * the walk is not affected. */
+int hh_set_fused_piece(hh_ctx* ctx, int runs_per_workgroup);
+/* Dynamic LDS bytes of one workgroup of the fused pass: walk 1 = panel + one table slice (8 ky x rows_lds x 8 B) + two
+ * factor sets (kg x n x 4 B + (n / 4 + 4) x 4 B each), walk 2 = panel + two slices + one set; 0 for walk 2 where the
+ * size has no twist walk (n = 1024).  Pure host arithmetic. */
+int64_t hh_fused_lds_bytes(int n, int rows_lds, int kg, int walk);
+/* The walk a launch of `runs` whole runs of `run_len` candidates takes under `mode` (hh_set_fused_walk) when the device
+ * holds slots_rises rise-walking and slots_twists twist-walking workgroups at a time (0: the twist walk cannot run), and
+ * both schedules: out = {walk (1 or 2), then for the rise walk and for the twist walk: the model's launch length in
+ * candidates and hh_fused_schedule's six numbers — for the twist walk with the roles swapped (runs_a counts rises, cpw
+ * counts runs)}.  Pure host arithmetic. */
+int hh_fused_walk_choice(int64_t runs, int run_len, int n_kb, int slots_rises, int slots_twists, int mode, int64_t out[15]);
+/* The fused pass's shape for a sweep of this context (geometry and reference set) whose smallest rise is rise_min:
+ * out = {table rows staged per ky, table rows per group of four columns, LDS bytes of the rise walk, of the twist walk,
+ * workgroups a compute unit holds of the rise walk, of the twist walk (the first six are zero when the fused pass does
+ * not fit), compute units of the device, ky blocks the reference's mask touches}. */
+int hh_fused_walk_footprint(hh_ctx* ctx, double rise_min, int64_t out[8]);
 /* Which row kernel the last sweep of a general-size context (hh_create2, not a power-of-two square) ran, read-only:
  * out = {R1, R2, dynamic LDS bytes} for the two-step kernel of the pair nx = R1 R2, {0, 0, LDS bytes} for the Stockham
  * kernel, {0, 0, 0} for the float64 direct path (a row length with a prime factor above 31, tilt / psi, a launch that

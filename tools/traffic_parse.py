@@ -51,7 +51,7 @@ def main(fetch_dir, write_dir, source=None, n=512, batch=256, out=None):
                            "calib_write_FETCH_SIZE": pick(fetch, "k_calib_write")[0]}}
     kernels = {}
     for name, frag in (("first_pass", f"k_first_pass<{n}, 0>"), ("second_pass", f"k_second_pass<{n}, 0, 1>"),
-                       ("first_pass_table", f"k_first_pass_table<{n}>"), ("fused_pass", f"k_fused_pass<{n}, 0, 1>"),
+                       ("first_pass_table", f"k_first_pass_table<{n}>"), ("fused_pass", f"k_fused_pass<{n}, 0, 1"),
                        ("column_factors", f"k_column_factors<{n}>"), ("run_table", f"k_run_table<{n}>")):
         try:
             fv, fl = pick(fetch, frag)
