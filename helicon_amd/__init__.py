@@ -16,6 +16,6 @@ from .symmetry_search import SymmetrySearch, helical_symmetry_search
 from .fsc import (calc_frc_2d, calc_fsc, calc_fsc_batch, calc_fsc_per_shell, frc_score, fsc_resolution, half_map_fsc,
                   half_map_fsc_batch)
 # the function true_fsc.true_fsc is not re-exported under its own name: that would hide the module helicon_amd.true_fsc
-from .true_fsc import TrueFSC, randomize_phases_lowpass
+from .true_fsc import TrueFSC, distance_transform_edt_sq, randomize_phases_lowpass, soft_mask_device
 
 __version__ = "0.1.0"

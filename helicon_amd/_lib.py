@@ -184,6 +184,13 @@ EXPORTS = {
     "hh_tfsc_download": (C.c_int, [C.c_void_p, C.c_int, _f32p, _f32p]),
     "hh_tfsc_masked": (C.c_int, [C.c_void_p, _f32p, _f32p, C.c_int32, C.c_int, _f64p, _f64p]),
     "hh_tfsc_destroy": (C.c_int, [C.c_void_p]),
+    # soft masks built on the device from a resident support (helicon_amd/true_fsc.py, csrc/soft_mask.inc)
+    "hh_edt_3d": (C.c_int, [C.c_int, C.POINTER(C.c_uint8), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), _f64p]),
+    "hh_soft_mask_3d": (C.c_int, [C.c_int, C.POINTER(C.c_uint8), C.c_int32, C.c_int32, C.c_int32, C.c_double, _f32p, _f64p]),
+    "hh_soft_mask_taps": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _f64p, _f64p, C.POINTER(C.c_int32)]),
+    "hh_tfsm_set_support": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8)]),
+    "hh_tfsm_soft_mask": (C.c_int, [C.c_void_p, C.c_int, C.c_double, _f32p]),
+    "hh_tfsm_soft_masked": (C.c_int, [C.c_void_p, _f64p, C.c_int32, C.c_int, _f64p, _f64p]),
 }
 
 _lib = None

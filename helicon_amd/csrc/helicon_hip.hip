@@ -4891,3 +4891,4 @@ int hh_profile_get(hh_ctx* c, hh_profile* out) try {
 #include "symmetry_search.inc"  // helical symmetry search of a 3-D map: batched (twist, rise, Csym) scores of a device-resident map (hh_hs_*)
 #include "fourier_correlation.inc"  // Fourier shell / ring correlation of batches of map or image pairs: DFT passes on the f32 MFMA, fused last pass (hh_fsc_3d, hh_frc_2d)
 #include "true_fsc.inc"  // phase-randomised (noise-substituted) true FSC of two half maps on a resident context: stored spectrum, inverse passes, masked curves (hh_tfsc_*)
+#include "soft_mask.inc"  // the true FSC's soft masks built on the device from a resident support: exact distance transform, zoom(order=1) taps, cosine edge (hh_edt_3d, hh_soft_mask_3d, hh_tfsm_set_support / _soft_mask / _soft_masked)

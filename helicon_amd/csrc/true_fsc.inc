@@ -15,6 +15,9 @@
 //          the pairs (map1 m1, map2 m2) and (map1r m1, map2r m2) then come from fc_device unchanged: bit-identical from run to
 //          run, independent of the batch and of a mask's place in it.  Only the masks cross the bus.
 
+struct SmState;               // soft_mask.inc: the supports of hh_tfsm_set_support and the distance transform's scratch
+void sm_release(SmState* s);
+
 struct hh_tfsc {
   int device = 0, n = 0, ncol = 0, nshell = 0;
   int64_t per_map = 0, per_spec = 0;    // n^3 and n n (n / 2 + 1)
@@ -31,6 +34,7 @@ struct hh_tfsc {
   double *scale = nullptr, *sums = nullptr;
   long long* acc = nullptr;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  SmState* soft = nullptr;
   void free_scratch() {
     (void)hipFree(in); (void)hipFree(p1); (void)hipFree(p2); (void)hipFree(amax); (void)hipFree(scale); (void)hipFree(sums); (void)hipFree(acc);
     in = p1 = p2 = nullptr; amax = nullptr; scale = sums = nullptr; acc = nullptr; cap = 0;
@@ -38,6 +42,7 @@ struct hh_tfsc {
   ~hh_tfsc() {
     (void)hipSetDevice(device);
     free_scratch();
+    sm_release(soft);
     (void)hipFree(mats); (void)hipFree(maps); (void)hipFree(spec); (void)hipFree(curves); (void)hipFree(masks);
     if (ev0) (void)hipEventDestroy(ev0);
     if (ev1) (void)hipEventDestroy(ev1);

@@ -31,9 +31,21 @@ Two deliberate deviations from the reference, both at inputs it handles by accid
 Precision: float32 transforms, float64 shell sums, like ``helicon_amd.fsc``.  The mask helpers (``soft_mask``,
 ``adaptive_mask``, ``otsu_threshold_eman``, ``fit_fsc_curve``) run on the host and call SciPy where the reference does.
 
+Soft masks on the device (csrc/soft_mask.inc): ``soft_mask``'s definition with its quirks (the 1 -> 0.5 -> 0 edge, the planes
+``zoom`` leaves at 0 distance) from a binary support that is uploaded once.
+
+``distance_transform_edt_sq(support, stride=1)``
+    the exact squared Euclidean distance transform (int32) of ``~support[::stride, ::stride, ::stride]``.
+``soft_mask_device(mask, soft_width)``
+    ``soft_mask`` of any 3-D box on the device, float32.
+``TrueFSC.set_support`` / ``.soft_mask`` / ``.soft_masked`` / ``.soft_masked_batch``
+    the supports stay on the context; every width becomes a mask in device memory that feeds the masked curves directly.
+``true_fsc(..., device_masks=True)``
+    the soft edge and every trial of ``refine_mask`` on the device; ``adaptive_mask`` stays on the host.
+
     python -m helicon_amd.true_fsc half1.mrc half2.mrc [--apix A] [--mask M [M2]] [--one-mask] [--cutoff-res R]
         [--mask-soft W] [--refine-mask] [--mask-fraction-thresh F | --mask-thresh T | --mask-mass KDA] [--seed S]
-        [--out-prefix P] [--device 0]
+        [--out-prefix P] [--device 0] [--device-masks]
 
 prints a JSON report and, with ``--out-prefix``, writes ``P.unmasked.txt``, ``P.randomized-unmasked.txt``, ``P.masked.txt``,
 ``P.randomized-masked.txt``, ``P.true.txt``, ``P.true.fit.txt`` (the reference's six text files) and the mask(s).
@@ -52,10 +64,12 @@ from . import _lib
 from .fsc import _f32, _fsc_rows, _ratio, _read_map, calc_fsc, fsc_resolution
 
 __all__ = ["randomize_phases_lowpass", "TrueFSC", "true_fsc", "cutoff_m", "choose_cutoff", "soft_mask", "adaptive_mask",
-           "otsu_threshold_eman", "fit_fsc_curve", "main"]
+           "otsu_threshold_eman", "fit_fsc_curve", "distance_transform_edt_sq", "soft_mask_device", "soft_step", "zoom_taps", "main"]
 
 _MIN_SIDE, _MAX_SIDE = 8, 512
 _f32p, _f64p = C.POINTER(C.c_float), C.POINTER(C.c_double)
+_u8p, _i32p = C.POINTER(C.c_uint8), C.POINTER(C.c_int32)
+_MAX_BOX = 1024
 
 
 # ------------------------------------------------------------------------------------------
@@ -232,6 +246,87 @@ def soft_mask(mask, soft_width):
 
 
 # ------------------------------------------------------------------------------------------
+# masks (device)
+# ------------------------------------------------------------------------------------------
+def soft_step(soft_width):
+    """``soft_mask``'s decimation step ``max(1, int(soft_width / 4))``."""
+    return max(1, int(soft_width / 4))
+
+
+def zoom_taps(n, m):
+    """The per-axis tables of ``scipy.ndimage.zoom(order=1)`` (``mode="constant"``) from ``m`` samples to ``n``:
+    ``(i0, i1, w0, w1, outside)``, ``[n]`` each.  Coordinate ``c = i (m - 1) / (n - 1)`` in float64, taps ``floor(c)`` and
+    ``floor(c) + 1`` clamped to the line with weights ``1 - f`` and ``f``; ``outside`` marks ``c > m - 1``, where ``zoom``
+    returns 0 (for some ``(n, m)`` the last index lands one ulp beyond the last sample).  The library's host function
+    (``hh_soft_mask_taps``): the tables the device kernel reads; no device is needed."""
+    n, m = int(n), int(m)
+    if not 1 <= m <= n <= _MAX_BOX:
+        raise ValueError(f"zoom_taps: 1 <= m <= n <= {_MAX_BOX} is needed; got n = {n}, m = {m}")
+    i0, i1, out = np.empty(n, np.int32), np.empty(n, np.int32), np.empty(n, np.int32)
+    w0, w1 = np.empty(n, np.float64), np.empty(n, np.float64)
+    _lib.check(_lib.lib().hh_soft_mask_taps(n, m, i0.ctypes.data_as(_i32p), i1.ctypes.data_as(_i32p), w0.ctypes.data_as(_f64p),
+                                            w1.ctypes.data_as(_f64p), out.ctypes.data_as(_i32p)), None)
+    return i0, i1, w0, w1, out.astype(bool)
+
+
+def _width(w, name):
+    w = float(w)
+    if not math.isfinite(w):
+        raise ValueError(f"{name}: the width of the soft edge is NaN or infinite")
+    return w
+
+
+def _support(mask, name, shape=None):
+    """uint8 0 / 1 of a 3-D mask (nonzero = inside)."""
+    m = np.asarray(mask)
+    if m.ndim != 3 or min(m.shape, default=0) < 1 or max(m.shape) > _MAX_BOX:
+        raise ValueError(f"{name}: a 3-D support with sides in [1, {_MAX_BOX}] is needed; got {m.shape}")
+    if shape is not None and m.shape != shape:
+        raise ValueError(f"{name}: a support must have the maps' shape {shape}; got {m.shape}")
+    if m.dtype.kind == "f" and not np.isfinite(m).all():
+        raise ValueError(f"{name}: the support holds NaN or infinite values")
+    return np.ascontiguousarray(m != 0, dtype=np.uint8)
+
+
+def _not_empty(sup, step, name):
+    if not sup[::step, ::step, ::step].any():
+        raise ValueError(f"{name}: the support has no inside voxel left at every {step}-th voxel (step {step}): there is no distance to take")
+
+
+def distance_transform_edt_sq(support, stride=1, *, device=0):
+    """``np.rint(scipy.ndimage.distance_transform_edt(~S[::stride, ::stride, ::stride]) ** 2)`` exactly, as int32, on the
+    device: the squared Euclidean distance of every (decimated) voxel to the nearest inside one.  Sides 1 ... 1024."""
+    sup = _support(support, "distance_transform_edt_sq")
+    stride = int(stride)
+    if stride < 1:
+        raise ValueError(f"distance_transform_edt_sq: stride must be >= 1; got {stride}")
+    _not_empty(sup, stride, "distance_transform_edt_sq")
+    out = np.empty(tuple(-(-v // stride) for v in sup.shape), dtype=np.int32)
+    nz, ny, nx = sup.shape
+    ms = C.c_double(0.0)
+    _lib.check(_lib.lib().hh_edt_3d(int(device), sup.ctypes.data_as(_u8p), nz, ny, nx, stride, out.ctypes.data_as(_i32p), C.byref(ms)), None)
+    distance_transform_edt_sq.kernel_ms = ms.value
+    return out
+
+
+def soft_mask_device(mask, soft_width, *, device=0):
+    """``soft_mask(mask, soft_width)`` on the device, float32: the same step, exact distances, ``zoom``'s taps and edge rule,
+    evaluated in float64 and rounded once.  ``soft_width <= 0``: the support as 0 / 1, no device call.  A support with no
+    inside voxel at the step, a NaN or an infinite width raise ``ValueError``."""
+    sup = _support(mask, "soft_mask_device")
+    w = _width(soft_width, "soft_mask_device")
+    if w <= 0:
+        return sup.astype(np.float32)
+    _not_empty(sup, soft_step(w), "soft_mask_device")
+    out = np.empty(sup.shape, dtype=np.float32)
+    nz, ny, nx = sup.shape
+    ms = C.c_double(0.0)
+    _lib.check(_lib.lib().hh_soft_mask_3d(int(device), sup.ctypes.data_as(_u8p), nz, ny, nx, w, out.ctypes.data_as(_f32p), C.byref(ms)), None)
+    soft_mask_device.kernel_ms = ms.value
+    return out
+
+
+# ------------------------------------------------------------------------------------------
 # the resident context
 # ------------------------------------------------------------------------------------------
 def _cube(a, name):
@@ -285,6 +380,21 @@ class _Context:
         ms = C.c_double(0.0)
         _lib.check(_lib.lib().hh_tfsc_masked(self._h, masks1.ctypes.data_as(_f32p), masks2.ctypes.data_as(_f32p) if masks2 is not None else None,
                                              batch, 1 if full_spectrum else 0, sums.ctypes.data_as(_f64p), C.byref(ms)), None)
+        return sums, ms.value
+
+    def set_support(self, sup1, sup2):
+        _lib.check(_lib.lib().hh_tfsm_set_support(self._h, sup1.ctypes.data_as(_u8p), sup2.ctypes.data_as(_u8p) if sup2 is not None else None), None)
+
+    def soft_mask(self, which, width):
+        out = np.empty((self.n,) * 3, dtype=np.float32)
+        _lib.check(_lib.lib().hh_tfsm_soft_mask(self._h, int(which), float(width), out.ctypes.data_as(_f32p)), None)
+        return out
+
+    def soft_masked(self, widths, full_spectrum):
+        sums = np.empty((len(widths), 2, self.n // 2 + 1, 3), dtype=np.float64)
+        ms = C.c_double(0.0)
+        _lib.check(_lib.lib().hh_tfsm_soft_masked(self._h, widths.ctypes.data_as(_f64p), len(widths), 1 if full_spectrum else 0,
+                                                  sums.ctypes.data_as(_f64p), C.byref(ms)), None)
         return sums, ms.value
 
     def close(self):
@@ -417,6 +527,52 @@ class TrueFSC:
         sums = self.masked_sums(np.asarray(mask1)[None], None if mask2 is None else np.asarray(mask2)[None], per_shell)
         return self._curves(sums[:, 0], per_shell)[0], self._curves(sums[:, 1], per_shell)[0]
 
+    # ---- soft masks built on the device from a resident support (csrc/soft_mask.inc)
+    def set_support(self, support1, support2=None):
+        """Upload the binary support(s) (nonzero = inside) the soft masks are built from: one for both members, or one each."""
+        want = (self.n,) * 3
+        s1 = _support(support1, "TrueFSC.set_support", want)
+        s2 = None if support2 is None else _support(support2, "TrueFSC.set_support", want)
+        self._supports = [s1] if s2 is None else [s1, s2]
+        self._ctx.set_support(s1, s2)
+
+    def _widths(self, widths, name):
+        if not getattr(self, "_supports", None):
+            raise ValueError(f"{name}: no support is set (TrueFSC.set_support)")
+        w = np.ascontiguousarray(widths, dtype=np.float64)
+        if w.ndim != 1 or len(w) < 1:
+            raise ValueError(f"{name}: a list of widths is needed; got an array of shape {w.shape}")
+        if not np.isfinite(w).all():
+            raise ValueError(f"{name}: the width of the soft edge is NaN or infinite")
+        for step in sorted({soft_step(v) for v in w if v > 0}):
+            for sup in self._supports:
+                _not_empty(sup, step, name)
+        return w
+
+    def soft_mask(self, width, which=0):
+        """The mask ``soft_masked(width)`` applies to member ``which`` (0 / 1), downloaded: float32 ``[n, n, n]``."""
+        if which not in (0, 1):
+            raise ValueError(f"TrueFSC.soft_mask: which must be 0 or 1; got {which}")
+        w = self._widths([width], "TrueFSC.soft_mask")
+        return self._ctx.soft_mask(which, w[0])
+
+    def soft_masked_sums(self, widths, per_shell=False):
+        """``masked_sums`` of the soft masks of these widths, built on the device: ``[B, 2, n // 2 + 1, 3]``."""
+        w = self._widths(widths, "TrueFSC.soft_masked")
+        sums, self.kernel_ms = self._ctx.soft_masked(w, bool(per_shell))
+        return sums
+
+    def soft_masked_batch(self, widths, per_shell=False):
+        """``masked_batch`` of the supports' soft masks, one per width, none of them uploaded.  Every curve is bit for bit the
+        one ``masked(soft_mask(width, 0), soft_mask(width, 1))`` gives, whatever the list and the width's place in it."""
+        sums = self.soft_masked_sums(widths, per_shell)
+        return self._curves(sums[:, 0], per_shell), self._curves(sums[:, 1], per_shell)
+
+    def soft_masked(self, width, per_shell=False):
+        """``(fsc_t, fsc_n)`` under the supports' soft masks of this width, as ``masked`` returns them."""
+        sums = self.soft_masked_sums([width], per_shell)
+        return self._curves(sums[:, 0], per_shell)[0], self._curves(sums[:, 1], per_shell)[0]
+
     def true_fsc(self, mask1, mask2=None):
         """trueFSC.py:342-348: ``[saxis, fsc_true]`` rows; ``fsc_t`` up to ``cutoff_index``, ``(fsc_t - fsc_n) / (1 - fsc_n)``
         beyond it, NaN -> 1.0."""
@@ -446,12 +602,17 @@ def refine_score(fsc_t, fsc_n, cutoff_i):
 # the composition of trueFSC.py:main
 # ------------------------------------------------------------------------------------------
 def true_fsc(map1, map2, apix, *, mask=None, one_mask=False, cutoff_res=0, mask_soft=0, refine_mask=False, mask_fraction_thresh=0,
-             mask_thresh=0, mask_mass=0, seed=None, phases=None, device=0, context=None):
+             mask_thresh=0, mask_mass=0, seed=None, phases=None, device=0, context=None, device_masks=False):
     """trueFSC.py:102-366.  ``mask``: one mask or a pair, used as given (a pair is averaged with ``one_mask``); without one, the
     adaptive mask of each map (of the maps' average with ``one_mask``) with a soft edge of ``mask_soft`` Angstrom, or of the
     width ``refine_mask`` finds (``minimize_scalar``, bounded to ``(0, n / 3)`` pixels, ``xatol=2``, every evaluation one
     ``.masked(..., per_shell=True)`` call on the resident context), or of ``3 res_unmasked / apix`` pixels.  ``context``
     stands in for ``TrueFSC`` (tests).
+
+    ``device_masks``: the adaptive supports go up once (``set_support``), every trial of ``refine_mask`` is one
+    ``.soft_masked(x, per_shell=True)``, the final curves come from ``.soft_masked(soft_px)`` and ``mask1`` / ``mask2`` are
+    the device's masks, downloaded (float32); ``host_mask_s`` then counts ``adaptive_mask`` alone.  Refused with ``mask=``:
+    a given mask is used as it is, there is no support to soften.
 
     Returns a dict: ``unmasked``, ``randomized_unmasked``, ``masked``, ``randomized_masked``, ``true`` (``[saxis, fsc]``
     rows), ``true_fit`` (500 rows), ``resolution`` (``unmasked``, ``masked``, ``true``, ``true_fit`` at 0.143),
@@ -459,6 +620,8 @@ def true_fsc(map1, map2, apix, *, mask=None, one_mask=False, cutoff_res=0, mask_
     spent in the host's mask helpers)."""
     import time
 
+    if device_masks and mask is not None:
+        raise ValueError("true_fsc: device_masks builds the soft edge of the adaptive support; a given mask is used as it is")
     a64, b64 = np.asarray(map1, dtype=np.float64), np.asarray(map2, dtype=np.float64)
     ctx = (context or TrueFSC)(map1, map2, apix, cutoff_res, phases=phases, seed=seed, device=device)
     host_s = 0.0
@@ -483,6 +646,9 @@ def true_fsc(map1, map2, apix, *, mask=None, one_mask=False, cutoff_res=0, mask_
             else:
                 mask1, mask2 = adaptive_mask(a64, apix, cutoff, **kw), adaptive_mask(b64, apix, cutoff, **kw)
             host_s += time.perf_counter() - t0
+            same = mask2 is mask1
+            if device_masks:
+                ctx.set_support(mask1, None if same else mask2)
             if mask_soft > 0:
                 soft_px = mask_soft / apix
             elif refine_mask:
@@ -490,6 +656,9 @@ def true_fsc(map1, map2, apix, *, mask=None, one_mask=False, cutoff_res=0, mask_
 
                 def score(x):
                     nonlocal host_s
+                    if device_masks:
+                        fsc_t, fsc_n = ctx.soft_masked(x, per_shell=True)
+                        return refine_score(fsc_t, fsc_n, ctx.cutoff_index + 2)
                     t0 = time.perf_counter()
                     trial = soft_mask(mask1, x)
                     host_s += time.perf_counter() - t0
@@ -499,12 +668,17 @@ def true_fsc(map1, map2, apix, *, mask=None, one_mask=False, cutoff_res=0, mask_
                 soft_px = float(minimize_scalar(score, bounds=(0, n / 3), method="bounded", options={"xatol": 2}).x)
             else:
                 soft_px = 3 * res_unmasked / apix
-            t0 = time.perf_counter()
-            same = mask2 is mask1
-            mask1 = soft_mask(mask1, soft_px)
-            mask2 = mask1 if same else soft_mask(mask2, soft_px)
-            host_s += time.perf_counter() - t0
-        fsc_t, fsc_n = ctx.masked(mask1, None if mask2 is mask1 else mask2)
+            if not device_masks:
+                t0 = time.perf_counter()
+                mask1 = soft_mask(mask1, soft_px)
+                mask2 = mask1 if same else soft_mask(mask2, soft_px)
+                host_s += time.perf_counter() - t0
+        if device_masks:
+            fsc_t, fsc_n = ctx.soft_masked(soft_px)
+            mask1 = ctx.soft_mask(soft_px, 0)
+            mask2 = mask1 if same else ctx.soft_mask(soft_px, 1)
+        else:
+            fsc_t, fsc_n = ctx.masked(mask1, None if mask2 is mask1 else mask2)
         true = np.column_stack((fsc_t[:, 0], corrected(fsc_t[:, 1], fsc_n[:, 1], ctx.cutoff_index)))
         s_fit, f_fit, _ = fit_fsc_curve(true[:, 0], true[:, 1])
         return {
@@ -538,6 +712,7 @@ def add_args(parser: argparse.ArgumentParser) -> argparse.ArgumentParser:
     parser.add_argument("--seed", type=int, default=None, help="seed of the device's phase generator (default: NumPy's global stream, as the reference)")
     parser.add_argument("--out-prefix", default=None, help="write P.unmasked.txt ... P.true.fit.txt and the mask(s)")
     parser.add_argument("--device", type=int, default=0)
+    parser.add_argument("--device-masks", action="store_true", help="build the soft edge of the adaptive mask, and every trial of --refine-mask, on the device (not with --mask)")
     return parser
 
 
@@ -562,7 +737,8 @@ def run(args, context=None) -> dict:
     try:
         out = true_fsc(m1, m2, float(apix), mask=mask, one_mask=args.one_mask, cutoff_res=args.cutoff_res, mask_soft=args.mask_soft,
                        refine_mask=args.refine_mask and not args.mask_soft > 0, mask_fraction_thresh=args.mask_fraction_thresh,
-                       mask_thresh=args.mask_thresh, mask_mass=args.mask_mass, seed=args.seed, device=args.device, context=context)
+                       mask_thresh=args.mask_thresh, mask_mass=args.mask_mass, seed=args.seed, device=args.device, context=context,
+                       device_masks=getattr(args, "device_masks", False))
     except ValueError as e:
         raise SystemExit(str(e))
     curves = ("unmasked", "randomized_unmasked", "masked", "randomized_masked", "true")

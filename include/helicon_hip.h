@@ -627,6 +627,34 @@ int hh_tfsc_masked(hh_tfsc* ctx, const float* masks1, const float* masks2, int32
                    double* kernel_ms);
 int hh_tfsc_destroy(hh_tfsc* ctx);
 
+/*
+ * Soft masks of the true FSC built on the device (csrc/soft_mask.inc; commands/trueFSC.py:738-781 _soft_mask as
+ * helicon_amd.true_fsc.soft_mask restates it).  support: uint8, nonzero = inside.  step = max(1, int(w / 4)); the support is
+ * taken at every step-th voxel (m_a = ceil(n_a / step) samples per axis); D2 is the exact squared Euclidean distance, in
+ * decimated voxels, to the nearest decimated inside voxel; step sqrt(D2) is interpolated back as scipy.ndimage.zoom(order=1,
+ * mode="constant") does it (a coordinate beyond the last sample reads 0); on outside voxels the mask is
+ * (cos(dist / w pi / 2) + 1) / 2 for 0 < dist <= w and 0 for dist > w, everywhere else 1.  A support without an inside voxel
+ * at that step is an argument error; w <= 0 returns the support as 0 / 1; a NaN or infinite w is an argument error.
+ * Results are bit-identical from run to run.  Errors: hh_last_error(NULL).
+ */
+/* sqdist_out: int32 [ceil(nz / stride)][ceil(ny / stride)][ceil(nx / stride)]; sides in [1, 1024] */
+int hh_edt_3d(int device, const uint8_t* support, int32_t nz, int32_t ny, int32_t nx, int32_t stride, int32_t* sqdist_out,
+              double* kernel_ms);
+/* mask_out: float32 [nz][ny][nx] */
+int hh_soft_mask_3d(int device, const uint8_t* support, int32_t nz, int32_t ny, int32_t nx, double soft_width, float* mask_out,
+                    double* kernel_ms);
+/* host only: the per-axis tables of zoom(order=1) the mask kernel reads, n outputs over m <= n samples; [n] each */
+int hh_soft_mask_taps(int32_t n, int32_t m, int32_t* i0, int32_t* i1, double* w0, double* w1, int32_t* outside);
+/* the supports [n][n][n] of a true-FSC context, uploaded once (support2 NULL: one support for both members) */
+int hh_tfsm_set_support(hh_tfsc* ctx, const uint8_t* support1, const uint8_t* support2);
+/* the mask hh_tfsm_soft_masked would use for member `which` (0 / 1) at this width, float32 [n][n][n] */
+int hh_tfsm_soft_mask(hh_tfsc* ctx, int which, double soft_width, float* mask_out);
+/* hh_tfsc_masked with the masks built on the device from the supports, one per width: nothing but the widths' tap tables is
+ * uploaded.  sums: [batch][2][n / 2 + 1][3]; the same guarantees: bit-identical from run to run, independent of the batch and
+ * of a width's place in it, and equal to hh_tfsc_masked of hh_tfsm_soft_mask's masks bit for bit. */
+int hh_tfsm_soft_masked(hh_tfsc* ctx, const double* soft_widths, int32_t batch, int full_spectrum, double* sums,
+                        double* kernel_ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2,6 +2,7 @@
 """Times of the phase-randomised true FSC on the device (helicon_amd/true_fsc.py, csrc/true_fsc.inc).
 
     python tools/true_fsc_bench.py [--out profiles/true_fsc.json] [--sizes 64 128 256] [--repeats 5] [--accuracy LOG]
+                                   [--soft-out profiles/soft_mask.json] [--soft-only]
 
 Per size, one pair of n^3 maps (a blob plus noise, so that the adaptive mask has something to find), after a warm-up of every
 call that is timed; medians of REPEATS:
@@ -16,6 +17,18 @@ call that is timed; medians of REPEATS:
   mask on the host — wall;
 * ``refine``: a whole ``true_fsc(one_mask=True, refine_mask=True, seed=1)`` run — wall, the seconds of it spent in the host's
   mask helpers (``host_mask_s``), the number of ``.masked`` evaluations, one run.
+
+With ``--soft-out`` (``--soft-only``: nothing else) the soft masks built on the device (csrc/soft_mask.inc), per size:
+
+* ``refine``: a whole ``true_fsc(one_mask=True, refine_mask=True, seed=1)`` run with ``device_masks=True`` and without: wall,
+  ``host_mask_s``, the share of the wall that is not the host's mask helpers, the widths the refinement visited;
+* ``trials``: at every width the device run visited, alternating in one loop, ``soft_masked(w, per_shell=True)`` beside the
+  parent's trial, ``soft_mask(support, w)`` on the host + ``.masked(trial, per_shell=True)`` — wall, and the device's
+  ``kernel_ms``; every width is listed, none is folded into a median over widths;
+* ``kernels``: per visited step, device-event times of the three transform passes (``distance_transform_edt_sq``) and of
+  transform + mask kernel (``soft_mask_device``); their difference is the mask kernel.
+
+ITS GATE: at 128^3 and 256^3 the device trial's wall must not exceed the parent trial's at ANY visited width.
 
 THE GATE: at 128^3 and 256^3 ``masked.wall_ms`` must not exceed ``parent_one_mask.wall_ms`` of the same run (same kernels,
 one mask uploaded instead of four maps): both are printed, and the tool exits 1 if it is missed.  With ``--accuracy LOG`` the
@@ -79,6 +92,74 @@ def host_composition(a, b, mask, m_sel, shell_full, angles):
     return out
 
 
+def soft_mask_legs(n, a, b, apix, cutoff, repeats):
+    """The legs of the device soft masks for one size; (case, gate passed)."""
+    import helicon_amd as H
+
+    T = importlib.import_module("helicon_amd.true_fsc")
+    case = {"case": f"1 x {n}^3", "n": n}
+    visited = []
+
+    class Recording(H.TrueFSC):
+        def soft_masked(self, width, per_shell=False):
+            if per_shell:
+                visited.append(float(width))
+            return super().soft_masked(width, per_shell)
+
+    T.true_fsc(a, b, apix, cutoff_res=cutoff, one_mask=True, mask_soft=3 * apix, seed=1, device_masks=True)      # warm-up
+    runs = {}
+    for name, flag, ctx in (("device_masks", True, Recording), ("host_masks", False, H.TrueFSC)):
+        t0 = time.perf_counter()
+        out = T.true_fsc(a, b, apix, cutoff_res=cutoff, one_mask=True, refine_mask=True, seed=1, device_masks=flag, context=ctx)
+        wall = time.perf_counter() - t0
+        runs[name] = {"wall_s": wall, "host_mask_s": out["host_mask_s"], "rest_s": wall - out["host_mask_s"],
+                      "share_outside_host_masks": (wall - out["host_mask_s"]) / wall, "mask_soft_px": out["mask_soft_px"],
+                      "resolution_true": out["resolution"]["true"]}
+    runs["speedup"] = runs["host_masks"]["wall_s"] / runs["device_masks"]["wall_s"]
+    runs["widths_visited"] = list(visited)
+    case["refine"] = runs
+    support = T.adaptive_mask((a.astype(np.float64) + b) / 2, apix, cutoff)
+    trials, ok = [], True
+    with H.TrueFSC(a, b, apix, cutoff, seed=1) as ctx:
+        ctx.set_support(support)
+        for w in visited:
+            ctx.soft_masked(w, per_shell=True)
+            ctx.masked(T.soft_mask(support, w), per_shell=True)
+            w_dev, k_dev, w_par, w_host = [], [], [], []
+            for _ in range(repeats):
+                t0 = time.perf_counter()
+                ctx.soft_masked(w, per_shell=True)
+                w_dev.append((time.perf_counter() - t0) * 1e3)
+                k_dev.append(ctx.kernel_ms)
+                t0 = time.perf_counter()
+                trial = T.soft_mask(support, w)
+                t1 = time.perf_counter()
+                ctx.masked(trial, per_shell=True)
+                w_par.append((time.perf_counter() - t0) * 1e3)
+                w_host.append((t1 - t0) * 1e3)
+            row = {"width": w, "step": T.soft_step(w), "device_wall_ms": float(np.median(w_dev)), "device_kernel_ms": float(np.median(k_dev)),
+                   "parent_wall_ms": float(np.median(w_par)), "parent_host_soft_mask_ms": float(np.median(w_host))}
+            row["ratio"] = row["parent_wall_ms"] / row["device_wall_ms"]
+            ok = ok and row["device_wall_ms"] <= row["parent_wall_ms"]
+            trials.append(row)
+    case["trials"] = trials
+    kernels = []
+    for step in sorted({T.soft_step(w) for w in visited}):
+        w = max(v for v in visited if T.soft_step(v) == step)
+        T.distance_transform_edt_sq(support, step)
+        T.soft_mask_device(support, w)
+        edt, both = [], []
+        for _ in range(repeats):
+            T.distance_transform_edt_sq(support, step)
+            edt.append(T.distance_transform_edt_sq.kernel_ms)
+            T.soft_mask_device(support, w)
+            both.append(T.soft_mask_device.kernel_ms)
+        kernels.append({"step": step, "width": w, "decimated_side": -(-n // step), "transform_ms": float(np.median(edt)),
+                        "transform_and_mask_ms": float(np.median(both)), "mask_kernel_ms": float(np.median(both) - np.median(edt))})
+    case["kernels"] = kernels
+    return case, ok
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--out", default=None)
@@ -86,6 +167,8 @@ def main(argv=None):
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--accuracy", default=None, help="log of `pytest tests/test_gpu_true_fsc.py -s` to take the measured errors from")
     ap.add_argument("--no-refine", action="store_true", help="leave the whole-run timing out")
+    ap.add_argument("--soft-out", default=None, help="also time the soft masks built on the device and write this file")
+    ap.add_argument("--soft-only", action="store_true", help="only the soft-mask legs")
     args = ap.parse_args(argv)
 
     import fsc_oracle as O
@@ -95,6 +178,7 @@ def main(argv=None):
     T = importlib.import_module("helicon_amd.true_fsc")
     apix = 2.0
     result = {"repeats": args.repeats, "cases": [], "gate": {}}
+    soft = {"repeats": args.repeats, "cases": [], "gate": {}}
     missed = False
     for n in args.sizes:
         a, b = O.make_map_pair(n, 500 + n, dc="auto")
@@ -102,6 +186,18 @@ def main(argv=None):
         blob = 6.0 * np.exp(-(g[:, None, None] ** 2 + g[None, :, None] ** 2 + g[None, None, :] ** 2) / (2.0 * (n / 6.0) ** 2))
         a, b = (a + blob).astype(np.float32), (b + blob).astype(np.float32)
         cutoff = apix * n / (n / 4 + 0.5)
+        if args.soft_out or args.soft_only:
+            case, ok = soft_mask_legs(n, a, b, apix, cutoff, args.repeats)
+            soft["cases"].append(case)
+            print(json.dumps(case), flush=True)
+            if n >= 128:
+                worst = min(case["trials"], key=lambda r: r["ratio"])
+                soft["gate"][str(n)] = {"passed": bool(ok), "slowest_ratio": worst["ratio"], "at_width": worst["width"]}
+                print(f"SOFT GATE n={n}: device trial no slower than the parent's at every visited width: {'ok' if ok else 'MISSED'} "
+                      f"(smallest parent / device = {worst['ratio']:.2f} at w = {worst['width']:.2f})", flush=True)
+                missed = missed or not ok
+            if args.soft_only:
+                continue
         masks = np.stack([TO.sphere_mask(n, (0.2 + 0.02 * j) * n, 4.0) for j in range(8)]).astype(np.float32)
         mask = masks[5]
         case = {"case": f"1 x {n}^3", "n": n}
@@ -174,6 +270,9 @@ def main(argv=None):
         print(json.dumps(case), flush=True)
     if args.accuracy:
         result["accuracy"] = parse_figures(args.accuracy)
+    if args.soft_out:
+        Path(args.soft_out).parent.mkdir(parents=True, exist_ok=True)
+        Path(args.soft_out).write_text(json.dumps(soft, indent=1) + "\n")
     if args.out:
         Path(args.out).parent.mkdir(parents=True, exist_ok=True)
         Path(args.out).write_text(json.dumps(result, indent=1) + "\n")
