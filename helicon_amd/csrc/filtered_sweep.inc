@@ -44,9 +44,8 @@ __global__ __launch_bounds__(256) void k_filter_xpass(FiltArgs a) {
   __shared__ float as[FS_T][FS_K + 1];
   __shared__ float bs[FS_K][FS_T + 1];
   __shared__ double red[4][3];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int r = lane & 31, h = lane >> 5;
-  const int wm = (wave >> 1) * 32, wp = (wave & 1) * 32;
+  const Tile64 t = tile64();
+  const int tid = t.tid;
   const int b = blockIdx.y, batch = gridDim.y, n_tiles = gridDim.x;
   const int tile = a.tiles[blockIdx.x];
   const int u0 = (tile / a.tiles_v) * FS_T, v0 = (tile % a.tiles_v) * FS_T;
@@ -57,27 +56,25 @@ __global__ __launch_bounds__(256) void k_filter_xpass(FiltArgs a) {
     const float* const tj = a.t + ((size_t)j * batch + b) * plane;
     const float* const axj = a.ax + (size_t)j * onx * onx;
     for (int k0 = 0; k0 < onx; k0 += FS_K) {
-      for (int e = tid; e < FS_T * FS_K; e += 256) {
+      for (int e = tid; e < FS_T * FS_K; e += 256) {   // its own: both operands lie along k and fill from one index
         const int mm = e / FS_K, kk = e % FS_K, k = k0 + kk;
         const int u = u0 + mm, v = v0 + mm;
         as[mm][kk] = (u < ony && k < onx) ? tj[(size_t)u * onx + k] : 0.f;
         bs[kk][mm] = (v < onx && k < onx) ? axj[(size_t)v * onx + k] : 0.f;
       }
       __syncthreads();
-#pragma unroll
-      for (int kk = 0; kk < FS_K; kk += 2)
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(as[wm + r][kk + h], bs[kk + h][wp + r], acc, 0, 0, 0);
+      tile_mac<false>(acc, as, bs, t);
       __syncthreads();
     }
   }
-  // L q of this lane's 16 bins (32x32 C/D map: column = lane & 31)
+  // L q of this lane's 16 bins
   float val[16];
   int at[16];
   bool ok[16];
-  const int v = v0 + wp + r;
+  const int v = v0 + t.wp + t.r;
 #pragma unroll
   for (int i = 0; i < 16; ++i) {
-    const int u = u0 + wm + (i & 3) + 8 * (i >> 2) + 4 * h;
+    const int u = u0 + t.wm + acc_row(i, t.h);
     ok[i] = u < ony && v < onx;
     at[i] = u * onx + v;
     val[i] = acc[i];
@@ -101,23 +98,8 @@ __global__ __launch_bounds__(256) void k_filter_xpass(FiltArgs a) {
             f3 = fmaf(wec[at[i]], val[i], f3);
           }
         }
-      double s1 = f1, s2 = f2, s3 = f3;
-      for (int o = 32; o > 0; o >>= 1) {
-        s1 += __shfl_down(s1, o, 64);
-        s2 += __shfl_down(s2, o, 64);
-        s3 += __shfl_down(s3, o, 64);
-      }
-      if (lane == 0) {
-        red[wave][0] = s1;
-        red[wave][1] = s2;
-        red[wave][2] = s3;
-      }
-      __syncthreads();
-      if (tid < 3) {
-        double* const out = a.partials + (((size_t)s * batch + b) * n_tiles + blockIdx.x) * 3;
-        out[tid] = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];   // fixed order
-      }
-      __syncthreads();
+      double sum[3] = {f1, f2, f3};
+      block_sums(sum, red, tid, a.partials + (((size_t)s * batch + b) * n_tiles + blockIdx.x) * 3);
     }
   }
 }

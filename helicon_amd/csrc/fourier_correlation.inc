@@ -11,8 +11,8 @@
 //                          (Re = [C | S][re; im], Im = [-S | C][re; im]), both through k_circ_gemm;
 //     2-D, F(ky, kx):      y pass on the real input;
 //     last (x) pass:       k_fc_xpass, only the columns that are needed (n / 2 + 1 in 3-D, all nx in 2-D), for both members
-//                          of the pair in one workgroup, which forms the three products from its accumulator registers
-//                          and adds them to the shell sums.  The spectrum of the last pass is never stored.
+//                          of the pair in one workgroup (fc_pair_product), which forms the three products from its
+//                          accumulator registers and adds them to the shell sums (fc_add_products, fc_flush).  The spectrum of the last pass is never stored.
 // Shell of a 3-D bin: round(sqrt(m)), m = kz^2 + ky^2 + kx^2 in integers, decided without a square root's rounding
 // (shell = k iff k (k - 1) < m <= k (k + 1); sqrt(m) is never k + 1/2), clipped to n / 2.  A 2-D bin reads the host's table
 // (ties are real there and follow NumPy's float64 expression).  Weight: 1, or — the full spectrum seen from its half —
@@ -76,35 +76,20 @@ __device__ __forceinline__ int fc_shell_3d(int kz, int ky, int kx, int n) {
   return k < h ? k : h;
 }
 
-// One workgroup: 64 rows x 64 columns of F1 and of F2 (4 wavefronts in 2 x 2, each four 32 x 32 accumulators: Re and Im of
-// both members), then the products of the tile into the shell sums.
-__global__ __launch_bounds__(256) void k_fc_xpass(FcXPass g) {
+// The x pass of one pair's 64 x 64 tile on the shared tile (mfma_tile.inc): the four source planes src = {re1, im1, re2, im2}
+// ([rows][nx]) times the tables cs / sn ([nx][ncol]), into four 32 x 32 accumulators per wavefront: Re and Im of both
+// members.  A wavefront whose sub-tile lies wholly outside is not `active` and does no product.  Holds the x pass's LDS.
+__device__ __forceinline__ void fc_pair_product(const float* const (&src)[4], const float* cs, const float* sn, int rows, int nx, int ncol,
+                                                int row0, int col0, bool active, const Tile64& t, f32x16& re1, f32x16& im1, f32x16& re2,
+                                                f32x16& im2) {
   __shared__ float as[4][FC_T][FC_K + 1];   // re1, im1, re2, im2
   __shared__ float os[2][FC_K][FC_T + 1];   // cos, sin
-  __shared__ unsigned long long sh[FC_MAX_SHELLS * 3];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int r = lane & 31, h = lane >> 5;
-  const int row0 = blockIdx.x * FC_T, col0 = blockIdx.y * FC_T, b = blockIdx.z;
-  const int wm = (wave >> 1) * 32, wp = (wave & 1) * 32;
-  const int64_t plane = (int64_t)g.rows * g.nx;
-  const float* src[4] = {g.re + (int64_t)b * plane, g.im + (int64_t)b * plane, g.re + (int64_t)(g.batch + b) * plane,
-                         g.im + (int64_t)(g.batch + b) * plane};
-  for (int e = tid; e < g.nshell * 3; e += 256) sh[e] = 0ull;
-  const bool active = col0 + wp < g.ncol && row0 + wm < g.rows;   // wavefront-uniform: a sub-tile wholly outside does no product
-  f32x16 re1 = {0}, im1 = {0}, re2 = {0}, im2 = {0};
-  for (int k0 = 0; k0 < g.nx; k0 += FC_K) {
+  const float* const tab[2] = {cs, sn};
+  const int r = t.r, h = t.h, wm = t.wm, wp = t.wp;
+  for (int k0 = 0; k0 < nx; k0 += FC_K) {
 #pragma unroll
-    for (int q = 0; q < 4; ++q)
-      for (int e = tid; e < FC_T * FC_K; e += 256) {
-        const int mm = e / FC_K, kk = e % FC_K, row = row0 + mm, k = k0 + kk;   // lanes along x: contiguous in memory
-        as[q][mm][kk] = (row < g.rows && k < g.nx) ? src[q][(int64_t)row * g.nx + k] : 0.f;
-      }
-    for (int e = tid; e < FC_K * FC_T; e += 256) {
-      const int kk = e / FC_T, cc = e % FC_T, k = k0 + kk, col = col0 + cc;
-      const bool in = k < g.nx && col < g.ncol;
-      os[0][kk][cc] = in ? g.cs[(int64_t)k * g.ncol + col] : 0.f;
-      os[1][kk][cc] = in ? g.sn[(int64_t)k * g.ncol + col] : 0.f;
-    }
+    for (int q = 0; q < 4; ++q) stage_rows(as[q], src[q], nx, row0, rows, k0, nx, t.tid);
+    stage_cols(os, tab, ncol, k0, nx, col0, ncol, t.tid);
     __syncthreads();
     if (active) {
 #pragma unroll
@@ -125,12 +110,48 @@ __global__ __launch_bounds__(256) void k_fc_xpass(FcXPass g) {
     }
     __syncthreads();
   }
-  const double s_num = g.scale[b * 3 + 0], s_d1 = g.scale[b * 3 + 1], s_d2 = g.scale[b * 3 + 2];
+}
+
+// The three products of one bin, F1 = x1 + i y1 and F2 = x2 + i y2 with weight w, into a shell's three LDS slots: formed in
+// float64, scaled by the pair's powers of two (scale[3]: num, den1, den2), rounded to a 64-bit integer, added with integer
+// atomics.  The one place the fixed-point rule is written.
+__device__ __forceinline__ void fc_add_products(unsigned long long* slot, double w, double x1, double y1, double x2, double y2,
+                                                const double (&scale)[3]) {
+  const long long qn = __double2ll_rn(w * (x1 * x2 + y1 * y2) * scale[0]);
+  const long long q1 = __double2ll_rn(w * (x1 * x1 + y1 * y1) * scale[1]);
+  const long long q2 = __double2ll_rn(w * (x2 * x2 + y2 * y2) * scale[2]);
+  if (qn != 0) atomicAdd(slot + 0, (unsigned long long)qn);
+  if (q1 != 0) atomicAdd(slot + 1, (unsigned long long)q1);
+  if (q2 != 0) atomicAdd(slot + 2, (unsigned long long)q2);
+}
+
+// a workgroup's n LDS sums into the global ones
+__device__ __forceinline__ void fc_flush(const unsigned long long* sh, int n, long long* acc, int tid) {
+  unsigned long long* const G = reinterpret_cast<unsigned long long*>(acc);
+  for (int e = tid; e < n; e += TILE_THREADS) {
+    const unsigned long long v = sh[e];
+    if (v != 0ull) atomicAdd(G + e, v);
+  }
+}
+
+// One workgroup: 64 rows x 64 columns of F1 and of F2, then the products of the tile into the shell sums.
+__global__ __launch_bounds__(256) void k_fc_xpass(FcXPass g) {
+  __shared__ unsigned long long sh[FC_MAX_SHELLS * 3];
+  const Tile64 t = tile64();
+  const int row0 = blockIdx.x * FC_T, col0 = blockIdx.y * FC_T, b = blockIdx.z;
+  const int64_t plane = (int64_t)g.rows * g.nx;
+  const float* const src[4] = {g.re + (int64_t)b * plane, g.im + (int64_t)b * plane, g.re + (int64_t)(g.batch + b) * plane,
+                               g.im + (int64_t)(g.batch + b) * plane};
+  for (int e = t.tid; e < g.nshell * 3; e += 256) sh[e] = 0ull;
+  const bool active = col0 + t.wp < g.ncol && row0 + t.wm < g.rows;   // wavefront-uniform
+  f32x16 re1 = {0}, im1 = {0}, re2 = {0}, im2 = {0};
+  fc_pair_product(src, g.cs, g.sn, g.rows, g.nx, g.ncol, row0, col0, active, t, re1, im1, re2, im2);
+  const double scale[3] = {g.scale[b * 3 + 0], g.scale[b * 3 + 1], g.scale[b * 3 + 2]};
   if (active) {
-    const int col = col0 + wp + r;   // 32x32 C/D map: column = lane & 31
+    const int col = col0 + t.wp + t.r;
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
-      const int row = row0 + wm + (i & 3) + 8 * (i >> 2) + 4 * h;
+      const int row = row0 + t.wm + acc_row(i, t.h);
       if (row >= g.rows || col >= g.ncol) continue;
       int s;
       double w = 1.0;
@@ -141,28 +162,19 @@ __global__ __launch_bounds__(256) void k_fc_xpass(FcXPass g) {
         s = fc_shell_3d(row / g.n, row % g.n, col, g.n);
         if (g.weighted && col != 0 && 2 * col != g.n) w = 2.0;
       }
-      const double x1 = re1[i], y1 = im1[i], x2 = re2[i], y2 = im2[i];
-      const long long qn = __double2ll_rn(w * (x1 * x2 + y1 * y2) * s_num);
-      const long long q1 = __double2ll_rn(w * (x1 * x1 + y1 * y1) * s_d1);
-      const long long q2 = __double2ll_rn(w * (x2 * x2 + y2 * y2) * s_d2);
-      if (qn != 0) atomicAdd(&sh[s * 3 + 0], (unsigned long long)qn);
-      if (q1 != 0) atomicAdd(&sh[s * 3 + 1], (unsigned long long)q1);
-      if (q2 != 0) atomicAdd(&sh[s * 3 + 2], (unsigned long long)q2);
+      fc_add_products(&sh[s * 3], w, re1[i], im1[i], re2[i], im2[i], scale);
     }
   }
   __syncthreads();
-  unsigned long long* const G = reinterpret_cast<unsigned long long*>(g.acc + (int64_t)b * g.nshell * 3);
-  for (int e = tid; e < g.nshell * 3; e += 256) {
-    const unsigned long long v = sh[e];
-    if (v != 0ull) atomicAdd(G + e, v);
-  }
+  fc_flush(sh, g.nshell * 3, g.acc + (int64_t)b * g.nshell * 3, t.tid);
 }
 
-__global__ __launch_bounds__(256) void k_fc_finish(const long long* __restrict__ acc, const double* __restrict__ scale, int nshell,
+// sums = acc / scale; `sets` curve sets of nshell x 3 sums share a pair's three scales
+__global__ __launch_bounds__(256) void k_fc_finish(const long long* __restrict__ acc, const double* __restrict__ scale, int nshell, int sets,
                                                    int64_t total, double* __restrict__ sums) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= total) return;
-  const int64_t b = i / ((int64_t)nshell * 3);
+  const int64_t b = i / ((int64_t)sets * nshell * 3);
   const double s = scale[b * 3 + i % 3];
   sums[i] = s == 0.0 ? 0.0 : (double)acc[i] / s;   // a NaN scale (a map that is not finite) gives NaN
 }
@@ -202,6 +214,8 @@ size_t fc_xtable(std::vector<float>& mats, int n, int ncol, const std::vector<do
 
 constexpr int64_t FC_SCRATCH_BYTES = (int64_t)8 << 30;   // device planes of one chunk of the batch
 
+// Device scratch of the forward passes and the sums, grow-only, plus a caller's operators / shell table and the two events
+// that time a chunk.
 struct FcBuffers {
   float *in = nullptr, *p1 = nullptr, *p2 = nullptr, *mats = nullptr;   // p1 / p2: [re | im] plane pairs
   int32_t* shell = nullptr;
@@ -209,9 +223,38 @@ struct FcBuffers {
   double *scale = nullptr, *sums = nullptr;
   long long* acc = nullptr;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  int64_t cap = 0, cap_per_map = 0;   // pairs the scratch holds, and the shape it was sized for
+  int cap_nshell = 0;
+  void release() {
+    (void)hipFree(in); (void)hipFree(p1); (void)hipFree(p2); (void)hipFree(amax); (void)hipFree(scale); (void)hipFree(sums); (void)hipFree(acc);
+    in = p1 = p2 = nullptr; amax = nullptr; scale = sums = nullptr; acc = nullptr; cap = 0;
+  }
+  // Room for `pairs` pairs of maps of per_map voxels: 2 input maps per pair (`with_in`; else the caller's maps are read in
+  // place), 4 planes per pair in p1 and (cubes) p2, and at least two curve sets of nshell x 3 sums (the two curves of a
+  // one-pair context; a one-pair fc_run carries the second set unused, a few KB).  Only `pairs` may grow between calls:
+  // per_map, nshell and cube are those of the holder's one plan.
+  int reserve(int64_t pairs, int64_t per_map, int nshell, bool cube, bool with_in) {
+    if (!ev0) HH_HIP(nullptr, hipEventCreate(&ev0));
+    if (!ev1) HH_HIP(nullptr, hipEventCreate(&ev1));
+    if (cap > 0 && (per_map != cap_per_map || nshell != cap_nshell)) return fail(nullptr, HH_ERR_STATE, "FcBuffers::reserve: another shape than the holder's");
+    if (pairs <= cap && (!with_in || in)) return HH_OK;
+    pairs = std::max(pairs, cap);
+    release();
+    const size_t map_bytes = (size_t)per_map * sizeof(float);
+    if (with_in) HH_HIP(nullptr, hipMalloc(&in, 2 * (size_t)pairs * map_bytes));
+    HH_HIP(nullptr, hipMalloc(&p1, 4 * (size_t)pairs * map_bytes));
+    if (cube) HH_HIP(nullptr, hipMalloc(&p2, 4 * (size_t)pairs * map_bytes));
+    const size_t n_sums = (size_t)std::max<int64_t>(pairs, 2) * nshell * 3;
+    HH_HIP(nullptr, hipMalloc(&amax, 2 * (size_t)pairs * sizeof(unsigned)));
+    HH_HIP(nullptr, hipMalloc(&scale, (size_t)pairs * 3 * sizeof(double)));
+    HH_HIP(nullptr, hipMalloc(&acc, n_sums * sizeof(long long)));
+    HH_HIP(nullptr, hipMalloc(&sums, n_sums * sizeof(double)));
+    cap = pairs; cap_per_map = per_map; cap_nshell = nshell;
+    return HH_OK;
+  }
   ~FcBuffers() {
-    (void)hipFree(in); (void)hipFree(p1); (void)hipFree(p2); (void)hipFree(mats); (void)hipFree(shell); (void)hipFree(amax);
-    (void)hipFree(scale); (void)hipFree(sums); (void)hipFree(acc);
+    release();
+    (void)hipFree(mats); (void)hipFree(shell);
     if (ev0) (void)hipEventDestroy(ev0);
     if (ev1) (void)hipEventDestroy(ev1);
   }
@@ -249,10 +292,13 @@ void fc_plan(FcPlan& p, int nz, int ny, int nx) {
 }
 
 // The passes before the last one on device-resident input: `in` holds 2 nb real maps (the first members, then the second
-// members), p1 / p2 are [re | im] plane pairs of 4 nb maps each (p2: cubes only), mats the plan's operators on the device.
+// members), d.p1 / d.p2 are [re | im] plane pairs of 4 nb maps each (p2: cubes only), d.mats the plan's operators on the device.
 // Also max |x| of every map and the pairs' scales.  The planes the x pass reads come back in xre / xim.
-void fc_passes(const FcPlan& p, const float* in, float* p1, float* p2, const float* mats, unsigned* amax, double* scale, int64_t nb,
-               const float** xre, const float** xim) {
+void fc_passes(const FcPlan& p, const float* in, const FcBuffers& d, int64_t nb, const float** xre, const float** xim) {
+  float *const p1 = d.p1, *const p2 = d.p2;
+  const float* const mats = d.mats;
+  unsigned* const amax = d.amax;
+  double* const scale = d.scale;
   const int64_t maps = 2 * nb, per_map = p.per_map;
   const int nx = p.nx, ny = p.ny, nz = p.nz, n1 = p.n1;
   float* const re1 = p1;
@@ -289,23 +335,22 @@ void fc_passes(const FcPlan& p, const float* in, float* p1, float* p2, const flo
   }
 }
 
-// All passes of nb pairs on device-resident input, down to the float64 sums [nb][nshell][3] on the device (acc: zeroed here)
-void fc_device(const FcPlan& p, const float* in, float* p1, float* p2, const float* mats, const int32_t* shell, unsigned* amax, double* scale,
-               long long* acc, double* sums, int64_t nb, int nshell, bool weighted) {
-  (void)hipMemsetAsync(amax, 0, (size_t)(2 * nb) * sizeof(unsigned), nullptr);
-  (void)hipMemsetAsync(acc, 0, (size_t)nb * nshell * 3 * sizeof(long long), nullptr);
+// All passes of nb pairs on device-resident input, down to the float64 sums [nb][nshell][3] in d.sums (d.acc: zeroed here)
+void fc_device(const FcPlan& p, const float* in, const FcBuffers& d, int64_t nb, int nshell, bool weighted) {
+  (void)hipMemsetAsync(d.amax, 0, (size_t)(2 * nb) * sizeof(unsigned), nullptr);
+  (void)hipMemsetAsync(d.acc, 0, (size_t)nb * nshell * 3 * sizeof(long long), nullptr);
   const float *xre = nullptr, *xim = nullptr;
-  fc_passes(p, in, p1, p2, mats, amax, scale, nb, &xre, &xim);
+  fc_passes(p, in, d, nb, &xre, &xim);
   FcXPass x{};
   x.re = xre; x.im = xim;
-  x.cs = mats + p.o_xc; x.sn = mats + p.o_xs;
-  x.shell = p.cube ? nullptr : shell;
-  x.scale = scale; x.acc = acc;
+  x.cs = d.mats + p.o_xc; x.sn = d.mats + p.o_xs;
+  x.shell = p.cube ? nullptr : d.shell;
+  x.scale = d.scale; x.acc = d.acc;
   x.batch = (int)nb; x.rows = p.rows; x.nx = p.nx; x.ncol = p.ncol; x.n = p.nx; x.nshell = nshell; x.weighted = weighted ? 1 : 0;
   hipLaunchKernelGGL(k_fc_xpass, dim3((unsigned)((p.rows + FC_T - 1) / FC_T), (unsigned)((p.ncol + FC_T - 1) / FC_T), (unsigned)nb), dim3(256), 0,
                      nullptr, x);
   const int64_t total = nb * nshell * 3;
-  hipLaunchKernelGGL(k_fc_finish, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, nullptr, acc, scale, nshell, total, sums);
+  hipLaunchKernelGGL(k_fc_finish, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, nullptr, d.acc, d.scale, nshell, 1, total, d.sums);
 }
 
 // chunk of a batch of pairs: input + one or two plane pairs within the scratch cap, and the y pass's grid.z = 2 chunk nz <= 65535
@@ -331,29 +376,20 @@ int fc_run(const char* name, int device, const float* a, const float* b, int64_t
   const int64_t chunk = fc_chunk(p, batch);
   FcBuffers d;
   const size_t map_bytes = (size_t)per_map * sizeof(float);
-  HH_HIP(nullptr, hipMalloc(&d.in, 2 * (size_t)chunk * map_bytes));
-  HH_HIP(nullptr, hipMalloc(&d.p1, 4 * (size_t)chunk * map_bytes));
-  if (cube) HH_HIP(nullptr, hipMalloc(&d.p2, 4 * (size_t)chunk * map_bytes));
+  if (int rc = d.reserve(chunk, per_map, nshell, cube, true)) return rc;
   HH_HIP(nullptr, hipMalloc(&d.mats, p.mats.size() * sizeof(float)));
   HH_HIP(nullptr, hipMemcpy(d.mats, p.mats.data(), p.mats.size() * sizeof(float), hipMemcpyHostToDevice));
   if (!cube) {
     HH_HIP(nullptr, hipMalloc(&d.shell, (size_t)per_map * sizeof(int32_t)));
     HH_HIP(nullptr, hipMemcpy(d.shell, shell, (size_t)per_map * sizeof(int32_t), hipMemcpyHostToDevice));
   }
-  const size_t n_sums = (size_t)chunk * nshell * 3;
-  HH_HIP(nullptr, hipMalloc(&d.amax, 2 * (size_t)chunk * sizeof(unsigned)));
-  HH_HIP(nullptr, hipMalloc(&d.scale, (size_t)chunk * 3 * sizeof(double)));
-  HH_HIP(nullptr, hipMalloc(&d.acc, n_sums * sizeof(long long)));
-  HH_HIP(nullptr, hipMalloc(&d.sums, n_sums * sizeof(double)));
-  HH_HIP(nullptr, hipEventCreate(&d.ev0));
-  HH_HIP(nullptr, hipEventCreate(&d.ev1));
   double ms_total = 0.0;
   for (int64_t b0 = 0; b0 < batch; b0 += chunk) {
     const int64_t nb = std::min(chunk, batch - b0);
     HH_HIP(nullptr, hipMemcpy(d.in, a + b0 * per_map, (size_t)nb * map_bytes, hipMemcpyHostToDevice));
     HH_HIP(nullptr, hipMemcpy(d.in + nb * per_map, b + b0 * per_map, (size_t)nb * map_bytes, hipMemcpyHostToDevice));
     HH_HIP(nullptr, hipEventRecord(d.ev0, nullptr));
-    fc_device(p, d.in, d.p1, d.p2, d.mats, d.shell, d.amax, d.scale, d.acc, d.sums, nb, nshell, weighted);
+    fc_device(p, d.in, d, nb, nshell, weighted);
     HH_HIP(nullptr, hipGetLastError());
     HH_HIP(nullptr, hipEventRecord(d.ev1, nullptr));
     HH_HIP(nullptr, hipMemcpy(sums + b0 * nshell * 3, d.sums, (size_t)nb * nshell * 3 * sizeof(double), hipMemcpyDeviceToHost));

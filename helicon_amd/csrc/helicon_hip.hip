@@ -2102,13 +2102,17 @@ __global__ __launch_bounds__(N, (N >= 256 ? KF<N>::WPS : 1)) void k_fused_pass(F
 }
 
 // ------------------------------------------------------------------------------------------
+// The f32-MFMA tile every dense product below and in the .inc files at the end of this file is built on
+// ------------------------------------------------------------------------------------------
+#include "mfma_tile.inc"  // what the f32-MFMA tile products share: f32x16, lane and accumulator-row maps, K-slice staging and step, block_sums
+
+// ------------------------------------------------------------------------------------------
 // Several experimental segments against one candidate grid (BASELINE config 5): the covariance
 // numerators S3[s][c] = sum_k WEC[s][k] * Q[c][k] are a dense contraction over the K = (N/2+1) N
 // half-plane bins, so they run on the matrix cores with the exact-f32 MFMA (32x32x2, f32 in /
 // f32 accumulate): one wavefront owns a 64-candidate x 64-segment tile of ONE spectrum row (N bins)
 // and streams its operands straight from L2 / Infinity Cache into registers, 16 B per lane.
 // ------------------------------------------------------------------------------------------
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 // A workgroup of four wavefronts owns up to 256 candidates x 64 segments of ONE spectrum row (n_k bins):
 // the operands are staged through LDS in slices of 32 bins with whole-line global loads (eight lanes per
@@ -2187,13 +2191,12 @@ __global__ __launch_bounds__(256) void k_segment_corr(const float* __restrict__ 
       acc11 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1.y, b1.y, acc11, 0, 0, 0);
     }
   }
-  // D layout of the 32x32 MFMA: column = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)
   const int cw = c0 + wave * 64;
   if (cw >= Bp) return;
   float* const out = part + (size_t)blockIdx.x * Bp * Sp;
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
-    const int ci = (r & 3) + 8 * (r >> 2) + 4 * h;
+    const int ci = acc_row(r, h);   // column = lane & 31 = i
     out[(size_t)(cw + ci) * Sp + s0 + i] = acc00[r];
     out[(size_t)(cw + ci) * Sp + s0 + 32 + i] = acc01[r];
     out[(size_t)(cw + 32 + ci) * Sp + s0 + i] = acc10[r];
@@ -4880,6 +4883,7 @@ int hh_profile_get(hh_ctx* c, hh_profile* out) try {
 
 }  // extern "C"
 
+// (mfma_tile.inc — what the f32-MFMA tile products below share: lane and accumulator-row maps, K-slice staging and step, block_sums — is included above, ahead of k_segment_corr)
 #include "image_prep.inc"    // pre-sweep image preparation that is scikit-image in the reference (warp, rescale, closing + moments)
 #include "fourier_zoom.inc"  // compute_power_spectra with cutoff_res / output_size: direct non-uniform DFT (hh_power_spectrum_zoom)
 #include "zoom_sweep.inc"    // the sweep on those zoomed spectra: factors + complex product on the f32 MFMA + fused moments (hh_set_spectrum_zoom)

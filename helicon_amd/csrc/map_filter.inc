@@ -29,25 +29,22 @@ struct CircPass {
   int64_t sb;        // element stride of one batch (the y pass: one z slice)
 };
 
-// Y[b][m][p] = sum_k A[m][k] B[b][k][p].  4 wavefronts in 2 x 2, each one 32 x 32 accumulator.  TR swaps the MFMA's
-// operands so that the accumulator's lane index runs along m: with the x pass's strides (sk = 1) the stores coalesce.
+// Y[b][m][p] = sum_k A[m][k] B[b][k][p] on the shared tile (mfma_tile.inc), one 32 x 32 accumulator per wavefront.  TR swaps
+// the MFMA's operands so that the accumulator's lane index runs along m: with the x pass's strides (sk = 1) the stores coalesce.
 template <bool TR>
 __global__ __launch_bounds__(256) void k_circ_gemm(CircPass g) {
   __shared__ float as[MF_T][MF_K + 1];
   __shared__ float bs[MF_K][MF_T + 1];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int r = lane & 31, h = lane >> 5;
-  const int m0 = blockIdx.y * MF_T, wm = (wave >> 1) * 32, wp = (wave & 1) * 32;
+  const Tile64 t = tile64();
+  const int tid = t.tid, r = t.r, h = t.h, wm = t.wm, wp = t.wp;
+  const int m0 = blockIdx.y * MF_T;
   const int64_t p0 = (int64_t)blockIdx.x * MF_T, boff = (int64_t)blockIdx.z * g.sb;
   const float* b0 = g.b0 + boff;
   const float* b1 = g.b1 ? g.b1 + boff : nullptr;
   f32x16 acc = {0};
   for (int k0 = 0; k0 < g.ka; k0 += MF_K) {
-    for (int e = tid; e < MF_T * MF_K; e += 256) {
-      const int mm = e / MF_K, kk = e % MF_K, m = m0 + mm, k = k0 + kk;
-      as[mm][kk] = (m < g.n && k < g.ka) ? g.a[(int64_t)m * g.ka + k] : 0.f;
-    }
-    for (int e = tid; e < MF_T * MF_K; e += 256) {
+    stage_rows(as, g.a, g.ka, m0, g.n, k0, g.ka, tid);
+    for (int e = tid; e < MF_T * MF_K; e += 256) {   // its own: the stride along P and the split of K over b0 / b1
       int kk, pp;
       if (g.sp == 1) { kk = e / MF_T; pp = e % MF_T; }   // P contiguous: lanes along P
       else { pp = e / MF_K; kk = e % MF_K; }             // the x pass: lanes along k
@@ -58,16 +55,12 @@ __global__ __launch_bounds__(256) void k_circ_gemm(CircPass g) {
       bs[kk][pp] = v;
     }
     __syncthreads();
-#pragma unroll
-    for (int kk = 0; kk < MF_K; kk += 2) {
-      const float av = as[wm + r][kk + h], bv = bs[kk + h][wp + r];
-      acc = TR ? __builtin_amdgcn_mfma_f32_32x32x2f32(bv, av, acc, 0, 0, 0) : __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc, 0, 0, 0);
-    }
+    tile_mac<TR>(acc, as, bs, t);
     __syncthreads();
   }
 #pragma unroll
   for (int i = 0; i < 16; ++i) {
-    const int row = (i & 3) + 8 * (i >> 2) + 4 * h;   // 32x32 C/D map: column = lane & 31
+    const int row = acc_row(i, h);
     const int m = m0 + wm + (TR ? r : row);
     const int64_t p = p0 + wp + (TR ? row : r);
     if (m < g.n && p < g.np) g.y[boff + (int64_t)m * g.sk + p * g.sp] = acc[i];

@@ -12,8 +12,8 @@
 // real, so Gy_c at -f_y is the conjugate of Gy_c at f_y: with P1 = sum ar br, P2 = sum ai bi, P3 = sum ar bi,
 // P4 = sum ai br (a = Gy, b = Gx)
 //     F = (P1 - P2) + i (P3 + P4),     F~ = (P1 + P2) + i (P3 - P4)
-// and k_phase_sweep is k_zoom_sweep with the four products kept in accumulators of their own: the same lattice walk,
-// factors, K slices and MFMA count, an epilogue with two more sums (sum w M^2, sum (w M_exp) M).  F~ needs no partner
+// and k_phase_sweep runs k_zoom_sweep's product body (zoom_product, zoom_sweep.inc) with the four products kept in
+// accumulators of their own: the same MFMA count, an epilogue with two more sums (sum w M^2, sum (w M_exp) M).  F~ needs no partner
 // row on the grid, so the unpaired row u = ony/2 of a zoomed plane is scored like any other.  Both q and M enter their
 // scores up to a constant factor, so the logarithm is taken in base 2 as everywhere in the sweep.
 // The reference side is k_zoom_rows plus k_phase_cols (F and F~ of the experimental image in float64) and
@@ -51,135 +51,20 @@ template <int LOG, bool LDSP>
 __global__ __launch_bounds__(ZS_THREADS) void k_phase_sweep(PhaseSweepArgs pa) {
   extern __shared__ __align__(16) unsigned char phase_lds_raw[];
   PhaseLds& PL = *reinterpret_cast<PhaseLds*>(phase_lds_raw);
-  ZoomLds& L = PL.z;
   const ZoomSweepArgs& a = pa.z;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int r = lane & 31, h = lane >> 5;
-  const int wu = wave & 3, wv = wave >> 2;   // 4 x 2 wavefronts of 32 x 64
+  const ZoomTile z = zoom_tile(a);
   const int b = blockIdx.y, n_tiles = gridDim.x, batch = gridDim.y;
-  const int tile = a.tiles[blockIdx.x];
-  const int u0 = (tile / a.tiles_v) * ZS_TU, v0 = (tile % a.tiles_v) * ZS_TV;
-  const DevGeom& g = a.g;
-  const int ny = a.d.ny, nx = a.d.nx, ony = a.d.ony, onx = a.d.onx;
-  const float rp = (float)g.rpx;
-  const float k2 = g.inv_sigma2 * 1.44269504088896341f;
-  const Cand c = decode_candidate(a.params + 4 * (size_t)b, g);
-
-  // the two frequencies this lane builds factors for, and their unit steps w = e^{-2 pi i f}
-  const int ul = tid & (ZS_TU - 1), vl = tid & (ZS_TV - 1);
-  const bool u_ok = u0 + ul < ony, v_ok = v0 + vl < onx;
-  const double fy = u_ok ? zoom_freq(u0 + ul, ony, a.d.sy, a.apix, a.cutoff_y) : 0.0;
-  const double fx = v_ok ? zoom_freq(v0 + vl, onx, a.d.sx, a.apix, a.cutoff_x) : 0.0;
-  float2 wy, wx;
-  {
-    double sn, cs;
-    sincospi(-2.0 * fy, &sn, &cs);
-    wy = make_float2((float)cs, (float)sn);
-    sincospi(-2.0 * fx, &sn, &cs);
-    wx = make_float2((float)cs, (float)sn);
-  }
+  const int ony = a.d.ony, onx = a.d.onx;
 
   // P1 = sum ar br, P2 = sum ai bi, P3 = sum ar bi, P4 = sum ai br
-  f32x16 p1[2] = {{0}, {0}}, p2[2] = {{0}, {0}}, p3[2] = {{0}, {0}}, p4[2] = {{0}, {0}};
-
-  // one K slice: list entries [s0, s0 + cnt), cnt <= ZS_K (the rest of the slice is zero)
-  auto slice = [&](int s0, int cnt) __attribute__((always_inline)) {
-    if constexpr (LDSP) {
-      for (int e = tid; e < ZS_K * ZS_TAPS; e += ZS_THREADS) {
-        const int k = e / ZS_TAPS, j = e % ZS_TAPS;
-        if (k < cnt) {
-          L.prof_y[k][j] = j < L.ly[s0 + k] ? zoom_tap(L.y0[s0 + k] + j, ny / 2, g.apix, L.yc[s0 + k], k2) : 0.f;
-          L.prof_x[k][j] = j < L.lx[s0 + k] ? zoom_tap(L.x0[s0 + k] + j, nx / 2, g.apix, L.xc[s0 + k], k2) : 0.f;
-        }
-      }
-      __syncthreads();
-    }
-    for (int k = tid / ZS_TU; k < ZS_K; k += ZS_THREADS / ZS_TU) {
-      float2 v = make_float2(0.f, 0.f);
-      if (k < cnt && u_ok)
-        v = zoom_factor<LDSP>(fy, wy, L.y0[s0 + k], L.ly[s0 + k], ny / 2, L.yc[s0 + k], g.apix, k2, L.prof_y[k]);
-      L.as_re[ul][k] = v.x;
-      L.as_im[ul][k] = v.y;
-    }
-    for (int k = tid / ZS_TV; k < ZS_K; k += ZS_THREADS / ZS_TV) {
-      float2 v = make_float2(0.f, 0.f);
-      if (k < cnt && v_ok)
-        v = zoom_factor<LDSP>(fx, wx, L.x0[s0 + k], L.lx[s0 + k], nx / 2, L.xc[s0 + k], g.apix, k2, L.prof_x[k]);
-      L.bs_re[k][vl] = v.x;
-      L.bs_im[k][vl] = v.y;
-    }
-    __syncthreads();
-#pragma unroll 4
-    for (int kk = 0; kk < ZS_K; kk += 2) {
-      const float ar = L.as_re[wu * 32 + r][kk + h], ai = L.as_im[wu * 32 + r][kk + h];
-#pragma unroll
-      for (int t = 0; t < 2; ++t) {
-        const float br = L.bs_re[kk + h][wv * 64 + t * 32 + r], bi = L.bs_im[kk + h][wv * 64 + t * 32 + r];
-        p1[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(ar, br, p1[t], 0, 0, 0);
-        p2[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(ai, bi, p2[t], 0, 0, 0);
-        p3[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(ar, bi, p3[t], 0, 0, 0);
-        p4[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(ai, br, p4[t], 0, 0, 0);
-      }
-    }
-    __syncthreads();
-  };
-
-  // k_zoom_sweep's walk of the lattice: chunks of one centre per lane, the centres whose footprint meets the image are
-  // appended in lattice order (ballot + prefix), full K slices are consumed, the remainder waits for the next chunk.
-  int pending = 0;
-  for (int base = 0; base < c.M; base += ZS_CHUNK) {
-    const int ci = base + tid;
-    bool hit = false;
-    float2 p = make_float2(0.f, 0.f);
-    int y0 = 0, y1 = -1, x0 = 0, x1 = -1;
-    if (ci < c.M) {
-      p = centre_position(c, g, a.units, ci);
-      const float cy = p.x * g.inv_apix + (float)(ny / 2), cx = p.y * g.inv_apix + (float)(nx / 2);
-      if (cy >= -rp - 1.f && cy <= (float)ny + rp && cx >= -rp - 1.f && cx <= (float)nx + rp) {
-        y0 = max(0, (int)ceilf(cy - rp));
-        y1 = min(ny - 1, (int)floorf(cy + rp));
-        x0 = max(0, (int)ceilf(cx - rp));
-        x1 = min(nx - 1, (int)floorf(cx + rp));
-        hit = y0 <= y1 && x0 <= x1;
-      }
-    }
-    const unsigned long long bal = __ballot(hit);
-    if (lane == 0) L.wave_cnt[wave] = __popcll(bal);
-    __syncthreads();
-    int off = pending, total = pending;
-    for (int w = 0; w < ZS_WAVES; ++w) {
-      if (w < wave) off += L.wave_cnt[w];
-      total += L.wave_cnt[w];
-    }
-    if (hit) {
-      const int at = off + __popcll(bal & ((1ull << lane) - 1ull));
-      L.yc[at] = p.x;
-      L.xc[at] = p.y;
-      L.y0[at] = y0;
-      L.ly[at] = y1 - y0 + 1;
-      L.x0[at] = x0;
-      L.lx[at] = x1 - x0 + 1;
-    }
-    __syncthreads();
-    const bool last = base + ZS_CHUNK >= c.M;   // the last chunk also consumes the partial slice
-    int s0 = 0;
-    for (; total - s0 >= ZS_K || (last && s0 < total); s0 += ZS_K) slice(s0, min(ZS_K, total - s0));
-    pending = max(0, total - s0);
-    if (s0 > 0 && pending > 0) {   // move the remainder (< ZS_K entries) to the front
-      float ryc = 0.f, rxc = 0.f;
-      int ry0 = 0, rly = 0, rx0 = 0, rlx = 0;
-      if (tid < pending) {
-        ryc = L.yc[s0 + tid]; rxc = L.xc[s0 + tid];
-        ry0 = L.y0[s0 + tid]; rly = L.ly[s0 + tid]; rx0 = L.x0[s0 + tid]; rlx = L.lx[s0 + tid];
-      }
-      __syncthreads();
-      if (tid < pending) {
-        L.yc[tid] = ryc; L.xc[tid] = rxc;
-        L.y0[tid] = ry0; L.ly[tid] = rly; L.x0[tid] = rx0; L.lx[tid] = rlx;
-      }
-    }
-    __syncthreads();
-  }
+  f32x16 acc[4][2];
+  zoom_product<LDSP>(a, PL.z, z, acc, [](f32x16 (&p)[4][2], float ar, float ai, float br, float bi, int t) __attribute__((always_inline)) {
+    p[0][t] = __builtin_amdgcn_mfma_f32_32x32x2f32(ar, br, p[0][t], 0, 0, 0);
+    p[1][t] = __builtin_amdgcn_mfma_f32_32x32x2f32(ai, bi, p[1][t], 0, 0, 0);
+    p[2][t] = __builtin_amdgcn_mfma_f32_32x32x2f32(ar, bi, p[2][t], 0, 0, 0);
+    p[3][t] = __builtin_amdgcn_mfma_f32_32x32x2f32(ai, br, p[3][t], 0, 0, 0);
+  });
+  const auto &p1 = acc[0], &p2 = acc[1], &p3 = acc[2], &p4 = acc[3];
 
   // epilogue: per masked bin q, c and M = q c; per segment the three amplitude moments, sum w M^2 and sum (w M_exp) M
   const size_t plane = (size_t)ony * onx;
@@ -191,8 +76,7 @@ __global__ __launch_bounds__(ZS_THREADS) void k_phase_sweep(PhaseSweepArgs pa) {
     for (int t = 0; t < 2; ++t)
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
-        const int u = u0 + wu * 32 + (i & 3) + 8 * (i >> 2) + 4 * h;   // 32x32 C/D map: column = lane & 31
-        const int v = v0 + wv * 64 + t * 32 + r;
+        const int u = zoom_u(z, i), v = zoom_v(z, t);
         if (u < ony && v < onx) {
           const size_t at = (size_t)u * onx + v;
           const float wt = a.w[at];
@@ -213,20 +97,7 @@ __global__ __launch_bounds__(ZS_THREADS) void k_phase_sweep(PhaseSweepArgs pa) {
         }
       }
     double sum[5] = {f1, f2, f3, f4, f5};
-    for (int o = 32; o > 0; o >>= 1)
-#pragma unroll
-      for (int e = 0; e < 5; ++e) sum[e] += __shfl_down(sum[e], o, 64);
-    if (lane == 0)
-#pragma unroll
-      for (int e = 0; e < 5; ++e) PL.red[wave][e] = sum[e];
-    __syncthreads();
-    if (tid < 5) {
-      double* const out = a.partials + (((size_t)s * batch + b) * n_tiles + blockIdx.x) * 5;
-      double tot = 0;
-      for (int w = 0; w < ZS_WAVES; ++w) tot += PL.red[w][tid];   // fixed order
-      out[tid] = tot;
-    }
-    __syncthreads();
+    block_sums(sum, PL.red, z.tid, a.partials + (((size_t)s * batch + b) * n_tiles + blockIdx.x) * 5);
   }
 }
 

@@ -395,7 +395,8 @@ extern "C" int hh_tfsm_soft_masked(hh_tfsc* ctx, const double* soft_widths, int3
   int64_t per_launch = std::max<int64_t>(1, FC_SCRATCH_BYTES / (20 * per_map * (int64_t)sizeof(float)));
   per_launch = std::min<int64_t>(per_launch, 65535 / (4 * n));
   per_launch = std::min<int64_t>(per_launch, batch);
-  if (int rc = tf_scratch(c, 2 * per_launch, true)) return rc;
+  FcBuffers& d = c->fc;
+  if (int rc = d.reserve(2 * per_launch, per_map, nshell, true, true)) return rc;
   int64_t cells = 1;   // the largest decimated grid of the list
   for (int32_t j = 0; j < batch; ++j)
     if (soft_widths[j] > 0) {
@@ -416,14 +417,14 @@ extern "C" int hh_tfsm_soft_masked(hh_tfsc* ctx, const double* soft_widths, int3
     }
     HH_HIP(nullptr, hipMemcpy(s->taps, taps.data(), (size_t)(nb * 3 * n) * sizeof(SmTap), hipMemcpyHostToDevice));
     HH_HIP(nullptr, hipMemsetAsync(s->probe, 0, (size_t)(nb * n_sup) * sizeof(int32_t), nullptr));
-    HH_HIP(nullptr, hipEventRecord(c->ev0, nullptr));
+    HH_HIP(nullptr, hipEventRecord(d.ev0, nullptr));
     const int64_t P = 2 * nb;   // k_tfsc_mask's layout of `in`
     for (int64_t j = 0; j < nb; ++j) {
       const double w = soft_widths[b0 + j];
       const int step = w > 0 ? sm_step(w) : 1;
       const int m = (n + step - 1) / step;
-      float* const in1 = c->in + (2 * j) * per_map;
-      float* const in2 = c->in + (P + 2 * j) * per_map;
+      float* const in1 = d.in + (2 * j) * per_map;
+      float* const in2 = d.in + (P + 2 * j) * per_map;
       for (int k = 0; k < n_sup; ++k) {
         SmApply g{};
         g.sup = s->sup + k * per_map;
@@ -442,15 +443,15 @@ extern "C" int hh_tfsm_soft_masked(hh_tfsc* ctx, const double* soft_widths, int3
       }
     }
     HH_HIP(nullptr, hipGetLastError());
-    fc_device(c->plan, c->in, c->p1, c->p2, c->mats, nullptr, c->amax, c->scale, c->acc, c->sums, 2 * nb, nshell, full_spectrum != 0);
+    fc_device(c->plan, d.in, d, 2 * nb, nshell, full_spectrum != 0);
     HH_HIP(nullptr, hipGetLastError());
-    HH_HIP(nullptr, hipEventRecord(c->ev1, nullptr));
+    HH_HIP(nullptr, hipEventRecord(d.ev1, nullptr));
     HH_HIP(nullptr, hipMemcpy(probe.data(), s->probe, (size_t)(nb * n_sup) * sizeof(int32_t), hipMemcpyDeviceToHost));
     for (int64_t e = 0; e < nb * n_sup; ++e)
       if (probe[(size_t)e] >= SM_INF) return sm_empty("hh_tfsm_soft_masked", sm_step(soft_widths[b0 + e / n_sup]));
-    HH_HIP(nullptr, hipMemcpy(sums + b0 * 2 * nshell * 3, c->sums, (size_t)(2 * nb) * nshell * 3 * sizeof(double), hipMemcpyDeviceToHost));
+    HH_HIP(nullptr, hipMemcpy(sums + b0 * 2 * nshell * 3, d.sums, (size_t)(2 * nb) * nshell * 3 * sizeof(double), hipMemcpyDeviceToHost));
     float ms = 0.f;
-    HH_HIP(nullptr, hipEventElapsedTime(&ms, c->ev0, c->ev1));
+    HH_HIP(nullptr, hipEventElapsedTime(&ms, d.ev0, d.ev1));
     ms_total += ms;
   }
   if (kernel_ms) *kernel_ms = ms_total;

@@ -1,8 +1,8 @@
 // true_fsc.inc — the noise-substitution ("true") FSC of two half maps (commands/trueFSC.py, Chen et al. 2013,
 // Ultramicroscopy 135:24-35), on a context that keeps one pair of cubic maps of even side n on the device.
 //
-// create:  z and y forward passes as in fourier_correlation.inc, then k_tfsc_xpass: k_fc_xpass's product loop with an
-//          epilogue that STORES the half spectrum F(kz, ky, kx) of both maps, every bin with
+// create:  z and y forward passes as in fourier_correlation.inc, then k_tfsc_xpass: k_fc_xpass's product (fc_pair_product) with
+//          an epilogue that STORES the half spectrum F(kz, ky, kx) of both maps, every bin with
 //          m = kz^2 + ky^2 + kx^2 >= m_cut (folded frequencies, integers) replaced by |F| e^{i theta}
 //          (lib/filters.py:469-520, randomize_phases_lowpass), and adds the shell sums of two curves in the same pass: the
 //          unmasked one and the one of the substituted bins (every bin of the half spectrum once, as calc_fsc counts them).
@@ -22,30 +22,18 @@ struct hh_tfsc {
   int device = 0, n = 0, ncol = 0, nshell = 0;
   int64_t per_map = 0, per_spec = 0;    // n^3 and n n (n / 2 + 1)
   FcPlan plan;
-  size_t o_izr = 0, o_izi = 0, o_iyr = 0, o_iyi = 0, o_xcw = 0, o_xsw = 0;   // inverse operators, after the plan's in `mats`
-  float* mats = nullptr;
+  size_t o_izr = 0, o_izi = 0, o_iyr = 0, o_iyi = 0, o_xcw = 0, o_xsw = 0;   // inverse operators, after the plan's in fc.mats
+  FcBuffers fc;              // the forward passes' scratch, the operators (fc.mats) and the events
   float* maps = nullptr;     // [4][n^3]: map1, map2, map1r, map2r
   float* spec = nullptr;     // [re | im][2 maps][n n][ncol]: the substituted half spectra
   double* curves = nullptr;  // [2][nshell][3]
-  // scratch of the forward passes for `cap` pairs
-  int64_t cap = 0, cap_masks = 0;
-  float *in = nullptr, *p1 = nullptr, *p2 = nullptr, *masks = nullptr;
-  unsigned* amax = nullptr;
-  double *scale = nullptr, *sums = nullptr;
-  long long* acc = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  int64_t cap_masks = 0;
+  float* masks = nullptr;
   SmState* soft = nullptr;
-  void free_scratch() {
-    (void)hipFree(in); (void)hipFree(p1); (void)hipFree(p2); (void)hipFree(amax); (void)hipFree(scale); (void)hipFree(sums); (void)hipFree(acc);
-    in = p1 = p2 = nullptr; amax = nullptr; scale = sums = nullptr; acc = nullptr; cap = 0;
-  }
-  ~hh_tfsc() {
+  ~hh_tfsc() {   // (fc goes after this body, on the device set here)
     (void)hipSetDevice(device);
-    free_scratch();
     sm_release(soft);
-    (void)hipFree(mats); (void)hipFree(maps); (void)hipFree(spec); (void)hipFree(curves); (void)hipFree(masks);
-    if (ev0) (void)hipEventDestroy(ev0);
-    if (ev1) (void)hipEventDestroy(ev1);
+    (void)hipFree(maps); (void)hipFree(spec); (void)hipFree(curves); (void)hipFree(masks);
   }
 };
 
@@ -79,76 +67,34 @@ __device__ __forceinline__ unsigned tf_philox(unsigned c0, unsigned c1, unsigned
   return c0;
 }
 
-// One workgroup: 64 rows x 64 columns of F1 and F2, k_fc_xpass's product loop; the epilogue stores the (substituted) bins and
-// adds the products of the original and of the substituted bins to the two curves' shell sums.
+// One workgroup: 64 rows x 64 columns of F1 and F2 by k_fc_xpass's product (fc_pair_product); the epilogue stores the
+// (substituted) bins and adds the products of the original and of the substituted bins to the two curves' shell sums.
 __global__ __launch_bounds__(256) void k_tfsc_xpass(TfXPass g) {
-  __shared__ float as[4][FC_T][FC_K + 1];   // re1, im1, re2, im2
-  __shared__ float os[2][FC_K][FC_T + 1];   // cos, sin
   __shared__ unsigned long long sh[2 * 257 * 3];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int r = lane & 31, h = lane >> 5;
+  const Tile64 t = tile64();
   const int row0 = blockIdx.x * FC_T, col0 = blockIdx.y * FC_T;
-  const int wm = (wave >> 1) * 32, wp = (wave & 1) * 32;
   const int64_t plane = (int64_t)g.rows * g.nx;
-  const float* src[4] = {g.re, g.im, g.re + plane, g.im + plane};
+  const float* const src[4] = {g.re, g.im, g.re + plane, g.im + plane};
   const int nsh = 2 * g.nshell * 3;
-  for (int e = tid; e < nsh; e += 256) sh[e] = 0ull;
-  const bool active = col0 + wp < g.ncol && row0 + wm < g.rows;
+  for (int e = t.tid; e < nsh; e += 256) sh[e] = 0ull;
+  const bool active = col0 + t.wp < g.ncol && row0 + t.wm < g.rows;
   f32x16 re1 = {0}, im1 = {0}, re2 = {0}, im2 = {0};
-  for (int k0 = 0; k0 < g.nx; k0 += FC_K) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-      for (int e = tid; e < FC_T * FC_K; e += 256) {
-        const int mm = e / FC_K, kk = e % FC_K, row = row0 + mm, k = k0 + kk;
-        as[q][mm][kk] = (row < g.rows && k < g.nx) ? src[q][(int64_t)row * g.nx + k] : 0.f;
-      }
-    for (int e = tid; e < FC_K * FC_T; e += 256) {
-      const int kk = e / FC_T, cc = e % FC_T, k = k0 + kk, col = col0 + cc;
-      const bool in = k < g.nx && col < g.ncol;
-      os[0][kk][cc] = in ? g.cs[(int64_t)k * g.ncol + col] : 0.f;
-      os[1][kk][cc] = in ? g.sn[(int64_t)k * g.ncol + col] : 0.f;
-    }
-    __syncthreads();
-    if (active) {
-#pragma unroll
-      for (int kk = 0; kk < FC_K; kk += 2) {
-        const float c = os[0][kk + h][wp + r], s = os[1][kk + h][wp + r];
-        const float a1 = as[0][wm + r][kk + h], b1 = as[1][wm + r][kk + h];
-        const float a2 = as[2][wm + r][kk + h], b2 = as[3][wm + r][kk + h];
-        re1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, c, re1, 0, 0, 0);
-        re1 = __builtin_amdgcn_mfma_f32_32x32x2f32(b1, s, re1, 0, 0, 0);
-        im1 = __builtin_amdgcn_mfma_f32_32x32x2f32(b1, c, im1, 0, 0, 0);
-        im1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, -s, im1, 0, 0, 0);
-        re2 = __builtin_amdgcn_mfma_f32_32x32x2f32(a2, c, re2, 0, 0, 0);
-        re2 = __builtin_amdgcn_mfma_f32_32x32x2f32(b2, s, re2, 0, 0, 0);
-        im2 = __builtin_amdgcn_mfma_f32_32x32x2f32(b2, c, im2, 0, 0, 0);
-        im2 = __builtin_amdgcn_mfma_f32_32x32x2f32(a2, -s, im2, 0, 0, 0);
-      }
-    }
-    __syncthreads();
-  }
-  const double s_num = g.scale[0], s_d1 = g.scale[1], s_d2 = g.scale[2];
+  fc_pair_product(src, g.cs, g.sn, g.rows, g.nx, g.ncol, row0, col0, active, t, re1, im1, re2, im2);
+  const double scale[3] = {g.scale[0], g.scale[1], g.scale[2]};
   if (active) {
-    const int col = col0 + wp + r;
+    const int col = col0 + t.wp + t.r;
     const int hn = g.n / 2;
     const int64_t splane = (int64_t)g.rows * g.ncol;
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
-      const int row = row0 + wm + (i & 3) + 8 * (i >> 2) + 4 * h;
+      const int row = row0 + t.wm + acc_row(i, t.h);
       if (row >= g.rows || col >= g.ncol) continue;
       const int kz = row / g.n, ky = row % g.n;
       const int s = fc_shell_3d(kz, ky, col, g.n);
       const int fz = kz <= hn ? kz : g.n - kz, fy = ky <= hn ? ky : g.n - ky;
       const long long m = (long long)fz * fz + (long long)fy * fy + (long long)col * col;
       const double x1 = re1[i], y1 = im1[i], x2 = re2[i], y2 = im2[i];
-      {   // the unmasked curve: k_fc_xpass's expressions
-        const long long qn = __double2ll_rn(1.0 * (x1 * x2 + y1 * y2) * s_num);
-        const long long q1 = __double2ll_rn(1.0 * (x1 * x1 + y1 * y1) * s_d1);
-        const long long q2 = __double2ll_rn(1.0 * (x2 * x2 + y2 * y2) * s_d2);
-        if (qn != 0) atomicAdd(&sh[s * 3 + 0], (unsigned long long)qn);
-        if (q1 != 0) atomicAdd(&sh[s * 3 + 1], (unsigned long long)q1);
-        if (q2 != 0) atomicAdd(&sh[s * 3 + 2], (unsigned long long)q2);
-      }
+      fc_add_products(&sh[s * 3], 1.0, x1, y1, x2, y2, scale);   // the unmasked curve: calc_fsc's sums
       const int64_t bin = (int64_t)row * g.ncol + col;
       float u1 = re1[i], v1 = im1[i], u2 = re2[i], v2 = im2[i];
       if (m >= g.m_cut) {
@@ -170,33 +116,11 @@ __global__ __launch_bounds__(256) void k_tfsc_xpass(TfXPass g) {
       }
       g.sre[bin] = u1; g.sim[bin] = v1;
       g.sre[splane + bin] = u2; g.sim[splane + bin] = v2;
-      {   // the randomised-unmasked curve, from the bins as stored
-        const double p1 = u1, q1d = v1, p2 = u2, q2d = v2;
-        const long long qn = __double2ll_rn((p1 * p2 + q1d * q2d) * s_num);
-        const long long q1 = __double2ll_rn((p1 * p1 + q1d * q1d) * s_d1);
-        const long long q2 = __double2ll_rn((p2 * p2 + q2d * q2d) * s_d2);
-        const int o = (g.nshell + s) * 3;
-        if (qn != 0) atomicAdd(&sh[o + 0], (unsigned long long)qn);
-        if (q1 != 0) atomicAdd(&sh[o + 1], (unsigned long long)q1);
-        if (q2 != 0) atomicAdd(&sh[o + 2], (unsigned long long)q2);
-      }
+      fc_add_products(&sh[(g.nshell + s) * 3], 1.0, u1, v1, u2, v2, scale);   // the randomised-unmasked curve, from the bins as stored
     }
   }
   __syncthreads();
-  unsigned long long* const G = reinterpret_cast<unsigned long long*>(g.acc);
-  for (int e = tid; e < nsh; e += 256) {
-    const unsigned long long v = sh[e];
-    if (v != 0ull) atomicAdd(G + e, v);
-  }
-}
-
-// sums[c][s][q] = acc / scale[q] for the two curves of the one pair
-__global__ __launch_bounds__(256) void k_tfsc_finish(const long long* __restrict__ acc, const double* __restrict__ scale, int total,
-                                                     double* __restrict__ sums) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= total) return;
-  const double s = scale[i % 3];
-  sums[i] = s == 0.0 ? 0.0 : (double)acc[i] / s;
+  fc_flush(sh, nsh, g.acc, t.tid);
 }
 
 struct TfC2R {
@@ -208,34 +132,25 @@ struct TfC2R {
   int rows, nx, ncol;
 };
 
-// The last inverse pass: y[row][x] = sum_k re[row][k] cw[k][x] + im[row][k] sw[k][x].  64 rows x 64 x per workgroup, 4
-// wavefronts in 2 x 2, one 32 x 32 accumulator each; the accumulator's lane index runs along x: the stores coalesce.
+// The last inverse pass: y[row][x] = sum_k re[row][k] cw[k][x] + im[row][k] sw[k][x] on the shared tile (mfma_tile.inc), one
+// 32 x 32 accumulator per wavefront; the accumulator's lane index runs along x: the stores coalesce.
 __global__ __launch_bounds__(256) void k_tfsc_c2r(TfC2R g) {
   __shared__ float as[2][FC_T][FC_K + 1];   // re, im
   __shared__ float os[2][FC_K][FC_T + 1];   // cw, sw
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int r = lane & 31, h = lane >> 5;
+  const Tile64 t = tile64();
+  const int r = t.r, h = t.h, wm = t.wm, wp = t.wp;
   const int row0 = blockIdx.x * FC_T, col0 = blockIdx.y * FC_T;
-  const int wm = (wave >> 1) * 32, wp = (wave & 1) * 32;
   const int64_t splane = (int64_t)g.rows * g.ncol;
-  const float* src[2] = {g.re + (int64_t)blockIdx.z * splane, g.im + (int64_t)blockIdx.z * splane};
-  const float* op[2] = {g.cw, g.sw};
+  const float* const src[2] = {g.re + (int64_t)blockIdx.z * splane, g.im + (int64_t)blockIdx.z * splane};
+  const float* const op[2] = {g.cw, g.sw};
   const bool active = col0 + wp < g.nx && row0 + wm < g.rows;
   f32x16 acc = {0};
   for (int k0 = 0; k0 < g.ncol; k0 += FC_K) {
 #pragma unroll
-    for (int q = 0; q < 2; ++q) {
-      for (int e = tid; e < FC_T * FC_K; e += 256) {
-        const int mm = e / FC_K, kk = e % FC_K, row = row0 + mm, k = k0 + kk;
-        as[q][mm][kk] = (row < g.rows && k < g.ncol) ? src[q][(int64_t)row * g.ncol + k] : 0.f;
-      }
-      for (int e = tid; e < FC_K * FC_T; e += 256) {
-        const int kk = e / FC_T, cc = e % FC_T, k = k0 + kk, col = col0 + cc;
-        os[q][kk][cc] = (k < g.ncol && col < g.nx) ? op[q][(int64_t)k * g.nx + col] : 0.f;
-      }
-    }
+    for (int q = 0; q < 2; ++q) stage_rows(as[q], src[q], g.ncol, row0, g.rows, k0, g.ncol, t.tid);
+    stage_cols(os, op, g.nx, k0, g.ncol, col0, g.nx, t.tid);
     __syncthreads();
-    if (active) {
+    if (active) {   // its own step: the Re and Im products alternate within the slice (tile_mac twice would reorder the sum)
 #pragma unroll
       for (int kk = 0; kk < FC_K; kk += 2) {
         acc = __builtin_amdgcn_mfma_f32_32x32x2f32(as[0][wm + r][kk + h], os[0][kk + h][wp + r], acc, 0, 0, 0);
@@ -249,7 +164,7 @@ __global__ __launch_bounds__(256) void k_tfsc_c2r(TfC2R g) {
   float* const y = g.y + (int64_t)blockIdx.z * g.rows * g.nx;
 #pragma unroll
   for (int i = 0; i < 16; ++i) {
-    const int row = row0 + wm + (i & 3) + 8 * (i >> 2) + 4 * h;
+    const int row = row0 + wm + acc_row(i, h);
     if (row < g.rows && col < g.nx) y[(int64_t)row * g.nx + col] = acc[i];
   }
 }
@@ -267,24 +182,6 @@ __global__ __launch_bounds__(256) void k_tfsc_mask(const float* __restrict__ map
     in[(2 * j + 1) * per_map + i] = maps[2 * per_map + i] * a;
     in[(P + 2 * j + 1) * per_map + i] = maps[3 * per_map + i] * b;
   }
-}
-
-// scratch of the forward passes for `pairs` pairs (`with_in`: the input chunk too; create reads the resident maps in place)
-int tf_scratch(hh_tfsc* c, int64_t pairs, bool with_in) {
-  if (pairs <= c->cap && (!with_in || c->in)) return HH_OK;
-  pairs = std::max(pairs, c->cap);
-  c->free_scratch();
-  const size_t map_bytes = (size_t)c->per_map * sizeof(float);
-  if (with_in) HH_HIP(nullptr, hipMalloc(&c->in, 2 * (size_t)pairs * map_bytes));
-  HH_HIP(nullptr, hipMalloc(&c->p1, 4 * (size_t)pairs * map_bytes));
-  HH_HIP(nullptr, hipMalloc(&c->p2, 4 * (size_t)pairs * map_bytes));
-  const size_t n_sums = (size_t)std::max<int64_t>(pairs, 2) * c->nshell * 3;
-  HH_HIP(nullptr, hipMalloc(&c->amax, 2 * (size_t)pairs * sizeof(unsigned)));
-  HH_HIP(nullptr, hipMalloc(&c->scale, (size_t)pairs * 3 * sizeof(double)));
-  HH_HIP(nullptr, hipMalloc(&c->acc, n_sums * sizeof(long long)));
-  HH_HIP(nullptr, hipMalloc(&c->sums, n_sums * sizeof(double)));
-  c->cap = pairs;
-  return HH_OK;
 }
 
 // row-major [ncol][n] table of the c2r pass: w_k p[(k x) mod n] scale, w = 1 on k = 0 and k = n / 2, 2 elsewhere; `sine`: those
@@ -319,14 +216,13 @@ int tf_create(hh_tfsc* c, const float* map1, const float* map2, int64_t m_cut, c
     c->o_xsw = tf_c2r_table(mats, n, ncol, sn, -q, true);
   }
   const size_t map_bytes = (size_t)per_map * sizeof(float);
-  HH_HIP(nullptr, hipMalloc(&c->mats, mats.size() * sizeof(float)));
-  HH_HIP(nullptr, hipMemcpy(c->mats, mats.data(), mats.size() * sizeof(float), hipMemcpyHostToDevice));
+  FcBuffers& d = c->fc;
+  HH_HIP(nullptr, hipMalloc(&d.mats, mats.size() * sizeof(float)));
+  HH_HIP(nullptr, hipMemcpy(d.mats, mats.data(), mats.size() * sizeof(float), hipMemcpyHostToDevice));
   HH_HIP(nullptr, hipMalloc(&c->maps, 4 * map_bytes));
   HH_HIP(nullptr, hipMalloc(&c->spec, 4 * (size_t)per_spec * sizeof(float)));
   HH_HIP(nullptr, hipMalloc(&c->curves, (size_t)2 * nshell * 3 * sizeof(double)));
-  HH_HIP(nullptr, hipEventCreate(&c->ev0));
-  HH_HIP(nullptr, hipEventCreate(&c->ev1));
-  if (int rc = tf_scratch(c, 1, false)) return rc;
+  if (int rc = d.reserve(1, per_map, nshell, true, false)) return rc;   // create reads the resident maps in place
   HH_HIP(nullptr, hipMemcpy(c->maps, map1, map_bytes, hipMemcpyHostToDevice));
   HH_HIP(nullptr, hipMemcpy(c->maps + per_map, map2, map_bytes, hipMemcpyHostToDevice));
   double* d_ph = nullptr;   // the host's angles: both maps, freed below
@@ -336,32 +232,32 @@ int tf_create(hh_tfsc* c, const float* map1, const float* map2, int64_t m_cut, c
     HH_HIP(nullptr, hipMemcpy(d_ph, phases1, (size_t)per_spec * sizeof(double), hipMemcpyHostToDevice));
     HH_HIP(nullptr, hipMemcpy(d_ph + per_spec, phases2, (size_t)per_spec * sizeof(double), hipMemcpyHostToDevice));
   }
-  HH_HIP(nullptr, hipMemsetAsync(c->amax, 0, 2 * sizeof(unsigned), nullptr));
-  HH_HIP(nullptr, hipMemsetAsync(c->acc, 0, (size_t)2 * nshell * 3 * sizeof(long long), nullptr));
+  HH_HIP(nullptr, hipMemsetAsync(d.amax, 0, 2 * sizeof(unsigned), nullptr));
+  HH_HIP(nullptr, hipMemsetAsync(d.acc, 0, (size_t)2 * nshell * 3 * sizeof(long long), nullptr));
   const float *xre = nullptr, *xim = nullptr;
-  fc_passes(c->plan, c->maps, c->p1, c->p2, c->mats, c->amax, c->scale, 1, &xre, &xim);
+  fc_passes(c->plan, c->maps, d, 1, &xre, &xim);
   float* const sre = c->spec;
   float* const sim = c->spec + 2 * per_spec;
   TfXPass x{};
   x.re = xre; x.im = xim;
-  x.cs = c->mats + c->plan.o_xc; x.sn = c->mats + c->plan.o_xs;
-  x.scale = c->scale;
+  x.cs = d.mats + c->plan.o_xc; x.sn = d.mats + c->plan.o_xs;
+  x.scale = d.scale;
   x.ph1 = d_ph; x.ph2 = d_ph ? d_ph + per_spec : nullptr;
   x.sre = sre; x.sim = sim;
-  x.acc = c->acc;
+  x.acc = d.acc;
   x.seed = seed; x.m_cut = m_cut;
   x.rows = n * n; x.nx = n; x.ncol = ncol; x.n = n; x.nshell = nshell;
   hipLaunchKernelGGL(k_tfsc_xpass, dim3((unsigned)((n * n + FC_T - 1) / FC_T), (unsigned)((ncol + FC_T - 1) / FC_T), 1), dim3(256), 0, nullptr, x);
-  hipLaunchKernelGGL(k_tfsc_finish, dim3((unsigned)((2 * nshell * 3 + 255) / 256)), dim3(256), 0, nullptr, c->acc, c->scale, 2 * nshell * 3,
-                     c->curves);
+  hipLaunchKernelGGL(k_fc_finish, dim3((unsigned)((2 * nshell * 3 + 255) / 256)), dim3(256), 0, nullptr, d.acc, d.scale, nshell, 2,
+                     (int64_t)2 * nshell * 3, c->curves);   // the two curves share the one pair's scales
   // inverse: z pass (one map per grid.z, P = n ncol), y pass (one z slice per grid.z, P = ncol), both K = 2 n over [re; im]
-  float* const zr = c->p1;
-  float* const zi = c->p1 + 2 * per_spec;
-  float* const yr = c->p2;
-  float* const yi = c->p2 + 2 * per_spec;
+  float* const zr = d.p1;
+  float* const zi = d.p1 + 2 * per_spec;
+  float* const yr = d.p2;
+  float* const yi = d.p2 + 2 * per_spec;
   for (int part = 0; part < 2; ++part) {
     CircPass g{};
-    g.a = c->mats + (part == 0 ? c->o_izr : c->o_izi);
+    g.a = d.mats + (part == 0 ? c->o_izr : c->o_izi);
     g.b0 = sre; g.b1 = sim;
     g.y = part == 0 ? zr : zi;
     g.n = n; g.ka = 2 * n;
@@ -370,7 +266,7 @@ int tf_create(hh_tfsc* c, const float* map1, const float* map2, int64_t m_cut, c
   }
   for (int part = 0; part < 2; ++part) {
     CircPass g{};
-    g.a = c->mats + (part == 0 ? c->o_iyr : c->o_iyi);
+    g.a = d.mats + (part == 0 ? c->o_iyr : c->o_iyi);
     g.b0 = zr; g.b1 = zi;
     g.y = part == 0 ? yr : yi;
     g.n = n; g.ka = 2 * n;
@@ -380,7 +276,7 @@ int tf_create(hh_tfsc* c, const float* map1, const float* map2, int64_t m_cut, c
   }
   TfC2R r{};
   r.re = yr; r.im = yi;
-  r.cw = c->mats + c->o_xcw; r.sw = c->mats + c->o_xsw;
+  r.cw = d.mats + c->o_xcw; r.sw = d.mats + c->o_xsw;
   r.y = c->maps + 2 * per_map;
   r.rows = n * n; r.nx = n; r.ncol = ncol;
   hipLaunchKernelGGL(k_tfsc_c2r, dim3((unsigned)((n * n + FC_T - 1) / FC_T), (unsigned)((n + FC_T - 1) / FC_T), 2), dim3(256), 0, nullptr, r);
@@ -449,7 +345,8 @@ extern "C" int hh_tfsc_masked(hh_tfsc* ctx, const float* masks1, const float* ma
   int64_t chunk = std::max<int64_t>(1, FC_SCRATCH_BYTES / (20 * per_map * (int64_t)sizeof(float)));
   chunk = std::min<int64_t>(chunk, 65535 / (4 * c->n));
   chunk = std::min<int64_t>(chunk, batch);
-  if (int rc = tf_scratch(c, 2 * chunk, true)) return rc;
+  FcBuffers& d = c->fc;
+  if (int rc = d.reserve(2 * chunk, per_map, nshell, true, true)) return rc;
   const int n_sets = masks2 ? 2 : 1;
   if (c->cap_masks < n_sets * chunk) {
     (void)hipFree(c->masks);
@@ -464,15 +361,15 @@ extern "C" int hh_tfsc_masked(hh_tfsc* ctx, const float* masks1, const float* ma
     float* const d_m2 = masks2 ? c->masks + nb * per_map : nullptr;
     HH_HIP(nullptr, hipMemcpy(d_m1, masks1 + b0 * per_map, (size_t)nb * per_map * sizeof(float), hipMemcpyHostToDevice));
     if (masks2) HH_HIP(nullptr, hipMemcpy(d_m2, masks2 + b0 * per_map, (size_t)nb * per_map * sizeof(float), hipMemcpyHostToDevice));
-    HH_HIP(nullptr, hipEventRecord(c->ev0, nullptr));
+    HH_HIP(nullptr, hipEventRecord(d.ev0, nullptr));
     hipLaunchKernelGGL(k_tfsc_mask, dim3((unsigned)std::min<int64_t>((per_map + 255) / 256, 4096), (unsigned)nb), dim3(256), 0, nullptr, c->maps, d_m1,
-                       d_m2, per_map, (int)nb, c->in);
-    fc_device(c->plan, c->in, c->p1, c->p2, c->mats, nullptr, c->amax, c->scale, c->acc, c->sums, 2 * nb, nshell, full_spectrum != 0);
+                       d_m2, per_map, (int)nb, d.in);
+    fc_device(c->plan, d.in, d, 2 * nb, nshell, full_spectrum != 0);
     HH_HIP(nullptr, hipGetLastError());
-    HH_HIP(nullptr, hipEventRecord(c->ev1, nullptr));
-    HH_HIP(nullptr, hipMemcpy(sums + b0 * 2 * nshell * 3, c->sums, (size_t)(2 * nb) * nshell * 3 * sizeof(double), hipMemcpyDeviceToHost));
+    HH_HIP(nullptr, hipEventRecord(d.ev1, nullptr));
+    HH_HIP(nullptr, hipMemcpy(sums + b0 * 2 * nshell * 3, d.sums, (size_t)(2 * nb) * nshell * 3 * sizeof(double), hipMemcpyDeviceToHost));
     float ms = 0.f;
-    HH_HIP(nullptr, hipEventElapsedTime(&ms, c->ev0, c->ev1));
+    HH_HIP(nullptr, hipEventElapsedTime(&ms, d.ev0, d.ev1));
     ms_total += ms;
   }
   if (kernel_ms) *kernel_ms = ms_total;

@@ -7,7 +7,7 @@
 // over the lattice centres c whose footprint meets the image: one complex [ony x C] . [C x onx] product per candidate.
 // k_zoom_sweep does all of it for one output tile of one candidate: lattice centres with the sweep's own device code
 // (decode_candidate / centre_position), the raster's window tests, the factors by Horner's rule over a footprint's taps,
-// the product on the exact-f32 MFMA (32x32x2, K staged through LDS: the layout of k_circ_gemm, four real products for
+// the product on the exact-f32 MFMA (32x32x2, K staged through LDS in mfma_tile.inc's layout, four real products for
 // the complex one), and the epilogue |F| -> log1p -> masked moments fused, so F never leaves the registers.  The
 // reference side is k_zoom_rows / k_zoom_cols on the device plus k_zoom_weights ({w, w (E - Ebar)} per segment).
 // With a spectrum filter set (hh_set_spectrum_filter, at the end of this file) the kernel's other epilogue stores q instead
@@ -132,21 +132,33 @@ __device__ __forceinline__ float2 zoom_factor(double f, float2 w, int p0, int le
   return make_float2(sr * cs - si * sn, sr * sn + si * cs);
 }
 
-template <int LOG, bool LDSP, bool QS>
-__global__ __launch_bounds__(ZS_THREADS) void k_zoom_sweep(ZoomSweepArgs a) {
-  extern __shared__ __align__(16) unsigned char zoom_lds_raw[];
-  ZoomLds& L = *reinterpret_cast<ZoomLds*>(zoom_lds_raw);
+// A lane's place in k_zoom_sweep's tile: 4 x 2 wavefronts of 32 x 64 (two 32 x 32 accumulator columns t = 0, 1), r and h as
+// in mfma_tile.inc, the tile's origin (u0, v0) on the plane.
+struct ZoomTile {
+  int tid, lane, wave, r, h, wu, wv, u0, v0;
+};
+__device__ __forceinline__ ZoomTile zoom_tile(const ZoomSweepArgs& a) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int r = lane & 31, h = lane >> 5;
-  const int wu = wave & 3, wv = wave >> 2;   // 4 x 2 wavefronts of 32 x 64
-  const int b = blockIdx.y, n_tiles = gridDim.x, batch = gridDim.y;
   const int tile = a.tiles[blockIdx.x];
-  const int u0 = (tile / a.tiles_v) * ZS_TU, v0 = (tile % a.tiles_v) * ZS_TV;
+  return {tid, lane, wave, lane & 31, lane >> 5, wave & 3, wave >> 2, (tile / a.tiles_v) * ZS_TU, (tile % a.tiles_v) * ZS_TV};
+}
+// row u and column v of accumulator register i of column block t
+__device__ __forceinline__ int zoom_u(const ZoomTile& z, int i) { return z.u0 + z.wu * 32 + acc_row(i, z.h); }
+__device__ __forceinline__ int zoom_v(const ZoomTile& z, int t) { return z.v0 + z.wv * 64 + t * 32 + z.r; }
+
+// The product of one output tile of candidate blockIdx.y, up to the accumulators: the lane's two frequencies, the walk of
+// the lattice and, per K slice of centres, profiles, Horner factors, staging and the MFMA steps, into the caller's N
+// accumulators per column block, out[n][t].  step(acc, ar, ai, br, bi, t) accumulates one step of column block t from the
+// operands (ar + i ai) = Gy, (br + i bi) = Gx: the caller decides which real products it keeps apart.  The walk runs on
+// accumulators of its own, zeroed after the set-up and handed over at the end, so that none is live across the set-up.
+template <bool LDSP, int N, class Step>
+__device__ __forceinline__ void zoom_product(const ZoomSweepArgs& a, ZoomLds& L, const ZoomTile& z, f32x16 (&out)[N][2], Step step) {
+  const int tid = z.tid, lane = z.lane, wave = z.wave, r = z.r, h = z.h, wu = z.wu, wv = z.wv, u0 = z.u0, v0 = z.v0;
   const DevGeom& g = a.g;
   const int ny = a.d.ny, nx = a.d.nx, ony = a.d.ony, onx = a.d.onx;
   const float rp = (float)g.rpx;
   const float k2 = g.inv_sigma2 * 1.44269504088896341f;
-  const Cand c = decode_candidate(a.params + 4 * (size_t)b, g);
+  const Cand c = decode_candidate(a.params + 4 * (size_t)blockIdx.y, g);
 
   // the two frequencies this lane builds factors for, and their unit steps w = e^{-2 pi i f}
   const int ul = tid & (ZS_TU - 1), vl = tid & (ZS_TV - 1);
@@ -162,7 +174,9 @@ __global__ __launch_bounds__(ZS_THREADS) void k_zoom_sweep(ZoomSweepArgs a) {
     wx = make_float2((float)cs, (float)sn);
   }
 
-  f32x16 acc_re[2] = {{0}, {0}}, acc_im[2] = {{0}, {0}};
+  f32x16 acc[N][2];
+#pragma unroll
+  for (int n = 0; n < N; ++n) acc[n][0] = acc[n][1] = f32x16{0};
 
   // one K slice: list entries [s0, s0 + cnt), cnt <= ZS_K (the rest of the slice is zero)
   auto slice = [&](int s0, int cnt) __attribute__((always_inline)) {
@@ -195,13 +209,7 @@ __global__ __launch_bounds__(ZS_THREADS) void k_zoom_sweep(ZoomSweepArgs a) {
     for (int kk = 0; kk < ZS_K; kk += 2) {
       const float ar = L.as_re[wu * 32 + r][kk + h], ai = L.as_im[wu * 32 + r][kk + h];
 #pragma unroll
-      for (int t = 0; t < 2; ++t) {
-        const float br = L.bs_re[kk + h][wv * 64 + t * 32 + r], bi = L.bs_im[kk + h][wv * 64 + t * 32 + r];
-        acc_re[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(ar, br, acc_re[t], 0, 0, 0);
-        acc_re[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(-ai, bi, acc_re[t], 0, 0, 0);
-        acc_im[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(ar, bi, acc_im[t], 0, 0, 0);
-        acc_im[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(ai, br, acc_im[t], 0, 0, 0);
-      }
+      for (int t = 0; t < 2; ++t) step(acc, ar, ai, L.bs_re[kk + h][wv * 64 + t * 32 + r], L.bs_im[kk + h][wv * 64 + t * 32 + r], t);
     }
     __syncthreads();
   };
@@ -262,6 +270,30 @@ __global__ __launch_bounds__(ZS_THREADS) void k_zoom_sweep(ZoomSweepArgs a) {
     }
     __syncthreads();
   }
+#pragma unroll
+  for (int n = 0; n < N; ++n) {
+    out[n][0] = acc[n][0];
+    out[n][1] = acc[n][1];
+  }
+}
+
+template <int LOG, bool LDSP, bool QS>
+__global__ __launch_bounds__(ZS_THREADS) void k_zoom_sweep(ZoomSweepArgs a) {
+  extern __shared__ __align__(16) unsigned char zoom_lds_raw[];
+  ZoomLds& L = *reinterpret_cast<ZoomLds*>(zoom_lds_raw);
+  const ZoomTile z = zoom_tile(a);
+  const int b = blockIdx.y, n_tiles = gridDim.x, batch = gridDim.y;
+  const int ony = a.d.ony, onx = a.d.onx;
+
+  // F = sum_c Gy_c Gx_c: Re and Im, two accumulators per column block (the -ai operand folds the subtraction in)
+  f32x16 acc[2][2];
+  zoom_product<LDSP>(a, L, z, acc, [](f32x16 (&p)[2][2], float ar, float ai, float br, float bi, int t) __attribute__((always_inline)) {
+    p[0][t] = __builtin_amdgcn_mfma_f32_32x32x2f32(ar, br, p[0][t], 0, 0, 0);
+    p[0][t] = __builtin_amdgcn_mfma_f32_32x32x2f32(-ai, bi, p[0][t], 0, 0, 0);
+    p[1][t] = __builtin_amdgcn_mfma_f32_32x32x2f32(ar, bi, p[1][t], 0, 0, 0);
+    p[1][t] = __builtin_amdgcn_mfma_f32_32x32x2f32(ai, br, p[1][t], 0, 0, 0);
+  });
+  const auto &acc_re = acc[0], &acc_im = acc[1];
 
   const size_t plane = (size_t)ony * onx;
   if constexpr (QS) {   // the q-storing epilogue: the tile of q itself, for the filter passes (filtered_sweep.inc)
@@ -270,8 +302,7 @@ __global__ __launch_bounds__(ZS_THREADS) void k_zoom_sweep(ZoomSweepArgs a) {
     for (int t = 0; t < 2; ++t)
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
-        const int u = u0 + wu * 32 + (i & 3) + 8 * (i >> 2) + 4 * h;
-        const int v = v0 + wv * 64 + t * 32 + r;
+        const int u = zoom_u(z, i), v = zoom_v(z, t);
         if (u < ony && v < onx) qb[(size_t)u * onx + v] = amp_to_q<LOG>(make_float2(acc_re[t][i], acc_im[t][i]));
       }
     return;
@@ -284,8 +315,7 @@ __global__ __launch_bounds__(ZS_THREADS) void k_zoom_sweep(ZoomSweepArgs a) {
     for (int t = 0; t < 2; ++t)
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
-        const int u = u0 + wu * 32 + (i & 3) + 8 * (i >> 2) + 4 * h;   // 32x32 C/D map: column = lane & 31
-        const int v = v0 + wv * 64 + t * 32 + r;
+        const int u = zoom_u(z, i), v = zoom_v(z, t);
         if (u < ony && v < onx) {
           const size_t at = (size_t)u * onx + v;
           const float wt = a.w[at];
@@ -297,25 +327,8 @@ __global__ __launch_bounds__(ZS_THREADS) void k_zoom_sweep(ZoomSweepArgs a) {
           }
         }
       }
-    double s1 = f1, s2 = f2, s3 = f3;
-    for (int o = 32; o > 0; o >>= 1) {
-      s1 += __shfl_down(s1, o, 64);
-      s2 += __shfl_down(s2, o, 64);
-      s3 += __shfl_down(s3, o, 64);
-    }
-    if (lane == 0) {
-      L.red[wave][0] = s1;
-      L.red[wave][1] = s2;
-      L.red[wave][2] = s3;
-    }
-    __syncthreads();
-    if (tid < 3) {
-      double* const out = a.partials + (((size_t)s * batch + b) * n_tiles + blockIdx.x) * 3;
-      double sum = 0;
-      for (int w = 0; w < ZS_WAVES; ++w) sum += L.red[w][tid];   // fixed order
-      out[tid] = sum;
-    }
-    __syncthreads();
+    double sum[3] = {f1, f2, f3};
+    block_sums(sum, L.red, z.tid, a.partials + (((size_t)s * batch + b) * n_tiles + blockIdx.x) * 3);
   }
 }
 
