@@ -16,6 +16,7 @@ from .symmetry_search import SymmetrySearch, helical_symmetry_search
 from .fsc import (calc_frc_2d, calc_fsc, calc_fsc_batch, calc_fsc_per_shell, frc_score, fsc_resolution, half_map_fsc,
                   half_map_fsc_batch)
 # the function true_fsc.true_fsc is not re-exported under its own name: that would hide the module helicon_amd.true_fsc
-from .true_fsc import TrueFSC, distance_transform_edt_sq, randomize_phases_lowpass, soft_mask_device
+from .true_fsc import (TrueFSC, adaptive_mask_device, distance_transform_edt_sq, gaussian_filter_device, gaussian_taps, label_components,
+                       otsu_from_counts, randomize_phases_lowpass, soft_mask_device)
 
 __version__ = "0.1.0"

@@ -191,6 +191,15 @@ EXPORTS = {
     "hh_tfsm_set_support": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8)]),
     "hh_tfsm_soft_mask": (C.c_int, [C.c_void_p, C.c_int, C.c_double, _f32p]),
     "hh_tfsm_soft_masked": (C.c_int, [C.c_void_p, _f64p, C.c_int32, C.c_int, _f64p, _f64p]),
+    # the adaptive mask built on the device (helicon_amd/true_fsc.py, csrc/adaptive_mask.inc)
+    "hh_am_otsu": (C.c_int, [C.POINTER(C.c_int64), C.c_double, C.c_double, _f64p, _f64p]),
+    "hh_am_stage_ms": (C.c_int, [_f64p, C.c_int]),
+    "hh_am_gaussian_3d": (C.c_int, [C.c_int, _f64p, C.c_int32, C.c_int32, C.c_int32, C.c_double, _f64p, _f64p]),
+    "hh_am_label_3d": (C.c_int, [C.c_int, C.POINTER(C.c_uint8), C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
+    "hh_am_mask_3d": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int32, C.c_int32, C.c_int32, C.c_double, _f64p, C.c_int, C.c_double,
+                                C.POINTER(C.c_uint8), _f64p]),
+    "hh_am_context_support": (C.c_int, [C.c_void_p, C.c_int, C.c_double, _f64p, C.c_int, C.c_double, _f64p]),
+    "hh_am_context_get_support": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_uint8)]),
 }
 
 _lib = None

@@ -43,9 +43,30 @@ Soft masks on the device (csrc/soft_mask.inc): ``soft_mask``'s definition with i
 ``true_fsc(..., device_masks=True)``
     the soft edge and every trial of ``refine_mask`` on the device; ``adaptive_mask`` stays on the host.
 
+Adaptive masks on the device (csrc/adaptive_mask.inc): ``adaptive_mask``'s definition from the volume in float64 (a float32
+volume is widened exactly).  One deviation: ``np.argpartition`` keeps an arbitrary 1000 of the voxels tied at the 1000th
+largest value ``v*``; the device takes every voxel ``>= v*`` as a seed.  Fewer than 1000 voxels, a NaN or infinite voxel and
+a constant volume in Otsu mode raise ``ValueError``.
+
+``gaussian_taps(sigma)``
+    the half kernel ``w[0 ... r]`` of ``scipy.ndimage.gaussian_filter``, ``r = int(4 sigma + 0.5)``, by SciPy's NumPy expression.
+``gaussian_filter_device(volume, sigma)``
+    ``gaussian_filter(volume.astype(float64), sigma)`` (mode ``reflect``): the same taps, passes z, y, x, unfused float64.
+``label_components(binary)``
+    ``scipy.ndimage.label(binary, structure=np.ones((3, 3, 3)))``: ``(labels, n)``, numbered in order of first occurrence.
+``otsu_from_counts(counts, hmin, hmax)``
+    ``otsu_threshold_eman`` from the histogram on.
+``adaptive_mask_device(volume, apix, cutoff_res, ...)``
+    the mask as uint8 0 / 1; ``info=True`` adds the threshold, ``v*`` and the counts.
+``TrueFSC.adaptive_support`` / ``.support``
+    the support(s) built from the context's resident maps, left where ``set_support`` leaves them, and downloaded.
+``true_fsc(..., device_masks=True, device_support=True)``
+    nothing of the masks runs on the host: ``host_mask_s`` is 0.  The maps must be exactly representable in float32 (the
+    context holds float32; the host path filters the caller's float64).
+
     python -m helicon_amd.true_fsc half1.mrc half2.mrc [--apix A] [--mask M [M2]] [--one-mask] [--cutoff-res R]
         [--mask-soft W] [--refine-mask] [--mask-fraction-thresh F | --mask-thresh T | --mask-mass KDA] [--seed S]
-        [--out-prefix P] [--device 0] [--device-masks]
+        [--out-prefix P] [--device 0] [--device-masks [--device-support]]
 
 prints a JSON report and, with ``--out-prefix``, writes ``P.unmasked.txt``, ``P.randomized-unmasked.txt``, ``P.masked.txt``,
 ``P.randomized-masked.txt``, ``P.true.txt``, ``P.true.fit.txt`` (the reference's six text files) and the mask(s).
@@ -64,12 +85,15 @@ from . import _lib
 from .fsc import _f32, _fsc_rows, _ratio, _read_map, calc_fsc, fsc_resolution
 
 __all__ = ["randomize_phases_lowpass", "TrueFSC", "true_fsc", "cutoff_m", "choose_cutoff", "soft_mask", "adaptive_mask",
-           "otsu_threshold_eman", "fit_fsc_curve", "distance_transform_edt_sq", "soft_mask_device", "soft_step", "zoom_taps", "main"]
+           "otsu_threshold_eman", "fit_fsc_curve", "distance_transform_edt_sq", "soft_mask_device", "soft_step", "zoom_taps",
+           "gaussian_taps", "gaussian_filter_device", "label_components", "otsu_from_counts", "adaptive_mask_device", "adaptive_stage_ms", "main"]
 
 _MIN_SIDE, _MAX_SIDE = 8, 512
 _f32p, _f64p = C.POINTER(C.c_float), C.POINTER(C.c_double)
 _u8p, _i32p = C.POINTER(C.c_uint8), C.POINTER(C.c_int32)
 _MAX_BOX = 1024
+_i64p = C.POINTER(C.c_int64)
+_MAX_VOXELS, _MAX_RADIUS, _N_SEEDS = 2**28, 4096, 1000
 
 
 # ------------------------------------------------------------------------------------------
@@ -327,6 +351,153 @@ def soft_mask_device(mask, soft_width, *, device=0):
 
 
 # ------------------------------------------------------------------------------------------
+# adaptive masks (device)
+# ------------------------------------------------------------------------------------------
+def gaussian_taps(sigma):
+    """``w[0 ... r]``, ``r = int(4 sigma + 0.5)``: the half of ``scipy.ndimage``'s Gaussian kernel from its centre, computed by
+    SciPy's own NumPy expression (``exp(-0.5 / sigma^2 x^2)`` over ``x = -r ... r``, divided by its sum), in float64."""
+    sigma = float(sigma)
+    if not (math.isfinite(sigma) and sigma > 0):
+        raise ValueError(f"gaussian_taps: sigma must be positive and finite; got {sigma}")
+    if 4.0 * sigma + 0.5 >= _MAX_RADIUS + 1:
+        raise ValueError(f"gaussian_taps: int(4 sigma + 0.5) must not exceed {_MAX_RADIUS}; got sigma = {sigma}")
+    r = int(4.0 * sigma + 0.5)
+    x = np.arange(-r, r + 1)
+    phi = np.exp(-0.5 / (sigma * sigma) * x ** 2)
+    phi = phi / phi.sum()
+    return np.ascontiguousarray(phi[r:])
+
+
+def _volume(volume, name, min_voxels=1):
+    """(contiguous float32 or float64 array, is_f64) of a finite 3-D volume within the library's limits."""
+    v = np.asarray(volume)
+    if v.ndim != 3 or min(v.shape, default=0) < 1 or max(v.shape) > _MAX_BOX:
+        raise ValueError(f"{name}: a 3-D volume with sides in [1, {_MAX_BOX}] is needed; got {v.shape}")
+    if v.size > _MAX_VOXELS:
+        raise ValueError(f"{name}: at most 2^28 voxels; got {v.size}")
+    if v.size < min_voxels:
+        raise ValueError(f"{name}: at least {min_voxels} voxels are needed (the seeds are the {_N_SEEDS} brightest); got {v.size}")
+    v = np.ascontiguousarray(v, dtype=np.float32 if v.dtype == np.float32 else np.float64)
+    if not np.isfinite(v).all():
+        raise ValueError(f"{name}: the volume holds NaN or infinite values")
+    return v, v.dtype == np.float64
+
+
+def gaussian_filter_device(volume, sigma, *, device=0):
+    """``scipy.ndimage.gaussian_filter(volume.astype(float64), sigma)`` (mode ``reflect``, truncate 4) on the device, float64:
+    SciPy's taps (``gaussian_taps``), its passes z, y, x and its order of operations, products and sums unfused."""
+    v, _ = _volume(volume, "gaussian_filter_device")
+    v = np.ascontiguousarray(v, dtype=np.float64)
+    taps = gaussian_taps(sigma)
+    out = np.empty_like(v)
+    nz, ny, nx = v.shape
+    _lib.check(_lib.lib().hh_am_gaussian_3d(int(device), v.ctypes.data_as(_f64p), nz, ny, nx, float(sigma), taps.ctypes.data_as(_f64p),
+                                            out.ctypes.data_as(_f64p)), None)
+    return out
+
+
+def label_components(binary, *, device=0):
+    """``scipy.ndimage.label(binary, structure=np.ones((3, 3, 3)))`` on the device: ``(labels, n)``, int32 labels 1 ... n in the
+    order of each component's first voxel (its root, the smallest flat index), 0 on background."""
+    sup = _support(binary, "label_components")
+    roots = np.empty(sup.shape, dtype=np.int32)
+    n = C.c_int64(0)
+    nz, ny, nx = sup.shape
+    _lib.check(_lib.lib().hh_am_label_3d(int(device), sup.ctypes.data_as(_u8p), nz, ny, nx, roots.ctypes.data_as(_i32p), C.byref(n)), None)
+    flat = roots.ravel()
+    ids = np.flatnonzero(flat == np.arange(flat.size))      # the roots, ascending
+    if len(ids) != n.value:
+        raise _lib.HeliconHipError(f"label_components: {len(ids)} roots in the array, {n.value} counted on the device")
+    labels = np.zeros(flat.size, dtype=np.int32)
+    inside = flat >= 0
+    labels[inside] = np.searchsorted(ids, flat[inside]) + 1
+    return labels.reshape(sup.shape), int(n.value)
+
+
+def otsu_from_counts(counts, hmin, hmax):
+    """``otsu_threshold_eman`` from its histogram on: the threshold from 256 counts over ``[hmin, hmax]``."""
+    hist = np.asarray(counts).astype(np.float64)
+    n_bins = len(hist)
+    hmin, hmax = float(hmin), float(hmax)
+    bin_width = (hmax - hmin) / n_bins
+    total = hist.sum()
+    if total == 0:
+        return hmin
+    sum_all = np.dot(np.arange(n_bins, dtype=np.float64), hist)
+    cumsum = np.cumsum(hist)
+    cumsum_val = np.cumsum(np.arange(n_bins, dtype=np.float64) * hist)
+    w_b, w_f = cumsum, total - cumsum
+    m_b, m_f = np.zeros(n_bins), np.zeros(n_bins)
+    valid = (w_b > 0) & (w_f > 0)
+    m_b[valid] = cumsum_val[valid] / w_b[valid]
+    m_f[valid] = (sum_all - cumsum_val[valid]) / w_f[valid]
+    between = w_b * w_f * (m_b - m_f) ** 2
+    max_bi = np.argmax(between[1:]) + 1
+    return hmin + (max_bi + 1) * bin_width
+
+
+_STAGES = ("gauss_z", "gauss_y", "gauss_x", "statistics", "runs", "unions", "flatten", "pick")
+
+
+def adaptive_stage_ms(reset=True):
+    """Device-event milliseconds the mask calls (``adaptive_mask_device``, ``TrueFSC.adaptive_support``) spent per stage since
+    the last reset: the three Gaussian passes, the statistics (minimum, maximum, histogram, selections), runs, unions,
+    flatten, and the pick of the seeded components."""
+    ms = np.zeros(8, dtype=np.float64)
+    _lib.check(_lib.lib().hh_am_stage_ms(ms.ctypes.data_as(_f64p), 1 if reset else 0), None)
+    return dict(zip(_STAGES, (float(v) for v in ms)))
+
+
+_INFO_KEYS = ("threshold", "min", "max", "v_star", "above", "kept", "components")
+
+
+def _mask_mode(n_voxels, apix, cutoff_res, mask_fraction_thresh, mask_thresh, mask_mass, name):
+    """(sigma, taps or None, mode, value) of ``adaptive_mask``'s arguments, in its order of precedence."""
+    apix, cutoff_res = float(apix), float(cutoff_res)
+    if not (math.isfinite(apix) and apix > 0 and math.isfinite(cutoff_res)):
+        raise ValueError(f"{name}: apix must be positive and the cutoff finite; got {apix}, {cutoff_res}")
+    sigma = cutoff_res / (3.81 * apix) if cutoff_res > 2 * apix else 0.0
+    taps = gaussian_taps(sigma) if sigma else None
+    if mask_fraction_thresh > 0:
+        mode, value = 1, float(mask_fraction_thresh)
+    elif mask_thresh and mask_thresh > 0:
+        mode, value = 2, float(mask_thresh)
+    elif mask_mass > 0:
+        mode, value = 3, float(min(int(mask_mass * 1e3 / (0.81 * apix**3)), n_voxels - 1))
+    else:
+        mode, value = 0, 0.0
+    if not math.isfinite(value):
+        raise ValueError(f"{name}: the threshold argument is NaN or infinite")
+    return sigma, taps, mode, value
+
+
+def _info(row):
+    out = {k: (float(v) if k in ("threshold", "min", "max", "v_star") else int(v)) for k, v in zip(_INFO_KEYS, row)}
+    out["fallback"] = bool(int(row[7]) & 1)
+    out["ties_at_v_star"] = bool(int(row[7]) & 2)
+    return out
+
+
+def adaptive_mask_device(volume, apix, cutoff_res, mask_fraction_thresh=0, mask_thresh=0, mask_mass=0, *, device=0, info=False):
+    """``adaptive_mask(volume.astype(float64), ...)`` on the device, uint8 0 / 1: the float64 Gaussian, the threshold (a
+    fraction of the maximum, a value, the mass, or Otsu's on ``np.linspace``'s edges), the 26-connected components of the
+    voxels above it that hold a seed; without such a component, every voxel above it.  Seeds: EVERY voxel ``>= v*``, the
+    1000th largest value.  ``info=True``: ``(mask, dict)`` with ``threshold``, ``min``, ``max``, ``v_star``, ``above``, ``kept``,
+    ``components``, ``fallback``, ``ties_at_v_star``."""
+    v, is_f64 = _volume(volume, "adaptive_mask_device", _N_SEEDS)
+    sigma, taps, mode, value = _mask_mode(v.size, apix, cutoff_res, mask_fraction_thresh, mask_thresh, mask_mass, "adaptive_mask_device")
+    if mode == 0 and v.min() == v.max():
+        raise ValueError("adaptive_mask_device: a constant volume has no Otsu threshold")
+    out = np.empty(v.shape, dtype=np.uint8)
+    row = np.zeros(8, dtype=np.float64)
+    nz, ny, nx = v.shape
+    _lib.check(_lib.lib().hh_am_mask_3d(int(device), v.ctypes.data_as(C.c_void_p), 1 if is_f64 else 0, nz, ny, nx, sigma,
+                                        taps.ctypes.data_as(_f64p) if taps is not None else None, mode, value, out.ctypes.data_as(_u8p),
+                                        row.ctypes.data_as(_f64p)), None)
+    return (out, _info(row)) if info else out
+
+
+# ------------------------------------------------------------------------------------------
 # the resident context
 # ------------------------------------------------------------------------------------------
 def _cube(a, name):
@@ -384,6 +555,17 @@ class _Context:
 
     def set_support(self, sup1, sup2):
         _lib.check(_lib.lib().hh_tfsm_set_support(self._h, sup1.ctypes.data_as(_u8p), sup2.ctypes.data_as(_u8p) if sup2 is not None else None), None)
+
+    def adaptive_support(self, one_mask, sigma, taps, mode, value):
+        info = np.zeros((2, 8), dtype=np.float64)
+        _lib.check(_lib.lib().hh_am_context_support(self._h, 1 if one_mask else 0, float(sigma), taps.ctypes.data_as(_f64p) if taps is not None else None,
+                                                    int(mode), float(value), info.ctypes.data_as(_f64p)), None)
+        return info
+
+    def get_support(self, which):
+        out = np.empty((self.n,) * 3, dtype=np.uint8)
+        _lib.check(_lib.lib().hh_am_context_get_support(self._h, int(which), out.ctypes.data_as(_u8p)), None)
+        return out
 
     def soft_mask(self, which, width):
         out = np.empty((self.n,) * 3, dtype=np.float32)
@@ -536,6 +718,29 @@ class TrueFSC:
         self._supports = [s1] if s2 is None else [s1, s2]
         self._ctx.set_support(s1, s2)
 
+    # ---- adaptive supports built on the device from the resident maps (csrc/adaptive_mask.inc)
+    def adaptive_support(self, one_mask=False, mask_fraction_thresh=0, mask_thresh=0, mask_mass=0):
+        """Build the support(s) on the device from the resident maps, as ``adaptive_mask`` defines them at this context's
+        ``apix`` and ``cutoff_res`` (every voxel tied at the 1000th largest value is a seed): of the two maps' average for both
+        members (``one_mask``), or one of each map.  They stay where ``set_support`` leaves them.  Returns the ``info`` dicts."""
+        if self.n**3 < _N_SEEDS:
+            raise ValueError(f"TrueFSC.adaptive_support: at least {_N_SEEDS} voxels are needed; the maps have {self.n**3}")
+        sigma, taps, mode, value = _mask_mode(self.n**3, self.apix, self.cutoff_res, mask_fraction_thresh, mask_thresh, mask_mass,
+                                              "TrueFSC.adaptive_support")
+        self._supports = None                                    # a build that fails leaves no support behind
+        rows = self._ctx.adaptive_support(bool(one_mask), sigma, taps, mode, value)
+        self._supports = [self._ctx.get_support(k) for k in range(1 if one_mask else 2)]
+        self.support_info = [_info(r) for r in rows[: len(self._supports)]]
+        return self.support_info
+
+    def support(self, which=0):
+        """The support of member ``which`` (0 / 1) as it lies on the device: uint8 0 / 1."""
+        if which not in (0, 1):
+            raise ValueError(f"TrueFSC.support: which must be 0 or 1; got {which}")
+        if not getattr(self, "_supports", None):
+            raise ValueError("TrueFSC.support: no support is set (TrueFSC.set_support, TrueFSC.adaptive_support)")
+        return self._ctx.get_support(which)
+
     def _widths(self, widths, name):
         if not getattr(self, "_supports", None):
             raise ValueError(f"{name}: no support is set (TrueFSC.set_support)")
@@ -602,7 +807,7 @@ def refine_score(fsc_t, fsc_n, cutoff_i):
 # the composition of trueFSC.py:main
 # ------------------------------------------------------------------------------------------
 def true_fsc(map1, map2, apix, *, mask=None, one_mask=False, cutoff_res=0, mask_soft=0, refine_mask=False, mask_fraction_thresh=0,
-             mask_thresh=0, mask_mass=0, seed=None, phases=None, device=0, context=None, device_masks=False):
+             mask_thresh=0, mask_mass=0, seed=None, phases=None, device=0, context=None, device_masks=False, device_support=False):
     """trueFSC.py:102-366.  ``mask``: one mask or a pair, used as given (a pair is averaged with ``one_mask``); without one, the
     adaptive mask of each map (of the maps' average with ``one_mask``) with a soft edge of ``mask_soft`` Angstrom, or of the
     width ``refine_mask`` finds (``minimize_scalar``, bounded to ``(0, n / 3)`` pixels, ``xatol=2``, every evaluation one
@@ -614,6 +819,10 @@ def true_fsc(map1, map2, apix, *, mask=None, one_mask=False, cutoff_res=0, mask_
     the device's masks, downloaded (float32); ``host_mask_s`` then counts ``adaptive_mask`` alone.  Refused with ``mask=``:
     a given mask is used as it is, there is no support to soften.
 
+    ``device_support`` (needs ``device_masks``): the adaptive supports are built on the device from the context's resident
+    maps (``adaptive_support``) instead of ``adaptive_mask`` + ``set_support``; ``host_mask_s`` is then 0.0.  The maps must be
+    exactly representable in float32, because the context holds float32 while the host path filters the caller's float64.
+
     Returns a dict: ``unmasked``, ``randomized_unmasked``, ``masked``, ``randomized_masked``, ``true`` (``[saxis, fsc]``
     rows), ``true_fit`` (500 rows), ``resolution`` (``unmasked``, ``masked``, ``true``, ``true_fit`` at 0.143),
     ``cutoff_res``, ``cutoff_index``, ``mask_soft_px`` (None with a given mask), ``mask1``, ``mask2``, ``host_mask_s`` (the seconds
@@ -622,7 +831,12 @@ def true_fsc(map1, map2, apix, *, mask=None, one_mask=False, cutoff_res=0, mask_
 
     if device_masks and mask is not None:
         raise ValueError("true_fsc: device_masks builds the soft edge of the adaptive support; a given mask is used as it is")
+    if device_support and not device_masks:
+        raise ValueError("true_fsc: device_support needs device_masks=True (the supports stay on the device for the soft masks built there)")
     a64, b64 = np.asarray(map1, dtype=np.float64), np.asarray(map2, dtype=np.float64)
+    if device_support and not all(np.array_equal(m.astype(np.float32), m) for m in (a64, b64)):
+        raise ValueError("true_fsc: device_support needs maps that float32 represents exactly (the context holds float32; "
+                         "the host's adaptive_mask filters the maps in float64)")
     ctx = (context or TrueFSC)(map1, map2, apix, cutoff_res, phases=phases, seed=seed, device=device)
     host_s = 0.0
     try:
@@ -639,16 +853,20 @@ def true_fsc(map1, map2, apix, *, mask=None, one_mask=False, cutoff_res=0, mask_
             if len(masks) == 2 and one_mask:
                 mask1 = mask2 = (mask1 + mask2) / 2
         else:
-            t0 = time.perf_counter()
             kw = dict(mask_fraction_thresh=mask_fraction_thresh, mask_thresh=mask_thresh, mask_mass=mask_mass)
-            if one_mask:
-                mask1 = mask2 = adaptive_mask((a64 + b64) / 2, apix, cutoff, **kw)
+            if device_support:
+                ctx.adaptive_support(one_mask=bool(one_mask), **kw)
+                same = bool(one_mask)
             else:
-                mask1, mask2 = adaptive_mask(a64, apix, cutoff, **kw), adaptive_mask(b64, apix, cutoff, **kw)
-            host_s += time.perf_counter() - t0
-            same = mask2 is mask1
-            if device_masks:
-                ctx.set_support(mask1, None if same else mask2)
+                t0 = time.perf_counter()
+                if one_mask:
+                    mask1 = mask2 = adaptive_mask((a64 + b64) / 2, apix, cutoff, **kw)
+                else:
+                    mask1, mask2 = adaptive_mask(a64, apix, cutoff, **kw), adaptive_mask(b64, apix, cutoff, **kw)
+                host_s += time.perf_counter() - t0
+                same = mask2 is mask1
+                if device_masks:
+                    ctx.set_support(mask1, None if same else mask2)
             if mask_soft > 0:
                 soft_px = mask_soft / apix
             elif refine_mask:
@@ -713,11 +931,14 @@ def add_args(parser: argparse.ArgumentParser) -> argparse.ArgumentParser:
     parser.add_argument("--out-prefix", default=None, help="write P.unmasked.txt ... P.true.fit.txt and the mask(s)")
     parser.add_argument("--device", type=int, default=0)
     parser.add_argument("--device-masks", action="store_true", help="build the soft edge of the adaptive mask, and every trial of --refine-mask, on the device (not with --mask)")
+    parser.add_argument("--device-support", action="store_true", help="build the adaptive mask itself on the device from the resident maps (needs --device-masks)")
     return parser
 
 
 def run(args, context=None) -> dict:
     """``context`` stands in for ``TrueFSC`` (tests): everything else, the masks included, runs as it does on a device."""
+    if getattr(args, "device_support", False) and not getattr(args, "device_masks", False):
+        raise SystemExit("--device-support needs --device-masks")
     m1, apix = _read_map(args.half1, args.apix)
     m2, _ = _read_map(args.half2, args.apix)
     if not apix or apix <= 0:
@@ -738,7 +959,7 @@ def run(args, context=None) -> dict:
         out = true_fsc(m1, m2, float(apix), mask=mask, one_mask=args.one_mask, cutoff_res=args.cutoff_res, mask_soft=args.mask_soft,
                        refine_mask=args.refine_mask and not args.mask_soft > 0, mask_fraction_thresh=args.mask_fraction_thresh,
                        mask_thresh=args.mask_thresh, mask_mass=args.mask_mass, seed=args.seed, device=args.device, context=context,
-                       device_masks=getattr(args, "device_masks", False))
+                       device_masks=getattr(args, "device_masks", False), device_support=getattr(args, "device_support", False))
     except ValueError as e:
         raise SystemExit(str(e))
     curves = ("unmasked", "randomized_unmasked", "masked", "randomized_masked", "true")

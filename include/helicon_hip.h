@@ -655,6 +655,40 @@ int hh_tfsm_soft_mask(hh_tfsc* ctx, int which, double soft_width, float* mask_ou
 int hh_tfsm_soft_masked(hh_tfsc* ctx, const double* soft_widths, int32_t batch, int full_spectrum, double* sums,
                         double* kernel_ms);
 
+/*
+ * The adaptive mask of the true FSC built on the device (csrc/adaptive_mask.inc; commands/trueFSC.py:660-735
+ * _generate_adaptive_mask as helicon_amd.true_fsc.adaptive_mask restates it): the volume in float64, low-passed by
+ * scipy.ndimage.gaussian_filter's rule (sigma > 0; passes z, y, x, "reflect" boundary, unfused products and sums),
+ * thresholded, and the 26-connected components of {LP > threshold} that hold a voxel >= v*, the 1000th largest value, kept
+ * (all of them, if none holds one).  Every voxel tied at v* is a seed (np.argpartition keeps an arbitrary 1000).
+ * taps: host float64 [int(4 sigma + 0.5) + 1], w[j] = exp(-0.5 / sigma^2 j^2) / sum as NumPy computes them
+ * (helicon_amd.true_fsc.gaussian_taps): the library does not recompute them, so that the filter equals SciPy's bit for
+ * bit; int(4 sigma + 0.5) <= 4096.  Sides in [1, 1024], at most 2^28 voxels; a mask needs at least 1000.  A NaN or infinite
+ * voxel, and a constant volume in Otsu mode, are argument errors.  The labelling's loops are bounded: a defect returns
+ * HH_ERR_INTERNAL.  Results are bit-identical from run to run.  Errors: hh_last_error(NULL).
+ */
+/* host only: np.linspace(hmin, hmax, 257) (edges_out [257], may be NULL) and Otsu's threshold from 256 counts */
+int hh_am_otsu(const int64_t* counts, double hmin, double hmax, double* edges_out, double* threshold_out);
+/* device-event milliseconds of the mask calls since the last reset, [8]: the z, y, x passes, statistics (minimum, maximum,
+ * histogram, selection), runs, unions, flatten, pick; out may be NULL; reset != 0 zeroes them */
+int hh_am_stage_ms(double* out, int reset);
+/* vol, out: host float64 [nz][ny][nx] */
+int hh_am_gaussian_3d(int device, const double* vol, int32_t nz, int32_t ny, int32_t nx, double sigma, const double* taps, double* out);
+/* binary: host uint8, nonzero = foreground; roots_out: int32, the smallest flat index of the voxel's 26-connected component,
+ * -1 on background */
+int hh_am_label_3d(int device, const uint8_t* binary, int32_t nz, int32_t ny, int32_t nx, int32_t* roots_out, int64_t* n_components);
+/* vol: host float64 (is_f64 != 0) or float32, widened exactly.  sigma = 0: no filter (taps may be NULL).  mode 0: Otsu;
+ * 1: value x max(LP); 2: value; 3: the voxel at index `value` (a whole number) of LP sorted in descending order.
+ * support_out: uint8 0 / 1.  info (may be NULL) [8]: threshold, min(LP), max(LP), v*, voxels above the threshold, voxels
+ * kept, components, bits (1: no component held a seed and the mask is {LP > threshold}; 2: more than 1000 voxels >= v*) */
+int hh_am_mask_3d(int device, const void* vol, int is_f64, int32_t nz, int32_t ny, int32_t nx, double sigma, const double* taps, int mode,
+                  double value, uint8_t* support_out, double* info);
+/* the support(s) of a true-FSC context from its resident float32 maps: of (double(map1) + double(map2)) / 2 for both members
+ * (one_mask != 0), or one of each map; left where hh_tfsm_set_support leaves them.  info (may be NULL): [2][8] */
+int hh_am_context_support(hh_tfsc* ctx, int one_mask, double sigma, const double* taps, int mode, double value, double* info);
+/* the context's support for member `which` (0 / 1), uint8 [n][n][n] */
+int hh_am_context_get_support(hh_tfsc* ctx, int which, uint8_t* support_out);
+
 #ifdef __cplusplus
 }
 #endif

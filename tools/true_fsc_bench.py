@@ -3,6 +3,7 @@
 
     python tools/true_fsc_bench.py [--out profiles/true_fsc.json] [--sizes 64 128 256] [--repeats 5] [--accuracy LOG]
                                    [--soft-out profiles/soft_mask.json] [--soft-only]
+                                   [--adaptive-out profiles/adaptive_mask.json] [--adaptive-only]
 
 Per size, one pair of n^3 maps (a blob plus noise, so that the adaptive mask has something to find), after a warm-up of every
 call that is timed; medians of REPEATS:
@@ -29,6 +30,19 @@ With ``--soft-out`` (``--soft-only``: nothing else) the soft masks built on the 
   transform + mask kernel (``soft_mask_device``); their difference is the mask kernel.
 
 ITS GATE: at 128^3 and 256^3 the device trial's wall must not exceed the parent trial's at ANY visited width.
+
+With ``--adaptive-out`` (``--adaptive-only``: nothing else) the adaptive mask built on the device (csrc/adaptive_mask.inc),
+per size, on the average of the two maps:
+
+* ``calls``: alternating in one loop after a warm-up, the host's ``adaptive_mask``, the standalone ``adaptive_mask_device``
+  (upload of the float64 volume included) and the resident context's ``adaptive_support(one_mask=True)`` (download of the
+  support included) — wall, medians; whether the three masks are equal;
+* ``stages``: device-event times of the context's call per stage (``adaptive_stage_ms``): the three Gaussian passes, the
+  statistics (minimum, maximum, histogram, selection), runs, unions, flatten, pick — medians;
+* ``refine``: a whole ``true_fsc(one_mask=True, refine_mask=True, seed=1)`` run three ways — host masks, ``device_masks``,
+  ``device_masks`` + ``device_support`` — each with its wall and ``host_mask_s``.
+
+ITS GATE: at 128^3 and 256^3 the context's call must take less wall time than the host's ``adaptive_mask`` of the same run.
 
 THE GATE: at 128^3 and 256^3 ``masked.wall_ms`` must not exceed ``parent_one_mask.wall_ms`` of the same run (same kernels,
 one mask uploaded instead of four maps): both are printed, and the tool exits 1 if it is missed.  With ``--accuracy LOG`` the
@@ -160,6 +174,45 @@ def soft_mask_legs(n, a, b, apix, cutoff, repeats):
     return case, ok
 
 
+def adaptive_mask_legs(n, a, b, apix, cutoff, repeats):
+    """The legs of the device adaptive mask for one size; (case, gate passed)."""
+    import helicon_amd as H
+
+    T = importlib.import_module("helicon_amd.true_fsc")
+    case = {"case": f"1 x {n}^3", "n": n, "sigma": cutoff / (3.81 * apix) if cutoff > 2 * apix else 0.0}
+    avg = (a.astype(np.float64) + b) / 2
+    with H.TrueFSC(a, b, apix, cutoff, seed=1) as ctx:
+        host = T.adaptive_mask(avg, apix, cutoff)                 # warm-up of all three
+        alone = T.adaptive_mask_device(avg, apix, cutoff)
+        info = ctx.adaptive_support(one_mask=True)
+        case["info"] = info[0]
+        case["masks_equal"] = bool(np.array_equal(alone, host != 0) and np.array_equal(ctx.support(0), host != 0))
+        w_host, w_alone, w_ctx, stages = [], [], [], []
+        for _ in range(repeats):
+            t0 = time.perf_counter()
+            T.adaptive_mask(avg, apix, cutoff)
+            w_host.append((time.perf_counter() - t0) * 1e3)
+            t0 = time.perf_counter()
+            T.adaptive_mask_device(avg, apix, cutoff)
+            w_alone.append((time.perf_counter() - t0) * 1e3)
+            T.adaptive_stage_ms(reset=True)
+            t0 = time.perf_counter()
+            ctx.adaptive_support(one_mask=True)
+            w_ctx.append((time.perf_counter() - t0) * 1e3)
+            stages.append(T.adaptive_stage_ms(reset=True))
+    case["calls"] = {"host_wall_ms": float(np.median(w_host)), "standalone_wall_ms": float(np.median(w_alone)), "context_wall_ms": float(np.median(w_ctx))}
+    case["calls"]["host_over_context"] = case["calls"]["host_wall_ms"] / case["calls"]["context_wall_ms"]
+    case["stages_ms"] = {k: float(np.median([s[k] for s in stages])) for k in stages[0]}
+    runs = {}
+    for name, kw in (("host_masks", dict()), ("device_masks", dict(device_masks=True)), ("device_masks_and_support", dict(device_masks=True, device_support=True))):
+        t0 = time.perf_counter()
+        out = T.true_fsc(a, b, apix, cutoff_res=cutoff, one_mask=True, refine_mask=True, seed=1, **kw)
+        wall = time.perf_counter() - t0
+        runs[name] = {"wall_s": wall, "host_mask_s": out["host_mask_s"], "mask_soft_px": out["mask_soft_px"], "resolution_true": out["resolution"]["true"]}
+    case["refine"] = runs
+    return case, case["calls"]["context_wall_ms"] < case["calls"]["host_wall_ms"]
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--out", default=None)
@@ -169,6 +222,8 @@ def main(argv=None):
     ap.add_argument("--no-refine", action="store_true", help="leave the whole-run timing out")
     ap.add_argument("--soft-out", default=None, help="also time the soft masks built on the device and write this file")
     ap.add_argument("--soft-only", action="store_true", help="only the soft-mask legs")
+    ap.add_argument("--adaptive-out", default=None, help="also time the adaptive mask built on the device and write this file")
+    ap.add_argument("--adaptive-only", action="store_true", help="only the adaptive-mask legs")
     args = ap.parse_args(argv)
 
     import fsc_oracle as O
@@ -179,6 +234,7 @@ def main(argv=None):
     apix = 2.0
     result = {"repeats": args.repeats, "cases": [], "gate": {}}
     soft = {"repeats": args.repeats, "cases": [], "gate": {}}
+    adaptive = {"repeats": args.repeats, "cases": [], "gate": {}}
     missed = False
     for n in args.sizes:
         a, b = O.make_map_pair(n, 500 + n, dc="auto")
@@ -186,6 +242,17 @@ def main(argv=None):
         blob = 6.0 * np.exp(-(g[:, None, None] ** 2 + g[None, :, None] ** 2 + g[None, None, :] ** 2) / (2.0 * (n / 6.0) ** 2))
         a, b = (a + blob).astype(np.float32), (b + blob).astype(np.float32)
         cutoff = apix * n / (n / 4 + 0.5)
+        if args.adaptive_out or args.adaptive_only:
+            case, ok = adaptive_mask_legs(n, a, b, apix, cutoff, args.repeats)
+            adaptive["cases"].append(case)
+            print(json.dumps(case), flush=True)
+            if n >= 128:
+                adaptive["gate"][str(n)] = {"passed": bool(ok), "host_wall_ms": case["calls"]["host_wall_ms"], "context_wall_ms": case["calls"]["context_wall_ms"]}
+                print(f"ADAPTIVE GATE n={n}: the context's call {case['calls']['context_wall_ms']:.3f} ms, the host's adaptive_mask "
+                      f"{case['calls']['host_wall_ms']:.3f} ms: {'ok' if ok else 'MISSED'}", flush=True)
+                missed = missed or not ok
+            if args.adaptive_only:
+                continue
         if args.soft_out or args.soft_only:
             case, ok = soft_mask_legs(n, a, b, apix, cutoff, args.repeats)
             soft["cases"].append(case)
@@ -270,6 +337,9 @@ def main(argv=None):
         print(json.dumps(case), flush=True)
     if args.accuracy:
         result["accuracy"] = parse_figures(args.accuracy)
+    if args.adaptive_out:
+        Path(args.adaptive_out).parent.mkdir(parents=True, exist_ok=True)
+        Path(args.adaptive_out).write_text(json.dumps(adaptive, indent=1) + "\n")
     if args.soft_out:
         Path(args.soft_out).parent.mkdir(parents=True, exist_ok=True)
         Path(args.soft_out).write_text(json.dumps(soft, indent=1) + "\n")
