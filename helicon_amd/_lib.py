@@ -118,6 +118,7 @@ EXPORTS = {
     "hh_general_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
     "hh_rise_columns_shared": (C.c_int, [_f64p, C.c_int64, C.c_int64]),
     "hh_table_extent": (C.c_int64, [C.c_int, C.c_double, C.c_int, C.c_double, C.c_double]),
+    "hh_pair_table_slot": (C.c_int, [C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
     "hh_affine_transform_2d": (C.c_int, [C.c_int, _f32p, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), _f32p]),
     "hh_affine_transform_2d_cubic": (C.c_int, [C.c_int, _f32p, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), _f32p]),
     "hh_warp_affine_2d": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_int, C.c_double, C.c_int,

@@ -829,6 +829,7 @@ struct TableArgs {
   float2* table_ky;       // the same values ky-major, [runs][N/2][rows_pad], zero past a run's rows (the fused pass's twist
                           // walk: a wavefront's ky row of one run is contiguous); nullptr: not wanted
   int rows_pad;           // multiple of SUB (4), >= every run's rows
+  int ky_pairs;           // table_ky in the pair layout (pair_slot), runs counted from this launch's first
   const int* run_imax;    // [runs] subunit index range [-imax, imax] a run's table covers
   float2* inter;
   FinArgs fin;
@@ -838,6 +839,14 @@ struct TableArgs {
   int rows_lds;           // table rows a workgroup of k_first_pass_table can stage
   DevGeom g;
 };
+
+// The ky-major table two runs to an entry, [pair][ky][rows][2] complex (the fused pass's twist walk at N = 512 builds two
+// consecutive runs from one read): pair = run / 2 and the inner index run & 1, runs counted from the first of the table
+// group.  A group of an odd number of runs ends on a zeroed partner.  -> complex words from the group's base
+__host__ __device__ inline size_t pair_slot(int64_t run, int ky, int row, int nky, int rows) {
+  return ((((size_t)(run >> 1) * nky + ky) * rows + row) << 1) | (size_t)(run & 1);
+}
+inline size_t pair_table_words(int64_t runs, int nky, int rows) { return (size_t)((runs + 1) / 2) * 2 * nky * rows; }
 
 template <int N>
 struct KT {
@@ -877,10 +886,20 @@ __global__ __launch_bounds__(256) void k_run_table(TableArgs a) {
   const float k2 = g.inv_sigma2 * 1.44269504088896341f;
   const int row0 = blockIdx.x * K::SUB;
   const int nrow = min(K::SUB, rows - row0);
+  // pair layout: the last run of an odd number has no partner and writes the zeros that stand in for one
+  const bool lone = a.ky_pairs && !(run & 1) && run + 1 == (int)gridDim.y;
   if (nrow <= 0) {
     // ky-major form: the launch covers rows_pad table rows; those past the run's own are the zeros the row build reads
     if (a.table_ky && row0 < a.rows_pad)
       for (int ky = threadIdx.x; ky < K::NKY; ky += 256) {
+        if (a.ky_pairs) {
+          float2* const dst = a.table_ky + pair_slot(run, ky, row0, K::NKY, a.rows_pad);
+          for (int r = 0; r < K::SUB; ++r) {
+            dst[2 * r] = make_float2(0.f, 0.f);
+            if (lone) dst[2 * r + 1] = make_float2(0.f, 0.f);
+          }
+          continue;
+        }
         float4* const dst = reinterpret_cast<float4*>(a.table_ky + ((size_t)run * K::NKY + ky) * a.rows_pad + row0);
         dst[0] = dst[1] = make_float4(0.f, 0.f, 0.f, 0.f);
       }
@@ -954,6 +973,15 @@ __global__ __launch_bounds__(256) void k_run_table(TableArgs a) {
       for (int r = 0; r < K::SUB; ++r) {
         o[r] = r < nrow ? acc[r][q] : make_float2(0.f, 0.f);
         if (ky == 0 && r < nrow) o[r].y = alt[r];
+      }
+      if (a.ky_pairs) {  // ... and four 8-byte pieces at a 16-byte stride here (the partner run's workgroup writes between them)
+        float2* const dst = a.table_ky + pair_slot(run, ky, row0, K::NKY, a.rows_pad);
+#pragma unroll
+        for (int r = 0; r < K::SUB; ++r) {
+          dst[2 * r] = o[r];
+          if (lone) dst[2 * r + 1] = make_float2(0.f, 0.f);
+        }
+        continue;
       }
       float4* const dst = reinterpret_cast<float4*>(a.table_ky + ((size_t)run * K::NKY + ky) * a.rows_pad + row0);
       dst[0] = make_float4(o[0].x, o[0].y, o[1].x, o[1].y);
@@ -1550,7 +1578,9 @@ struct FusedArgs {
   const double* params;
   const float2* twtab;
   const float2* table;    // [runs][cap][N/2]
-  const float2* table_ky; // twist walk: [runs][N/2][rows_lds], zero past a run's rows (k_run_table)
+  const float2* table_ky; // twist walk: [runs][N/2][rows_lds], zero past a run's rows (k_run_table); N = 512: the table
+                          // group's base in the pair layout, [pairs][N/2][rows_lds][2] (pair_slot)
+  int ky_run0;            // pair layout: the launch's first run, counted from the table group's first
   const int* run_imax;    // [runs]
   const float* eg;        // [B][kg][N], or [run_len][kg][N] shared by every run (factor_stride = 0)
   const int* cgs;         // [B][N/4 + 4], or [run_len][N/4 + 4]
@@ -1597,6 +1627,13 @@ __device__ __forceinline__ void lds_dma16(const void* gsrc_lane, unsigned lds_ba
                : "v"(gsrc_lane), "s"(lds_base)
                : "memory", "m0");  // M0 is written here: the compiler must not keep a value of its own in it across this
 }
+// The same with a wave-uniform global base and a 32-bit byte offset per lane (one vector register instead of two).
+__device__ __forceinline__ void lds_dma16(const void* gsrc_wave, unsigned lane_off, unsigned lds_base) {
+  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1"
+               :
+               : "v"(lane_off), "s"(gsrc_wave), "s"(lds_base)
+               : "memory", "m0");
+}
 #pragma clang diagnostic pop
 __device__ __forceinline__ void lds_dma_wait() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 __device__ __forceinline__ unsigned lds_offset_of(const void* p) {  // wave-uniform LDS byte address as a scalar
@@ -1623,6 +1660,11 @@ constexpr int WALK_RISES = 0, WALK_TWISTS = 1;  // k_fused_pass's candidate loop
 // candidate (shared by the eight rows: one workgroup barrier per candidate).  WALK_TWISTS (factor_stride = 0, N <= 512):
 // a workgroup owns (rise, ky block) and walks RUNS — the factor set stays, and per candidate each wavefront fetches its
 // own ky row(s) of the next run's table into a buffer nobody else reads: no workgroup barrier in the loop.
+// At N = 512 (PAIR: one spectrum row per wavefront) the twist walk takes the runs two at a time: the ky-major table keeps
+// two consecutive runs to an entry (pair_slot), the wavefront copies its row of a pair, rows_lds x {G_A, G_B}, into its
+// one buffer and builds both runs in one pass over the factor rows — per table row and column group one 16-byte read of
+// the two table values and one of the four factors for 16 FMAs, where a run alone reads the factors again — then hands A
+// and B to the transform one after the other, B's 16 sums waiting in registers.
 template <int N, int EPI, int LOG, int WALK>
 __global__ __launch_bounds__(N, (N >= 256 ? KF<N>::WPS : 1)) void k_fused_pass(FusedArgs a) {
   using K = KF<N>;
@@ -1630,10 +1672,11 @@ __global__ __launch_bounds__(N, (N >= 256 ? KF<N>::WPS : 1)) void k_fused_pass(F
   constexpr int T = K::T, TL = T < 64 ? T : 64, NKY = N / 2;
   constexpr bool TW = WALK == WALK_TWISTS;
   static_assert(!TW || N <= 512, "the twist walk has no SPLIT form");
+  constexpr bool PAIR = TW && N == 512;  // two runs per pass over the factor rows (one spectrum row per wavefront)
   constexpr int GBUF = TW ? 2 : 1, FBUF = TW ? 1 : 2;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   float2* const bufs = reinterpret_cast<float2*>(smem);
-  float2* const gs = reinterpret_cast<float2*>(smem + K::LDS_BUF);                       // [8][rows_lds]; twist walk: [2][8][rows_lds]
+  float2* const gs = reinterpret_cast<float2*>(smem + K::LDS_BUF);                       // [8][rows_lds]; twist walk: [2][8][rows_lds], PAIR: [8][rows_lds][2]
   float* const eg = reinterpret_cast<float*>(smem + K::LDS_BUF + (size_t)GBUF * 8 * a.rows_lds * sizeof(float2));  // [2][kg][N]; twist walk: [kg][N]
   int* const cgs = reinterpret_cast<int*>(eg + (size_t)FBUF * a.kg * N);                 // [2][N/4 + 4]; twist walk: [N/4 + 4]
   constexpr int CGS = cgs_stride<N>();
@@ -1649,7 +1692,9 @@ __global__ __launch_bounds__(N, (N >= 256 ? KF<N>::WPS : 1)) void k_fused_pass(F
     finalize_layer(a.fin);
     return;
   }
-  const int gi = tid / T, t = tid % T;
+  // (PAIR: a row is one wavefront's, and the compiler is told so — row, candidate and table addresses are then scalar
+  // arithmetic, which is what leaves the vector registers for run B's sums)
+  const int gi = PAIR ? __builtin_amdgcn_readfirstlane(tid / T) : tid / T, t = tid % T;
   float2* const buf = bufs + gi * K::BROW;
   // Work layers -> (layer of candidates gy, ky block): workgroups are dealt round-robin over the 8 XCDs in dispatch
   // order, so ids that are equal mod 8 share an L2.  Every ky block of one layer reads the same column factors and
@@ -1772,9 +1817,22 @@ __global__ __launch_bounds__(N, (N >= 256 ? KF<N>::WPS : 1)) void k_fused_pass(F
     for (int p0 = 0; p0 < pieces; p0 += LANES)
       if (p0 + lane < pieces) lds_dma16(gsrc + (size_t)(p0 + lane) * 16, lds_offset_of(ldst + (size_t)p0 * 16));
   };
+  // PAIR: the wavefront's ky row of runs 2 pair, 2 pair + 1 of the table group, rows_lds entries {G_A[k], G_B[k]} of 16
+  // bytes, contiguous in the pair layout and in the wavefront's one buffer.
+  [[maybe_unused]] auto stage_pair = [&](int pair) {
+    const int lane = tid & 63;   // (gi is the wavefront)
+    const char* const gsrc = reinterpret_cast<const char*>(a.table_ky + pair_slot(2 * (int64_t)pair, 8 * kb + gi, 0, NKY, a.rows_lds));
+    const unsigned ldst = lds_offset_of(gs + (size_t)gi * 2 * a.rows_lds);
+    for (int p0 = 0; p0 < a.rows_lds; p0 += 64)
+      if (p0 + lane < a.rows_lds) lds_dma16(gsrc + (size_t)p0 * 16, (unsigned)lane * 16u, ldst + (unsigned)p0 * 16u);
+  };
+  // PAIR: the piece's runs counted from the table group's first, [pr_first, pr_first + nc)
+  [[maybe_unused]] const int pr_first = PAIR ? a.ky_run0 + off : 0;
   // the run's table slice of this ky block, transposed to [ky in block][table row]; rows past the
   // run's own count are zero
-  if constexpr (TW) {
+  if constexpr (PAIR) {
+    stage_pair(pr_first >> 1);
+  } else if constexpr (TW) {
     stage_rows(0, 0);
     if (nc > 1) stage_rows(1, 1);
   } else {
@@ -1829,6 +1887,46 @@ __global__ __launch_bounds__(N, (N >= 256 ? KF<N>::WPS : 1)) void k_fused_pass(F
   // (see flush_q) — not for the packed row's group (its two rows are un-packed through the exchange buffer)
   const bool defer_q = EPI == EPI_QSTORE && STAGGER && !late && !(kb == 0 && gi == 0);
 
+  // The row is handed to the transform through the group's exchange buffer.  A lane stores 2 x 32 bytes at a
+  // 32-byte lane stride: the eight lanes of a ds_write_b128 group would hit four bank groups twice, so the
+  // 16-byte chunk c = x / 2 lives at c ^ ((c >> 3) & 1) (chunks 2 xg, 2 xg + 1 of lanes xg and xg + 4 then fall
+  // into different halves of the 128-byte bank span); the reader un-swizzles with one precomputed base.
+  auto chunk = [](int c) { return c ^ ((c >> 3) & 1); };
+  // sums of column groups t and t + T -> the group's panel (every size but SPLIT)
+  auto hand_over = [&](float2 p0, float2 p1, float2 p2, float2 p3, float2 q0, float2 q1, float2 q2, float2 q3) {
+    const int xg0 = t, xg1 = t + T;
+    float4* const row4 = reinterpret_cast<float4*>(buf);
+    row4[chunk(2 * xg0)] = make_float4(p0.x, p0.y, p1.x, p1.y);
+    row4[chunk(2 * xg0 + 1)] = make_float4(p2.x, p2.y, p3.x, p3.y);
+    row4[chunk(2 * xg1)] = make_float4(q0.x, q0.y, q1.x, q1.y);
+    row4[chunk(2 * xg1 + 1)] = make_float4(q2.x, q2.y, q3.x, q3.y);
+  };
+  // the panel row -> the lane's eight points, and the transform up to its first exchange
+  auto first_stage = [&]() {
+    // (SPLIT: the one workgroup barrier of the transform.  Tried and dropped: an LDS-counter meeting of just the row's
+    // two wavefronts, -3.5 %; every wavefront building its own half's input from all the row's columns — twice the
+    // accumulation, no barrier, stagger possible — -16 %)
+    group_sync<T>();
+    float2 v[8];
+    if constexpr (SPLIT) {  // n = tf + 64 m of the wavefront's own half
+      const int ps = (((tf >> 1) ^ ((tf >> 4) & 1)) << 1) | (tf & 1);
+#pragma unroll
+      for (int m = 0; m < 8; ++m) v[m] = fbuf[ps + m * TF];
+    } else if constexpr (T % 32 == 0) {  // x = t + m T: bit 4 of x is bit 4 of t, one swizzled base serves every m
+      const int ps = (((t >> 1) ^ ((t >> 4) & 1)) << 1) | (t & 1);
+#pragma unroll
+      for (int m = 0; m < 8; ++m) v[m] = buf[ps + m * T];
+    } else {
+#pragma unroll
+      for (int m = 0; m < 8; ++m) {
+        const int x = t + m * T;
+        v[m] = buf[(((x >> 1) ^ ((x >> 4) & 1)) << 1) | (x & 1)];
+      }
+    }
+    if constexpr (T > 64 && !SPLIT) __syncthreads();  // both wavefronts of a row have read it before either exchanges in it
+    fft_lanes_part<NF, true, TwRegs, 1, 1>(v, twsrc, tf, fbuf);
+  };
+
   auto part_a = [&](int cc) {
     const int cur = cc & 1;
     const float* const egc = TW ? eg : eg + (size_t)cur * a.kg * N;
@@ -1836,7 +1934,8 @@ __global__ __launch_bounds__(N, (N >= 256 ? KF<N>::WPS : 1)) void k_fused_pass(F
     const float2* const gsc = TW ? gs + (size_t)cur * 8 * a.rows_lds : gs;   // twist walk: the candidate's slice buffer
     // ---- this group's row of H, built by the group itself into its own exchange buffer (no workgroup barrier).
     // A lane owns two groups of four consecutive columns (x = 4 t + c and 4 (t + T) + c): two independent
-    // accumulation chains, and the operands of the next table row are in flight while this row's FMAs issue.
+    // accumulation chains.  (The compiler waits for a table row's operands right behind their reads: no read of the
+    // next row is in flight under this row's FMAs.)
     {
       // table rows this candidate needs (<= kg; a wave-uniform LDS word written by the factor kernel)
       // (clamped to the buffer's kg: whatever the word holds, the walk is bounded)
@@ -1875,11 +1974,6 @@ __global__ __launch_bounds__(N, (N >= 256 ? KF<N>::WPS : 1)) void k_fused_pass(F
           q3.x = fmaf(eb.w, gb.x, q3.x); q3.y = fmaf(eb.w, gb.y, q3.y);
         }
       };
-      // The row is handed to the transform through the group's exchange buffer.  A lane stores 2 x 32 bytes at a
-      // 32-byte lane stride: the eight lanes of a ds_write_b128 group would hit four bank groups twice, so the
-      // 16-byte chunk c = x / 2 lives at c ^ ((c >> 3) & 1) (chunks 2 xg, 2 xg + 1 of lanes xg and xg + 4 then fall
-      // into different halves of the 128-byte bank span); the reader un-swizzles with one precomputed base.
-      auto chunk = [](int c) { return c ^ ((c >> 3) & 1); };
       if constexpr (SPLIT) {
         accumulate(t, t + T);
         // the radix-2 step, then y0 into the row's first half and y1 into its second (chunks 2 t, 2 t + 1 of each)
@@ -1895,43 +1989,55 @@ __global__ __launch_bounds__(N, (N >= 256 ? KF<N>::WPS : 1)) void k_fused_pass(F
         y1[chunk(2 * t)] = make_float4(q0.x, q0.y, q1.x, q1.y);
         y1[chunk(2 * t + 1)] = make_float4(q2.x, q2.y, q3.x, q3.y);
       } else {
-        const int xg0 = t, xg1 = t + T;
-        accumulate(xg0, xg1);
-        float4* const row4 = reinterpret_cast<float4*>(buf);
-        row4[chunk(2 * xg0)] = make_float4(p0.x, p0.y, p1.x, p1.y);
-        row4[chunk(2 * xg0 + 1)] = make_float4(p2.x, p2.y, p3.x, p3.y);
-        row4[chunk(2 * xg1)] = make_float4(q0.x, q0.y, q1.x, q1.y);
-        row4[chunk(2 * xg1 + 1)] = make_float4(q2.x, q2.y, q3.x, q3.y);
+        accumulate(t, t + T);
+        hand_over(p0, p1, p2, p3, q0, q1, q2, q3);
       }
     }
-    // (SPLIT: the one workgroup barrier of the transform.  Tried and dropped: an LDS-counter meeting of just the row's
-    // two wavefronts, -3.5 %; every wavefront building its own half's input from all the row's columns — twice the
-    // accumulation, no barrier, stagger possible — -16 %)
-    group_sync<T>();
-    float2 v[8];
-    if constexpr (SPLIT) {  // n = tf + 64 m of the wavefront's own half
-      const int ps = (((tf >> 1) ^ ((tf >> 4) & 1)) << 1) | (tf & 1);
-#pragma unroll
-      for (int m = 0; m < 8; ++m) v[m] = fbuf[ps + m * TF];
-    } else if constexpr (T % 32 == 0) {  // x = t + m T: bit 4 of x is bit 4 of t, one swizzled base serves every m
-      const int ps = (((t >> 1) ^ ((t >> 4) & 1)) << 1) | (t & 1);
-#pragma unroll
-      for (int m = 0; m < 8; ++m) v[m] = buf[ps + m * T];
-    } else {
-#pragma unroll
-      for (int m = 0; m < 8; ++m) {
-        const int x = t + m * T;
-        v[m] = buf[(((x >> 1) ^ ((x >> 4) & 1)) << 1) | (x & 1)];
-      }
-    }
-    if constexpr (T > 64 && !SPLIT) __syncthreads();  // both wavefronts of a row have read it before either exchanges in it
-    fft_lanes_part<NF, true, TwRegs, 1, 1>(v, twsrc, tf, fbuf);
+    first_stage();
   };
 
-  auto part_b = [&](int cc) {
+  // PAIR: the sums of runs A and B of the wavefront's pair buffer in one pass over the factor rows.  Per table row and
+  // column group one 16-byte read of {G_A, G_B} and one of the four factors feed 16 FMAs; every sum keeps the operands
+  // and the order it has in part_a's build.
+  [[maybe_unused]] auto build_pair = [&](float2 (&sa)[8], float2 (&sb)[8]) {
+    const float4* const grow0 = reinterpret_cast<const float4*>(gs) + gi * a.rows_lds + tw_cg0;
+    const float4* const grow1 = reinterpret_cast<const float4*>(gs) + gi * a.rows_lds + tw_cg1;
+    const float* const erow0 = eg + 4 * t;
+    const float* const erow1 = eg + 4 * (t + T);
+    {
+      const float4 g0 = grow0[0], g1 = grow1[0];
+      const float4 ea = *reinterpret_cast<const float4*>(erow0), eb = *reinterpret_cast<const float4*>(erow1);
+      const float e0[4] = {ea.x, ea.y, ea.z, ea.w}, e1[4] = {eb.x, eb.y, eb.z, eb.w};
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        sa[c] = make_float2(e0[c] * g0.x, e0[c] * g0.y);
+        sb[c] = make_float2(e0[c] * g0.z, e0[c] * g0.w);
+        sa[4 + c] = make_float2(e1[c] * g1.x, e1[c] * g1.y);
+        sb[4 + c] = make_float2(e1[c] * g1.z, e1[c] * g1.w);
+      }
+    }
+#pragma unroll 1
+    for (int k = 1; k < tw_kgn; ++k) {
+      const float4 g0 = grow0[k], g1 = grow1[k];
+      const float4 ea = *reinterpret_cast<const float4*>(erow0 + (size_t)k * N);
+      const float4 eb = *reinterpret_cast<const float4*>(erow1 + (size_t)k * N);
+      const float e0[4] = {ea.x, ea.y, ea.z, ea.w}, e1[4] = {eb.x, eb.y, eb.z, eb.w};
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        sa[c].x = fmaf(e0[c], g0.x, sa[c].x); sa[c].y = fmaf(e0[c], g0.y, sa[c].y);
+        sb[c].x = fmaf(e0[c], g0.z, sb[c].x); sb[c].y = fmaf(e0[c], g0.w, sb[c].y);
+        sa[4 + c].x = fmaf(e1[c], g1.x, sa[4 + c].x); sa[4 + c].y = fmaf(e1[c], g1.y, sa[4 + c].y);
+        sb[4 + c].x = fmaf(e1[c], g1.z, sb[4 + c].x); sb[4 + c].y = fmaf(e1[c], g1.w, sb[4 + c].y);
+      }
+    }
+  };
+
+  // wait_copy (PAIR): retire the wavefront's table copy between the transform and the candidate's stores
+  auto part_b = [&](int cc, bool wait_copy = false) {
     const size_t b = cand_of(cc);
     float2 v[8];
     fft_lanes_part<NF, true, TwRegs, 2, 1>(v, twsrc, tf, fbuf);  // v[m] = C[kx = t + m*T] (SPLIT: kx = 2 (tf + 64 m) + h); the exchanges reuse the row's panel slots
+    if (wait_copy) lds_dma_wait();
 
     bool scored = false;
     if (kb == 0 && (gi == 0 || (T > 64 && !SPLIT))) {
@@ -1941,12 +2047,17 @@ __global__ __launch_bounds__(N, (N >= 256 ? KF<N>::WPS : 1)) void k_fused_pass(F
       group_sync<TF>();
       if (gi == 0) {
         // the packed row also carries ky = N/2: its weights come from L2 here (one wavefront in 256)
-        const float2* const nrow = a.w2 + ((size_t)(N / 2) * T + wl) * 8;
+        // (N <= 512: a uniform base and a 32-bit lane offset worked out here, once per candidate of this one row — as eight
+        // 64-bit pointers the compiler keeps them across the candidate loop, in registers the loop then spills)
+        const float2* nw2 = a.w2 + (size_t)(N / 2) * T * 8;
+        unsigned nlane = (unsigned)wl * 8u;
+        if constexpr (SPLIT) nw2 += nlane, nlane = 0;
+        else asm volatile("" : "+v"(nlane));
         float a1 = 0.f, a2 = 0.f, a3 = 0.f, n1 = 0.f, n2 = 0.f, n3 = 0.f;
         [[maybe_unused]] int nbase = (EPI == EPI_QSTORE && compact) ? a.q_roff[N / 2] : 0, zbase = qrow_base;
 #pragma unroll
         for (int m = 0; m < 8; ++m) {
-          const float2 wnm = nrow[m];
+          const float2 wnm = nw2[nlane + m];
           const int kx = SPLIT ? 2 * (tf + m * TF) + h : t + m * T;
           const float2 ck = v[m];
           // C[N - kx]: the same parity as kx, so (SPLIT) it is in this wavefront's half, at k' = NF - k - h (mod NF)
@@ -2053,7 +2164,34 @@ __global__ __launch_bounds__(N, (N >= 256 ? KF<N>::WPS : 1)) void k_fused_pass(F
     }
   };
 
-  if constexpr (TW) {
+  if constexpr (PAIR) {
+    // Pair p holds runs 2 p (A) and 2 p + 1 (B) of the table group; the piece may begin at a B and end at an A, and the half
+    // that is not its own is built with the other (the build's cost is the reads, which serve both) and dropped.  One
+    // buffer: the copy of pair p + 1 is issued when build(p), its only reader, is done, flies under A's transform and
+    // epilogue and B's transform, and is retired in front of B's stores — the youngest stores ahead of that wait are
+    // A's, a transform old (the flush_q lesson), and nothing of the copy is left for the next build to wait for.  No
+    // workgroup barrier: rows and panel are the wavefront's own, the factor set never changes.
+    const int pair_end = (pr_first + nc + 1) >> 1;
+#pragma unroll 1
+    for (int p = pr_first >> 1; p < pair_end; ++p) {
+      float2 sa[8], sb[8];
+      build_pair(sa, sb);
+      const bool more = p + 1 < pair_end;
+      if (more) stage_pair(p + 1);
+      const int ca = 2 * p - pr_first;   // A's candidate number in the piece; B's is ca + 1
+      if (ca >= 0) {
+        hand_over(sa[0], sa[1], sa[2], sa[3], sa[4], sa[5], sa[6], sa[7]);
+        first_stage();
+        part_b(ca);
+      }
+      if (ca + 1 < nc) {   // (always, when another pair follows)
+        hand_over(sb[0], sb[1], sb[2], sb[3], sb[4], sb[5], sb[6], sb[7]);
+        first_stage();
+        part_b(ca + 1, more);
+      }
+    }
+    return;
+  } else if constexpr (TW) {
     // Candidate it = run off + it.  Its rows were copied a whole candidate ago: the copy for it + 2 goes into the buffer
     // build(it) has just finished with, right after the wait that retires the copy for it + 1 — which has been flying
     // since build(it - 1), and behind which the only stores (B(it - 1)'s moments and q) are a build old, so the wait does not
@@ -2601,7 +2739,7 @@ struct hh_ctx {
   int n_kb = 0;
   float2* d_table = nullptr;     // shared-twist first pass: [runs per batch][rows][N/2] column-transform table
   size_t cap_table = 0;          // bytes
-  float2* d_table_ky = nullptr;  // the same tables ky-major, [runs][N/2][rows_f], for the fused pass's twist walk
+  float2* d_table_ky = nullptr;  // the same tables ky-major, [runs][N/2][rows_f] (N = 512: [pairs][N/2][rows_f][2]), for the fused pass's twist walk
   size_t cap_table_ky = 0;       // bytes
   int fused_walk = 0;            // hh_set_fused_walk: 0 auto, 1 rises, 2 twists
   int last_fused_walk = 0;       // hh_last_fused_walk
@@ -3101,6 +3239,8 @@ int launch_factors(hh_ctx* c, const FactorArgs& a, int batch) {
   return HH_OK;
 }
 
+// The size whose twist walk builds two runs per pass (k_fused_pass's PAIR) and reads the ky-major table in the pair layout
+constexpr bool pair_walk_built(int n) { return n == 512; }
 // Sizes whose k_fused_pass has a twist-walking candidate loop (N = 1024 keeps the rise walk: its rows are split over
 // two wavefronts, which meet at a workgroup barrier per candidate either way).
 constexpr bool twist_walk_built(int n) { return n <= 512; }
@@ -3408,8 +3548,9 @@ int sweep_runs(hh_ctx* c, const double* d_params, int64_t g, float* d_scores, co
     HH_HIP(c, hipMalloc(&c->d_table, need));
     c->cap_table = need;
   }
+  const bool ky_pairs = pair_walk_built(c->n);  // the twist walk of this size reads its tables two runs to an entry
   if (any_twists) {
-    const size_t need_ky = (size_t)per_group * nky * plan.rows_f * sizeof(float2);
+    const size_t need_ky = (ky_pairs ? pair_table_words(per_group, nky, plan.rows_f) : (size_t)per_group * nky * plan.rows_f) * sizeof(float2);
     if (need_ky > c->cap_table_ky) {
       if (c->d_table_ky) HH_HIP(c, hipFree(c->d_table_ky));
       c->d_table_ky = nullptr;
@@ -3458,6 +3599,7 @@ int sweep_runs(hh_ctx* c, const double* d_params, int64_t g, float* d_scores, co
         (plan.fused && walks[bj].walk == WALK_TWISTS ? ky_major : rows_major) = true;
       ta.table = rows_major ? c->d_table : nullptr;
       ta.table_ky = ky_major ? c->d_table_ky : nullptr;
+      ta.ky_pairs = ky_major && ky_pairs;
       ta.rows_pad = plan.rows_f;
       ta.run_imax = c->d_run_imax + bt.q0;
       ta.run_len = (int)std::min<int64_t>(plan.len, 1 << 30);
@@ -3490,7 +3632,9 @@ int sweep_runs(hh_ctx* c, const double* d_params, int64_t g, float* d_scores, co
       fu.twtab = c->d_tw;
       const bool twists = walks[bi].walk == WALK_TWISTS;
       fu.table = ta.table;
-      fu.table_ky = twists ? c->d_table_ky + (size_t)(bt.r0 - bt.q0) * nky * plan.rows_f : nullptr;
+      // (pair layout: the group's base and the launch's first run in it: a launch may begin at the second run of a pair)
+      fu.table_ky = !twists ? nullptr : ky_pairs ? c->d_table_ky : c->d_table_ky + (size_t)(bt.r0 - bt.q0) * nky * plan.rows_f;
+      fu.ky_run0 = twists && ky_pairs ? (int)(bt.r0 - bt.q0) : 0;
       fu.run_imax = ta.run_imax;
       fu.eg = shared ? c->d_eg : c->d_eg + half * eg_half;
       fu.cgs = shared ? c->d_cgs : c->d_cgs + half * cg_half;
@@ -3921,6 +4065,15 @@ int64_t hh_table_extent(int nx, double apix, int rpx, double slack, double rise)
   if (nx < 1 || !(apix > 0) || rpx < 0 || !(slack >= 0) || !(rise > 0) || !(rise < INFINITY)) return HH_ERR_ARG;
   return table_extent(nx, (double)(float)apix, rpx, (double)(float)slack, (double)nx * apix, rise);
 } HH_CATCH_CTX(nullptr, "hh_table_extent")
+
+// Host-only: where run `run` of a table group of `runs` runs keeps (ky, row) in the pair layout of the ky-major table.
+int hh_pair_table_slot(int64_t runs, int64_t run, int nky, int rows, int ky, int row, int64_t out[3]) try {
+  if (!out || runs < 1 || run < 0 || run >= runs || nky < 1 || rows < 1 || ky < 0 || ky >= nky || row < 0 || row >= rows) return HH_ERR_ARG;
+  out[0] = (int64_t)pair_slot(run, ky, row, nky, rows);
+  out[1] = (int64_t)pair_table_words(runs, nky, rows);
+  out[2] = (runs & 1) && run == runs - 1 ? out[0] + 1 : -1;
+  return HH_OK;
+} HH_CATCH_CTX(nullptr, "hh_pair_table_slot")
 
 int hh_set_stream(hh_ctx* c, void* hip_stream) try {
   if (!c) return HH_ERR_ARG;

@@ -140,6 +140,12 @@ int hh_rise_columns_shared(const double* params, int64_t n, int64_t run_len);
  * device's float32 roundings), never more than the lattice's own ceil(nx apix / rise).  rpx = truncation half-window in
  * pixels, slack = largest |axial offset| of a unit + 1e-3 Angstrom (hh_set_geometry's values).  Pure host arithmetic. */
 int64_t hh_table_extent(int nx, double apix, int rpx, double slack, double rise);
+/* Where the twist walk at N = 512 keeps its tables: two runs to an entry, [pair][ky][rows][2] complex
+ * words, pair = run / 2 and the inner index run & 1, runs counted from the first of the table group (`runs` of them, built
+ * by one launch).  out = {offset of (run, ky, row) in complex words from the group's base, words the group occupies,
+ * offset of the zeroed word that stands in for the missing partner when `run` is the last of an odd number, else -1}.
+ * Pure host arithmetic. */
+int hh_pair_table_slot(int64_t runs, int64_t run, int nky, int rows, int ky, int row, int64_t out[3]);
 /* Which row kernel hh_sweep takes for an image that is not a power-of-two square, and its launch shape: nx = row length
  * (helical axis), rows_lds = table rows a run keeps in LDS ((2 ceil(nx apix / rise_min) + 1) n_units), kg = table rows
  * one column group may reach (<= 32).  out = {r1, r2, spectrum rows per workgroup, threads per workgroup, LDS buffers
