@@ -1270,6 +1270,20 @@ __device__ __forceinline__ void group_sum3(float& a, float& b, float& c) {
   }
 }
 
+// Two registers of a full wavefront exchange halves (gfx950's v_permlane32_swap_b32 / v_permlane16_swap_b32): lanes 32-63
+// of d with lanes 0-31 of s, or the odd 16-lane rows of d with the even rows of s — a 2 x 2 transpose between one lane
+// bit (5 or 4) and the choice of register.
+__device__ __forceinline__ void lane_swap32(float& d, float& s) {
+  const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(d), __float_as_uint(s), false, false);
+  d = __uint_as_float(r[0]);
+  s = __uint_as_float(r[1]);
+}
+__device__ __forceinline__ void lane_swap16(float& d, float& s) {
+  const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(d), __float_as_uint(s), false, false);
+  d = __uint_as_float(r[0]);
+  s = __uint_as_float(r[1]);
+}
+
 // A workgroup owns ONE ky block (8 spectrum rows, one per transform group) and walks CPW candidates:
 // the rows' mask weights and centred reference values are loaded once into registers and serve all
 // of them, so the second pass reads the weight table once per 16 candidates instead of once per
@@ -1926,6 +1940,52 @@ __global__ __launch_bounds__(N, (N >= 256 ? KF<N>::WPS : 1)) void k_fused_pass(F
     if constexpr (T > 64 && !SPLIT) __syncthreads();  // both wavefronts of a row have read it before either exchanges in it
     fft_lanes_part<NF, true, TwRegs, 1, 1>(v, twsrc, tf, fbuf);
   };
+  // PAIR: a built row goes to the transform in registers, not through the panel.  Lane t holds the sums of columns
+  // x = 256 h + 4 t + c in s[4 h + c]; the first stage wants x = 64 m + j in one lane.  With m = 4 h + (t >> 4) and
+  // j = 4 (t & 15) + c that is a 4 x 4 transpose between lane bits [5:4] and c: v_permlane32_swap on the registers
+  // (c, c + 2), v_permlane16_swap on (c, c + 1), 16 swaps for the 16 floats and no register more.  Lane L then holds
+  // s[m] = x[64 m + j'], j' = 4 (L & 15) + (L >> 4): the inputs of butterfly j'.  The stage has no twiddles, so only the
+  // exchange has to know j': the outputs are elements o = 8 j' + r = 32 a + 8 u + r with a = L & 15, u = L >> 4.
+  // The 16 lanes of a ds_write_b64 group are the 16 a of one u: 256 bytes apart in plain slots, and still four to a bank
+  // pair under fft_stage's xor.  Element o = 32 a + w (w = o & 31) is kept in
+  //   slot(o) = 32 a + (a >> 2) + (w ^ 4 (a & 3))
+  // — one slot of padding per four a (three of the panel row's four spare slots: the highest slot is 514 of 516) and a's
+  // two low bits xored into bits 3:2 of w.  Modulo the 16 bank pairs a store group's slots are (a >> 2) + 4 k(a & 3) +
+  // const with k a permutation of 0..3: all 16.  Writer: bit 3 of the xor is a lane constant and bit 2 turns r into
+  // r ^ 4 (a & 1), so r < 4 go to one base + r and r >= 4 to a second base + r (two base registers, the immediates
+  // stay, no xor per store).  Reader of element n = t + 64 m: a = 2 m + (t >> 5), w = t & 31, so the slot is
+  // 64 m + (m >> 1) + e0 for even m and + (e0 ^ 8) for odd m, e0 = t ^ ((t >> 5) << 2): two bases plus immediates, and
+  // the 32 lanes of a ds_read_b64 group (16 of a ds_read2_b64 group) on as many consecutive slots up to that xor.
+  // Every later exchange and stage is fft_stage's own, so v[m] = X[t + 64 m] comes out as from the panel.
+  [[maybe_unused]] auto first_stage_regs = [&](float2 (&s)[8]) {
+    if constexpr (!PAIR) return;
+#pragma unroll
+    for (int h4 = 0; h4 < 8; h4 += 4) {
+      lane_swap32(s[h4].x, s[h4 + 2].x); lane_swap32(s[h4].y, s[h4 + 2].y);
+      lane_swap32(s[h4 + 1].x, s[h4 + 3].x); lane_swap32(s[h4 + 1].y, s[h4 + 3].y);
+      lane_swap16(s[h4].x, s[h4 + 1].x); lane_swap16(s[h4].y, s[h4 + 1].y);
+      lane_swap16(s[h4 + 2].x, s[h4 + 3].x); lane_swap16(s[h4 + 2].y, s[h4 + 3].y);
+    }
+    bfly<8>(s);
+    const int al = t & 15, u = t >> 4;
+    float2* const base = buf + 32 * al + (al >> 2) + 16 * (u >> 1) + 8 * ((u ^ (al >> 1)) & 1);
+    float2* const lo = base + 4 * (al & 1);
+    float2* const hi = base - 4 * (al & 1);
+#pragma unroll
+    for (int r = 0; r < 8; ++r) (r < 4 ? lo : hi)[r] = s[r];
+  };
+  // ... and the rest of the transform from that exchange on (part_b's fft_lanes_part for the panel's first stage)
+  [[maybe_unused]] auto rest_from_regs = [&](float2 (&v)[8]) {
+    if constexpr (!PAIR) return;
+    using W = TwN<NF>;
+    group_sync<T>();
+    const int e0 = t ^ ((t >> 5) << 2), e1 = e0 ^ 8;
+#pragma unroll
+    for (int m = 0; m < 8; ++m) v[m] = buf[((m & 1) ? e1 : e0) + 64 * m + (m >> 1)];
+    group_sync<T>();
+    fft_stage<NF, 8, 8, false, W::off1, W::lds1, true, TwRegs, 0>(v, twsrc, tf, fbuf);
+    fft_stage<NF, 8, 64, true, W::off2, W::lds2, false, TwRegs, 0>(v, twsrc, tf, fbuf);
+  };
 
   auto part_a = [&](int cc) {
     const int cur = cc & 1;
@@ -2036,7 +2096,8 @@ __global__ __launch_bounds__(N, (N >= 256 ? KF<N>::WPS : 1)) void k_fused_pass(F
   auto part_b = [&](int cc, bool wait_copy = false) {
     const size_t b = cand_of(cc);
     float2 v[8];
-    fft_lanes_part<NF, true, TwRegs, 2, 1>(v, twsrc, tf, fbuf);  // v[m] = C[kx = t + m*T] (SPLIT: kx = 2 (tf + 64 m) + h); the exchanges reuse the row's panel slots
+    if constexpr (PAIR) rest_from_regs(v);
+    else fft_lanes_part<NF, true, TwRegs, 2, 1>(v, twsrc, tf, fbuf);  // v[m] = C[kx = t + m*T] (SPLIT: kx = 2 (tf + 64 m) + h); the exchanges reuse the row's panel slots
     if (wait_copy) lds_dma_wait();
 
     bool scored = false;
@@ -2180,13 +2241,11 @@ __global__ __launch_bounds__(N, (N >= 256 ? KF<N>::WPS : 1)) void k_fused_pass(F
       if (more) stage_pair(p + 1);
       const int ca = 2 * p - pr_first;   // A's candidate number in the piece; B's is ca + 1
       if (ca >= 0) {
-        hand_over(sa[0], sa[1], sa[2], sa[3], sa[4], sa[5], sa[6], sa[7]);
-        first_stage();
+        first_stage_regs(sa);
         part_b(ca);
       }
       if (ca + 1 < nc) {   // (always, when another pair follows)
-        hand_over(sb[0], sb[1], sb[2], sb[3], sb[4], sb[5], sb[6], sb[7]);
-        first_stage();
+        first_stage_regs(sb);
         part_b(ca + 1, more);
       }
     }
