@@ -1270,19 +1270,7 @@ __device__ __forceinline__ void group_sum3(float& a, float& b, float& c) {
   }
 }
 
-// Two registers of a full wavefront exchange halves (gfx950's v_permlane32_swap_b32 / v_permlane16_swap_b32): lanes 32-63
-// of d with lanes 0-31 of s, or the odd 16-lane rows of d with the even rows of s — a 2 x 2 transpose between one lane
-// bit (5 or 4) and the choice of register.
-__device__ __forceinline__ void lane_swap32(float& d, float& s) {
-  const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(d), __float_as_uint(s), false, false);
-  d = __uint_as_float(r[0]);
-  s = __uint_as_float(r[1]);
-}
-__device__ __forceinline__ void lane_swap16(float& d, float& s) {
-  const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(d), __float_as_uint(s), false, false);
-  d = __uint_as_float(r[0]);
-  s = __uint_as_float(r[1]);
-}
+typedef float f32x4 __attribute__((ext_vector_type(4)));  // one tile of v_mfma_f32_4x4x1_16b_f32's accumulator (the pair build)
 
 // A workgroup owns ONE ky block (8 spectrum rows, one per transform group) and walks CPW candidates:
 // the rows' mask weights and centred reference values are loaded once into registers and serve all
@@ -1691,7 +1679,7 @@ __global__ __launch_bounds__(N, (N >= 256 ? KF<N>::WPS : 1)) void k_fused_pass(F
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   float2* const bufs = reinterpret_cast<float2*>(smem);
   float2* const gs = reinterpret_cast<float2*>(smem + K::LDS_BUF);                       // [8][rows_lds]; twist walk: [2][8][rows_lds], PAIR: [8][rows_lds][2]
-  float* const eg = reinterpret_cast<float*>(smem + K::LDS_BUF + (size_t)GBUF * 8 * a.rows_lds * sizeof(float2));  // [2][kg][N]; twist walk: [kg][N]
+  float* const eg = reinterpret_cast<float*>(smem + K::LDS_BUF + (size_t)GBUF * 8 * a.rows_lds * sizeof(float2));  // [2][kg][N]; twist walk: [kg][N], PAIR: a row's columns 64 m + lane at [m >> 2][lane][m & 3] (stage_factors)
   int* const cgs = reinterpret_cast<int*>(eg + (size_t)FBUF * a.kg * N);                 // [2][N/4 + 4]; twist walk: [N/4 + 4]
   constexpr int CGS = cgs_stride<N>();
   const int tid = threadIdx.x;
@@ -1863,8 +1851,19 @@ __global__ __launch_bounds__(N, (N >= 256 ? KF<N>::WPS : 1)) void k_fused_pass(F
   // column factors of the first candidate (later ones are fetched under the previous transform)
   const int n_e4 = a.kg * (N / 4);  // float4 pieces of one candidate's factors
   auto stage_factors = [&](int b) {
-    const float4* const src = reinterpret_cast<const float4*>(a.eg + (size_t)b * a.kg * N);
-    for (int e = tid; e < n_e4; e += K::THREADS) reinterpret_cast<float4*>(eg)[e] = src[e];
+    if constexpr (PAIR) {
+      // the pair build reads a table row's factors as the matrix pipe's B operands, tile m = columns 64 m + lane: piece
+      // e = (k, half, lane) holds columns 64 (4 half + i) + lane, i < 4 — a permutation inside every table row
+      static_assert(N == 512, "the pair walk's factor layout is [k][2][64][4]");
+      const float* const srcf = a.eg + (size_t)b * a.kg * N;
+      for (int e = tid; e < n_e4; e += K::THREADS) {
+        const float* const s = srcf + (size_t)(e >> 7) * N + ((e >> 6) & 1) * 256 + (e & 63);
+        reinterpret_cast<float4*>(eg)[e] = make_float4(s[0], s[64], s[128], s[192]);
+      }
+    } else {
+      const float4* const src = reinterpret_cast<const float4*>(a.eg + (size_t)b * a.kg * N);
+      for (int e = tid; e < n_e4; e += K::THREADS) reinterpret_cast<float4*>(eg)[e] = src[e];
+    }
     if (tid < CGS) cgs[tid] = a.cgs[(size_t)b * CGS + tid];
   };
   stage_factors(ffirst);  // buffer 0
@@ -1880,10 +1879,18 @@ __global__ __launch_bounds__(N, (N >= 256 ? KF<N>::WPS : 1)) void k_fused_pass(F
   // twist walk: what the build needs of the factor set is the same for every candidate of the workgroup — the first
   // table rows of the lane's two column groups and the row count
   [[maybe_unused]] int tw_cg0 = 0, tw_cg1 = 0, tw_kgn = 1;
+  // PAIR: the lane's eight A-operand addresses in the wavefront's pair buffer (bytes from gs).  In tile m (columns
+  // 64 m + lane) lane L = 4 b + i stands in column group 16 m + b and supplies float i of the group's 16-byte entries.
+  [[maybe_unused]] unsigned tw_ao[8];
   if constexpr (TW) {
-    tw_cg0 = cgs[t];
-    tw_cg1 = cgs[t + T];
-    tw_kgn = max(1, min(a.kg, __builtin_amdgcn_readfirstlane(cgs[N / 4])));
+    if constexpr (PAIR) {
+#pragma unroll
+      for (int m = 0; m < 8; ++m) tw_ao[m] = (unsigned)(gi * a.rows_lds + cgs[16 * m + (t >> 2)]) * 16u + 4u * (unsigned)(t & 3);
+    } else {
+      tw_cg0 = cgs[t];
+      tw_cg1 = cgs[t + T];
+    }
+    tw_kgn = max(1, min(PAIR ? min(a.kg, 16) : a.kg, __builtin_amdgcn_readfirstlane(cgs[N / 4])));
   }
 
   // One candidate = part A (build the row from the table slice and the candidate's factors, first butterflies, data
@@ -1940,53 +1947,12 @@ __global__ __launch_bounds__(N, (N >= 256 ? KF<N>::WPS : 1)) void k_fused_pass(F
     if constexpr (T > 64 && !SPLIT) __syncthreads();  // both wavefronts of a row have read it before either exchanges in it
     fft_lanes_part<NF, true, TwRegs, 1, 1>(v, twsrc, tf, fbuf);
   };
-  // PAIR: a built row goes to the transform in registers, not through the panel.  Lane t holds the sums of columns
-  // x = 256 h + 4 t + c in s[4 h + c]; the first stage wants x = 64 m + j in one lane.  With m = 4 h + (t >> 4) and
-  // j = 4 (t & 15) + c that is a 4 x 4 transpose between lane bits [5:4] and c: v_permlane32_swap on the registers
-  // (c, c + 2), v_permlane16_swap on (c, c + 1), 16 swaps for the 16 floats and no register more.  Lane L then holds
-  // s[m] = x[64 m + j'], j' = 4 (L & 15) + (L >> 4): the inputs of butterfly j'.  The stage has no twiddles, so only the
-  // exchange has to know j': the outputs are elements o = 8 j' + r = 32 a + 8 u + r with a = L & 15, u = L >> 4.
-  // The 16 lanes of a ds_write_b64 group are the 16 a of one u: 256 bytes apart in plain slots, and still four to a bank
-  // pair under fft_stage's xor.  Element o = 32 a + w (w = o & 31) is kept in
-  //   slot(o) = 32 a + (a >> 2) + (w ^ 4 (a & 3))
-  // — one slot of padding per four a (three of the panel row's four spare slots: the highest slot is 514 of 516) and a's
-  // two low bits xored into bits 3:2 of w.  Modulo the 16 bank pairs a store group's slots are (a >> 2) + 4 k(a & 3) +
-  // const with k a permutation of 0..3: all 16.  Writer: bit 3 of the xor is a lane constant and bit 2 turns r into
-  // r ^ 4 (a & 1), so r < 4 go to one base + r and r >= 4 to a second base + r (two base registers, the immediates
-  // stay, no xor per store).  Reader of element n = t + 64 m: a = 2 m + (t >> 5), w = t & 31, so the slot is
-  // 64 m + (m >> 1) + e0 for even m and + (e0 ^ 8) for odd m, e0 = t ^ ((t >> 5) << 2): two bases plus immediates, and
-  // the 32 lanes of a ds_read_b64 group (16 of a ds_read2_b64 group) on as many consecutive slots up to that xor.
-  // Every later exchange and stage is fft_stage's own, so v[m] = X[t + 64 m] comes out as from the panel.
+  // PAIR: a built row goes to the transform in registers, not through the panel.  build_pair leaves tile m of the
+  // matrix pipe's accumulators = columns 64 m + lane, so s[m] = x[64 m + t] is the first stage's own input order: the
+  // stage and its exchange are fft_stage's, as after the panel's read in FFT order.
   [[maybe_unused]] auto first_stage_regs = [&](float2 (&s)[8]) {
-    if constexpr (!PAIR) return;
-#pragma unroll
-    for (int h4 = 0; h4 < 8; h4 += 4) {
-      lane_swap32(s[h4].x, s[h4 + 2].x); lane_swap32(s[h4].y, s[h4 + 2].y);
-      lane_swap32(s[h4 + 1].x, s[h4 + 3].x); lane_swap32(s[h4 + 1].y, s[h4 + 3].y);
-      lane_swap16(s[h4].x, s[h4 + 1].x); lane_swap16(s[h4].y, s[h4 + 1].y);
-      lane_swap16(s[h4 + 2].x, s[h4 + 3].x); lane_swap16(s[h4 + 2].y, s[h4 + 3].y);
-    }
-    bfly<8>(s);
-    const int al = t & 15, u = t >> 4;
-    float2* const base = buf + 32 * al + (al >> 2) + 16 * (u >> 1) + 8 * ((u ^ (al >> 1)) & 1);
-    float2* const lo = base + 4 * (al & 1);
-    float2* const hi = base - 4 * (al & 1);
-#pragma unroll
-    for (int r = 0; r < 8; ++r) (r < 4 ? lo : hi)[r] = s[r];
+    if constexpr (PAIR) fft_lanes_part<NF, true, TwRegs, 1, 1>(s, twsrc, tf, fbuf);
   };
-  // ... and the rest of the transform from that exchange on (part_b's fft_lanes_part for the panel's first stage)
-  [[maybe_unused]] auto rest_from_regs = [&](float2 (&v)[8]) {
-    if constexpr (!PAIR) return;
-    using W = TwN<NF>;
-    group_sync<T>();
-    const int e0 = t ^ ((t >> 5) << 2), e1 = e0 ^ 8;
-#pragma unroll
-    for (int m = 0; m < 8; ++m) v[m] = buf[((m & 1) ? e1 : e0) + 64 * m + (m >> 1)];
-    group_sync<T>();
-    fft_stage<NF, 8, 8, false, W::off1, W::lds1, true, TwRegs, 0>(v, twsrc, tf, fbuf);
-    fft_stage<NF, 8, 64, true, W::off2, W::lds2, false, TwRegs, 0>(v, twsrc, tf, fbuf);
-  };
-
   auto part_a = [&](int cc) {
     const int cur = cc & 1;
     const float* const egc = TW ? eg : eg + (size_t)cur * a.kg * N;
@@ -2056,39 +2022,33 @@ __global__ __launch_bounds__(N, (N >= 256 ? KF<N>::WPS : 1)) void k_fused_pass(F
     first_stage();
   };
 
-  // PAIR: the sums of runs A and B of the wavefront's pair buffer in one pass over the factor rows.  Per table row and
-  // column group one 16-byte read of {G_A, G_B} and one of the four factors feed 16 FMAs; every sum keeps the operands
-  // and the order it has in part_a's build.
-  [[maybe_unused]] auto build_pair = [&](float2 (&sa)[8], float2 (&sb)[8]) {
-    const float4* const grow0 = reinterpret_cast<const float4*>(gs) + gi * a.rows_lds + tw_cg0;
-    const float4* const grow1 = reinterpret_cast<const float4*>(gs) + gi * a.rows_lds + tw_cg1;
-    const float* const erow0 = eg + 4 * t;
-    const float* const erow1 = eg + 4 * (t + T);
+  // PAIR: the sums of runs A and B of the wavefront's pair buffer in one pass over the factor rows, on the matrix pipe.
+  // v_mfma_f32_4x4x1_16b_f32 is sixteen 4 x 4 outer products, one per block of four lanes: D_b[i][j] += A[4 b + i] B[4 b + j],
+  // D_b[i][j] in register i of lane 4 b + j.  Block b of tile m is column group 16 m + b: A is its table entry
+  // {G_A.re, G_A.im, G_B.re, G_B.im} (one float per lane), B its four column factors, D one table row of both runs' sums
+  // for the group's four columns.  Register i of acc[m] in lane L is then component i of column 64 m + L.  f32 MFMA is an
+  // fmaf chain (mfma_tile.inc), the rows come in the order of part_a's build and the first row starts from a zero C:
+  // fma(e, g, +0) is e g, but for a -0 product, which becomes +0.  A lane's eight factors of a row are two 16-byte reads
+  // (stage_factors' layout); the A addresses are tw_ao plus the row as an instruction offset: the rows are unrolled,
+  // each behind a scalar test.
+  [[maybe_unused]] auto build_pair = [&](f32x4 (&acc)[8]) {
+    const char* const gb = reinterpret_cast<const char*>(gs);
+    const float4* const erow = reinterpret_cast<const float4*>(eg) + t;
     {
-      const float4 g0 = grow0[0], g1 = grow1[0];
-      const float4 ea = *reinterpret_cast<const float4*>(erow0), eb = *reinterpret_cast<const float4*>(erow1);
-      const float e0[4] = {ea.x, ea.y, ea.z, ea.w}, e1[4] = {eb.x, eb.y, eb.z, eb.w};
+      const float4 ea = erow[0], eb = erow[64];
+      const float e[8] = {ea.x, ea.y, ea.z, ea.w, eb.x, eb.y, eb.z, eb.w};
 #pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        sa[c] = make_float2(e0[c] * g0.x, e0[c] * g0.y);
-        sb[c] = make_float2(e0[c] * g0.z, e0[c] * g0.w);
-        sa[4 + c] = make_float2(e1[c] * g1.x, e1[c] * g1.y);
-        sb[4 + c] = make_float2(e1[c] * g1.z, e1[c] * g1.w);
-      }
+      for (int m = 0; m < 8; ++m)
+        acc[m] = __builtin_amdgcn_mfma_f32_4x4x1f32(*reinterpret_cast<const float*>(gb + tw_ao[m]), e[m], f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
     }
-#pragma unroll 1
-    for (int k = 1; k < tw_kgn; ++k) {
-      const float4 g0 = grow0[k], g1 = grow1[k];
-      const float4 ea = *reinterpret_cast<const float4*>(erow0 + (size_t)k * N);
-      const float4 eb = *reinterpret_cast<const float4*>(erow1 + (size_t)k * N);
-      const float e0[4] = {ea.x, ea.y, ea.z, ea.w}, e1[4] = {eb.x, eb.y, eb.z, eb.w};
 #pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        sa[c].x = fmaf(e0[c], g0.x, sa[c].x); sa[c].y = fmaf(e0[c], g0.y, sa[c].y);
-        sb[c].x = fmaf(e0[c], g0.z, sb[c].x); sb[c].y = fmaf(e0[c], g0.w, sb[c].y);
-        sa[4 + c].x = fmaf(e1[c], g1.x, sa[4 + c].x); sa[4 + c].y = fmaf(e1[c], g1.y, sa[4 + c].y);
-        sb[4 + c].x = fmaf(e1[c], g1.z, sb[4 + c].x); sb[4 + c].y = fmaf(e1[c], g1.w, sb[4 + c].y);
-      }
+    for (int k = 1; k < 16; ++k) {   // (fused_shape: kg <= 16)
+      if (k >= tw_kgn) break;
+      const float4 ea = erow[k * (N / 4)], eb = erow[k * (N / 4) + 64];
+      const float e[8] = {ea.x, ea.y, ea.z, ea.w, eb.x, eb.y, eb.z, eb.w};
+#pragma unroll
+      for (int m = 0; m < 8; ++m)
+        acc[m] = __builtin_amdgcn_mfma_f32_4x4x1f32(*reinterpret_cast<const float*>(gb + tw_ao[m] + k * 16), e[m], acc[m], 0, 0, 0);
     }
   };
 
@@ -2096,8 +2056,7 @@ __global__ __launch_bounds__(N, (N >= 256 ? KF<N>::WPS : 1)) void k_fused_pass(F
   auto part_b = [&](int cc, bool wait_copy = false) {
     const size_t b = cand_of(cc);
     float2 v[8];
-    if constexpr (PAIR) rest_from_regs(v);
-    else fft_lanes_part<NF, true, TwRegs, 2, 1>(v, twsrc, tf, fbuf);  // v[m] = C[kx = t + m*T] (SPLIT: kx = 2 (tf + 64 m) + h); the exchanges reuse the row's panel slots
+    fft_lanes_part<NF, true, TwRegs, 2, 1>(v, twsrc, tf, fbuf);  // v[m] = C[kx = t + m*T] (SPLIT: kx = 2 (tf + 64 m) + h); the exchanges reuse the row's panel slots
     if (wait_copy) lds_dma_wait();
 
     bool scored = false;
@@ -2235,8 +2194,11 @@ __global__ __launch_bounds__(N, (N >= 256 ? KF<N>::WPS : 1)) void k_fused_pass(F
     const int pair_end = (pr_first + nc + 1) >> 1;
 #pragma unroll 1
     for (int p = pr_first >> 1; p < pair_end; ++p) {
+      f32x4 acc[8];
+      build_pair(acc);
       float2 sa[8], sb[8];
-      build_pair(sa, sb);
+#pragma unroll
+      for (int m = 0; m < 8; ++m) sa[m] = make_float2(acc[m][0], acc[m][1]), sb[m] = make_float2(acc[m][2], acc[m][3]);
       const bool more = p + 1 < pair_end;
       if (more) stage_pair(p + 1);
       const int ca = 2 * p - pr_first;   // A's candidate number in the piece; B's is ca + 1
