@@ -62,7 +62,7 @@ def filtered(eng, img, mask, cutoff, size, lp, hp, params, log=True):
 
 
 @pytest.mark.parametrize("lp,hp", FILTERS)
-@pytest.mark.parametrize("size", [(48, 48), (45, 63)])
+@pytest.mark.parametrize("size", [(48, 48), (45, 63), (45, 64), (64, 45)])   # even, odd and mixed parity: the operator pairs
 def test_filtered_zoomed_sweep_finds_the_truth(size, lp, hp):
     ny = nx = 64
     apix, cutoff = 2.0, (8, 8)
