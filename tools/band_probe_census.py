@@ -3,8 +3,11 @@
 length the smallest change of a band's oracle score over all adjacent-column swaps, the same for a kx <-> -kx mirror, the
 float32 floor of the reference pipeline and the tolerance that follows from it, for both experimental images of the probe
 (each with the candidate it was made from); prints the worst of each (DESIGN.md,
-"Row-length census").
-    python tools/band_probe_census.py [--jobs 8] [--lo 8] [--hi 1024]"""
+"Row-length census").  With --square: the same figures on the square planes N = 32 ... 1024 of the tuned sweep with the
+4 x 8 list of tests/square_bands.py, and the one-line-shift sensitivity of the quadrant masks ("Square-plane
+census"; about a minute, N = 1024 most of it).
+    python tools/band_probe_census.py [--jobs 8] [--lo 8] [--hi 1024]
+    python tools/band_probe_census.py --square [--sizes 32 64 128]"""
 import argparse
 import sys
 from concurrent.futures import ProcessPoolExecutor
@@ -31,12 +34,36 @@ def one(nx):
     return rows
 
 
+def square(sizes):
+    """The host table of the square-plane census: one row per size, the worst of log1p|F| and |F|."""
+    import square_bands as Q
+
+    print("| N | subunits | kg | smallest swap, \\|kx\\| bands (cand 0 / last) | smallest swap, \\|ky\\| bands (cand 0 / last) | smallest mirror | "
+          "largest floor | smallest own score | quadrant masks | smallest one-line shift (image / image2) |")
+    print("|---|---|---|---|---|---|---|---|---|---|")
+    bad = 0
+    for n in sizes or Q.SIZES:
+        (_, units, kg, kx0, kx1, ky0, ky1, mirror, floor, own), = Q.host_table((n,))
+        f = Q.fold_side(n)
+        s0, s1 = f.shift_sensitivity(0), f.shift_sensitivity(1)
+        tol = max(SB.ORACLE_TOL, SB.FLOOR_FACTOR * floor)
+        bad += min(kx0, kx1, ky0, ky1, mirror) < SB.MARGIN * tol or bool((np.minimum(s0, s1) < SB.MARGIN * f.tol).any()) or own < Q.MIN_OWN_SCORE
+        print(f"| {n} | {units} | {kg} | {kx0:.1e} / {kx1:.1e} | {ky0:.1e} / {ky1:.1e} | {mirror:.1e} | {floor:.1e} | {own:.3f} | {len(f.masks)} | "
+              f"{s0.min():.1e} / {s1.min():.1e} |", flush=True)
+    print(f"{bad} sizes below {SB.MARGIN:.0f} x tolerance or below an own-candidate score of {Q.MIN_OWN_SCORE}")
+    return 1 if bad else 0
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--square", action="store_true", help="the square planes of the tuned sweep (tests/square_bands.py)")
+    ap.add_argument("--sizes", type=int, nargs="*", default=None, help="with --square: the sizes (default: all six)")
     ap.add_argument("--jobs", type=int, default=8)
     ap.add_argument("--lo", type=int, default=8)
     ap.add_argument("--hi", type=int, default=1024)
     a = ap.parse_args()
+    if a.square:
+        return square(a.sizes)
     two, stockham, direct = SB.census()
     family = {**{n: "two-step" for n in two}, **{n: "stockham" for n in stockham}, **{n: "direct" for n in direct}}
     with ProcessPoolExecutor(a.jobs) as ex:
