@@ -388,14 +388,12 @@ int am_radius(double sigma) {
 unsigned am_grid(int64_t n, int64_t cap) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, cap)); }
 
 struct AmScratch {
-  double *a = nullptr, *b = nullptr, *taps = nullptr, *small = nullptr;   // small: edges [257], pmin [AM_GRID], pmax [AM_GRID]
-  int32_t* parent = nullptr;
-  uint8_t *above = nullptr, *keep = nullptr, *mask = nullptr;
-  unsigned long long* words = nullptr;   // [AM_WORDS + 256]
+  DevBuf<double> a, b, taps, small;        // small: edges [257], pmin [AM_GRID], pmax [AM_GRID]
+  DevBuf<int32_t> parent;
+  DevBuf<uint8_t> above, keep, mask;
+  DevBuf<unsigned long long> words;        // [AM_WORDS + 256]
   hipEvent_t ev[AM_EVENTS] = {};
   ~AmScratch() {
-    (void)hipFree(a); (void)hipFree(b); (void)hipFree(taps); (void)hipFree(small); (void)hipFree(parent);
-    (void)hipFree(above); (void)hipFree(keep); (void)hipFree(mask); (void)hipFree(words);
     for (hipEvent_t e : ev)
       if (e) (void)hipEventDestroy(e);
   }
@@ -403,21 +401,23 @@ struct AmScratch {
 };
 
 int am_reserve(AmScratch* s, int64_t n, bool planes, bool labels, bool keep, bool mask, const double* taps, int r) {
+  int rc = HH_OK;
   if (planes) {
-    HH_HIP(nullptr, hipMalloc(&s->a, (size_t)n * sizeof(double)));
-    HH_HIP(nullptr, hipMalloc(&s->b, (size_t)n * sizeof(double)));
-    HH_HIP(nullptr, hipMalloc(&s->small, (size_t)(257 + 2 * AM_GRID) * sizeof(double)));
+    rc = ensure(nullptr, s->a, (size_t)n);
+    if (!rc) rc = ensure(nullptr, s->b, (size_t)n);
+    if (!rc) rc = ensure(nullptr, s->small, (size_t)(257 + 2 * AM_GRID));
   }
-  if (labels) {
-    HH_HIP(nullptr, hipMalloc(&s->parent, (size_t)n * sizeof(int32_t)));
-    HH_HIP(nullptr, hipMalloc(&s->above, (size_t)n));
+  if (!rc && labels) {
+    rc = ensure(nullptr, s->parent, (size_t)n);
+    if (!rc) rc = ensure(nullptr, s->above, (size_t)n);
   }
-  if (keep) HH_HIP(nullptr, hipMalloc(&s->keep, (size_t)n));
-  if (mask) HH_HIP(nullptr, hipMalloc(&s->mask, (size_t)n));
-  HH_HIP(nullptr, hipMalloc(&s->words, (size_t)(AM_WORDS + 256) * sizeof(unsigned long long)));
-  HH_HIP(nullptr, hipMemset(s->words, 0, (size_t)(AM_WORDS + 256) * sizeof(unsigned long long)));
+  if (!rc && keep) rc = ensure(nullptr, s->keep, (size_t)n);
+  if (!rc && mask) rc = ensure(nullptr, s->mask, (size_t)n);
+  if (!rc) rc = ensure(nullptr, s->words, (size_t)(AM_WORDS + 256));
+  if (!rc && taps) rc = ensure(nullptr, s->taps, (size_t)(r + 1));
+  if (rc) return rc;
+  HH_HIP(nullptr, hipMemset(s->words, 0, s->words.bytes()));
   if (taps) {
-    HH_HIP(nullptr, hipMalloc(&s->taps, (size_t)(r + 1) * sizeof(double)));
     HH_HIP(nullptr, hipMemcpy(s->taps, taps, (size_t)(r + 1) * sizeof(double), hipMemcpyHostToDevice));
   }
   for (hipEvent_t& e : s->ev) HH_HIP(nullptr, hipEventCreate(&e));
@@ -645,7 +645,7 @@ extern "C" int hh_am_mask_3d(int device, const void* vol, int is_f64, int32_t nz
   if (is_f64) {
     HH_HIP(nullptr, hipMemcpy(s.a, vol, (size_t)n * sizeof(double), hipMemcpyHostToDevice));
   } else {   // the float32 volume is staged in the second plane and widened into the first
-    float* const stage = reinterpret_cast<float*>(s.b);
+    float* const stage = reinterpret_cast<float*>(s.b.get());
     HH_HIP(nullptr, hipMemcpy(stage, vol, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
     hipLaunchKernelGGL(k_am_widen, dim3(am_grid(n, 4096)), dim3(256), 0, nullptr, stage, (const float*)nullptr, s.a, n);
     HH_HIP(nullptr, hipGetLastError());
@@ -666,9 +666,9 @@ extern "C" int hh_am_context_support(hh_tfsc* ctx, int one_mask, double sigma, c
   const int n_sup = one_mask ? 1 : 2;
   const int64_t n = c->per_map;
   if (sm->n_sup != n_sup) {
-    (void)hipFree(sm->sup);
-    sm->sup = nullptr; sm->n_sup = 0;
-    HH_HIP(nullptr, hipMalloc(&sm->sup, (size_t)n_sup * (size_t)n));
+    sm->sup.reset();
+    sm->n_sup = 0;
+    if (int rc = ensure(nullptr, sm->sup, (size_t)n_sup * (size_t)n)) return rc;
   }
   AmScratch s;
   if (int rc = am_reserve(&s, n, true, true, true, false, sigma != 0.0 ? taps : nullptr, sigma != 0.0 ? am_radius(sigma) : 0)) return rc;

@@ -194,12 +194,12 @@ int filt_prepare(hh_ctx* c, const uint8_t* mask) {
   z->f_all_tiles = ftu * ftv;
   for (int i = 0; i < ftu * ftv; ++i) ft.push_back(i);
   int rc;
-  if ((rc = ensure_bytes(c, (void**)&z->d_ay, &z->cap_ay, ay.size() * sizeof(float)))) return rc;
-  if ((rc = ensure_bytes(c, (void**)&z->d_ax, &z->cap_ax, ax.size() * sizeof(float)))) return rc;
-  if ((rc = ensure_bytes(c, (void**)&z->d_tiles_all, &z->cap_tiles_all, all.size() * sizeof(int)))) return rc;
-  if ((rc = ensure_bytes(c, (void**)&z->d_ftiles, &z->cap_ftiles, ft.size() * sizeof(int)))) return rc;
-  if ((rc = ensure_bytes(c, (void**)&z->d_fq, &z->cap_fq, plane * sizeof(float)))) return rc;
-  if ((rc = ensure_bytes(c, (void**)&z->d_ft, &z->cap_ft, (size_t)terms * plane * sizeof(float)))) return rc;
+  if ((rc = ensure(c, z->d_ay, ay.size()))) return rc;
+  if ((rc = ensure(c, z->d_ax, ax.size()))) return rc;
+  if ((rc = ensure(c, z->d_tiles_all, all.size()))) return rc;
+  if ((rc = ensure(c, z->d_ftiles, ft.size()))) return rc;
+  if ((rc = ensure(c, z->d_fq, plane))) return rc;
+  if ((rc = ensure(c, z->d_ft, (size_t)terms * plane))) return rc;
   HH_HIP(c, hipMemcpyAsync(z->d_ay, ay.data(), ay.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
   HH_HIP(c, hipMemcpyAsync(z->d_ax, ax.data(), ax.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
   HH_HIP(c, hipMemcpyAsync(z->d_tiles_all, all.data(), all.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
@@ -231,9 +231,9 @@ int filt_sweep(hh_ctx* c, const double* d_params, int64_t n_cand, float* d_score
   const int64_t fit = std::max<int64_t>(1, FS_BYTES / (int64_t)((1 + J) * plane * sizeof(float)));
   const int64_t cap = std::min<int64_t>(n_cand, std::min<int64_t>(fit, FS_BATCH));
   int rc;
-  if ((rc = ensure_bytes(c, (void**)&z->d_fq, &z->cap_fq, (size_t)cap * plane * sizeof(float)))) return rc;
-  if ((rc = ensure_bytes(c, (void**)&z->d_ft, &z->cap_ft, (size_t)J * cap * plane * sizeof(float)))) return rc;
-  if ((rc = ensure_bytes(c, (void**)&z->d_fpart, &z->cap_fpart, (size_t)S * cap * npart * 3 * sizeof(double)))) return rc;
+  if ((rc = ensure(c, z->d_fq, (size_t)cap * plane))) return rc;
+  if ((rc = ensure(c, z->d_ft, (size_t)J * cap * plane))) return rc;
+  if ((rc = ensure(c, z->d_fpart, (size_t)S * cap * npart * 3))) return rc;
   c->last_first_pass = 4;
   const int all_tiles = ((z->r_ony + ZS_TU - 1) / ZS_TU) * ((z->r_onx + ZS_TV - 1) / ZS_TV);
   for (int64_t b0 = 0; b0 < n_cand; b0 += cap) {

@@ -217,17 +217,16 @@ constexpr int64_t FC_SCRATCH_BYTES = (int64_t)8 << 30;   // device planes of one
 // Device scratch of the forward passes and the sums, grow-only, plus a caller's operators / shell table and the two events
 // that time a chunk.
 struct FcBuffers {
-  float *in = nullptr, *p1 = nullptr, *p2 = nullptr, *mats = nullptr;   // p1 / p2: [re | im] plane pairs
-  int32_t* shell = nullptr;
-  unsigned* amax = nullptr;
-  double *scale = nullptr, *sums = nullptr;
-  long long* acc = nullptr;
+  DevBuf<float> in, p1, p2, mats;   // p1 / p2: [re | im] plane pairs
+  DevBuf<int32_t> shell;
+  DevBuf<unsigned> amax;            // [pairs][2]: its size says how many pairs the scratch holds
+  DevBuf<double> scale, sums;
+  DevBuf<long long> acc;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  int64_t cap = 0, cap_per_map = 0;   // pairs the scratch holds, and the shape it was sized for
-  int cap_nshell = 0;
-  void release() {
-    (void)hipFree(in); (void)hipFree(p1); (void)hipFree(p2); (void)hipFree(amax); (void)hipFree(scale); (void)hipFree(sums); (void)hipFree(acc);
-    in = p1 = p2 = nullptr; amax = nullptr; scale = sums = nullptr; acc = nullptr; cap = 0;
+  int64_t shape_per_map = 0;        // the shape the scratch was sized for
+  int shape_nshell = 0;
+  void release() {                  // the scratch only: mats and shell are the caller's
+    in.reset(); p1.reset(); p2.reset(); amax.reset(); scale.reset(); sums.reset(); acc.reset();
   }
   // Room for `pairs` pairs of maps of per_map voxels: 2 input maps per pair (`with_in`; else the caller's maps are read in
   // place), 4 planes per pair in p1 and (cubes) p2, and at least two curve sets of nshell x 3 sums (the two curves of a
@@ -236,25 +235,28 @@ struct FcBuffers {
   int reserve(int64_t pairs, int64_t per_map, int nshell, bool cube, bool with_in) {
     if (!ev0) HH_HIP(nullptr, hipEventCreate(&ev0));
     if (!ev1) HH_HIP(nullptr, hipEventCreate(&ev1));
-    if (cap > 0 && (per_map != cap_per_map || nshell != cap_nshell)) return fail(nullptr, HH_ERR_STATE, "FcBuffers::reserve: another shape than the holder's");
+    const int64_t cap = (int64_t)amax.size() / 2;
+    if (cap > 0 && (per_map != shape_per_map || nshell != shape_nshell)) return fail(nullptr, HH_ERR_STATE, "FcBuffers::reserve: another shape than the holder's");
     if (pairs <= cap && (!with_in || in)) return HH_OK;
     pairs = std::max(pairs, cap);
-    release();
-    const size_t map_bytes = (size_t)per_map * sizeof(float);
-    if (with_in) HH_HIP(nullptr, hipMalloc(&in, 2 * (size_t)pairs * map_bytes));
-    HH_HIP(nullptr, hipMalloc(&p1, 4 * (size_t)pairs * map_bytes));
-    if (cube) HH_HIP(nullptr, hipMalloc(&p2, 4 * (size_t)pairs * map_bytes));
+    release();   // all of the old scratch goes before any of the new is asked for
+    const size_t maps = (size_t)pairs * per_map;
     const size_t n_sums = (size_t)std::max<int64_t>(pairs, 2) * nshell * 3;
-    HH_HIP(nullptr, hipMalloc(&amax, 2 * (size_t)pairs * sizeof(unsigned)));
-    HH_HIP(nullptr, hipMalloc(&scale, (size_t)pairs * 3 * sizeof(double)));
-    HH_HIP(nullptr, hipMalloc(&acc, n_sums * sizeof(long long)));
-    HH_HIP(nullptr, hipMalloc(&sums, n_sums * sizeof(double)));
-    cap = pairs; cap_per_map = per_map; cap_nshell = nshell;
+    int rc = with_in ? ensure(nullptr, in, 2 * maps) : HH_OK;
+    if (!rc) rc = ensure(nullptr, p1, 4 * maps);
+    if (!rc && cube) rc = ensure(nullptr, p2, 4 * maps);
+    if (!rc) rc = ensure(nullptr, scale, (size_t)pairs * 3);
+    if (!rc) rc = ensure(nullptr, acc, n_sums);
+    if (!rc) rc = ensure(nullptr, sums, n_sums);
+    if (!rc) rc = ensure(nullptr, amax, 2 * (size_t)pairs);   // last: a scratch that counts as holding pairs is whole
+    if (rc) {
+      release();
+      return rc;
+    }
+    shape_per_map = per_map; shape_nshell = nshell;
     return HH_OK;
   }
   ~FcBuffers() {
-    release();
-    (void)hipFree(mats); (void)hipFree(shell);
     if (ev0) (void)hipEventDestroy(ev0);
     if (ev1) (void)hipEventDestroy(ev1);
   }
@@ -377,10 +379,10 @@ int fc_run(const char* name, int device, const float* a, const float* b, int64_t
   FcBuffers d;
   const size_t map_bytes = (size_t)per_map * sizeof(float);
   if (int rc = d.reserve(chunk, per_map, nshell, cube, true)) return rc;
-  HH_HIP(nullptr, hipMalloc(&d.mats, p.mats.size() * sizeof(float)));
+  if (int rc = ensure(nullptr, d.mats, p.mats.size())) return rc;
   HH_HIP(nullptr, hipMemcpy(d.mats, p.mats.data(), p.mats.size() * sizeof(float), hipMemcpyHostToDevice));
   if (!cube) {
-    HH_HIP(nullptr, hipMalloc(&d.shell, (size_t)per_map * sizeof(int32_t)));
+    if (int rc = ensure(nullptr, d.shell, (size_t)per_map)) return rc;
     HH_HIP(nullptr, hipMemcpy(d.shell, shell, (size_t)per_map * sizeof(int32_t), hipMemcpyHostToDevice));
   }
   double ms_total = 0.0;

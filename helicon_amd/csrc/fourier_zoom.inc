@@ -87,16 +87,14 @@ extern "C" int hh_power_spectrum_zoom(int device, const float* image, int ny, in
   HH_HIP(nullptr, hipSetDevice(device));
   const ZoomDims d{ny, nx, ony, onx, 2 * apix / cutoff_y, 2 * apix / cutoff_x};
   const size_t n_in = (size_t)ny * nx, n_out = (size_t)ony * onx;
-  float* d_img = nullptr;
-  double2* d_r = nullptr;
-  float* d_out = nullptr;
-  unsigned* d_mm = nullptr;
-  hipError_t e = hipMalloc(&d_img, n_in * sizeof(float));
-  if (e == hipSuccess) e = hipMalloc(&d_r, (size_t)ny * onx * sizeof(double2));
-  if (e == hipSuccess) e = hipMalloc(&d_out, 2 * n_out * sizeof(float));
-  if (e == hipSuccess) e = hipMalloc(&d_mm, 2 * sizeof(unsigned));
+  DevArena mem;
+  float* d_img = mem.get<float>(n_in);
+  double2* d_r = mem.get<double2>((size_t)ny * onx);
+  float* d_out = mem.get<float>(2 * n_out);
+  unsigned* d_mm = mem.get<unsigned>(2);
+  if (int rc = arena_ok(nullptr, mem)) return rc;
   const unsigned init[2] = {0x7f800000u, 0u};
-  if (e == hipSuccess) e = hipMemcpy(d_img, image, n_in * sizeof(float), hipMemcpyHostToDevice);
+  hipError_t e = hipMemcpy(d_img, image, n_in * sizeof(float), hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(d_mm, init, sizeof(init), hipMemcpyHostToDevice);
   if (e == hipSuccess) {
     hipLaunchKernelGGL(k_zoom_rows, dim3((onx + 127) / 128, ny), dim3(128), 0, 0, d_img, d, apix, cutoff_x, d_r);
@@ -107,7 +105,6 @@ extern "C" int hh_power_spectrum_zoom(int device, const float* image, int ny, in
   }
   if (e == hipSuccess) e = hipMemcpy(pwr_out, d_out, n_out * sizeof(float), hipMemcpyDeviceToHost);
   if (e == hipSuccess && phase_out) e = hipMemcpy(phase_out, d_out + n_out, n_out * sizeof(float), hipMemcpyDeviceToHost);
-  (void)hipFree(d_img); (void)hipFree(d_r); (void)hipFree(d_out); (void)hipFree(d_mm);
   if (e != hipSuccess) return fail(nullptr, HH_ERR_HIP, std::string("hh_power_spectrum_zoom: ") + hipGetErrorString(e));
   return HH_OK;
 } HH_CATCH_CTX(nullptr, "hh_power_spectrum_zoom")

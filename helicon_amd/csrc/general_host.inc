@@ -1,5 +1,5 @@
 // general_host.inc — host side of the general-size path (included by helicon_hip.hip inside its anonymous namespace,
-// after fail / HH_HIP / ensure_bytes).  Kernels: general_sizes.inc.
+// after fail / HH_HIP / ensure).  Kernels: general_sizes.inc.
 
 bool gen_factor(int n, GenPlan& plan) {
   plan.n_stages = 0;
@@ -31,13 +31,7 @@ bool gen_factor(int n, GenPlan& plan) {
 }
 
 void gen_free(hh_ctx* c) {
-  hh_gen* g = c->gen;
-  if (!g) return;
-  for (void* p : {(void*)g->d_tw_nx, (void*)g->d_tw_ny, (void*)g->d_w2, (void*)g->d_table, (void*)g->d_eg, (void*)g->d_cgs,
-                  (void*)g->d_runs, (void*)g->d_run_of, (void*)g->d_layers, (void*)g->d_partials, (void*)g->d_r, (void*)g->d_f, (void*)g->d_cent, (void*)g->d_plan_params, (void*)g->d_differ,
-                  (void*)g->d_q, (void*)g->d_wec, (void*)g->d_cpart, (void*)g->d_psum, (void*)g->d_ref, (void*)g->d_seg_slices})
-    if (p) (void)hipFree(p);
-  delete g;
+  delete c->gen;   // its buffers free themselves
   c->gen = nullptr;
 }
 
@@ -59,9 +53,9 @@ int gen_create(hh_ctx* c, int ny, int nx) {
       const double ang = -2.0 * M_PI * (double)k / (double)n;
       tw[k] = make_float2((float)std::cos(ang), (float)std::sin(ang));
     }
-    float2** dst = pass ? &g->d_tw_ny : &g->d_tw_nx;
-    HH_HIP(c, hipMalloc(dst, tw.size() * sizeof(float2)));
-    HH_HIP(c, hipMemcpy(*dst, tw.data(), tw.size() * sizeof(float2), hipMemcpyHostToDevice));
+    DevBuf<float2>& dst = pass ? g->d_tw_ny : g->d_tw_nx;
+    if (int rc = ensure(c, dst, tw.size())) return rc;
+    HH_HIP(c, hipMemcpy(dst, tw.data(), tw.size() * sizeof(float2), hipMemcpyHostToDevice));
   }
   return HH_OK;
 }
@@ -71,12 +65,10 @@ int gen_spectra(hh_ctx* c, const float* images, int count) {
   hh_gen* g = c->gen;
   const GenDims& d = g->d;
   const size_t npix = (size_t)d.ny * d.nx;
-  size_t cap_img_b = (size_t)c->cap_img * sizeof(float);
-  int rc = ensure_bytes(c, (void**)&c->d_img, &cap_img_b, (size_t)count * npix * sizeof(float));
-  c->cap_img = (int64_t)(cap_img_b / sizeof(float));
+  int rc = ensure(c, c->d_img, (size_t)count * npix);
   if (rc) return rc;
-  if ((rc = ensure_bytes(c, (void**)&g->d_r, &g->cap_r, (size_t)count * npix * sizeof(double2)))) return rc;
-  if ((rc = ensure_bytes(c, (void**)&g->d_f, &g->cap_f, (size_t)count * d.nky * d.nx * sizeof(double2)))) return rc;
+  if ((rc = ensure(c, g->d_r, (size_t)count * npix))) return rc;
+  if ((rc = ensure(c, g->d_f, (size_t)count * d.nky * d.nx))) return rc;
   HH_HIP(c, hipMemcpyAsync(c->d_img, images, (size_t)count * npix * sizeof(float), hipMemcpyHostToDevice, c->stream));
   hipLaunchKernelGGL(k_gen_dft_rows, dim3((d.nx + 127) / 128, d.ny, count), dim3(128), 0, c->stream, c->d_img, d, g->d_r);
   hipLaunchKernelGGL(k_gen_dft_cols, dim3((d.nx + 127) / 128, d.nky, count), dim3(128), 0, c->stream, g->d_r, d, g->d_f);
@@ -91,11 +83,12 @@ int gen_low_high_pass_filter(hh_ctx* c, const float* image, double low_pass_frac
   const size_t npix = (size_t)d.ny * d.nx;
   int rc = gen_spectra(c, image, 1);  // g->d_f: half plane [nky][nx]
   if (rc) return rc;
-  double2* d_full = nullptr;
-  float* d_out = nullptr;
-  HH_HIP(c, hipMalloc(&d_full, npix * sizeof(double2)));
-  hipError_t e = hipMalloc(&d_out, npix * sizeof(float));
-  if (e == hipSuccess) {
+  DevArena mem;
+  double2* d_full = mem.get<double2>(npix);
+  float* d_out = mem.get<float>(npix);
+  if ((rc = arena_ok(c, mem))) return rc;
+  hipError_t e = hipSuccess;
+  {
     // filters.py:362-369: each filter applies only for a fraction strictly inside (0, 1)
     const bool lp = low_pass_fraction > 0 && low_pass_fraction < 1, hp = high_pass_fraction > 0 && high_pass_fraction < 1;
     const double f2_lp = lp ? std::log(2.0) / (low_pass_fraction * low_pass_fraction) : 0.0;
@@ -108,8 +101,6 @@ int gen_low_high_pass_filter(hh_ctx* c, const float* image, double low_pass_frac
   }
   if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, npix * sizeof(float), hipMemcpyDeviceToHost, c->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  (void)hipFree(d_full);
-  (void)hipFree(d_out);
   if (e != hipSuccess) return fail(c, HH_ERR_HIP, std::string("hh_low_high_pass_filter: ") + hipGetErrorString(e));
   return HH_OK;
 }
@@ -171,11 +162,11 @@ int gen_set_reference(hh_ctx* c, const float* images, int n_segments, const uint
     }
     c->ref[s] = RefConsts{sw, swec, var_e};
   }
-  if ((rc = ensure_bytes(c, (void**)&g->d_w2, &g->cap_w2, w2.size() * sizeof(float2)))) return rc;
+  if ((rc = ensure(c, g->d_w2, w2.size()))) return rc;
   HH_HIP(c, hipMemcpyAsync(g->d_w2, w2.data(), w2.size() * sizeof(float2), hipMemcpyHostToDevice, c->stream));
   if (multi) {
-    if ((rc = ensure_bytes(c, (void**)&g->d_wec, &g->cap_wec, wecm.size() * sizeof(float)))) return rc;
-    if ((rc = ensure_bytes(c, (void**)&g->d_ref, &g->cap_ref, (size_t)n_segments * sizeof(RefConsts)))) return rc;
+    if ((rc = ensure(c, g->d_wec, wecm.size()))) return rc;
+    if ((rc = ensure(c, g->d_ref, (size_t)n_segments))) return rc;
     HH_HIP(c, hipMemcpyAsync(g->d_wec, wecm.data(), wecm.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
     HH_HIP(c, hipMemcpyAsync(g->d_ref, c->ref.data(), (size_t)n_segments * sizeof(RefConsts), hipMemcpyHostToDevice, c->stream));
     std::vector<int> slices;   // 512-bin slices of the flat bin axis that carry any weight: the contraction skips the rest
@@ -184,7 +175,7 @@ int gen_set_reference(hh_ctx* c, const float* images, int n_segments, const uint
       for (size_t i = sl * GEN_SEG_NK; i < std::min(nh, (sl + 1) * GEN_SEG_NK) && !any; ++i) any = w[i] > 0.f;
       if (any) slices.push_back((int)sl);
     }
-    if ((rc = ensure_bytes(c, (void**)&g->d_seg_slices, &g->cap_seg_slices, (kp / GEN_SEG_NK) * sizeof(int)))) return rc;
+    if ((rc = ensure(c, g->d_seg_slices, (kp / GEN_SEG_NK)))) return rc;
     HH_HIP(c, hipMemcpyAsync(g->d_seg_slices, slices.data(), slices.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
     g->n_seg_slices = (int)slices.size();
     if (s_pad != g->s_pad || kp != g->kp) g->b_pad = 0;   // the batch buffers' shapes change with them
@@ -222,13 +213,11 @@ int gen_sweep_direct(hh_ctx* c, const double* d_params, const double* h_params, 
   }
   int64_t batch = std::max<int64_t>(1, std::min<int64_t>(n_cand, ((int64_t)512 << 20) / (int64_t)(npix * 20 + nh * 16)));
   batch = std::min<int64_t>(batch, 65535);   // a batch is the z extent of the transform launches
-  size_t cap_img_b = (size_t)c->cap_img * sizeof(float);
-  int rc = ensure_bytes(c, (void**)&c->d_img, &cap_img_b, (size_t)batch * npix * sizeof(float));
-  c->cap_img = (int64_t)(cap_img_b / sizeof(float));
+  int rc = ensure(c, c->d_img, (size_t)batch * npix);
   if (rc) return rc;
-  if ((rc = ensure_bytes(c, (void**)&g->d_r, &g->cap_r, (size_t)batch * npix * sizeof(double2)))) return rc;
-  if ((rc = ensure_bytes(c, (void**)&g->d_f, &g->cap_f, (size_t)batch * nh * sizeof(double2)))) return rc;
-  if ((rc = ensure_bytes(c, (void**)&g->d_ref, &g->cap_ref, (size_t)c->n_segments * sizeof(RefConsts)))) return rc;
+  if ((rc = ensure(c, g->d_r, (size_t)batch * npix))) return rc;
+  if ((rc = ensure(c, g->d_f, (size_t)batch * nh))) return rc;
+  if ((rc = ensure(c, g->d_ref, (size_t)c->n_segments))) return rc;
   HH_HIP(c, hipMemcpyAsync(g->d_ref, c->ref.data(), (size_t)c->n_segments * sizeof(RefConsts), hipMemcpyHostToDevice, c->stream));
   HH_HIP(c, hipStreamSynchronize(c->stream));   // (c->ref may change under a later hh_set_reference)
   for (int64_t g0 = 0; g0 < n_cand; g0 += batch) {
@@ -242,7 +231,7 @@ int gen_sweep_direct(hh_ctx* c, const double* d_params, const double* h_params, 
       const int64_t m64 = im < 0 ? 0 : (int64_t)(2 * (int64_t)im + 1) * csym * c->geom.n_units;
       if (m64 > (1 << 26)) return fail(c, HH_ERR_ARG, "rise too small for this image");
       const int m = (int)m64;
-      if ((rc = ensure_bytes(c, (void**)&g->d_cent, &g->cap_cent, (size_t)std::max(m, 1) * sizeof(float2)))) return rc;
+      if ((rc = ensure(c, g->d_cent, (size_t)std::max(m, 1)))) return rc;
       // (one centre buffer: the launches of a stream run in order, candidate i's raster is done with it before i + 1's centres)
       if (m > 0)
         hipLaunchKernelGGL(k_gen_centres, dim3((m + 255) / 256), dim3(256), 0, c->stream, d_params + 4 * (g0 + i), c->d_units, c->geom, m, g->d_cent);
@@ -282,7 +271,7 @@ int gen_sweep(hh_ctx* c, const double* d_params, const double* h_params, int64_t
       int differ = 1;
       HH_HIP(c, hipMemsetAsync(g->d_differ, 0, sizeof(int), c->stream));
       hipLaunchKernelGGL(k_gen_same_list, dim3((unsigned)std::min<int64_t>(1024, (n_cand * 4 + 255) / 256)), dim3(256), 0, c->stream,
-                         reinterpret_cast<const unsigned long long*>(d_params), reinterpret_cast<const unsigned long long*>(g->d_plan_params),
+                         reinterpret_cast<const unsigned long long*>(d_params), reinterpret_cast<const unsigned long long*>(g->d_plan_params.get()),
                          n_cand * 4, g->d_differ);
       HH_HIP(c, hipMemcpyAsync(&differ, g->d_differ, sizeof(int), hipMemcpyDeviceToHost, c->stream));
       HH_HIP(c, hipStreamSynchronize(c->stream));
@@ -345,12 +334,12 @@ int gen_sweep(hh_ctx* c, const double* d_params, const double* h_params, int64_t
     const size_t lds = (size_t)16 * d.nxp * sizeof(float2) + (size_t)8 * rows_lds * sizeof(float2) +
                        (size_t)((d.nx + 1) & ~1) * sizeof(float2) + (size_t)kg * d.nxp * sizeof(float) +
                        (size_t)(d.nxp / 4 + 4) * sizeof(int);
-    if ((rc = ensure_bytes(c, (void**)&g->d_table, &g->cap_table, (size_t)runs * rows * d.nky * sizeof(float2)))) return rc;
-    if ((rc = ensure_bytes(c, (void**)&g->d_eg, &g->cap_eg, (size_t)nb * kg * d.nxp * sizeof(float)))) return rc;
-    if ((rc = ensure_bytes(c, (void**)&g->d_cgs, &g->cap_cgs, (size_t)nb * (d.nxp / 4 + 4) * sizeof(int)))) return rc;
-    if ((rc = ensure_bytes(c, (void**)&g->d_runs, &g->cap_runs_b, (size_t)3 * runs * sizeof(int)))) return rc;
-    if ((rc = ensure_bytes(c, (void**)&g->d_run_of, &g->cap_run_of, (size_t)nb * sizeof(int)))) return rc;
-    if ((rc = ensure_bytes(c, (void**)&g->d_partials, &g->cap_partials, (size_t)nb * npart * 3 * sizeof(double)))) return rc;
+    if ((rc = ensure(c, g->d_table, (size_t)runs * rows * d.nky))) return rc;
+    if ((rc = ensure(c, g->d_eg, (size_t)nb * kg * d.nxp))) return rc;
+    if ((rc = ensure(c, g->d_cgs, (size_t)nb * (d.nxp / 4 + 4)))) return rc;
+    if ((rc = ensure(c, g->d_runs, (size_t)3 * runs))) return rc;
+    if ((rc = ensure(c, g->d_run_of, (size_t)nb))) return rc;
+    if ((rc = ensure(c, g->d_partials, (size_t)nb * npart * 3))) return rc;
     // ---- the fused launch's layers: whole runs while they fill whole rounds of resident workgroups, the runs of the
     // last round in shorter pieces (fused_schedule, as for the tuned kernels).  nx = R1 R2 with both <= 32 takes the
     // two-step row kernel (gen_rows.hip), anything else k_gen_fused.
@@ -397,7 +386,7 @@ int gen_sweep(hh_ctx* c, const double* d_params, const double* h_params, int64_t
       }
     }
     const int layers = (int)layer_run.size();
-    if ((rc = ensure_bytes(c, (void**)&g->d_layers, &g->cap_layers, (size_t)3 * layers * sizeof(int)))) return rc;
+    if ((rc = ensure(c, g->d_layers, (size_t)3 * layers))) return rc;
     int* const d_first = g->d_runs;
     int* const d_count = g->d_runs + runs;
     int* const d_imax = g->d_runs + 2 * runs;
@@ -453,9 +442,9 @@ int gen_sweep(hh_ctx* c, const double* d_params, const double* h_params, int64_t
       const int b_pad = (nb + 63) / 64 * 64;
       const int rows_c = (int)(g->kp / GEN_SEG_NK);
       if (b_pad > g->b_pad || !g->d_q) {
-        if ((rc = ensure_bytes(c, (void**)&g->d_q, &g->cap_q, (size_t)b_pad * g->kp * sizeof(float)))) return rc;
-        if ((rc = ensure_bytes(c, (void**)&g->d_cpart, &g->cap_cpart, (size_t)rows_c * b_pad * g->s_pad * sizeof(float)))) return rc;
-        if ((rc = ensure_bytes(c, (void**)&g->d_psum, &g->cap_psum, (size_t)b_pad * 3 * sizeof(double)))) return rc;
+        if ((rc = ensure(c, g->d_q, (size_t)b_pad * g->kp))) return rc;
+        if ((rc = ensure(c, g->d_cpart, (size_t)rows_c * b_pad * g->s_pad))) return rc;
+        if ((rc = ensure(c, g->d_psum, (size_t)b_pad * 3))) return rc;
         HH_HIP(c, hipMemsetAsync(g->d_q, 0, (size_t)b_pad * g->kp * sizeof(float), c->stream));   // padding stays finite (and zero)
         g->b_pad = b_pad;
       }
@@ -568,8 +557,8 @@ int gen_sweep(hh_ctx* c, const double* d_params, const double* h_params, int64_t
       g->plan_stockham = std::getenv("HH_GEN_STOCKHAM") != nullptr;
       g->plan_batch_cap = batch_cap;
       g->plan_params.assign(h_params, h_params + (size_t)n_cand * 4);
-      if (!g->d_differ) HH_HIP(c, hipMalloc(&g->d_differ, sizeof(int)));
-      if ((rc = ensure_bytes(c, (void**)&g->d_plan_params, &g->cap_plan_params, (size_t)n_cand * 4 * sizeof(double)))) return rc;
+      if ((rc = ensure(c, g->d_differ, 1))) return rc;
+      if ((rc = ensure(c, g->d_plan_params, (size_t)n_cand * 4))) return rc;
       HH_HIP(c, hipMemcpyAsync(g->d_plan_params, d_params, (size_t)n_cand * 4 * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
       g->plan_valid = true;
     }
@@ -592,13 +581,12 @@ int gen_simulate(hh_ctx* c, const double* params, float* image_out) {
   const int64_t m64 = im < 0 ? 0 : (int64_t)(2 * (int64_t)im + 1) * csym * c->geom.n_units;
   if (m64 > (1 << 26)) return fail(c, HH_ERR_ARG, "hh_simulate: too many lattice centres");
   const int m = (int)m64;
-  size_t cap_img_b = (size_t)c->cap_img * sizeof(float);
-  int rc = ensure_bytes(c, (void**)&c->d_img, &cap_img_b, npix * sizeof(float));
-  c->cap_img = (int64_t)(cap_img_b / sizeof(float));
+  int rc = ensure(c, c->d_img, npix);
   if (rc) return rc;
-  if ((rc = ensure_bytes(c, (void**)&g->d_cent, &g->cap_cent, (size_t)std::max(m, 1) * sizeof(float2)))) return rc;
-  double* dp = nullptr;
-  HH_HIP(c, hipMalloc(&dp, 4 * sizeof(double)));
+  if ((rc = ensure(c, g->d_cent, (size_t)std::max(m, 1)))) return rc;
+  DevArena mem;
+  double* dp = mem.get<double>(4);
+  if ((rc = arena_ok(c, mem))) return rc;
   hipError_t e = hipMemcpyAsync(dp, params, 4 * sizeof(double), hipMemcpyHostToDevice, c->stream);
   if (e == hipSuccess) {
     if (m > 0)
@@ -608,7 +596,6 @@ int gen_simulate(hh_ctx* c, const double* params, float* image_out) {
     if (e == hipSuccess) e = hipMemcpyAsync(image_out, c->d_img, npix * sizeof(float), hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
   }
-  (void)hipFree(dp);
   if (e != hipSuccess) return fail(c, HH_ERR_HIP, std::string("hh_simulate: ") + hipGetErrorString(e));
   return HH_OK;
 }
@@ -619,12 +606,12 @@ int gen_power_spectrum(hh_ctx* c, const float* image, int log_flag, float* pwr_o
   const size_t npix = (size_t)d.ny * d.nx;
   int rc = gen_spectra(c, image, 1);
   if (rc) return rc;
-  float* d_out = nullptr;
-  unsigned* d_mm = nullptr;
-  HH_HIP(c, hipMalloc(&d_out, 2 * npix * sizeof(float)));
-  hipError_t e = hipMalloc(&d_mm, 2 * sizeof(unsigned));
+  DevArena mem;
+  float* d_out = mem.get<float>(2 * npix);
+  unsigned* d_mm = mem.get<unsigned>(2);
+  if ((rc = arena_ok(c, mem))) return rc;
   const unsigned init[2] = {0x7f800000u, 0u};
-  if (e == hipSuccess) e = hipMemcpyAsync(d_mm, init, sizeof(init), hipMemcpyHostToDevice, c->stream);
+  hipError_t e = hipMemcpyAsync(d_mm, init, sizeof(init), hipMemcpyHostToDevice, c->stream);
   if (e == hipSuccess) {
     hipLaunchKernelGGL(k_gen_expand, dim3(d.ny), dim3(256), 0, c->stream, g->d_f, d, log_flag ? 1 : 0, d_out,
                        phase_out ? d_out + npix : nullptr, d_mm);
@@ -635,8 +622,6 @@ int gen_power_spectrum(hh_ctx* c, const float* image, int log_flag, float* pwr_o
       e = hipMemcpyAsync(phase_out, d_out + npix, npix * sizeof(float), hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
   }
-  (void)hipFree(d_out);
-  if (d_mm) (void)hipFree(d_mm);
   if (e != hipSuccess) return fail(c, HH_ERR_HIP, std::string("hh_power_spectrum: ") + hipGetErrorString(e));
   return HH_OK;
 }

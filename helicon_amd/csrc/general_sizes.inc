@@ -609,33 +609,22 @@ struct GenBatchPlan {
 struct hh_gen {
   GenDims d{};
   GenPlan plan{};
-  float2* d_tw_nx = nullptr;
-  float2* d_tw_ny = nullptr;
-  float2* d_w2 = nullptr;          // [S][nky][nx]
-  size_t cap_w2 = 0;
-  float2* d_table = nullptr;
-  size_t cap_table = 0;
-  float* d_eg = nullptr;
-  size_t cap_eg = 0;
-  int* d_cgs = nullptr;
-  size_t cap_cgs = 0;
-  int* d_runs = nullptr;           // [4][cap_runs]: run_first, run_count, run_imax, (run_of: [cap_cand])
-  size_t cap_runs_b = 0;
-  int* d_run_of = nullptr;
-  size_t cap_run_of = 0;
-  int* d_layers = nullptr;         // [3][layers]: layer_run, layer_first, layer_count
-  size_t cap_layers = 0;
+  DevBuf<float2> d_tw_nx;
+  DevBuf<float2> d_tw_ny;
+  DevBuf<float2> d_w2;             // [S][nky][nx]
+  DevBuf<float2> d_table;
+  DevBuf<float> d_eg;
+  DevBuf<int> d_cgs;
+  DevBuf<int> d_runs;              // [4][cap_runs]: run_first, run_count, run_imax, (run_of: [cap_cand])
+  DevBuf<int> d_run_of;
+  DevBuf<int> d_layers;            // [3][layers]: layer_run, layer_first, layer_count
   int slots = 0;                   // resident k_gen_fused workgroups (for the LDS size slots_lds)
   size_t slots_lds = 0;
   bool slots_two_step = false;      // ... counted for k_gen_rows (gen_rows.hip) rather than k_gen_fused
-  double* d_partials = nullptr;
-  size_t cap_partials = 0;
-  double2* d_r = nullptr;          // DFT scratch
-  size_t cap_r = 0;
-  double2* d_f = nullptr;
-  size_t cap_f = 0;
-  float2* d_cent = nullptr;
-  size_t cap_cent = 0;
+  DevBuf<double> d_partials;
+  DevBuf<double2> d_r;             // DFT scratch
+  DevBuf<double2> d_f;
+  DevBuf<float2> d_cent;
   std::vector<double> h_params;    // host copy of a device-only candidate list
   // the last single-batch sweep: its list (host and device copies), geometry and launch plan; d_runs / d_run_of /
   // d_layers still hold its arrays
@@ -644,27 +633,20 @@ struct hh_gen {
   DevGeom plan_geom{};
   GenBatchPlan last{};
   std::vector<double> plan_params;
-  double* d_plan_params = nullptr;
-  size_t cap_plan_params = 0;
-  int* d_differ = nullptr;
+  DevBuf<double> d_plan_params;
+  DevBuf<int> d_differ;
   // several segments through the two-step row kernel: q of a batch [b_pad][kp] (kp = nky nx rounded up to GEN_SEG_NK),
   // all segments' centred spectra [s_pad][kp], covariance numerators [kp / GEN_SEG_NK][b_pad][s_pad], summed moments
-  float* d_q = nullptr;
-  size_t cap_q = 0;
-  float* d_wec = nullptr;
-  size_t cap_wec = 0;
-  float* d_cpart = nullptr;
-  size_t cap_cpart = 0;
-  double* d_psum = nullptr;
-  size_t cap_psum = 0;
-  RefConsts* d_ref = nullptr;
-  size_t cap_ref = 0;
+  DevBuf<float> d_q;
+  DevBuf<float> d_wec;
+  DevBuf<float> d_cpart;
+  DevBuf<double> d_psum;
+  DevBuf<RefConsts> d_ref;
   int32_t last_row_kernel[3] = {0, 0, 0};   // the last sweep's row kernel: {R1, R2, LDS bytes}, {0, 0, LDS} Stockham, all zero direct
   bool direct_only = false;       // nx without a row-transform plan (a prime factor above 31): every sweep is gen_sweep_direct
   int s_pad = 0, b_pad = 0;
   size_t kp = 0;
-  int* d_seg_slices = nullptr;     // [n_seg_slices] 512-bin slices of the flat bin axis with any weight
-  size_t cap_seg_slices = 0;
+  DevBuf<int> d_seg_slices;        // [n_seg_slices] 512-bin slices of the flat bin axis with any weight
   int n_seg_slices = 0;
 };
 

@@ -46,6 +46,7 @@
 #include <vector>
 
 #include "../../include/helicon_hip.h"
+#include "device_mem.h"  // DevBuf / DevArena: the owners of device memory
 #include "gen_rows.h"  // the general-size sweep's two-step row kernel (second translation unit, gen_rows.hip)
 
 // Tuning values are constants beside what they tune (the measured best).
@@ -2732,56 +2733,44 @@ struct hh_ctx {
   hipStream_t stream = nullptr;
   std::string err;
 
-  float2* d_tw = nullptr;
-  float2* d_inter = nullptr;     // [max_batch][N/2][N]
-  double* d_partials = nullptr;  // [2][max_batch][NPART][3], zero where the mask skips a ky block; the halves alternate
+  DevBuf<float2> d_tw;
+  DevBuf<float2> d_inter;        // [max_batch][N/2][N]
+  DevBuf<double> d_partials;     // [2][max_batch][NPART][3], zero where the mask skips a ky block; the halves alternate
                                  // between batches (the fused pass scores batch i-1 while it writes batch i)
-  double* d_psum = nullptr;      // S > 1: [b_pad][3] summed partials
-  double* d_params = nullptr;    // staging for hh_sweep
-  float* d_scores = nullptr;
-  int64_t cap_params = 0, cap_scores = 0;
-  double* d_units = nullptr;
-  float2* d_w2 = nullptr;        // [N/2+1][N/8][8] (lane-major within a row); with S > 1 only w is used
-  float* d_wec = nullptr;        // S > 1: [Sp][K] w (E_s - Ebar_s), rows in q's lane-major bin order, Sp = S rounded up to 64
-  float* d_q = nullptr;          // S > 1: [Bp][K] masked q of one batch, Bp = max_batch rounded up to 64
-  float* d_cpart = nullptr;      // S > 1: [N/2+1][Bp][Sp] per-row covariance numerators
-  RefConsts* d_ref = nullptr;    // S > 1: [S]
-  int64_t* d_argmax = nullptr;   // hh_argmax_device: one index per row
-  size_t cap_argmax = 0;
-  size_t cap_w2 = 0, cap_wec = 0, cap_q = 0, cap_cpart = 0, cap_ref = 0, cap_psum = 0, cap_kb = 0;  // bytes
-  int* d_kb_list = nullptr;      // ky blocks (8 rows) the mask touches, ascending; block 0 always
-  int* d_q_roff = nullptr;       // S > 1, N <= 512: compact q — first position of every spectrum row's weighted bins
-  size_t cap_q_roff = 0;
+  DevBuf<double> d_psum;         // S > 1: [b_pad][3] summed partials
+  DevBuf<double> d_params;       // staging for hh_sweep
+  DevBuf<float> d_scores;
+  DevBuf<double> d_units;
+  DevBuf<float2> d_w2;           // [N/2+1][N/8][8] (lane-major within a row); with S > 1 only w is used
+  DevBuf<float> d_wec;           // S > 1: [Sp][K] w (E_s - Ebar_s), rows in q's lane-major bin order, Sp = S rounded up to 64
+  DevBuf<float> d_q;             // S > 1: [Bp][K] masked q of one batch, Bp = max_batch rounded up to 64
+  DevBuf<float> d_cpart;         // S > 1: [N/2+1][Bp][Sp] per-row covariance numerators
+  DevBuf<RefConsts> d_ref;       // S > 1: [S]
+  DevBuf<int64_t> d_argmax;      // hh_argmax_device: one index per row
+  DevBuf<int> d_kb_list;         // ky blocks (8 rows) the mask touches, ascending; block 0 always
+  DevBuf<int> d_q_roff;          // S > 1, N <= 512: compact q — first position of every spectrum row's weighted bins
   size_t q_stride = 0;           // S > 1: floats per candidate in d_q (compact: weighted bins, rounded up to 512; else (N/2+1) N)
   int q_slices = 0;              // compact: 512-bin slices of the flat axis the contraction walks
-  int* d_seg_rows = nullptr;     // S > 1: spectrum rows with any weight, ascending (the contraction skips the others)
-  size_t cap_seg_rows = 0;
+  DevBuf<int> d_seg_rows;        // S > 1: spectrum rows with any weight, ascending (the contraction skips the others)
   int n_seg_rows = 0;
   int n_kb = 0;
-  float2* d_table = nullptr;     // shared-twist first pass: [runs per batch][rows][N/2] column-transform table
-  size_t cap_table = 0;          // bytes
-  float2* d_table_ky = nullptr;  // the same tables ky-major, [runs][N/2][rows_f] (N = 512: [pairs][N/2][rows_f][2]), for the fused pass's twist walk
-  size_t cap_table_ky = 0;       // bytes
+  DevBuf<float2> d_table;        // shared-twist first pass: [runs per batch][rows][N/2] column-transform table
+  DevBuf<float2> d_table_ky;     // the same tables ky-major, [runs][N/2][rows_f] (N = 512: [pairs][N/2][rows_f][2]), for the fused pass's twist walk
   int fused_walk = 0;            // hh_set_fused_walk: 0 auto, 1 rises, 2 twists
   int last_fused_walk = 0;       // hh_last_fused_walk
   int fused_piece = 0;           // hh_set_fused_piece: runs per workgroup of the twist walk (0: fused_schedule's own cut)
-  int* d_run_imax = nullptr;     // [runs of the sweep]
-  int64_t cap_runs = 0;
+  DevBuf<int> d_run_imax;        // [runs of the sweep]
   std::vector<int> h_run_imax;
   int table_path = 1;            // 0: never take the shared-twist first pass
   int fused_path = 1;            // 0: shared-twist runs go through the two-pass pipeline (k_first_pass_table + k_second_pass)
-  float* d_eg = nullptr;         // fused pass: column factors, [run_len][kg][N] shared by all runs or [2][batch][kg][N]
-  int* d_cgs = nullptr;          // fused pass: [sets][N/4 + 4]
-  size_t cap_eg = 0, cap_cgs = 0;  // bytes; factor sets
+  DevBuf<float> d_eg;            // fused pass: column factors, [run_len][kg][N] shared by all runs or [2][batch][kg][N]
+  DevBuf<int> d_cgs;             // fused pass: [sets][N/4 + 4]
   int64_t last_factor_sets = 0;  // factor sets the last fused sweep computed (0: another pipeline)
-  int cap_partials = 0;          // candidates per half of d_partials
   int last_first_pass = 0;       // what the last sweep ran: 0 per-candidate transform, 1 run tables, 2 fused, 3 zoomed spectra, 4 filtered spectra, 5 phase score
   unsigned long long kb_mask = ~0ull;
   int s_pad = 0, b_pad = 0;
-  float2* d_spec = nullptr;      // [N/2+1][N] scratch (grown for S segments)
-  int64_t cap_spec = 0;
-  float* d_img = nullptr;        // scratch images
-  int64_t cap_img = 0;
+  DevBuf<float2> d_spec;         // [N/2+1][N] scratch (grown for S segments)
+  DevBuf<float> d_img;           // scratch images
   std::vector<RefConsts> ref;
   int n_segments = 0;
   int log_flag = 1;
@@ -2971,41 +2960,18 @@ int dispatch_second(hh_ctx* c, const SecondArgs& a, int batch) {
   return dispatch_second_n<EPI, 0>(c, a, batch);
 }
 
-// grow-only device buffer
-int ensure_bytes(hh_ctx* c, void** p, size_t* cap, size_t need) {
-  if (need <= *cap && *p) return HH_OK;
-  if (*p) HH_HIP(c, hipFree(*p));
-  *p = nullptr;
-  *cap = 0;
-  if (hipMalloc(p, need) != hipSuccess) {
-    *p = nullptr;
-    return fail(c, HH_ERR_NOMEM, "device allocation of " + std::to_string(need) + " bytes failed");
-  }
-  *cap = need;
-  return HH_OK;
+// grow-only device buffer (device_mem.h) of at least `count` elements; a failure is this context's HH_ERR_NOMEM
+template <class T>
+int ensure(hh_ctx* c, DevBuf<T>& b, size_t count) {
+  return b.ensure(count) ? HH_OK : fail(c, HH_ERR_NOMEM, dev_alloc_failed(b.bytes_for(count)));
+}
+// ... and a call's arena: HH_OK when every get() so far gave memory
+int arena_ok(hh_ctx* c, const DevArena& mem) {
+  return mem.ok() ? HH_OK : fail(c, HH_ERR_NOMEM, dev_alloc_failed(mem.failed_bytes()));
 }
 
-int ensure_img(hh_ctx* c, int64_t count) {
-  const int64_t need = count * (int64_t)c->n * c->n;
-  if (need <= c->cap_img) return HH_OK;
-  if (c->d_img) HH_HIP(c, hipFree(c->d_img));
-  c->d_img = nullptr;
-  c->cap_img = 0;
-  HH_HIP(c, hipMalloc(&c->d_img, need * sizeof(float)));
-  c->cap_img = need;
-  return HH_OK;
-}
-
-int ensure_spec(hh_ctx* c, int64_t count) {
-  const int64_t need = count * (int64_t)(c->n / 2 + 1) * c->n;
-  if (need <= c->cap_spec) return HH_OK;
-  if (c->d_spec) HH_HIP(c, hipFree(c->d_spec));
-  c->d_spec = nullptr;
-  c->cap_spec = 0;
-  HH_HIP(c, hipMalloc(&c->d_spec, need * sizeof(float2)));
-  c->cap_spec = need;
-  return HH_OK;
-}
+int ensure_img(hh_ctx* c, int64_t count) { return ensure(c, c->d_img, (size_t)count * c->n * c->n); }
+int ensure_spec(hh_ctx* c, int64_t count) { return ensure(c, c->d_spec, (size_t)count * (c->n / 2 + 1) * c->n); }
 
 // images already in c->d_img ([count][N][N]); leaves the half-plane spectra in c->d_spec
 int spectra_of_images(hh_ctx* c, int count) {
@@ -3408,14 +3374,10 @@ WalkChoice choose_walk(int64_t runs, int run_len, int n_kb, int slots_rises, int
 // d_partials holds two halves of `batch` candidates each (zero-filled: rows of ky blocks the mask skips
 // are never written)
 int ensure_partials(hh_ctx* c, int batch) {
-  if (batch <= c->cap_partials) return HH_OK;
-  if (c->d_partials) HH_HIP(c, hipFree(c->d_partials));
-  c->d_partials = nullptr;
-  c->cap_partials = 0;
-  const size_t bytes = (size_t)2 * batch * npart_for(c->n) * 3 * sizeof(double);
-  HH_HIP(c, hipMalloc(&c->d_partials, bytes));
-  HH_HIP(c, hipMemsetAsync(c->d_partials, 0, bytes, c->stream));
-  c->cap_partials = batch;
+  const size_t count = (size_t)2 * batch * npart_for(c->n) * 3;
+  if (count <= c->d_partials.size()) return HH_OK;
+  if (int rc = ensure(c, c->d_partials, count)) return rc;
+  HH_HIP(c, hipMemsetAsync(c->d_partials, 0, c->d_partials.bytes(), c->stream));
   return HH_OK;
 }
 
@@ -3428,9 +3390,9 @@ int ensure_segment_buffers(hh_ctx* c, int batch) {
   if (want <= c->b_pad && c->d_q && c->d_cpart && c->d_psum) return HH_OK;
   const size_t nh = c->q_stride ? c->q_stride : (size_t)(c->n / 2 + 1) * c->n;
   int rc;
-  if ((rc = ensure_bytes(c, (void**)&c->d_q, &c->cap_q, (size_t)want * nh * sizeof(float)))) return rc;
-  if ((rc = ensure_bytes(c, (void**)&c->d_cpart, &c->cap_cpart, (size_t)(c->n / 2 + 1) * want * c->s_pad * sizeof(float)))) return rc;
-  if ((rc = ensure_bytes(c, (void**)&c->d_psum, &c->cap_psum, (size_t)want * 3 * sizeof(double)))) return rc;
+  if ((rc = ensure(c, c->d_q, (size_t)want * nh))) return rc;
+  if ((rc = ensure(c, c->d_cpart, (size_t)(c->n / 2 + 1) * want * c->s_pad))) return rc;
+  if ((rc = ensure(c, c->d_psum, (size_t)want * 3))) return rc;
   HH_HIP(c, hipMemsetAsync(c->d_q, 0, (size_t)want * nh * sizeof(float), c->stream));  // pad rows of a batch (and, compact, the pad bins of a row of q) stay finite
   c->b_pad = want;
   return HH_OK;
@@ -3483,32 +3445,13 @@ int sweep_runs(hh_ctx* c, const double* d_params, int64_t g, float* d_scores, co
   if (plan.fused) {
     // shared: one set per rise; else two halves of a launch's candidates, alternating
     const size_t sets = shared ? (size_t)plan.len : (size_t)2 * bmax;
-    const size_t need_eg = sets * plan.kg * c->n * sizeof(float);
-    if (need_eg > c->cap_eg) {
-      if (c->d_eg) HH_HIP(c, hipFree(c->d_eg));
-      c->d_eg = nullptr;
-      c->cap_eg = 0;
-      HH_HIP(c, hipMalloc(&c->d_eg, need_eg));
-      c->cap_eg = need_eg;
-    }
-    if (sets > c->cap_cgs) {
-      if (c->d_cgs) HH_HIP(c, hipFree(c->d_cgs));
-      c->d_cgs = nullptr;
-      c->cap_cgs = 0;
-      HH_HIP(c, hipMalloc(&c->d_cgs, sets * (c->n / 4 + 4) * sizeof(int)));
-      c->cap_cgs = sets;
-    }
+    int rc;
+    if ((rc = ensure(c, c->d_eg, sets * plan.kg * c->n))) return rc;
+    if ((rc = ensure(c, c->d_cgs, sets * (c->n / 4 + 4)))) return rc;
     c->last_factor_sets = shared ? plan.len : count_cand;
-    const int rc = ensure_partials(c, bmax);
-    if (rc) return rc;
+    if ((rc = ensure_partials(c, bmax))) return rc;
   }
-  if (runs > c->cap_runs) {
-    if (c->d_run_imax) HH_HIP(c, hipFree(c->d_run_imax));
-    c->d_run_imax = nullptr;
-    c->cap_runs = 0;
-    HH_HIP(c, hipMalloc(&c->d_run_imax, (size_t)runs * sizeof(int)));
-    c->cap_runs = runs;
-  }
+  if (int rc = ensure(c, c->d_run_imax, (size_t)runs)) return rc;
   HH_HIP(c, hipMemcpyAsync(c->d_run_imax, c->h_run_imax.data(), (size_t)runs * sizeof(int), hipMemcpyHostToDevice,
                            c->stream));
   // the batches of the sweep: whole runs (or pieces of one run), in order
@@ -3562,23 +3505,12 @@ int sweep_runs(hh_ctx* c, const double* d_params, int64_t g, float* d_scores, co
   }
   // each table layout is allocated (and built, below) only where a launch reads it
   const size_t need = (size_t)per_group * run_bytes;
-  if ((!plan.fused || any_rises) && need > c->cap_table) {
-    if (c->d_table) HH_HIP(c, hipFree(c->d_table));
-    c->d_table = nullptr;
-    c->cap_table = 0;
-    HH_HIP(c, hipMalloc(&c->d_table, need));
-    c->cap_table = need;
-  }
+  if (!plan.fused || any_rises)
+    if (int rc = ensure(c, c->d_table, need / sizeof(float2))) return rc;
   const bool ky_pairs = pair_walk_built(c->n);  // the twist walk of this size reads its tables two runs to an entry
   if (any_twists) {
-    const size_t need_ky = (ky_pairs ? pair_table_words(per_group, nky, plan.rows_f) : (size_t)per_group * nky * plan.rows_f) * sizeof(float2);
-    if (need_ky > c->cap_table_ky) {
-      if (c->d_table_ky) HH_HIP(c, hipFree(c->d_table_ky));
-      c->d_table_ky = nullptr;
-      c->cap_table_ky = 0;
-      HH_HIP(c, hipMalloc(&c->d_table_ky, need_ky));
-      c->cap_table_ky = need_ky;
-    }
+    const size_t need_ky = ky_pairs ? pair_table_words(per_group, nky, plan.rows_f) : (size_t)per_group * nky * plan.rows_f;
+    if (int rc = ensure(c, c->d_table_ky, need_ky)) return rc;
   }
   const size_t eg_half = (size_t)bmax * plan.kg * c->n;
   const size_t cg_half = (size_t)bmax * (c->n / 4 + 4);  // cgs_stride<N>()
@@ -3804,13 +3736,12 @@ int launch_filter(hh_ctx* c, float f2_lp, float f2_hp, const float2* spec, float
 template <typename T>
 int pair_reduce(hh_ctx* c, const T* a, const T* b, int64_t n, double mx, double my, double out[5]) {
   const int grid = (int)std::min<int64_t>(1024, (n + 255) / 256);
-  T *da = nullptr, *db = nullptr;
-  double* dp = nullptr;
   std::vector<double> hp((size_t)grid * 5);
-  hipError_t e = hipMalloc(&da, n * sizeof(T));
-  if (e == hipSuccess) e = hipMalloc(&db, n * sizeof(T));
-  if (e == hipSuccess) e = hipMalloc(&dp, (size_t)grid * 5 * sizeof(double));
-  if (e == hipSuccess) e = hipMemcpyAsync(da, a, n * sizeof(T), hipMemcpyHostToDevice, c->stream);
+  DevArena mem;
+  T *da = mem.get<T>(n), *db = mem.get<T>(n);
+  double* dp = mem.get<double>((size_t)grid * 5);
+  if (int rc = arena_ok(c, mem)) return rc;
+  hipError_t e = hipMemcpyAsync(da, a, n * sizeof(T), hipMemcpyHostToDevice, c->stream);
   if (e == hipSuccess) e = hipMemcpyAsync(db, b, n * sizeof(T), hipMemcpyHostToDevice, c->stream);
   if (e == hipSuccess) {
     hipLaunchKernelGGL((k_pair_sums<T>), dim3(grid), dim3(256), 0, c->stream, da, db, n, mx, my, dp);
@@ -3818,9 +3749,6 @@ int pair_reduce(hh_ctx* c, const T* a, const T* b, int64_t n, double mx, double 
   }
   if (e == hipSuccess) e = hipMemcpyAsync(hp.data(), dp, hp.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  (void)hipFree(da);
-  (void)hipFree(db);
-  (void)hipFree(dp);
   if (e != hipSuccess) return fail(c, HH_ERR_HIP, std::string("pair_reduce: ") + hipGetErrorString(e));
   for (int k = 0; k < 5; ++k) out[k] = 0;
   for (int g = 0; g < grid; ++g)
@@ -3950,7 +3878,7 @@ int hh_create2(hh_ctx** out, int device, int ny, int nx, int max_batch) try {
   HH_CREATE_HIP(hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking));
   c->stream = c->own_stream;
   if (general) {  // runtime-sized kernels; buffers grow with the sweeps
-    HH_CREATE_HIP(hipMalloc(&c->d_units, (size_t)HH_MAX_UNITS * 3 * sizeof(double)));
+    if (int rc = ensure(c, c->d_units, (size_t)HH_MAX_UNITS * 3)) return bail(rc, c->err);
     c->max_batch = (int)GEN_BATCH;
     const int rcg = gen_create(c, ny, nx);
     if (rcg) return bail(rcg, c->err);
@@ -3958,12 +3886,12 @@ int hh_create2(hh_ctx** out, int device, int ny, int nx, int max_batch) try {
     *out = c;
     return HH_OK;
   }
-  HH_CREATE_HIP(hipMalloc(&c->d_tw, (size_t)n * sizeof(float2)));
-  HH_CREATE_HIP(hipMalloc(&c->d_inter, (size_t)max_batch * (n / 2) * n * sizeof(float2)));
-  HH_CREATE_HIP(hipMalloc(&c->d_partials, (size_t)2 * max_batch * npart_for(n) * 3 * sizeof(double)));
-  HH_CREATE_HIP(hipMemset(c->d_partials, 0, (size_t)2 * max_batch * npart_for(n) * 3 * sizeof(double)));
-  c->cap_partials = max_batch;
-  HH_CREATE_HIP(hipMalloc(&c->d_units, (size_t)HH_MAX_UNITS * 3 * sizeof(double)));
+  int rc = ensure(c, c->d_tw, (size_t)n);
+  if (!rc) rc = ensure(c, c->d_inter, (size_t)max_batch * (n / 2) * n);
+  if (!rc) rc = ensure(c, c->d_partials, (size_t)2 * max_batch * npart_for(n) * 3);
+  if (!rc) rc = ensure(c, c->d_units, (size_t)HH_MAX_UNITS * 3);
+  if (rc) return bail(rc, c->err);
+  HH_CREATE_HIP(hipMemset(c->d_partials, 0, c->d_partials.bytes()));
 
   std::vector<float2> tw((size_t)n);
   for (int k = 0; k < n; ++k) {
@@ -3986,35 +3914,12 @@ void hh_destroy(hh_ctx* c) try {
     (void)hipEventDestroy(e.a);
     (void)hipEventDestroy(e.b);
   }
-  (void)hipFree(c->d_tw);
-  (void)hipFree(c->d_inter);
-  (void)hipFree(c->d_partials);
-  (void)hipFree(c->d_psum);
-  (void)hipFree(c->d_params);
-  (void)hipFree(c->d_scores);
-  (void)hipFree(c->d_units);
-  (void)hipFree(c->d_w2);
-  (void)hipFree(c->d_wec);
-  (void)hipFree(c->d_q);
-  (void)hipFree(c->d_cpart);
-  (void)hipFree(c->d_ref);
-  (void)hipFree(c->d_kb_list);
-  (void)hipFree(c->d_seg_rows);
-  (void)hipFree(c->d_q_roff);
-  (void)hipFree(c->d_table);
-  (void)hipFree(c->d_table_ky);
-  (void)hipFree(c->d_eg);
-  (void)hipFree(c->d_cgs);
-  (void)hipFree(c->d_run_imax);
-  (void)hipFree(c->d_argmax);
-
-  (void)hipFree(c->d_spec);
-  (void)hipFree(c->d_img);
   gen_free(c);
   phase_free(c);
   zoom_free(c);
-  if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
-  delete c;
+  const hipStream_t own = c->own_stream;
+  delete c;                                   // frees the context's buffers: before their stream goes
+  if (own) (void)hipStreamDestroy(own);
 } catch (...) {
 }
 
@@ -4281,7 +4186,7 @@ int hh_set_reference(hh_ctx* c, const float* images, int n_segments, const uint8
   // sweep returns HH_ERR_STATE) instead of a mix of old sizes and new tables.  The device tables are kept between
   // calls and only grow.
   c->n_segments = 0;
-  int rcg = ensure_bytes(c, (void**)&c->d_w2, &c->cap_w2, w2.size() * sizeof(float2));
+  int rcg = ensure(c, c->d_w2, w2.size());
   if (rcg) return rcg;
   HH_HIP(c, hipMemcpyAsync(c->d_w2, w2.data(), w2.size() * sizeof(float2), hipMemcpyHostToDevice, c->stream));
   if (multi) {
@@ -4291,27 +4196,27 @@ int hh_set_reference(hh_ctx* c, const float* images, int n_segments, const uint8
       for (int kx = 0; kx < n && !any; ++kx) any = w[(size_t)r * n + kx] > 0.f;
       if (any) seg_rows.push_back(r);
     }
-    if ((rcg = ensure_bytes(c, (void**)&c->d_seg_rows, &c->cap_seg_rows, (size_t)(n / 2 + 1) * sizeof(int)))) return rcg;
+    if ((rcg = ensure(c, c->d_seg_rows, (size_t)(n / 2 + 1)))) return rcg;
     HH_HIP(c, hipMemcpyAsync(c->d_seg_rows, seg_rows.data(), seg_rows.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
     c->n_seg_rows = (int)seg_rows.size();
     if (compact) {
-      if ((rcg = ensure_bytes(c, (void**)&c->d_q_roff, &c->cap_q_roff, roff.size() * sizeof(int)))) return rcg;
+      if ((rcg = ensure(c, c->d_q_roff, roff.size()))) return rcg;
       HH_HIP(c, hipMemcpyAsync(c->d_q_roff, roff.data(), roff.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
       HH_HIP(c, hipStreamSynchronize(c->stream));   // (roff is a local)
     }
     if (q_stride != c->q_stride) c->b_pad = 0;   // the buffers of a batch are laid out by it: start over
     c->q_stride = q_stride;
     c->q_slices = compact ? (int)(q_stride / 512) : 0;
-    if ((rcg = ensure_bytes(c, (void**)&c->d_wec, &c->cap_wec, wecm.size() * sizeof(float)))) return rcg;
-    if ((rcg = ensure_bytes(c, (void**)&c->d_ref, &c->cap_ref, (size_t)n_segments * sizeof(RefConsts)))) return rcg;
+    if ((rcg = ensure(c, c->d_wec, wecm.size()))) return rcg;
+    if ((rcg = ensure(c, c->d_ref, (size_t)n_segments))) return rcg;
     HH_HIP(c, hipMemcpyAsync(c->d_wec, wecm.data(), wecm.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
     HH_HIP(c, hipMemcpyAsync(c->d_ref, c->ref.data(), (size_t)n_segments * sizeof(RefConsts), hipMemcpyHostToDevice,
                              c->stream));
   }
-  if ((rcg = ensure_bytes(c, (void**)&c->d_kb_list, &c->cap_kb, (size_t)(n / 16) * sizeof(int)))) return rcg;
+  if ((rcg = ensure(c, c->d_kb_list, (size_t)(n / 16)))) return rcg;
   HH_HIP(c, hipMemcpyAsync(c->d_kb_list, kb_list.data(), kb_list.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
   // rows of skipped ky blocks keep zero moments
-  HH_HIP(c, hipMemsetAsync(c->d_partials, 0, (size_t)2 * c->cap_partials * npart_for(n) * 3 * sizeof(double), c->stream));
+  HH_HIP(c, hipMemsetAsync(c->d_partials, 0, c->d_partials.bytes(), c->stream));
   c->n_kb = (int)kb_list.size();
   c->kb_mask = kb_mask;
   if (s_pad != c->s_pad) {   // the covariance buffer's row length changes with the segment count: start over
@@ -4428,22 +4333,9 @@ int hh_sweep(hh_ctx* c, const double* params, int64_t g, float* scores) try {
   if (!params || !scores || g < 0) return fail(c, HH_ERR_ARG, "hh_sweep: bad argument");
   if (g == 0) return HH_OK;
   HH_HIP(c, hipSetDevice(c->device));
-  if (g > c->cap_params) {
-    if (c->d_params) HH_HIP(c, hipFree(c->d_params));
-    c->d_params = nullptr;
-    c->cap_params = 0;
-    HH_HIP(c, hipMalloc(&c->d_params, (size_t)g * 4 * sizeof(double)));
-    c->cap_params = g;
-  }
+  if (int rc = ensure(c, c->d_params, (size_t)g * 4)) return rc;
   // staging for the scores of all segments (S x G); kept between calls
-  const int64_t need_scores = g * c->n_segments;
-  if (need_scores > c->cap_scores) {
-    if (c->d_scores) HH_HIP(c, hipFree(c->d_scores));
-    c->d_scores = nullptr;
-    c->cap_scores = 0;
-    HH_HIP(c, hipMalloc(&c->d_scores, (size_t)need_scores * sizeof(float)));
-    c->cap_scores = need_scores;
-  }
+  if (int rc = ensure(c, c->d_scores, (size_t)g * c->n_segments)) return rc;
   float* const d_sc = c->d_scores;
   hipError_t e = hipMemcpyAsync(c->d_params, params, (size_t)g * 4 * sizeof(double), hipMemcpyHostToDevice, c->stream);
   if (e == hipSuccess) {
@@ -4475,7 +4367,7 @@ int hh_argmax_device(hh_ctx* c, const float* d_scores, int64_t n_rows, int64_t n
     return fail(c, HH_ERR_ARG, "hh_argmax_device: bad argument");
   HH_HIP(c, hipSetDevice(c->device));
   if (!d_index) {
-    int rc = ensure_bytes(c, (void**)&c->d_argmax, &c->cap_argmax, (size_t)n_rows * sizeof(int64_t));
+    int rc = ensure(c, c->d_argmax, (size_t)n_rows);
     if (rc) return rc;
     d_index = c->d_argmax;
   }
@@ -4586,8 +4478,9 @@ int hh_simulate(hh_ctx* c, const double* params, float* image_out) try {
   const size_t npix = (size_t)c->n * c->n;
   rc = ensure_img(c, 1);
   if (rc) return rc;
-  double* dp = nullptr;
-  HH_HIP(c, hipMalloc(&dp, 4 * sizeof(double)));
+  DevArena mem;
+  double* dp = mem.get<double>(4);
+  if ((rc = arena_ok(c, mem))) return rc;
   hipError_t e = hipMemcpyAsync(dp, params, 4 * sizeof(double), hipMemcpyHostToDevice, c->stream);
   if (e == hipSuccess) {
     FirstArgs fa{};
@@ -4604,7 +4497,6 @@ int hh_simulate(hh_ctx* c, const double* params, float* image_out) try {
       if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     }
   }
-  (void)hipFree(dp);
   if (rc) return rc;
   if (e != hipSuccess) return fail(c, HH_ERR_HIP, std::string("hh_simulate: ") + hipGetErrorString(e));
   return HH_OK;
@@ -4621,8 +4513,9 @@ int hh_power_spectrum(hh_ctx* c, const float* image, int log_flag, float* pwr_ou
   HH_HIP(c, hipMemcpyAsync(c->d_img, image, npix * sizeof(float), hipMemcpyHostToDevice, c->stream));
   rc = spectra_of_images(c, 1);
   if (rc) return rc;
-  unsigned* d_mm = nullptr;
-  HH_HIP(c, hipMalloc(&d_mm, 2 * sizeof(unsigned)));
+  DevArena mem;
+  unsigned* d_mm = mem.get<unsigned>(2);
+  if ((rc = arena_ok(c, mem))) return rc;
   const unsigned init[2] = {0x7f800000u, 0u};  // +inf, 0
   hipError_t e = hipMemcpyAsync(d_mm, init, sizeof(init), hipMemcpyHostToDevice, c->stream);
   if (e == hipSuccess) {
@@ -4637,7 +4530,6 @@ int hh_power_spectrum(hh_ctx* c, const float* image, int log_flag, float* pwr_ou
       e = hipMemcpyAsync(phase_out, d_phase, npix * sizeof(float), hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
   }
-  (void)hipFree(d_mm);
   if (e != hipSuccess) return fail(c, HH_ERR_HIP, std::string("hh_power_spectrum: ") + hipGetErrorString(e));
   return HH_OK;
 } HH_CATCH_CTX(c, "hh_power_spectrum")
@@ -4673,13 +4565,12 @@ int hh_low_high_pass_filter(hh_ctx* c, const float* image, double low_pass_fract
 int hh_threshold_data(hh_ctx* c, const float* data, int64_t n, int use_fraction, double thresh, float* out) try {
   if (!c || !data || !out || n <= 0) return fail(c, HH_ERR_ARG, "hh_threshold_data: bad argument");
   HH_HIP(c, hipSetDevice(c->device));
-  float *d_x = nullptr, *d_y = nullptr;
-  int* d_mx = nullptr;
-  HH_HIP(c, hipMalloc(&d_x, (size_t)n * sizeof(float)));
-  hipError_t e = hipMalloc(&d_y, (size_t)n * sizeof(float));
-  if (e == hipSuccess) e = hipMalloc(&d_mx, 2 * sizeof(int));
+  DevArena mem;
+  float *d_x = mem.get<float>((size_t)n), *d_y = mem.get<float>((size_t)n);
+  int* d_mx = mem.get<int>(2);
+  if (int rc = arena_ok(c, mem)) return rc;
   const int init[2] = {(int)0x80000000, -1};  // below every non-negative float's bits; above every negative float's (as unsigned)
-  if (e == hipSuccess) e = hipMemcpyAsync(d_x, data, (size_t)n * sizeof(float), hipMemcpyHostToDevice, c->stream);
+  hipError_t e = hipMemcpyAsync(d_x, data, (size_t)n * sizeof(float), hipMemcpyHostToDevice, c->stream);
   if (e == hipSuccess) e = hipMemcpyAsync(d_mx, init, sizeof(init), hipMemcpyHostToDevice, c->stream);
   if (e == hipSuccess) {
     const int grid = (int)std::min<int64_t>(1024, (n + 255) / 256);
@@ -4690,9 +4581,6 @@ int hh_threshold_data(hh_ctx* c, const float* data, int64_t n, int use_fraction,
   }
   if (e == hipSuccess) e = hipMemcpyAsync(out, d_y, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, c->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  (void)hipFree(d_x);
-  (void)hipFree(d_y);
-  (void)hipFree(d_mx);
   if (e != hipSuccess) return fail(c, HH_ERR_HIP, std::string("hh_threshold_data: ") + hipGetErrorString(e));
   return HH_OK;
 } HH_CATCH_CTX(c, "hh_threshold_data")
@@ -4836,19 +4724,17 @@ int hh_affine_transform_2d(int device, const float* data, int ny, int nx, const 
   if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
     return fail(nullptr, HH_ERR_HIP, "hh_affine_transform_2d: no such HIP device (there is no CPU fallback)");
   const size_t bytes = (size_t)ny * nx * sizeof(float);
-  float *d_in = nullptr, *d_out = nullptr;
-  hipError_t e = hipSetDevice(device);
-  if (e == hipSuccess) e = hipMalloc(&d_in, bytes);
-  if (e == hipSuccess) e = hipMalloc(&d_out, bytes);
-  if (e == hipSuccess) e = hipMemcpy(d_in, data, bytes, hipMemcpyHostToDevice);
+  HH_HIP(nullptr, hipSetDevice(device));
+  DevArena mem;
+  float *d_in = mem.get<float>((size_t)ny * nx), *d_out = mem.get<float>((size_t)ny * nx);
+  if (int rc = arena_ok(nullptr, mem)) return rc;
+  hipError_t e = hipMemcpy(d_in, data, bytes, hipMemcpyHostToDevice);
   if (e == hipSuccess) {
     hipLaunchKernelGGL(k_affine_bilinear, dim3((nx + 255) / 256, ny), dim3(256), 0, 0, d_in, ny, nx, matrix[0], matrix[1],
                        matrix[2], matrix[3], offset[0], offset[1], d_out);
     e = hipGetLastError();
   }
   if (e == hipSuccess) e = hipMemcpy(out, d_out, bytes, hipMemcpyDeviceToHost);
-  (void)hipFree(d_in);
-  (void)hipFree(d_out);
   if (e != hipSuccess) return fail(nullptr, HH_ERR_HIP, std::string("hh_affine_transform_2d: ") + hipGetErrorString(e));
   return HH_OK;
 } HH_CATCH_CTX(nullptr, "hh_affine_transform_2d")
@@ -4879,13 +4765,12 @@ int hh_transform_map(int device, const float* data, const int32_t shape[3], doub
     for (int r = 0; r < 3; ++r)
       for (int cidx = 0; cidx < 3; ++cidx) a.m[3 * r + cidx] = t[3 * r] * rz3[cidx] + t[3 * r + 1] * rz3[3 + cidx] + t[3 * r + 2] * rz3[6 + cidx];
   }
-  float *d_in = nullptr, *d_out = nullptr;
-  double* d_c = nullptr;
-  hipError_t e = hipSetDevice(device);
-  if (e == hipSuccess) e = hipMalloc(&d_in, (size_t)total * sizeof(float));
-  if (e == hipSuccess) e = hipMalloc(&d_out, (size_t)total * sizeof(float));
-  if (e == hipSuccess) e = hipMalloc(&d_c, (size_t)total * sizeof(double));
-  if (e == hipSuccess) e = hipMemcpy(d_in, data, (size_t)total * sizeof(float), hipMemcpyHostToDevice);
+  HH_HIP(nullptr, hipSetDevice(device));
+  DevArena mem;
+  float *d_in = mem.get<float>((size_t)total), *d_out = mem.get<float>((size_t)total);
+  double* d_c = mem.get<double>((size_t)total);
+  if (int rc = arena_ok(nullptr, mem)) return rc;
+  hipError_t e = hipMemcpy(d_in, data, (size_t)total * sizeof(float), hipMemcpyHostToDevice);
   if (e == hipSuccess) {
     const unsigned blocks = (unsigned)((total + 255) / 256);
     hipLaunchKernelGGL(k_f32_to_f64, dim3(blocks), dim3(256), 0, 0, d_in, total, d_c);
@@ -4901,9 +4786,6 @@ int hh_transform_map(int device, const float* data, const int32_t shape[3], doub
     e = hipGetLastError();
   }
   if (e == hipSuccess) e = hipMemcpy(out, d_out, (size_t)total * sizeof(float), hipMemcpyDeviceToHost);
-  (void)hipFree(d_in);
-  (void)hipFree(d_out);
-  (void)hipFree(d_c);
   if (e != hipSuccess) return fail(nullptr, HH_ERR_HIP, std::string("hh_transform_map: ") + hipGetErrorString(e));
   return HH_OK;
 } HH_CATCH_CTX(nullptr, "hh_transform_map")
@@ -4964,13 +4846,12 @@ int hh_apply_helical_symmetry(int device, const float* data, const int32_t in_sh
     return fail(nullptr, HH_ERR_HIP, "hh_apply_helical_symmetry: no such HIP device (no CPU fallback)");
   HH_HIP(nullptr, hipSetDevice(device));
   const size_t n_in = (size_t)nz0 * ny0 * nx0, n_out = (size_t)a.oz * a.oy * a.ox;
-  float *d_in = nullptr, *d_out = nullptr;
-  double* d_rot = nullptr;
+  DevArena mem;
+  float *d_in = mem.get<float>(n_in), *d_out = mem.get<float>(n_out);
+  double* d_rot = mem.get<double>(rot.size());
+  if (int rc = arena_ok(nullptr, mem)) return rc;
   hipEvent_t e0 = nullptr, e1 = nullptr;
-  hipError_t e = hipMalloc(&d_in, n_in * sizeof(float));
-  if (e == hipSuccess) e = hipMalloc(&d_out, n_out * sizeof(float));
-  if (e == hipSuccess) e = hipMalloc(&d_rot, rot.size() * sizeof(double));
-  if (e == hipSuccess) e = hipEventCreate(&e0);
+  hipError_t e = hipEventCreate(&e0);
   if (e == hipSuccess) e = hipEventCreate(&e1);
   if (e == hipSuccess) e = hipMemcpy(d_in, data, n_in * sizeof(float), hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(d_rot, rot.data(), rot.size() * sizeof(double), hipMemcpyHostToDevice);
@@ -4987,7 +4868,6 @@ int hh_apply_helical_symmetry(int device, const float* data, const int32_t in_sh
     e = hipEventElapsedTime(&ms, e0, e1);
     *kernel_ms = ms;
   }
-  (void)hipFree(d_in); (void)hipFree(d_out); (void)hipFree(d_rot);
   if (e0) (void)hipEventDestroy(e0);
   if (e1) (void)hipEventDestroy(e1);
   if (e != hipSuccess) return fail(nullptr, HH_ERR_HIP, std::string("hh_apply_helical_symmetry: ") + hipGetErrorString(e));
@@ -5000,10 +4880,10 @@ int hh_calibrate_traffic(hh_ctx* c, int mode, int64_t bytes) try {
   HH_HIP(c, hipSetDevice(c->device));
   const size_t unit = (size_t)256 * 512 * sizeof(float2);  // one 512-side half spectrum (1 MiB)
   const size_t n_units = std::max<size_t>(1, (size_t)bytes / unit);
-  float2* buf = nullptr;
-  float* sink = nullptr;
-  HH_HIP(c, hipMalloc(&buf, n_units * unit));
-  HH_HIP(c, hipMalloc(&sink, sizeof(float)));
+  DevArena mem;
+  float2* buf = mem.get<float2>(n_units * (unit / sizeof(float2)));
+  float* sink = mem.get<float>(1);
+  if (int rc = arena_ok(c, mem)) return rc;
   hipError_t e = hipMemsetAsync(buf, 0, n_units * unit, c->stream);
   if (e == hipSuccess) {
     if (mode == 0)
@@ -5014,8 +4894,6 @@ int hh_calibrate_traffic(hh_ctx* c, int mode, int64_t bytes) try {
     e = hipGetLastError();
   }
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  (void)hipFree(buf);
-  (void)hipFree(sink);
   if (e != hipSuccess) return fail(c, HH_ERR_HIP, std::string("hh_calibrate_traffic: ") + hipGetErrorString(e));
   return HH_OK;
 } HH_CATCH_CTX(c, "hh_calibrate_traffic")

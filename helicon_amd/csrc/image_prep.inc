@@ -19,19 +19,6 @@
 
 namespace {
 
-struct PrepMem {   // device buffers of one call, freed on every way out
-  std::vector<void*> held;
-  ~PrepMem() { for (void* v : held) (void)hipFree(v); }
-  template <typename T>
-  hipError_t get(T** out, size_t count) {
-    void* v = nullptr;
-    const hipError_t e = hipMalloc(&v, std::max<size_t>(count, 1) * sizeof(T));
-    if (e == hipSuccess) held.push_back(v);
-    *out = static_cast<T*>(v);
-    return e;
-  }
-};
-
 int prep_device(int device, const char* fn) {
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
@@ -395,13 +382,12 @@ __global__ __launch_bounds__(256) void k_joint_hist(const float* __restrict__ a,
 template <typename T>
 int prep_warp(const T* data, int rows, int cols, const double* inverse_matrix, int order, double cval, int clip, T* out) {
   const size_t n = (size_t)rows * cols;
-  PrepMem mem;
-  T *d_in = nullptr, *d_out = nullptr;
-  double* d_range = nullptr;
-  hipError_t e = mem.get(&d_in, n);
-  if (e == hipSuccess) e = mem.get(&d_out, n);
-  if (e == hipSuccess) e = mem.get(&d_range, 2);
-  if (e == hipSuccess) e = hipMemcpy(d_in, data, n * sizeof(T), hipMemcpyHostToDevice);
+  DevArena mem;
+  T* d_in = mem.get<T>(n);
+  T* d_out = mem.get<T>(n);
+  double* d_range = mem.get<double>(2);
+  if (int rc = arena_ok(nullptr, mem)) return rc;
+  hipError_t e = hipMemcpy(d_in, data, n * sizeof(T), hipMemcpyHostToDevice);
   if (e == hipSuccess) {
     WarpArgs<T> a{};
     for (int i = 0; i < 9; ++i) a.h[i] = (T)inverse_matrix[i];   // matrix.astype(image.dtype)
@@ -423,16 +409,15 @@ int prep_warp(const T* data, int rows, int cols, const double* inverse_matrix, i
 template <typename T>
 int prep_rescale(const T* data, int rows, int cols, int out_rows, int out_cols, int order, int anti_aliasing, int clip, T* out) {
   const size_t n = (size_t)rows * cols, m = (size_t)out_rows * out_cols;
-  PrepMem mem;
-  T *d_in = nullptr, *d_a = nullptr, *d_b = nullptr, *d_out = nullptr;
-  double *d_c = nullptr, *d_range = nullptr;
-  hipError_t e = mem.get(&d_in, n);
-  if (e == hipSuccess) e = mem.get(&d_a, n);
-  if (e == hipSuccess) e = mem.get(&d_b, n);
-  if (e == hipSuccess) e = mem.get(&d_out, m);
-  if (e == hipSuccess) e = mem.get(&d_c, n);
-  if (e == hipSuccess) e = mem.get(&d_range, 2);
-  if (e == hipSuccess) e = hipMemcpy(d_in, data, n * sizeof(T), hipMemcpyHostToDevice);
+  DevArena mem;
+  T* d_in = mem.get<T>(n);
+  T* d_a = mem.get<T>(n);
+  T* d_b = mem.get<T>(n);
+  T* d_out = mem.get<T>(m);
+  double* d_c = mem.get<double>(n);
+  double* d_range = mem.get<double>(2);
+  if (int rc = arena_ok(nullptr, mem)) return rc;
+  hipError_t e = hipMemcpy(d_in, data, n * sizeof(T), hipMemcpyHostToDevice);
   if (e != hipSuccess) return fail(nullptr, HH_ERR_HIP, std::string("hh_rescale_2d: ") + hipGetErrorString(e));
   const T* cur = d_in;
   // resize(): factors = input shape / output shape; anti_aliasing_sigma = max(0, (factors - 1) / 2); gaussian_filter skips an
@@ -449,9 +434,9 @@ int prep_rescale(const T* data, int rows, int cols, int out_rows, int out_cols, 
       double sum = 0.0;
       for (int j = -lw; j <= lw; ++j) sum += std::exp(-0.5 / (sigma * sigma) * (double)j * (double)j);
       for (int j = 0; j <= lw; ++j) w[(size_t)j] = std::exp(-0.5 / (sigma * sigma) * (double)j * (double)j) / sum;
-      double* d_wa = nullptr;
-      e = mem.get(&d_wa, w.size());
-      if (e == hipSuccess) e = hipMemcpy(d_wa, w.data(), w.size() * sizeof(double), hipMemcpyHostToDevice);
+      double* d_wa = mem.get<double>(w.size());
+      if (int rc = arena_ok(nullptr, mem)) return rc;
+      e = hipMemcpy(d_wa, w.data(), w.size() * sizeof(double), hipMemcpyHostToDevice);
       if (e != hipSuccess) return fail(nullptr, HH_ERR_HIP, std::string("hh_rescale_2d: ") + hipGetErrorString(e));
       hipLaunchKernelGGL(k_gauss_axis<T>, dim3((cols + 255) / 256, rows), dim3(256), 0, 0, cur, dst[pass], rows, cols, axis, d_wa, lw);
       cur = dst[pass];
@@ -483,15 +468,13 @@ int prep_rescale(const T* data, int rows, int cols, int out_rows, int out_cols, 
 template <typename T>
 int prep_moments(const T* data, int rows, int cols, double threshold, double* out) {
   const size_t n = (size_t)rows * cols;
-  PrepMem mem;
-  T* d_in = nullptr;
-  unsigned char *d_dil = nullptr, *d_clo = nullptr;
-  double* d_out = nullptr;
-  hipError_t e = mem.get(&d_in, n);
-  if (e == hipSuccess) e = mem.get(&d_dil, n);
-  if (e == hipSuccess) e = mem.get(&d_clo, n);
-  if (e == hipSuccess) e = mem.get(&d_out, 8);
-  if (e == hipSuccess) e = hipMemcpy(d_in, data, n * sizeof(T), hipMemcpyHostToDevice);
+  DevArena mem;
+  T* d_in = mem.get<T>(n);
+  unsigned char* d_dil = mem.get<unsigned char>(n);
+  unsigned char* d_clo = mem.get<unsigned char>(n);
+  double* d_out = mem.get<double>(8);
+  if (int rc = arena_ok(nullptr, mem)) return rc;
+  hipError_t e = hipMemcpy(d_in, data, n * sizeof(T), hipMemcpyHostToDevice);
   if (e == hipSuccess) {
     const dim3 grid((cols + 255) / 256, rows);
     hipLaunchKernelGGL((k_closing_cross<T, 0>), grid, dim3(256), 0, 0, d_in, (const unsigned char*)nullptr, rows, cols, threshold, d_dil);
@@ -530,13 +513,12 @@ int hh_affine_transform_2d_cubic(int device, const float* data, int ny, int nx, 
   if (!data || !out || !matrix || !offset || ny < 1 || nx < 1) return fail(nullptr, HH_ERR_ARG, "hh_affine_transform_2d_cubic: bad argument");
   if (int rc = prep_device(device, "hh_affine_transform_2d_cubic")) return rc;
   const size_t n = (size_t)ny * nx;
-  PrepMem mem;
-  float *d_in = nullptr, *d_out = nullptr;
-  double* d_c = nullptr;
-  hipError_t e = mem.get(&d_in, n);
-  if (e == hipSuccess) e = mem.get(&d_out, n);
-  if (e == hipSuccess) e = mem.get(&d_c, n);
-  if (e == hipSuccess) e = hipMemcpy(d_in, data, n * sizeof(float), hipMemcpyHostToDevice);
+  DevArena mem;
+  float* d_in = mem.get<float>(n);
+  float* d_out = mem.get<float>(n);
+  double* d_c = mem.get<double>(n);
+  if (int rc = arena_ok(nullptr, mem)) return rc;
+  hipError_t e = hipMemcpy(d_in, data, n * sizeof(float), hipMemcpyHostToDevice);
   if (e == hipSuccess) {
     hipLaunchKernelGGL(k_prep_to_f64<float>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, d_in, (int64_t)n, d_c);
     hipLaunchKernelGGL(k_spline_prefilter, dim3((unsigned)((nx + 127) / 128)), dim3(128), 0, 0, d_c, (int64_t)nx, ny, (int64_t)nx, (int64_t)nx);
@@ -562,16 +544,15 @@ int hh_ssim_2d(int device, const float* a, const float* b, int rows, int cols, d
     return fail(nullptr, HH_ERR_ARG, "hh_ssim_2d: bad argument (the 7 x 7 window must fit the image, data_range > 0)");
   if (int rc = prep_device(device, "hh_ssim_2d")) return rc;
   const size_t n = (size_t)rows * cols;
-  PrepMem mem;
-  float *d_a = nullptr, *d_b = nullptr, *d_m = nullptr;
-  double* d_sum = nullptr;
+  DevArena mem;
   const dim3 g0((cols + 255) / 256, rows - 6), g1((cols - 6 + 255) / 256, rows - 6);
   const int nsum = (int)(g1.x * g1.y);
-  hipError_t e = mem.get(&d_a, n);
-  if (e == hipSuccess) e = mem.get(&d_b, n);
-  if (e == hipSuccess) e = mem.get(&d_m, 5 * n);
-  if (e == hipSuccess) e = mem.get(&d_sum, (size_t)nsum);
-  if (e == hipSuccess) e = hipMemcpy(d_a, a, n * sizeof(float), hipMemcpyHostToDevice);
+  float* d_a = mem.get<float>(n);
+  float* d_b = mem.get<float>(n);
+  float* d_m = mem.get<float>(5 * n);
+  double* d_sum = mem.get<double>((size_t)nsum);
+  if (int rc = arena_ok(nullptr, mem)) return rc;
+  hipError_t e = hipMemcpy(d_a, a, n * sizeof(float), hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(d_b, b, n * sizeof(float), hipMemcpyHostToDevice);
   std::vector<double> sums((size_t)nsum);
   if (e == hipSuccess) {
@@ -594,17 +575,15 @@ int hh_joint_histogram(int device, const float* a, const float* b, int64_t n, co
   if (!a || !b || !edges_a || !edges_b || !hist || n < 1 || bins < 1 || bins > 4096)
     return fail(nullptr, HH_ERR_ARG, "hh_joint_histogram: bad argument");
   if (int rc = prep_device(device, "hh_joint_histogram")) return rc;
-  PrepMem mem;
-  float *d_a = nullptr, *d_b = nullptr;
-  double *d_ea = nullptr, *d_eb = nullptr;
-  unsigned long long* d_h = nullptr;
+  DevArena mem;
   const size_t nb = (size_t)bins * bins;
-  hipError_t e = mem.get(&d_a, (size_t)n);
-  if (e == hipSuccess) e = mem.get(&d_b, (size_t)n);
-  if (e == hipSuccess) e = mem.get(&d_ea, (size_t)bins + 1);
-  if (e == hipSuccess) e = mem.get(&d_eb, (size_t)bins + 1);
-  if (e == hipSuccess) e = mem.get(&d_h, nb);
-  if (e == hipSuccess) e = hipMemcpy(d_a, a, (size_t)n * sizeof(float), hipMemcpyHostToDevice);
+  float* d_a = mem.get<float>((size_t)n);
+  float* d_b = mem.get<float>((size_t)n);
+  double* d_ea = mem.get<double>((size_t)bins + 1);
+  double* d_eb = mem.get<double>((size_t)bins + 1);
+  unsigned long long* d_h = mem.get<unsigned long long>(nb);
+  if (int rc = arena_ok(nullptr, mem)) return rc;
+  hipError_t e = hipMemcpy(d_a, a, (size_t)n * sizeof(float), hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(d_b, b, (size_t)n * sizeof(float), hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(d_ea, edges_a, ((size_t)bins + 1) * sizeof(double), hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(d_eb, edges_b, ((size_t)bins + 1) * sizeof(double), hipMemcpyHostToDevice);

@@ -202,20 +202,21 @@ extern "C" int hh_low_high_pass_filter_3d(int device, const float* data, const i
     ops.push_back({-1, 0, 0, 5, -1, -1});   // marker: accumulate plane 5 with this term's coefficient
   }
   HH_HIP(nullptr, hipSetDevice(device));
+  DevArena mem;
   float* planes[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  float *d_acc = nullptr, *d_mats = nullptr;
+  float* d_mats = nullptr;
   const size_t bytes = (size_t)total * sizeof(float);
-  hipError_t e = hipMalloc(&planes[0], bytes);
-  if (e == hipSuccess) e = hipMalloc(&d_acc, bytes);
+  planes[0] = mem.get<float>((size_t)total);
+  float* d_acc = mem.get<float>((size_t)total);
   if (!ops.empty()) {
-    for (int p : {1, 3, 5})
-      if (e == hipSuccess) e = hipMalloc(&planes[p], bytes);
+    for (int p : {1, 3, 5}) planes[p] = mem.get<float>((size_t)total);
     if (any_odd)
-      for (int p : {2, 4})
-        if (e == hipSuccess) e = hipMalloc(&planes[p], bytes);
-    if (e == hipSuccess) e = hipMalloc(&d_mats, mats.size() * sizeof(float));
-    if (e == hipSuccess) e = hipMemcpy(d_mats, mats.data(), mats.size() * sizeof(float), hipMemcpyHostToDevice);
+      for (int p : {2, 4}) planes[p] = mem.get<float>((size_t)total);
+    d_mats = mem.get<float>(mats.size());
   }
+  if (int rc = arena_ok(nullptr, mem)) return rc;
+  hipError_t e = hipSuccess;
+  if (d_mats) e = hipMemcpy(d_mats, mats.data(), mats.size() * sizeof(float), hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(planes[0], data, bytes, hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemsetAsync(d_acc, 0, bytes, nullptr);
   const unsigned axpy_blocks = (unsigned)std::min<int64_t>((total + 255) / 256, 8192);
@@ -259,9 +260,6 @@ extern "C" int hh_low_high_pass_filter_3d(int device, const float* data, const i
     }
   }
   if (e == hipSuccess) e = hipMemcpy(out, d_acc, bytes, hipMemcpyDeviceToHost);
-  for (float* p : planes) (void)hipFree(p);
-  (void)hipFree(d_acc);
-  (void)hipFree(d_mats);
   if (e != hipSuccess) return fail(nullptr, HH_ERR_HIP, std::string("hh_low_high_pass_filter_3d: ") + hipGetErrorString(e));
   return HH_OK;
 } HH_CATCH_CTX(nullptr, "hh_low_high_pass_filter_3d")
@@ -279,12 +277,13 @@ extern "C" int hh_map_projections(int device, const float* data, const int32_t s
     return fail(nullptr, HH_ERR_HIP, "hh_map_projections: no such HIP device (there is no CPU fallback)");
   HH_HIP(nullptr, hipSetDevice(device));
   const int64_t plane = (int64_t)ny * nx, total = plane * nz;
-  float *d_v = nullptr, *d_x = nullptr, *d_y = nullptr, *d_z = nullptr;
-  hipError_t e = hipMalloc(&d_v, (size_t)total * sizeof(float));
-  if (e == hipSuccess) e = hipMalloc(&d_x, (size_t)nz * ny * sizeof(float));
-  if (e == hipSuccess) e = hipMalloc(&d_y, (size_t)nz * nx * sizeof(float));
-  if (e == hipSuccess) e = hipMalloc(&d_z, (size_t)plane * sizeof(float));
-  if (e == hipSuccess) e = hipMemcpy(d_v, data, (size_t)total * sizeof(float), hipMemcpyHostToDevice);
+  DevArena mem;
+  float* d_v = mem.get<float>((size_t)total);
+  float* d_x = mem.get<float>((size_t)nz * ny);
+  float* d_y = mem.get<float>((size_t)nz * nx);
+  float* d_z = mem.get<float>((size_t)plane);
+  if (int rc = arena_ok(nullptr, mem)) return rc;
+  hipError_t e = hipMemcpy(d_v, data, (size_t)total * sizeof(float), hipMemcpyHostToDevice);
   if (e == hipSuccess) {
     hipLaunchKernelGGL(k_map_proj_slices, dim3((unsigned)nz), dim3(256), 0, nullptr, d_v, ny, nx, d_x, d_y);
     hipLaunchKernelGGL(k_map_proj_columns, dim3((unsigned)((plane + 255) / 256)), dim3(256), 0, nullptr, d_v, nz, plane, slab_begin,
@@ -294,7 +293,6 @@ extern "C" int hh_map_projections(int device, const float* data, const int32_t s
   if (e == hipSuccess) e = hipMemcpy(out_x, d_x, (size_t)nz * ny * sizeof(float), hipMemcpyDeviceToHost);
   if (e == hipSuccess) e = hipMemcpy(out_y, d_y, (size_t)nz * nx * sizeof(float), hipMemcpyDeviceToHost);
   if (e == hipSuccess) e = hipMemcpy(out_z, d_z, (size_t)plane * sizeof(float), hipMemcpyDeviceToHost);
-  (void)hipFree(d_v); (void)hipFree(d_x); (void)hipFree(d_y); (void)hipFree(d_z);
   if (e != hipSuccess) return fail(nullptr, HH_ERR_HIP, std::string("hh_map_projections: ") + hipGetErrorString(e));
   return HH_OK;
 } HH_CATCH_CTX(nullptr, "hh_map_projections")

@@ -334,12 +334,12 @@ struct hh_pa {
   PaGeom g{};
   int64_t n = 0, m_data = 0, m_sym = 0;
   int n_ops_used = 0;
-  int* d_map = nullptr;          // [n_ops_used][L2][D2][D2]
-  int* d_ray_of_row = nullptr;   // [m_data] ray index (o * L2 + k) * D2 + j
-  int2* d_pairs = nullptr;       // [m_sym] (nearest neighbour)
-  PaEll16* d_sym16 = nullptr;    // [m_sym] (trilinear)
-  PaOp* d_ops = nullptr;         // [n_ops] (kept: the trilinear products recompute the geometry)
-  int* d_rank = nullptr;         // [mz][my][mx] voxel rank, -1 outside the cylinder
+  DevBuf<int> d_map;             // [n_ops_used][L2][D2][D2]
+  DevBuf<int> d_ray_of_row;      // [m_data] ray index (o * L2 + k) * D2 + j
+  DevBuf<int2> d_pairs;          // [m_sym] (nearest neighbour)
+  DevBuf<PaEll16> d_sym16;       // [m_sym] (trilinear)
+  DevBuf<PaOp> d_ops;            // [n_ops] (kept: the trilinear products recompute the geometry)
+  DevBuf<int> d_rank;            // [mz][my][mx] voxel rank, -1 outside the cylinder
   double colsum = 0;             // largest column sum of |A| (sizes the fixed-point scale of A^T y)
   // pinned host staging: vectors cross the boundary through these, never straight from / to the caller's pageable
   // arrays — the runtime pins such pages on the fly, and with the solver's stream of freshly allocated NumPy arrays
@@ -353,6 +353,5 @@ struct hh_pa {
   std::vector<float> b_data;     // [m_data]
   std::vector<int32_t> b_pid;    // [m_data]
   // work vectors (float64)
-  double *d_x = nullptr, *d_y = nullptr, *d_u = nullptr, *d_v = nullptr, *d_h = nullptr, *d_hbar = nullptr, *d_w = nullptr,
-         *d_scale = nullptr, *d_root = nullptr, *d_red = nullptr;
+  DevBuf<double> d_x, d_y, d_u, d_v, d_h, d_hbar, d_w, d_scale, d_root, d_red;
 };

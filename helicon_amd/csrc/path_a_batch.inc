@@ -1117,24 +1117,24 @@ struct hh_pab {
   int d2 = 0, d2p = 0;
   int sliced = 0, mz = 0, nslice = 0;   // tilt = psi = 0 and a slice fits LDS: the slice-major products
   int linear = 0;                       // trilinear projector (all candidates of a batch alike); needs `sliced`
-  unsigned* d_sidx2 = nullptr;
-  PaEll16* d_sym16 = nullptr;
-  int2* d_tent2 = nullptr;
-  long long* d_acc64 = nullptr;
+  DevBuf<unsigned> d_sidx2;
+  DevBuf<PaEll16> d_sym16;
+  DevBuf<int2> d_tent2;
+  DevBuf<long long> d_acc64;
   size_t lin_lds = 0;                   // dynamic LDS of the trilinear products
   int fac_G = 0, fac_ng = 0, fac_max_gl = 0, fac_max_lists = 0;   // separable form (path_a_factored.inc); G = 0: direct kernels
   int fac_split = 1;
   size_t fac_lds = 0;
   int band_T = 0;                       // banded form (path_a_banded.inc); T = 0: not this form
   size_t band_lds = 0;
-  int* d_band_y = nullptr;
-  int* d_band_v = nullptr;
-  double* d_bpart = nullptr;
+  DevBuf<int> d_band_y;
+  DevBuf<int> d_band_v;
+  DevBuf<double> d_bpart;
   int flat = 0;                         // every candidate has tilt = psi = 0
-  int* d_fac_ngl = nullptr;
-  PabfGroupList* d_fac_gl = nullptr;
-  PabfEntry* d_fac_entries = nullptr;
-  unsigned char* d_fac_count = nullptr;
+  DevBuf<int> d_fac_ngl;
+  DevBuf<PabfGroupList> d_fac_gl;
+  DevBuf<PabfEntry> d_fac_entries;
+  DevBuf<unsigned char> d_fac_count;
   int RB = 0;
   int nb_n = 0, nb_m = 0, nb_mv = 0, nb_mva = 0;   // grid.x of: vectors over n, over m (+ n), products without / with augmented rows
   int nb_fin = 0;                                  // ... of the trilinear A^T y's gather half (k_pabl_finish)
@@ -1142,30 +1142,30 @@ struct hh_pab {
   std::vector<float> b_data;      // concatenated
   std::vector<int32_t> b_pid;
   std::vector<int> n_ops_used;
-  PabState* d_st = nullptr;
-  unsigned* d_ctl = nullptr;
-  PaGeom* d_geom = nullptr;
-  PaOp* d_ops = nullptr;
-  int64_t* d_op0 = nullptr;
-  int* d_rank = nullptr;
-  int* d_map = nullptr;
-  uint16_t* d_map16 = nullptr;
-  int* d_maprow = nullptr;
-  int* d_srow = nullptr;
-  int* d_ray_of_row = nullptr;
-  float* d_bref = nullptr;        // device-side enumeration: b and pixel ids in the reference's row order (hh_pab_get_rhs)
-  int* d_pidref = nullptr;
-  int2* d_pairs = nullptr;
-  int* d_tptr = nullptr;
-  int* d_tent = nullptr;
-  double* d_nv = nullptr;
-  double* d_mv = nullptr;
-  double* d_red = nullptr;
-  float* d_xf = nullptr;
-  double* d_trace = nullptr;
+  DevBuf<PabState> d_st;
+  DevBuf<unsigned> d_ctl;
+  DevBuf<PaGeom> d_geom;
+  DevBuf<PaOp> d_ops;
+  DevBuf<int64_t> d_op0;
+  DevBuf<int> d_rank;
+  DevBuf<int> d_map;
+  DevBuf<uint16_t> d_map16;
+  DevBuf<int> d_maprow;
+  DevBuf<int> d_srow;
+  DevBuf<int> d_ray_of_row;
+  DevBuf<float> d_bref;           // device-side enumeration: b and pixel ids in the reference's row order (hh_pab_get_rhs)
+  DevBuf<int> d_pidref;
+  DevBuf<int2> d_pairs;
+  DevBuf<int> d_tptr;
+  DevBuf<int> d_tent;
+  DevBuf<double> d_nv;
+  DevBuf<double> d_mv;
+  DevBuf<double> d_red;
+  DevBuf<float> d_xf;
+  DevBuf<double> d_trace;
   int trace_c = -1, trace_run = 0;
-  int* d_flags = nullptr;
-  int* d_lists = nullptr;         // [2][K]: candidates not finished / of those, the ones outside an LSMR solve (k_pab_lists)
+  DevBuf<int> d_flags;
+  DevBuf<int> d_lists;            // [2][K]: candidates not finished / of those, the ones outside an LSMR solve (k_pab_lists)
   const int* cur_list = nullptr;  // the list the next launches cover (NULL: all K)
   int cur_n = 0;
   void* h_stage = nullptr;        // pinned staging of THIS object (no process-wide buffer, no lock)
@@ -1217,12 +1217,15 @@ int pab_to_host(hh_pab* p, void* dst, const void* src, size_t bytes) {
   std::memcpy(dst, p->h_stage, bytes);
   return HH_OK;
 }
+// a buffer of the object (at least one element), counted in device_bytes
 template <class T>
-int pab_alloc(hh_pab* p, T** out, size_t count) {
-  const size_t bytes = std::max<size_t>(count, 1) * sizeof(T);
-  PAB_HIP(p, hipMalloc(reinterpret_cast<void**>(out), bytes));
-  p->device_bytes += bytes;
+int pab_alloc(hh_pab* p, DevBuf<T>& out, size_t count) {
+  if (!out.ensure(std::max<size_t>(count, 1))) return pab_fail(p, HH_ERR_NOMEM, dev_alloc_failed(out.bytes_for(std::max<size_t>(count, 1))));
+  p->device_bytes += out.bytes();
   return HH_OK;
+}
+int pab_arena_ok(hh_pab* p, const DevArena& mem) {
+  return mem.ok() ? HH_OK : pab_fail(p, HH_ERR_NOMEM, dev_alloc_failed(mem.failed_bytes()));
 }
 
 inline int pab_slots(const hh_pab* p) { return p->cur_list ? p->cur_n : p->K; }
@@ -1596,17 +1599,11 @@ void hh_pab_destroy(hh_pab* p) try {
   if (!p) return;
   (void)hipSetDevice(p->device);
   if (p->stream) (void)hipStreamSynchronize(p->stream);
-  for (void* v : {(void*)p->d_st, (void*)p->d_ctl, (void*)p->d_geom, (void*)p->d_ops, (void*)p->d_op0, (void*)p->d_rank, (void*)p->d_map, (void*)p->d_map16, (void*)p->d_maprow,
-                  (void*)p->d_srow, (void*)p->d_ray_of_row, (void*)p->d_bref, (void*)p->d_pidref,
-                  (void*)p->d_pairs, (void*)p->d_tptr, (void*)p->d_tent, (void*)p->d_nv, (void*)p->d_mv, (void*)p->d_red, (void*)p->d_xf,
-                  (void*)p->d_flags, (void*)p->d_lists, (void*)p->d_trace, (void*)p->d_sidx2,
-                  (void*)p->d_sym16, (void*)p->d_tent2, (void*)p->d_acc64, (void*)p->d_fac_ngl, (void*)p->d_fac_gl, (void*)p->d_fac_entries,
-                  (void*)p->d_fac_count, (void*)p->d_band_y, (void*)p->d_band_v, (void*)p->d_bpart})
-    if (v) (void)hipFree(v);
   if (p->h_stage) (void)hipHostFree(p->h_stage);
   if (p->h_flags) (void)hipHostFree(p->h_flags);
-  if (p->stream) (void)hipStreamDestroy(p->stream);
-  delete p;
+  const hipStream_t stream = p->stream;
+  delete p;                                   // frees the device buffers: before their stream goes
+  if (stream) (void)hipStreamDestroy(stream);
 } catch (...) {
 }
 
@@ -1699,7 +1696,7 @@ int hh_pab_create_ex(hh_pab** out, int device, const float* image, int ny, int n
       }
     }
   }
-  PAB_RC(pab_alloc(p, &p->d_rank, rank.size()));
+  PAB_RC(pab_alloc(p, p->d_rank, rank.size()));
   PAB_RC(pab_to_device(p, p->d_rank, rank.data(), rank.size() * sizeof(int)));
   // geometry and symmetry operations of every candidate, in the reference's order (solver:1556-1571)
   std::vector<PaGeom> geoms((size_t)count);
@@ -1747,11 +1744,11 @@ int hh_pab_create_ex(hh_pab** out, int device, const float* image, int ny, int n
     for (const PaOp& op : ops) ok = ok && op.m_z[2] == 0 && op.m_z[5] == 0 && op.m_z[6] == 0 && op.m_z[7] == 0;
     if (!ok) { p->err = "hh_pab_create: the rotations are not of the form the trilinear ray arithmetic assumes (internal)"; return bail(HH_ERR_STATE); }
   }
-  PAB_RC(pab_alloc(p, &p->d_geom, geoms.size()));
+  PAB_RC(pab_alloc(p, p->d_geom, geoms.size()));
   PAB_RC(pab_to_device(p, p->d_geom, geoms.data(), geoms.size() * sizeof(PaGeom)));
-  PAB_RC(pab_alloc(p, &p->d_ops, ops.size()));
+  PAB_RC(pab_alloc(p, p->d_ops, ops.size()));
   PAB_RC(pab_to_device(p, p->d_ops, ops.data(), ops.size() * sizeof(PaOp)));
-  PAB_RC(pab_alloc(p, &p->d_op0, op0.size()));
+  PAB_RC(pab_alloc(p, p->d_op0, op0.size()));
   PAB_RC(pab_to_device(p, p->d_op0, op0.data(), op0.size() * sizeof(int64_t)));
   const PabGeomRef gr{p->d_geom, p->d_ops, p->d_op0};
   // which rays exist, operation chunk by chunk, until every candidate has passed its row target (solver:1647)
@@ -1769,27 +1766,21 @@ int hh_pab_create_ex(hh_pab** out, int device, const float* image, int ny, int n
   // second sweep over the used chunks writes the rows where they belong — no per-ray data crosses PCIe.
   bool dev_rows = std::getenv("HH_PAB_HOST_ROWS") == nullptr;
   for (int c = 0; c < count; ++c) dev_rows = dev_rows && qs[c].fsc_half == 0;
-  float* d_b_int = nullptr;              // device-order b of the data rows (device path; freed once MV_B is filled)
+  DevBuf<float> d_b_int;                 // device-order b of the data rows (device path; freed once MV_B is filled)
   std::vector<int> srow_h;               // [count][mz + 1] (device path)
   if (dev_rows) {
     const int mz1 = p->mz + 1;
-    int *d_cand = nullptr, *d_nops = nullptr, *d_counts = nullptr, *d_bmax = nullptr;
-    unsigned char* d_has = nullptr;
-    float* d_image = nullptr;
-    long long *d_bref_t = nullptr, *d_bint_t = nullptr, *d_row0_t = nullptr;
-    std::vector<void*> tmp;
-    auto dalloc = [&](void** out, size_t bytes) { const hipError_t e = hipMalloc(out, std::max<size_t>(bytes, 16)); if (e == hipSuccess) tmp.push_back(*out); return e; };
-    auto free_tmp = [&] { for (void* v : tmp) (void)hipFree(v); tmp.clear(); };
-    hipError_t e = dalloc(reinterpret_cast<void**>(&d_cand), (size_t)count * sizeof(int));
-    if (e == hipSuccess) e = dalloc(reinterpret_cast<void**>(&d_nops), (size_t)count * sizeof(int));
-    if (e == hipSuccess) e = dalloc(reinterpret_cast<void**>(&d_has), (size_t)count * chunk * rays);
-    if (e == hipSuccess) e = dalloc(reinterpret_cast<void**>(&d_counts), (size_t)count * chunk * mz1 * sizeof(int));
-    if (e == hipSuccess) e = dalloc(reinterpret_cast<void**>(&d_bmax), (size_t)count * sizeof(int));
-    if (e == hipSuccess) e = dalloc(reinterpret_cast<void**>(&d_image), (size_t)ny * nx * sizeof(float));
-    if (e == hipSuccess) e = dalloc(reinterpret_cast<void**>(&d_bref_t), (size_t)count * chunk * sizeof(long long));
-    if (e == hipSuccess) e = dalloc(reinterpret_cast<void**>(&d_bint_t), (size_t)count * chunk * mz1 * sizeof(long long));
-    if (e == hipSuccess) e = dalloc(reinterpret_cast<void**>(&d_row0_t), (size_t)count * sizeof(long long));
-    if (e != hipSuccess) { free_tmp(); p->err = std::string("hh_pab_create: ") + hipGetErrorString(e); return bail(HH_ERR_NOMEM); }
+    DevArena tmp;   // freed on every way out
+    int* d_cand = tmp.get<int>((size_t)count);
+    int* d_nops = tmp.get<int>((size_t)count);
+    unsigned char* d_has = tmp.get<unsigned char>((size_t)count * chunk * rays);
+    int* d_counts = tmp.get<int>((size_t)count * chunk * mz1);
+    int* d_bmax = tmp.get<int>((size_t)count);
+    float* d_image = tmp.get<float>((size_t)ny * nx);
+    long long* d_bref_t = tmp.get<long long>((size_t)count * chunk);
+    long long* d_bint_t = tmp.get<long long>((size_t)count * chunk * mz1);
+    long long* d_row0_t = tmp.get<long long>((size_t)count);
+    PAB_RC(pab_arena_ok(p, tmp));
     rc = pab_to_device(p, d_nops, n_ops.data(), n_ops.size() * sizeof(int));
     if (rc == HH_OK) rc = pab_to_device(p, d_image, image, (size_t)ny * nx * sizeof(float));
     // pass 1: counts per (candidate, operation, slice)
@@ -1845,12 +1836,11 @@ int hh_pab_create_ex(hh_pab** out, int device, const float* image, int ny, int n
       }
     }
     if (rc == HH_OK) {
-      hipError_t e2 = hipMalloc(&p->d_ray_of_row, std::max<size_t>((size_t)p->total_rows, 1) * sizeof(int));
-      if (e2 == hipSuccess) e2 = hipMalloc(&d_b_int, std::max<size_t>((size_t)p->total_rows, 1) * sizeof(float));
-      if (e2 == hipSuccess) e2 = hipMalloc(&p->d_bref, std::max<size_t>((size_t)p->total_rows, 1) * sizeof(float));
-      if (e2 == hipSuccess) e2 = hipMalloc(&p->d_pidref, std::max<size_t>((size_t)p->total_rows, 1) * sizeof(int));
-      if (e2 == hipSuccess) e2 = hipMemsetAsync(d_bmax, 0x80, (size_t)count * sizeof(int), p->stream);   // very negative ordered keys
-      if (e2 != hipSuccess) rc = pab_fail(p, HH_ERR_NOMEM, std::string("hh_pab_create: ") + hipGetErrorString(e2));
+      const size_t rows1 = std::max<size_t>((size_t)p->total_rows, 1);
+      if (!p->d_ray_of_row.ensure(rows1) || !d_b_int.ensure(rows1) || !p->d_bref.ensure(rows1) || !p->d_pidref.ensure(rows1))
+        rc = pab_fail(p, HH_ERR_NOMEM, "hh_pab_create: " + dev_alloc_failed(rows1 * 4));
+      else if (hipError_t e2 = hipMemsetAsync(d_bmax, 0x80, (size_t)count * sizeof(int), p->stream))   // very negative ordered keys
+        rc = pab_fail(p, HH_ERR_HIP, std::string("hh_pab_create: ") + hipGetErrorString(e2));
       p->device_bytes += (size_t)p->total_rows * 16;
     }
     // pass 2: the rows themselves, chunk by chunk over the operations that are used
@@ -1909,22 +1899,19 @@ int hh_pab_create_ex(hh_pab** out, int device, const float* image, int ny, int n
         p->st[(size_t)c].bmax = (double)f;
       }
     }
-    free_tmp();
-    if (rc) { if (d_b_int) (void)hipFree(d_b_int); return bail(rc); }
+    tmp.release();
+    if (rc) return bail(rc);
     lap("rays and rows (device)");
   } else {
   {
-    int* d_cand = nullptr;
-    int* d_nops = nullptr;
-    unsigned char* d_has = nullptr;
     std::vector<unsigned char> has;
     std::vector<int> live((size_t)count);
     for (int c = 0; c < count; ++c) live[(size_t)c] = c;
-    hipError_t e = hipMalloc(&d_cand, (size_t)count * sizeof(int));
-    if (e == hipSuccess) e = hipMalloc(&d_nops, (size_t)count * sizeof(int));
-    if (e == hipSuccess) e = hipMalloc(&d_has, (size_t)count * chunk * rays);
-    auto free_tmp = [&] { (void)hipFree(d_cand); (void)hipFree(d_nops); (void)hipFree(d_has); };
-    if (e != hipSuccess) { free_tmp(); p->err = std::string("hh_pab_create: ") + hipGetErrorString(e); return bail(HH_ERR_NOMEM); }
+    DevArena tmp;   // freed on every way out
+    int* d_cand = tmp.get<int>((size_t)count);
+    int* d_nops = tmp.get<int>((size_t)count);
+    unsigned char* d_has = tmp.get<unsigned char>((size_t)count * chunk * rays);
+    PAB_RC(pab_arena_ok(p, tmp));
     rc = pab_to_device(p, d_nops, n_ops.data(), n_ops.size() * sizeof(int));
     for (int lo = 0; rc == HH_OK && !live.empty(); lo += chunk) {
       rc = pab_to_device(p, d_cand, live.data(), live.size() * sizeof(int));
@@ -1959,7 +1946,6 @@ int hh_pab_create_ex(hh_pab** out, int device, const float* image, int ny, int n
       }
       live.swap(next);
     }
-    free_tmp();
     if (rc) return bail(rc);
   }
   lap("rays that exist");
@@ -1998,7 +1984,6 @@ int hh_pab_create_ex(hh_pab** out, int device, const float* image, int ny, int n
   // symmetry constraints (box (L3d, D3d, D3d) of lsq_reconstruct, solver:116-173): on the device (k_pab_sym), or with
   // HH_PAB_HOST_SYM on host threads through the single-candidate builder (the A/B reference of the tests)
   if (p->linear && !p->sliced) {
-    if (d_b_int) (void)hipFree(d_b_int);
     p->err = "hh_pab_create: not sliceable — a ray's samples lie in more than one cell layer (the single-candidate hh_pa has the general form)";
     return bail(HH_ERR_ARG);
   }
@@ -2042,42 +2027,36 @@ int hh_pab_create_ex(hh_pab** out, int device, const float* image, int ny, int n
     for (int c = 0; c < count; ++c) want = std::max<int64_t>(want, qs[c].min_sym_pairs);
     const int64_t cap = want > 0 ? want + p->n : 0;   // rows of a candidate: < min_sym_pairs before its last pair, which adds <= n
     for (int c = 0; c < count; ++c) p->st[(size_t)c].sym0 = (int64_t)c * cap;
-    PAB_RC(pab_alloc(p, &p->d_pairs, (size_t)count * cap));
+    PAB_RC(pab_alloc(p, p->d_pairs, (size_t)count * cap));
     if (cap > 0) {
       const int sym_chunk = 4;
       const int64_t nbox = (int64_t)l3 * d3 * d3;
       int* d_rank_sym = p->d_rank;
-      std::vector<void*> tmp;   // freed on every way out
-      auto free_tmp = [&] { for (void* v : tmp) (void)hipFree(v); tmp.clear(); };
-      auto dalloc = [&](void** out, size_t bytes) { const hipError_t e = hipMalloc(out, std::max<size_t>(bytes, 16)); if (e == hipSuccess) tmp.push_back(*out); return e; };
-      hipError_t e = hipSuccess;
+      DevArena tmp;   // freed on every way out
       if (d3 != d2) {   // the symmetry box has its own rank table (same cylinder, same ranks, other box)
         std::vector<int> rank3;
         const int64_t n3 = pa_mask_rank(l3, d3, d3, rmin, rmax, rank3);
         if (n3 != p->n) { p->err = "hh_pab_create: the cylinder does not fit the 2-D region's box"; return bail(HH_ERR_ARG); }
-        e = dalloc(reinterpret_cast<void**>(&d_rank_sym), rank3.size() * sizeof(int));
-        if (e == hipSuccess) rc = pab_to_device(p, d_rank_sym, rank3.data(), rank3.size() * sizeof(int));
+        d_rank_sym = tmp.get<int>(rank3.size());
+        if (tmp.ok()) rc = pab_to_device(p, d_rank_sym, rank3.data(), rank3.size() * sizeof(int));
       }
       unsigned T = 1;
       while ((int64_t)T < 2 * (want + (int64_t)sym_chunk * p->n)) T <<= 1;
-      unsigned long long *d_keys = nullptr, *d_tmin = nullptr;
-      PaSymOp* d_sops = nullptr;
-      int *d_cand = nullptr, *d_nvalid = nullptr, *d_counts = nullptr, *d_err = nullptr;
-      long long* d_base = nullptr;
-      unsigned char* d_flags8 = nullptr;
-      if (e == hipSuccess) e = dalloc(reinterpret_cast<void**>(&d_keys), (size_t)count * T * 8);
-      if (e == hipSuccess) e = dalloc(reinterpret_cast<void**>(&d_tmin), (size_t)count * T * 8);
-      if (e == hipSuccess) e = dalloc(reinterpret_cast<void**>(&d_sops), (size_t)count * sym_chunk * sizeof(PaSymOp));
-      if (e == hipSuccess) e = dalloc(reinterpret_cast<void**>(&d_cand), (size_t)count * sizeof(int));
-      if (e == hipSuccess) e = dalloc(reinterpret_cast<void**>(&d_nvalid), (size_t)count * sizeof(int));
-      if (e == hipSuccess) e = dalloc(reinterpret_cast<void**>(&d_counts), (size_t)count * sym_chunk * sizeof(int));
-      if (e == hipSuccess) e = dalloc(reinterpret_cast<void**>(&d_base), (size_t)count * sym_chunk * sizeof(long long));
-      if (e == hipSuccess) e = dalloc(reinterpret_cast<void**>(&d_flags8), (size_t)count * sym_chunk * nbox);
-      if (e == hipSuccess) e = dalloc(reinterpret_cast<void**>(&d_err), sizeof(int));
-      if (e == hipSuccess) e = hipMemsetAsync(d_keys, 0xff, (size_t)count * T * 8, p->stream);
+      unsigned long long* d_keys = tmp.get<unsigned long long>((size_t)count * T);
+      unsigned long long* d_tmin = tmp.get<unsigned long long>((size_t)count * T);
+      PaSymOp* d_sops = tmp.get<PaSymOp>((size_t)count * sym_chunk);
+      int* d_cand = tmp.get<int>((size_t)count);
+      int* d_nvalid = tmp.get<int>((size_t)count);
+      int* d_counts = tmp.get<int>((size_t)count * sym_chunk);
+      long long* d_base = tmp.get<long long>((size_t)count * sym_chunk);
+      unsigned char* d_flags8 = tmp.get<unsigned char>((size_t)count * sym_chunk * nbox);
+      int* d_err = tmp.get<int>(1);
+      if (!rc) rc = pab_arena_ok(p, tmp);
+      if (rc) return bail(rc);
+      hipError_t e = hipMemsetAsync(d_keys, 0xff, (size_t)count * T * 8, p->stream);
       if (e == hipSuccess) e = hipMemsetAsync(d_tmin, 0xff, (size_t)count * T * 8, p->stream);
       if (e == hipSuccess) e = hipMemsetAsync(d_err, 0, sizeof(int), p->stream);
-      if (e != hipSuccess || rc) { free_tmp(); if (!rc) p->err = std::string("hh_pab_create (symmetry pairs): ") + hipGetErrorString(e); return bail(rc ? rc : HH_ERR_NOMEM); }
+      if (e != hipSuccess) { p->err = std::string("hh_pab_create (symmetry pairs): ") + hipGetErrorString(e); return bail(HH_ERR_HIP); }
       // the walk of every candidate (cheap: a few rotations per pair of operations)
       std::vector<std::vector<PaSymOp>> walk((size_t)count);
       std::vector<int> live;
@@ -2130,7 +2109,7 @@ int hh_pab_create_ex(hh_pab** out, int device, const float* image, int ny, int n
       }
       int err_h = 0;
       if (rc == HH_OK) rc = pab_to_host(p, &err_h, d_err, sizeof(int));
-      free_tmp();
+      tmp.release();
       if (rc) return bail(rc);
       if (err_h) { p->err = "hh_pab_create: symmetry-pair table full (internal)"; return bail(HH_ERR_STATE); }
       for (int c = 0; c < count; ++c) {
@@ -2213,19 +2192,19 @@ int hh_pab_create_ex(hh_pab** out, int device, const float* image, int ny, int n
       }
     }
     if (!dev_rows) {
-      PAB_RC(pab_alloc(p, &p->d_ray_of_row, all_rows.size()));
+      PAB_RC(pab_alloc(p, p->d_ray_of_row, all_rows.size()));
       PAB_RC(pab_to_device(p, p->d_ray_of_row, all_rows.data(), all_rows.size() * sizeof(int)));
     }
     if (p->linear) {
-      PAB_RC(pab_alloc(p, &p->d_sym16, (size_t)p->total_sym));
+      PAB_RC(pab_alloc(p, p->d_sym16, (size_t)p->total_sym));
       for (int c = 0; c < count; ++c)   // candidate by candidate through the staging buffer (7.5 MB each at the bench size)
         PAB_RC(pab_to_device(p, p->d_sym16 + p->st[(size_t)c].sym0, rows16_of[(size_t)c].data(), rows16_of[(size_t)c].size() * sizeof(PaEll16)));
       std::vector<std::vector<PaEll16>>().swap(rows16_of);
     } else if (!dev_sym) {
-      PAB_RC(pab_alloc(p, &p->d_pairs, all_pairs.size()));
+      PAB_RC(pab_alloc(p, p->d_pairs, all_pairs.size()));
       PAB_RC(pab_to_device(p, p->d_pairs, all_pairs.data(), all_pairs.size() * sizeof(int2)));
     }
-    PAB_RC(pab_alloc(p, &p->d_srow, srow.size()));
+    PAB_RC(pab_alloc(p, p->d_srow, srow.size()));
     PAB_RC(pab_to_device(p, p->d_srow, srow.data(), srow.size() * sizeof(int)));
     if (p->linear) {   // no map at all: the disc's table and the accumulator of A^T y
       std::vector<unsigned> sidx2((size_t)d2 * d2);
@@ -2234,46 +2213,45 @@ int hh_pab_create_ex(hh_pab** out, int device, const float* image, int ny, int n
           const int a = rank[(size_t)yy * d2 + xx], b = xx + 1 < d2 ? rank[(size_t)yy * d2 + xx + 1] : -1;   // plane 0: rank = index inside the plane
           sidx2[(size_t)yy * d2 + xx] = (unsigned)(a < 0 ? 0xffff : a) | ((unsigned)(b < 0 ? 0xffff : b) << 16);
         }
-      PAB_RC(pab_alloc(p, &p->d_sidx2, sidx2.size()));
+      PAB_RC(pab_alloc(p, p->d_sidx2, sidx2.size()));
       PAB_RC(pab_to_device(p, p->d_sidx2, sidx2.data(), sidx2.size() * sizeof(unsigned)));
-      PAB_RC(pab_alloc(p, &p->d_acc64, (size_t)count * ((p->n + 63) / 64 * 64)));
+      PAB_RC(pab_alloc(p, p->d_acc64, (size_t)count * ((p->n + 63) / 64 * 64)));
       PAB_TRY(hipMemsetAsync(p->d_acc64, 0, (size_t)count * ((p->n + 63) / 64 * 64) * sizeof(long long), p->stream));
     } else if (p->sliced) {
-      PAB_RC(pab_alloc(p, &p->d_map16, (size_t)p->total_rows * p->d2p));
+      PAB_RC(pab_alloc(p, p->d_map16, (size_t)p->total_rows * p->d2p));
       PAB_TRY(hipMemsetAsync(p->d_map16, 0xff, (size_t)p->total_rows * p->d2p * sizeof(uint16_t), p->stream));
     } else {
-      PAB_RC(pab_alloc(p, &p->d_map, (size_t)p->total_rows * d2));
+      PAB_RC(pab_alloc(p, p->d_map, (size_t)p->total_rows * d2));
     }
-    PAB_RC(pab_alloc(p, &p->d_st, (size_t)count));
-    PAB_RC(pab_alloc(p, &p->d_ctl, (size_t)count));
+    PAB_RC(pab_alloc(p, p->d_st, (size_t)count));
+    PAB_RC(pab_alloc(p, p->d_ctl, (size_t)count));
     PAB_TRY(hipMemsetAsync(p->d_ctl, 0, (size_t)count * sizeof(unsigned), p->stream));
-    PAB_RC(pab_alloc(p, &p->d_tptr, (size_t)count * (p->n + 1)));
-    PAB_RC(pab_alloc(p, &p->d_nv, (size_t)NV_COUNT * count * p->N));
-    PAB_RC(pab_alloc(p, &p->d_mv, (size_t)MV_COUNT * count * p->MA));
-    PAB_RC(pab_alloc(p, &p->d_red, (size_t)count * PAB_SLOTS * p->RB));
-    PAB_RC(pab_alloc(p, &p->d_xf, (size_t)count * p->N));   // rows padded to N floats: whole cache lines per candidate
-    PAB_RC(pab_alloc(p, &p->d_flags, PAB_FLAG_WORDS));
-    PAB_RC(pab_alloc(p, &p->d_lists, (size_t)2 * count));
+    PAB_RC(pab_alloc(p, p->d_tptr, (size_t)count * (p->n + 1)));
+    PAB_RC(pab_alloc(p, p->d_nv, (size_t)NV_COUNT * count * p->N));
+    PAB_RC(pab_alloc(p, p->d_mv, (size_t)MV_COUNT * count * p->MA));
+    PAB_RC(pab_alloc(p, p->d_red, (size_t)count * PAB_SLOTS * p->RB));
+    PAB_RC(pab_alloc(p, p->d_xf, (size_t)count * p->N));   // rows padded to N floats: whole cache lines per candidate
+    PAB_RC(pab_alloc(p, p->d_flags, PAB_FLAG_WORDS));
+    PAB_RC(pab_alloc(p, p->d_lists, (size_t)2 * count));
     PAB_TRY(hipMemsetAsync(p->d_nv, 0, (size_t)NV_COUNT * count * p->N * sizeof(double), p->stream));
     PAB_TRY(hipMemsetAsync(p->d_mv, 0, (size_t)MV_COUNT * count * p->MA * sizeof(double), p->stream));
     PAB_TRY(hipMemsetAsync(p->d_tptr, 0, (size_t)count * (p->n + 1) * sizeof(int), p->stream));
     PAB_TRY(hipMemsetAsync(p->d_flags, 0, PAB_FLAG_WORDS * sizeof(int), p->stream));
     PAB_RC(pab_to_device(p, p->d_st, p->st.data(), p->st.size() * sizeof(PabState)));
     // right-hand sides: b of the data rows (float32 pixel values -> float64), zeros for the symmetry rows (the memset above)
-    float* d_bf = d_b_int;
-    if (!dev_rows) {
-      PAB_TRY(hipMalloc(&d_bf, all_b.size() * sizeof(float)));
-      rc = pab_to_device(p, d_bf, all_b.data(), all_b.size() * sizeof(float));
+    if (!dev_rows) {   // the host path's b takes the place the device path filled
+      if (!d_b_int.ensure(all_b.size())) { p->err = "hh_pab_create: " + dev_alloc_failed(all_b.size() * sizeof(float)); return bail(HH_ERR_NOMEM); }
+      rc = pab_to_device(p, d_b_int, all_b.data(), all_b.size() * sizeof(float));
     }
     if (rc == HH_OK) {
-      const float* bf = d_bf;
+      const float* bf = d_b_int;
       pab_vec<0>(p, CNT_MDATA, PabRed<0>{}, [] __device__(const auto&) { return true; },
                  [bf] __device__(const PabView& w, int c, int64_t i, const PabState& s, double*) {
                    w.mvec(MV_B, c)[i] = (double)bf[s.row0 + i];
                  });
       if (hipStreamSynchronize(p->stream) != hipSuccess) rc = pab_fail(p, HH_ERR_HIP, "hh_pab_create: right-hand sides failed");
     }
-    (void)hipFree(d_bf);
+    d_b_int.reset();
     if (rc) return bail(rc);
   }
   lap("row tables, buffers");
@@ -2288,14 +2266,15 @@ int hh_pab_create_ex(hh_pab** out, int device, const float* image, int ny, int n
       PAB_RC(pab_poll(p, f));
       if (f[9]) { p->err = "hh_pab_create: a ray left its slice (internal)"; return bail(HH_ERR_STATE); }
       // rows of one (operation, image row) read one copy of their map (k_pab_share_rows)
-      PAB_RC(pab_alloc(p, &p->d_maprow, (size_t)std::max<int64_t>(p->total_rows, 1)));
+      PAB_RC(pab_alloc(p, p->d_maprow, (size_t)std::max<int64_t>(p->total_rows, 1)));
       int max_ops_used = 0;
       for (int c = 0; c < count; ++c) max_ops_used = std::max(max_ops_used, p->n_ops_used[(size_t)c]);
       const size_t keys = (size_t)count * std::max(max_ops_used, 1) * d2;
-      int *d_first = nullptr, *d_second = nullptr;
-      hipError_t es = hipMalloc(&d_first, keys * sizeof(int));
-      if (es == hipSuccess) es = hipMalloc(&d_second, keys * sizeof(int));
-      if (es == hipSuccess) es = hipMemsetAsync(d_first, 0x7f, keys * sizeof(int), p->stream);
+      DevArena tmp;
+      int* d_first = tmp.get<int>(keys);
+      int* d_second = tmp.get<int>(keys);
+      PAB_RC(pab_arena_ok(p, tmp));
+      hipError_t es = hipMemsetAsync(d_first, 0x7f, keys * sizeof(int), p->stream);
       if (es == hipSuccess) es = hipMemsetAsync(d_second, 0x7f, keys * sizeof(int), p->stream);
       if (es == hipSuccess) {
         const dim3 grid = pab_grid((int)((md * 8 + 255) / 256), count);
@@ -2304,8 +2283,7 @@ int hh_pab_create_ex(hh_pab** out, int device, const float* image, int ny, int n
         hipLaunchKernelGGL(k_pab_share_rows<2>, grid, dim3(256), 0, p->stream, p->d_st, p->d_ray_of_row, p->d_map16, p->d2p, l2, d2, max_ops_used, d_first, d_second, p->d_maprow, count);
         es = hipStreamSynchronize(p->stream);
       }
-      (void)hipFree(d_first);
-      (void)hipFree(d_second);
+      tmp.release();
       if (es != hipSuccess) { p->err = std::string("hh_pab_create (shared map rows): ") + hipGetErrorString(es); return bail(HH_ERR_HIP); }
       if (timing) {
         std::vector<int> mr((size_t)p->total_rows);
@@ -2325,8 +2303,8 @@ int hh_pab_create_ex(hh_pab** out, int device, const float* image, int ny, int n
     int64_t span = 0;
     for (const PabState& s : p->st) span = std::max(span, p->linear ? s.m_sym * 16 : (p->sliced ? 0 : s.m_data * d2) + s.m_sym);
     const dim3 grid = pab_grid((int)std::max<int64_t>(1, (span + 255) / 256), count);
-    int* d_cursor = nullptr;
-    PAB_TRY(hipMalloc(&d_cursor, (size_t)count * (p->n + 1) * sizeof(int)));
+    DevBuf<int> d_cursor;
+    if (!d_cursor.ensure((size_t)count * (p->n + 1))) { p->err = "hh_pab_create: " + dev_alloc_failed(d_cursor.bytes_for((size_t)count * (p->n + 1))); return bail(HH_ERR_NOMEM); }
     if (p->linear) hipLaunchKernelGGL((k_pabl_transpose<false>), grid, dim3(256), 0, p->stream, w, p->d_tptr, (int2*)nullptr);
     else if (p->sliced) hipLaunchKernelGGL((k_pab_transpose<false, false>), grid, dim3(256), 0, p->stream, w, p->d_tptr, (int*)nullptr);
     else hipLaunchKernelGGL((k_pab_transpose<false, true>), grid, dim3(256), 0, p->stream, w, p->d_tptr, (int*)nullptr);
@@ -2340,16 +2318,16 @@ int hh_pab_create_ex(hh_pab** out, int device, const float* image, int ny, int n
       e = hipMemcpy2DAsync(p->h_stage, sizeof(int), p->d_tptr + p->n, (size_t)(p->n + 1) * sizeof(int), sizeof(int), (size_t)count,
                            hipMemcpyDeviceToHost, p->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(p->stream);
-    if (e != hipSuccess) { (void)hipFree(d_cursor); p->err = std::string("hh_pab_create: ") + hipGetErrorString(e); return bail(HH_ERR_HIP); }
+    if (e != hipSuccess) { p->err = std::string("hh_pab_create: ") + hipGetErrorString(e); return bail(HH_ERR_HIP); }
     std::memcpy(last.data(), p->h_stage, (size_t)count * sizeof(int));
     p->total_nnz = 0;
     for (int c = 0; c < count; ++c) {
       p->st[(size_t)c].t0 = p->total_nnz;
       p->total_nnz += last[(size_t)c];
     }
-    rc = p->linear ? pab_alloc(p, &p->d_tent2, (size_t)p->total_nnz) : pab_alloc(p, &p->d_tent, (size_t)p->total_nnz);
+    rc = p->linear ? pab_alloc(p, p->d_tent2, (size_t)p->total_nnz) : pab_alloc(p, p->d_tent, (size_t)p->total_nnz);
     if (rc == HH_OK) rc = pab_to_device(p, p->d_st, p->st.data(), p->st.size() * sizeof(PabState));
-    if (rc) { (void)hipFree(d_cursor); return bail(rc); }
+    if (rc) return bail(rc);
     w = pab_view(p);
     // the cursor of voxel v starts at tptr[v] (the scan is inclusive over cnt[v + 1], i.e. exclusive for v)
     if (p->linear) {
@@ -2362,7 +2340,7 @@ int hh_pab_create_ex(hh_pab** out, int device, const float* image, int ny, int n
     }
     e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(p->stream);
-    (void)hipFree(d_cursor);
+    d_cursor.reset();
     if (e != hipSuccess) { p->err = std::string("hh_pab_create: ") + hipGetErrorString(e); return bail(HH_ERR_HIP); }
   }
   lap("transposed lists");
@@ -2377,23 +2355,18 @@ int hh_pab_create_ex(hh_pab** out, int device, const float* image, int ny, int n
     int max_ops = 0;
     for (int c = 0; c < count; ++c) max_ops = std::max(max_ops, p->n_ops_used[(size_t)c]);
     const size_t cells = (size_t)count * max_ops * l2;
-    PabfZinfo* d_zi = nullptr;
-    unsigned long long *d_hash = nullptr, *d_jm = nullptr;
-    int *d_rb = nullptr, *d_nused = nullptr;
-    std::vector<void*> tmp;
-    auto free_tmp = [&] { for (void* v : tmp) (void)hipFree(v); tmp.clear(); };
-    auto dalloc = [&](void** out, size_t bytes) { const hipError_t e = hipMalloc(out, std::max<size_t>(bytes, 16)); if (e == hipSuccess) tmp.push_back(*out); return e; };
-    hipError_t e = dalloc(reinterpret_cast<void**>(&d_zi), cells * sizeof(PabfZinfo));
-    if (e == hipSuccess) e = dalloc(reinterpret_cast<void**>(&d_hash), cells * 8);
-    if (e == hipSuccess) e = dalloc(reinterpret_cast<void**>(&d_jm), cells * 16);
-    if (e == hipSuccess) e = dalloc(reinterpret_cast<void**>(&d_rb), cells * 4);
-    if (e == hipSuccess) e = dalloc(reinterpret_cast<void**>(&d_nused), (size_t)count * 4);
-    if (e == hipSuccess) e = hipMemsetAsync(d_hash, 0, cells * 8, p->stream);
+    DevArena tmp;   // freed on every way out
+    PabfZinfo* d_zi = tmp.get<PabfZinfo>(cells);
+    unsigned long long* d_hash = tmp.get<unsigned long long>(cells);
+    unsigned long long* d_jm = tmp.get<unsigned long long>(cells * 2);
+    int* d_rb = tmp.get<int>(cells);
+    int* d_nused = tmp.get<int>((size_t)count);
+    PAB_RC(pab_arena_ok(p, tmp));
+    hipError_t e = hipMemsetAsync(d_hash, 0, cells * 8, p->stream);
     if (e == hipSuccess) e = hipMemsetAsync(d_jm, 0, cells * 16, p->stream);
     if (e == hipSuccess) e = hipMemsetAsync(d_rb, 0x7f, cells * 4, p->stream);
-    if (e != hipSuccess) { free_tmp(); p->err = std::string("hh_pab_create (footprint lists): ") + hipGetErrorString(e); return bail(HH_ERR_NOMEM); }
-    rc = pab_to_device(p, d_nused, p->n_ops_used.data(), (size_t)count * sizeof(int));
-    if (rc) { free_tmp(); return bail(rc); }
+    if (e != hipSuccess) { p->err = std::string("hh_pab_create (footprint lists): ") + hipGetErrorString(e); return bail(HH_ERR_HIP); }
+    PAB_RC(pab_to_device(p, d_nused, p->n_ops_used.data(), (size_t)count * sizeof(int)));
     hipLaunchKernelGGL(k_pabf_zinfo, dim3((unsigned)((l2 + 127) / 128), (unsigned)max_ops, (unsigned)count), dim3(128), 0, p->stream, gr, count, max_ops,
                        d_nused, d_zi);
     hipLaunchKernelGGL(k_pabf_cellhash, dim3((unsigned)l2, (unsigned)max_ops, (unsigned)count), dim3(128), 0, p->stream, gr, count, max_ops, d_nused,
@@ -2410,7 +2383,7 @@ int hh_pab_create_ex(hh_pab** out, int device, const float* image, int ny, int n
     if (rc == HH_OK) rc = pab_to_host(p, hash.data(), d_hash, cells * 8);
     if (rc == HH_OK) rc = pab_to_host(p, jm.data(), d_jm, cells * 16);
     if (rc == HH_OK) rc = pab_to_host(p, rb.data(), d_rb, cells * 4);
-    free_tmp();
+    tmp.release();
     if (rc) return bail(rc);
     lap("separable form: axial data, cell hashes");
     // lists: (operation, z mask, cell hash) of the (o, k) that have rows; groups: home / G
@@ -2467,32 +2440,28 @@ int hh_pab_create_ex(hh_pab** out, int device, const float* image, int ny, int n
           std::copy(gg.begin(), gg.end(), all_gl.begin() + ((size_t)c * ng + g) * max_gl);
         }
       }
-      PabfListRef* d_lists = nullptr;
-      int* d_nlists = nullptr;
-      PAB_TRY(hipMalloc(&d_lists, all_lists.size() * sizeof(PabfListRef)));
-      hipError_t e2 = hipMalloc(&d_nlists, (size_t)count * sizeof(int));
-      auto free2 = [&] { (void)hipFree(d_lists); (void)hipFree(d_nlists); };
-      if (e2 != hipSuccess) { free2(); p->err = "hh_pab_create (footprint lists): out of device memory"; return bail(HH_ERR_NOMEM); }
+      DevArena tmp;   // freed on every way out
+      PabfListRef* d_lists = tmp.get<PabfListRef>(all_lists.size());
+      int* d_nlists = tmp.get<int>((size_t)count);
+      PAB_RC(pab_arena_ok(p, tmp));
       rc = pab_to_device(p, d_lists, all_lists.data(), all_lists.size() * sizeof(PabfListRef));
       if (rc == HH_OK) rc = pab_to_device(p, d_nlists, n_lists.data(), n_lists.size() * sizeof(int));
-      if (rc == HH_OK) rc = pab_alloc(p, &p->d_fac_ngl, ngl.size());
+      if (rc == HH_OK) rc = pab_alloc(p, p->d_fac_ngl, ngl.size());
       if (rc == HH_OK) rc = pab_to_device(p, p->d_fac_ngl, ngl.data(), ngl.size() * sizeof(int));
-      if (rc == HH_OK) rc = pab_alloc(p, &p->d_fac_gl, all_gl.size());
+      if (rc == HH_OK) rc = pab_alloc(p, p->d_fac_gl, all_gl.size());
       if (rc == HH_OK) rc = pab_to_device(p, p->d_fac_gl, all_gl.data(), all_gl.size() * sizeof(PabfGroupList));
-      if (rc == HH_OK) rc = pab_alloc(p, &p->d_fac_entries, (size_t)count * max_lists * d2 * d2);
-      if (rc == HH_OK) rc = pab_alloc(p, &p->d_fac_count, (size_t)count * max_lists * d2);
-      if (rc) { free2(); return bail(rc); }
+      if (rc == HH_OK) rc = pab_alloc(p, p->d_fac_entries, (size_t)count * max_lists * d2 * d2);
+      if (rc == HH_OK) rc = pab_alloc(p, p->d_fac_count, (size_t)count * max_lists * d2);
+      if (rc) return bail(rc);
       hipLaunchKernelGGL(k_pabf_entries, dim3((unsigned)((d2 + 63) / 64), (unsigned)max_lists, (unsigned)count), dim3(64), 0, p->stream, gr, count,
                          max_lists, d_nlists, d_lists, p->d_sidx2, p->d_fac_entries, p->d_fac_count);
       const hipError_t e3 = hipStreamSynchronize(p->stream);
-      free2();
       if (e3 != hipSuccess) { p->err = std::string("hh_pab_create (footprint lists): ") + hipGetErrorString(e3); return bail(HH_ERR_HIP); }
     }
     p->fac_G = G; p->fac_ng = ng; p->fac_max_gl = max_gl; p->fac_max_lists = max_lists;
     p->fac_lds = (size_t)(G + 1) * p->nslice * sizeof(double) + (size_t)max_gl * sizeof(PabfGroupList);
     if (p->fac_lds > ((size_t)160 << 10) && (flags & HH_PAB_ALLOW_BANDED)) {   // the banded form instead (cut below)
-      for (void* v : {(void*)p->d_fac_ngl, (void*)p->d_fac_gl, (void*)p->d_fac_entries, (void*)p->d_fac_count}) (void)hipFree(v);
-      p->d_fac_ngl = nullptr; p->d_fac_gl = nullptr; p->d_fac_entries = nullptr; p->d_fac_count = nullptr;
+      p->d_fac_ngl.reset(); p->d_fac_gl.reset(); p->d_fac_entries.reset(); p->d_fac_count.reset();
       p->fac_G = 0;
       p->band_T = -1;
     } else if (p->fac_lds > ((size_t)160 << 10)) {
@@ -2555,18 +2524,19 @@ int hh_pab_create_ex(hh_pab** out, int device, const float* image, int ny, int n
       p->err = "hh_pab_create: not sliceable — a band of the disc does not fit the LDS (internal)";
       return bail(HH_ERR_STATE);
     }
-    PAB_RC(pab_alloc(p, &p->d_band_y, band_y.size()));
+    PAB_RC(pab_alloc(p, p->d_band_y, band_y.size()));
     PAB_RC(pab_to_device(p, p->d_band_y, band_y.data(), band_y.size() * sizeof(int)));
-    PAB_RC(pab_alloc(p, &p->d_band_v, vrow.size()));
+    PAB_RC(pab_alloc(p, p->d_band_v, vrow.size()));
     PAB_RC(pab_to_device(p, p->d_band_v, vrow.data(), vrow.size() * sizeof(int)));
-    PAB_RC(pab_alloc(p, &p->d_bpart, (size_t)count * p->band_T * p->M));
+    PAB_RC(pab_alloc(p, p->d_bpart, (size_t)count * p->band_T * p->M));
     if (timing)
       std::fprintf(stderr, "hh_pab_create[%d]: banded form: %d bands, %zu bytes of LDS\n", count, p->band_T, p->band_lds);
     lap("banded form");
   }
   if (p->linear) {  // largest column sum of |A_data| per candidate, in 2^-20 units (the trilinear weights are not counts)
-    long long* d_colmax = nullptr;
-    PAB_TRY(hipMalloc(&d_colmax, (size_t)count * sizeof(long long)));
+    DevArena tmp;
+    long long* d_colmax = tmp.get<long long>((size_t)count);
+    PAB_RC(pab_arena_ok(p, tmp));
     hipError_t e = hipMemsetAsync(d_colmax, 0, (size_t)count * sizeof(long long), p->stream);
     auto all = [] __device__(const auto&) { return true; };
     if (p->fac_G) {
@@ -2592,7 +2562,7 @@ int hh_pab_create_ex(hh_pab** out, int device, const float* image, int ny, int n
     if (e == hipSuccess) e = hipGetLastError();
     std::vector<long long> colmax((size_t)count, 0);
     rc = e == hipSuccess ? pab_to_host(p, colmax.data(), d_colmax, colmax.size() * sizeof(long long)) : pab_fail(p, HH_ERR_HIP, hipGetErrorString(e));
-    (void)hipFree(d_colmax);
+    tmp.release();
     if (rc) return bail(rc);
     for (int c = 0; c < count; ++c) {
       PabState& s = p->st[(size_t)c];
@@ -2604,8 +2574,9 @@ int hh_pab_create_ex(hh_pab** out, int device, const float* image, int ny, int n
     PAB_RC(pab_to_device(p, p->d_st, p->st.data(), p->st.size() * sizeof(PabState)));
     lap("column sums");
   } else if (p->sliced) {  // largest column sum of |A_data| per candidate (hit counts): sizes the fixed-point scale of A^T y
-    int* d_colmax = nullptr;
-    PAB_TRY(hipMalloc(&d_colmax, (size_t)count * sizeof(int)));
+    DevArena tmp;
+    int* d_colmax = tmp.get<int>((size_t)count);
+    PAB_RC(pab_arena_ok(p, tmp));
     hipError_t e = hipMemsetAsync(d_colmax, 0, (size_t)count * sizeof(int), p->stream);
     auto all = [] __device__(const auto&) { return true; };
     hipLaunchKernelGGL((k_pabs_rmatvec<0, true, decltype(all)>), pab_grid(p->mz, count), dim3(PABS_THREADS), (size_t)p->nslice * sizeof(long long), p->stream,
@@ -2613,7 +2584,7 @@ int hh_pab_create_ex(hh_pab** out, int device, const float* image, int ny, int n
     if (e == hipSuccess) e = hipGetLastError();
     std::vector<int> colmax((size_t)count, 0);
     rc = e == hipSuccess ? pab_to_host(p, colmax.data(), d_colmax, colmax.size() * sizeof(int)) : pab_fail(p, HH_ERR_HIP, hipGetErrorString(e));
-    (void)hipFree(d_colmax);
+    tmp.release();
     if (rc) return bail(rc);
     for (int c = 0; c < count; ++c) {
       PabState& s = p->st[(size_t)c];
@@ -2685,7 +2656,7 @@ int hh_pab_solve(hh_pab* p, const int32_t* positive, const int32_t* clip, double
   p->launches = p->syncs = p->ticks = p->inconsistent = 0;
   if (const char* tc = std::getenv("HH_PAB_TRACE")) {
     p->trace_c = std::atoi(tc);
-    if (!p->d_trace) PAB_HIP(p, hipMalloc(&p->d_trace, (size_t)PAB_TRACE_ROWS * 8 * sizeof(double)));
+    if (!p->d_trace.ensure((size_t)PAB_TRACE_ROWS * 8)) return pab_fail(p, HH_ERR_NOMEM, dev_alloc_failed((size_t)PAB_TRACE_ROWS * 8 * sizeof(double)));
     PAB_HIP(p, hipMemsetAsync(p->d_trace, 0, (size_t)PAB_TRACE_ROWS * 8 * sizeof(double), p->stream));
   }
   PAB_HIP(p, hipMemsetAsync(p->d_flags, 0, PAB_FLAG_WORDS * sizeof(int), p->stream));
@@ -3160,11 +3131,11 @@ int hh_pab_check_ray_arithmetic(const hh_pa_params* q, int ny, int nx, int devic
     }
   if (device >= 0) {   // the same comparison by the device's own arithmetic
     PAB_HIP(nullptr, hipSetDevice(device));
-    PaOp* d_ops = nullptr;
-    unsigned long long* d_counts = nullptr;
-    PAB_HIP(nullptr, hipMalloc(&d_ops, all_ops.size() * sizeof(PaOp)));
-    hipError_t e = hipMalloc(&d_counts, 4 * sizeof(unsigned long long));
-    if (e == hipSuccess) e = hipMemcpy(d_ops, all_ops.data(), all_ops.size() * sizeof(PaOp), hipMemcpyHostToDevice);
+    DevArena tmp;
+    PaOp* d_ops = tmp.get<PaOp>(all_ops.size());
+    unsigned long long* d_counts = tmp.get<unsigned long long>(4);
+    if (int rc = pab_arena_ok(nullptr, tmp)) return rc;
+    hipError_t e = hipMemcpy(d_ops, all_ops.data(), all_ops.size() * sizeof(PaOp), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemset(d_counts, 0, 4 * sizeof(unsigned long long));
     unsigned long long h_counts[4] = {0, 0, 0, 0};
     if (e == hipSuccess) {
@@ -3172,7 +3143,6 @@ int hh_pab_check_ray_arithmetic(const hh_pa_params* q, int ny, int nx, int devic
       hipLaunchKernelGGL(k_pabl_check, dim3((unsigned)((rays + 255) / 256)), dim3(256), 0, 0, g, d_ops, (int)all_ops.size(), d_counts);
       e = hipMemcpy(h_counts, d_counts, sizeof(h_counts), hipMemcpyDeviceToHost);
     }
-    (void)hipFree(d_ops); (void)hipFree(d_counts);
     if (e != hipSuccess) return pab_fail(nullptr, HH_ERR_HIP, std::string("hh_pab_check_ray_arithmetic: ") + hipGetErrorString(e));
     out[4] = (int64_t)h_counts[0]; out[5] = (int64_t)h_counts[1]; out[6] = (int64_t)h_counts[2];
   }

@@ -271,12 +271,19 @@ hipError_t pa_copy(hh_pa* p, void* dst, const void* src, size_t bytes, bool to_d
   return hipSuccess;
 }
 
+// grow-only device buffer (device_mem.h); a failure is this object's HH_ERR_NOMEM
+template <class T>
+int pa_ensure(hh_pa* p, DevBuf<T>& b, size_t count) {
+  return b.ensure(count) ? HH_OK : pa_fail(p, HH_ERR_NOMEM, dev_alloc_failed(b.bytes_for(count)));
+}
+
 int pa_alloc_vectors(hh_pa* p) {
   const int64_t big = p->m_data + p->m_sym + p->n;
-  for (double** v : {&p->d_x, &p->d_v, &p->d_h, &p->d_hbar, &p->d_scale, &p->d_root})
-    PA_HIP(p, hipMalloc(v, (size_t)std::max<int64_t>(p->n, 1) * sizeof(double)));
-  for (double** v : {&p->d_y, &p->d_u, &p->d_w}) PA_HIP(p, hipMalloc(v, (size_t)std::max<int64_t>(big, 1) * sizeof(double)));
-  PA_HIP(p, hipMalloc(&p->d_red, 1024 * sizeof(double)));
+  for (DevBuf<double>* v : {&p->d_x, &p->d_v, &p->d_h, &p->d_hbar, &p->d_scale, &p->d_root})
+    if (int rc = pa_ensure(p, *v, (size_t)std::max<int64_t>(p->n, 1))) return rc;
+  for (DevBuf<double>* v : {&p->d_y, &p->d_u, &p->d_w})
+    if (int rc = pa_ensure(p, *v, (size_t)std::max<int64_t>(big, 1))) return rc;
+  if (int rc = pa_ensure(p, p->d_red, 1024)) return rc;
   PA_HIP(p, hipHostMalloc(&p->h_a, (size_t)std::max<int64_t>(big, 1) * sizeof(double), hipHostMallocDefault));
   PA_HIP(p, hipHostMalloc(&p->h_b, (size_t)std::max<int64_t>(p->n, 1) * sizeof(double), hipHostMallocDefault));
   PA_HIP(p, hipHostMalloc(&p->h_c, (size_t)std::max<int64_t>(p->n, 1) * sizeof(double), hipHostMallocDefault));
@@ -362,14 +369,12 @@ void hh_pa_destroy(hh_pa* p) try {
   if (!p) return;
   (void)hipSetDevice(p->device);
   if (p->stream) (void)hipStreamSynchronize(p->stream);
-  for (void* v : {(void*)p->d_map, (void*)p->d_ray_of_row, (void*)p->d_pairs, (void*)p->d_sym16, (void*)p->d_ops, (void*)p->d_rank, (void*)p->d_x, (void*)p->d_y, (void*)p->d_u,
-                  (void*)p->d_v, (void*)p->d_h, (void*)p->d_hbar, (void*)p->d_w, (void*)p->d_scale, (void*)p->d_root, (void*)p->d_red})
-    if (v) (void)hipFree(v);
   for (double* v : {p->h_a, p->h_b, p->h_c, p->h_out, p->h_red})
     if (v) (void)hipHostFree(v);
   if (p->h_stage) (void)hipHostFree(p->h_stage);
-  if (p->stream) (void)hipStreamDestroy(p->stream);
-  delete p;
+  const hipStream_t stream = p->stream;
+  delete p;                                   // frees the device buffers: before their stream goes
+  if (stream) (void)hipStreamDestroy(stream);
 } catch (...) {
 }
 
@@ -392,15 +397,15 @@ int hh_pa_create(hh_pa** out, int device, const float* image, int ny, int nx, co
   hh_pa* p = new (std::nothrow) hh_pa();
   if (!p) return pa_fail(nullptr, HH_ERR_NOMEM, "out of host memory");
   p->device = device;
-  unsigned char* d_has = nullptr;   // set-up scratch: released on every way out
-  struct Guard { hh_pa* p; unsigned char** scratch; ~Guard() { if (p) { if (*scratch) (void)hipFree(*scratch); hh_pa_destroy(p); } } } guard{p, &d_has};
+  DevBuf<unsigned char> d_has;      // set-up scratch: released on every way out
+  struct Guard { hh_pa* p; ~Guard() { if (p) hh_pa_destroy(p); } } guard{p};
   auto bail = [&](int rc) {
     g_create_error = p->err;
     guard.p = nullptr;
-    if (d_has) (void)hipFree(d_has);
     hh_pa_destroy(p);
     return rc;
   };
+#define PA_ENSURE(buf, count) do { if (int rc__ = pa_ensure(p, buf, count)) return bail(rc__); } while (0)
 #define PA_TRY(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) { p->err = std::string(#call) + ": " + hipGetErrorString(e__); return bail(HH_ERR_HIP); } } while (0)
   PA_TRY(hipSetDevice(device));
   PA_TRY(hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking));
@@ -424,7 +429,7 @@ int hh_pa_create(hh_pa** out, int device, const float* image, int ny, int nx, co
   const double rmax = (double)(q->reconstruct_diameter_3d_pixel / 2 - 1);
   p->n = pa_mask_rank(g.mz, g.my, g.mx, rmin, rmax, rank);
   if (p->n <= 0) { p->err = "hh_pa_create: the cylinder holds no voxel"; return bail(HH_ERR_ARG); }
-  PA_TRY(hipMalloc(&p->d_rank, rank.size() * sizeof(int)));
+  PA_ENSURE(p->d_rank, rank.size());
   PA_TRY(pa_copy(p, p->d_rank, rank.data(), rank.size() * sizeof(int), true));
   int* const d_rank = p->d_rank;
   // symmetry operations in the reference's order (solver:1556-1571)
@@ -443,16 +448,15 @@ int hh_pa_create(hh_pa** out, int device, const float* image, int ny, int nx, co
     pa_euler1('z', q->twist_degree * s.h + 360.0 * s.c / q->csym, ops[i].m_z);
     ops[i].shift = s.h * q->rise_pixel;
   }
-  PA_TRY(hipMalloc(&p->d_ops, ops.size() * sizeof(PaOp)));
+  PA_ENSURE(p->d_ops, ops.size());
   PA_TRY(pa_copy(p, p->d_ops, ops.data(), ops.size() * sizeof(PaOp), true));
   PaOp* const d_ops = p->d_ops;
   // index map, chunk of operations by chunk, until the row target is passed (solver:1647)
   const size_t rays_per_op = (size_t)l2 * d2, per_op = rays_per_op * d2;
   const int n_ops = (int)ops.size();
-  size_t cap_ops = 0;
   std::vector<unsigned char> has;
   std::vector<int> ray_of_row;
-  PA_TRY(hipMalloc(&d_has, rays_per_op * 64));
+  PA_ENSURE(d_has, rays_per_op * 64);
   int64_t n_b = 0;
   int used = 0;
   bool done = false;
@@ -462,17 +466,16 @@ int hh_pa_create(hh_pa** out, int device, const float* image, int ny, int nx, co
       hipLaunchKernelGGL(k_pa_has_lin, pa_grid((int64_t)(rays_per_op * chunk)), dim3(256), 0, p->stream, g, d_ops, used,
                          rays_per_op * chunk, d_rank, d_has);
     } else {
+    const size_t cap_ops = p->d_map.size() / per_op;
     if ((size_t)(used + chunk) > cap_ops) {  // grow the map (keep what is already there)
       const size_t ncap = std::max<size_t>(cap_ops * 2, (size_t)(used + chunk));
-      int* nm = nullptr;
-      PA_TRY(hipMalloc(&nm, ncap * per_op * sizeof(int)));
+      DevBuf<int> nm;
+      PA_ENSURE(nm, ncap * per_op);
       if (p->d_map) {
         const hipError_t ec = hipMemcpy(nm, p->d_map, (size_t)used * per_op * sizeof(int), hipMemcpyDeviceToDevice);
-        if (ec != hipSuccess) { (void)hipFree(nm); p->err = std::string("hh_pa_create: ") + hipGetErrorString(ec); return bail(HH_ERR_HIP); }
-        (void)hipFree(p->d_map);
+        if (ec != hipSuccess) { p->err = std::string("hh_pa_create: ") + hipGetErrorString(ec); return bail(HH_ERR_HIP); }
       }
-      p->d_map = nm;
-      cap_ops = ncap;
+      p->d_map = std::move(nm);
     }
     hipLaunchKernelGGL(k_pa_index, pa_grid((int64_t)(per_op * chunk)), dim3(256), 0, p->stream, g, d_ops, used, chunk, d_rank,
                        p->d_map + (size_t)used * per_op);
@@ -496,8 +499,7 @@ int hh_pa_create(hh_pa** out, int device, const float* image, int ny, int nx, co
     }
     used += chunk;
   }
-  (void)hipFree(d_has);
-  d_has = nullptr;
+  d_has.reset();
   if (q->fsc_half > 0) {
     // split_A_b (solver:175-203): the data rows of one half of the image's pixels — every second pixel id (mode 2),
     // the lower half of the ids (mode 3), or the outer thirds against the middle third (mode 4 and above)
@@ -526,7 +528,7 @@ int hh_pa_create(hh_pa** out, int device, const float* image, int ny, int nx, co
   }
   p->m_data = (int64_t)ray_of_row.size();
   if (p->m_data == 0) { p->err = "hh_pa_create: no projection ray meets the cylinder"; return bail(HH_ERR_ARG); }
-  PA_TRY(hipMalloc(&p->d_ray_of_row, ray_of_row.size() * sizeof(int)));
+  PA_ENSURE(p->d_ray_of_row, ray_of_row.size());
   PA_TRY(pa_copy(p, p->d_ray_of_row, ray_of_row.data(), ray_of_row.size() * sizeof(int), true));
   // symmetry constraints (box (L3d, D3d, D3d) of lsq_reconstruct, solver:116-173)
   std::vector<int2> pairs;
@@ -536,13 +538,14 @@ int hh_pa_create(hh_pa** out, int device, const float* image, int ny, int nx, co
                  rmin, rmax, q->min_sym_pairs, pairs, g.linear ? &rows16 : nullptr);
   p->m_sym = (int64_t)(g.linear ? rows16.size() : pairs.size());
   if (p->m_sym && g.linear) {
-    PA_TRY(hipMalloc(&p->d_sym16, rows16.size() * sizeof(PaEll16)));
+    PA_ENSURE(p->d_sym16, rows16.size());
     PA_TRY(pa_copy(p, p->d_sym16, rows16.data(), rows16.size() * sizeof(PaEll16), true));
   } else if (p->m_sym) {
-    PA_TRY(hipMalloc(&p->d_pairs, pairs.size() * sizeof(int2)));
+    PA_ENSURE(p->d_pairs, pairs.size());
     PA_TRY(pa_copy(p, p->d_pairs, pairs.data(), pairs.size() * sizeof(int2), true));
   }
 #undef PA_TRY
+#undef PA_ENSURE
   const int rc = pa_alloc_vectors(p);
   if (rc) return bail(rc);
   {  // largest column sum of |A|, itself in fixed point (2^20: exact for hit counts, 1e-6 for trilinear weights)

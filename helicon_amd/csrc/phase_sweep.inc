@@ -22,16 +22,15 @@
 struct hh_phase {
   bool on = false;
   double weight = 0;
-  float* d_pm = nullptr;          // [ony][onx] fftshifted M of one image
-  float* d_pc = nullptr;          // [ony][onx] fftshifted c of one image (hh_phase_map)
-  float* d_wm = nullptr;          // [S][ony][onx] unshifted w M_exp
-  double* d_see = nullptr;        // [S] sum of the float32-rounded (w M_exp)^2
-  double* d_partials = nullptr;   // [S][batch][n_tiles][5]
-  double* d_params = nullptr;     // hh_sweep_parts' staging
-  float* d_out = nullptr;         // hh_sweep_parts' staging: [3][S][g]
-  float* d_img = nullptr;         // hh_phase_map's image and row pass
-  double2* d_r = nullptr;
-  size_t cap_pm = 0, cap_pc = 0, cap_wm = 0, cap_see = 0, cap_partials = 0, cap_params = 0, cap_out = 0, cap_img = 0, cap_r = 0;
+  DevBuf<float> d_pm;             // [ony][onx] fftshifted M of one image
+  DevBuf<float> d_pc;             // [ony][onx] fftshifted c of one image (hh_phase_map)
+  DevBuf<float> d_wm;             // [S][ony][onx] unshifted w M_exp
+  DevBuf<double> d_see;           // [S] sum of the float32-rounded (w M_exp)^2
+  DevBuf<double> d_partials;      // [S][batch][n_tiles][5]
+  DevBuf<double> d_params;        // hh_sweep_parts' staging
+  DevBuf<float> d_out;            // hh_sweep_parts' staging: [3][S][g]
+  DevBuf<float> d_img;            // hh_phase_map's image and row pass
+  DevBuf<double2> d_r;
   std::vector<double> see;
 };
 
@@ -180,11 +179,7 @@ __global__ void k_phase_finalize(const double* __restrict__ partials, int npart,
 bool phase_on(const hh_ctx* c) { return c->phase && c->phase->on; }
 
 void phase_free(hh_ctx* c) {
-  hh_phase* p = c->phase;
-  if (!p) return;
-  (void)hipFree(p->d_pm); (void)hipFree(p->d_pc); (void)hipFree(p->d_wm); (void)hipFree(p->d_see); (void)hipFree(p->d_partials);
-  (void)hipFree(p->d_params); (void)hipFree(p->d_out); (void)hipFree(p->d_img); (void)hipFree(p->d_r);
-  delete p;
+  delete c->phase;   // its buffers free themselves
   c->phase = nullptr;
 }
 
@@ -192,9 +187,9 @@ void phase_free(hh_ctx* c) {
 int phase_prepare(hh_ctx* c, int n_segments, size_t plane) {
   hh_phase* p = c->phase;
   int rc;
-  if ((rc = ensure_bytes(c, (void**)&p->d_pm, &p->cap_pm, plane * sizeof(float)))) return rc;
-  if ((rc = ensure_bytes(c, (void**)&p->d_wm, &p->cap_wm, (size_t)n_segments * plane * sizeof(float)))) return rc;
-  if ((rc = ensure_bytes(c, (void**)&p->d_see, &p->cap_see, (size_t)n_segments * sizeof(double)))) return rc;
+  if ((rc = ensure(c, p->d_pm, plane))) return rc;
+  if ((rc = ensure(c, p->d_wm, (size_t)n_segments * plane))) return rc;
+  if ((rc = ensure(c, p->d_see, (size_t)n_segments))) return rc;
   p->see.assign(n_segments, 0.0);
   return HH_OK;
 }
@@ -230,7 +225,7 @@ int phase_sweep(hh_ctx* c, const double* d_params, int64_t n_cand, float* d_scor
   const int64_t stride = ld > 0 ? ld : n_cand;
   const int S = c->n_segments, npart = z->n_tiles;
   const int64_t cap = std::min<int64_t>(n_cand, ZS_BATCH);
-  if (int rc = ensure_bytes(c, (void**)&p->d_partials, &p->cap_partials, (size_t)S * cap * npart * 5 * sizeof(double))) return rc;
+  if (int rc = ensure(c, p->d_partials, (size_t)S * cap * npart * 5)) return rc;
   c->last_first_pass = 5;
   const bool ldsp = 2 * c->geom.rpx + 1 <= ZS_TAPS;
   for (int64_t b0 = 0; b0 < n_cand; b0 += cap) {
@@ -288,8 +283,8 @@ extern "C" int hh_sweep_parts(hh_ctx* c, const double* params, int64_t g, float*
   HH_HIP(c, hipSetDevice(c->device));
   hh_phase* p = c->phase;
   const size_t n = (size_t)g * c->n_segments;
-  if ((rc = ensure_bytes(c, (void**)&p->d_params, &p->cap_params, (size_t)g * 4 * sizeof(double)))) return rc;
-  if ((rc = ensure_bytes(c, (void**)&p->d_out, &p->cap_out, 3 * n * sizeof(float)))) return rc;
+  if ((rc = ensure(c, p->d_params, (size_t)g * 4))) return rc;
+  if ((rc = ensure(c, p->d_out, 3 * n))) return rc;
   HH_HIP(c, hipMemcpyAsync(p->d_params, params, (size_t)g * 4 * sizeof(double), hipMemcpyHostToDevice, c->stream));
   if ((rc = phase_sweep(c, p->d_params, g, p->d_out, 0, p->d_out + n, p->d_out + 2 * n))) return rc;
   float* const host[3] = {scores, amplitude, phase};
@@ -313,10 +308,10 @@ extern "C" int hh_phase_map(hh_ctx* c, const float* image, int log_flag, float* 
   const double cutoff_y = zoomed ? z->cutoff_y : 2 * apix, cutoff_x = zoomed ? z->cutoff_x : 2 * apix;
   const size_t plane = (size_t)ony * onx, npix = (size_t)ny * nx;
   int rc;
-  if ((rc = ensure_bytes(c, (void**)&p->d_img, &p->cap_img, npix * sizeof(float)))) return rc;
-  if ((rc = ensure_bytes(c, (void**)&p->d_r, &p->cap_r, (size_t)ny * onx * sizeof(double2)))) return rc;
-  if ((rc = ensure_bytes(c, (void**)&p->d_pm, &p->cap_pm, plane * sizeof(float)))) return rc;
-  if ((rc = ensure_bytes(c, (void**)&p->d_pc, &p->cap_pc, plane * sizeof(float)))) return rc;
+  if ((rc = ensure(c, p->d_img, npix))) return rc;
+  if ((rc = ensure(c, p->d_r, (size_t)ny * onx))) return rc;
+  if ((rc = ensure(c, p->d_pm, plane))) return rc;
+  if ((rc = ensure(c, p->d_pc, plane))) return rc;
   const ZoomDims d{ny, nx, ony, onx, 2 * apix / cutoff_y, 2 * apix / cutoff_x};
   HH_HIP(c, hipMemcpyAsync(p->d_img, image, npix * sizeof(float), hipMemcpyHostToDevice, c->stream));
   hipLaunchKernelGGL(k_zoom_rows, dim3((onx + 127) / 128, ny), dim3(128), 0, c->stream, p->d_img, d, apix, cutoff_x, p->d_r);

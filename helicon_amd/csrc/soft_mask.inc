@@ -24,18 +24,12 @@ struct SmTap {     // one full-grid index of one axis
 };
 
 struct SmState {
-  uint8_t* sup = nullptr;        // [n_sup][n^3]
+  DevBuf<uint8_t> sup;           // [n_sup][n^3]
   int n_sup = 0;
-  int32_t *g0 = nullptr, *g1 = nullptr;   // the transform's two grids, `cap` elements each
-  int64_t cap = 0;
-  SmTap* taps = nullptr;         // [cap_taps]
-  int64_t cap_taps = 0;
-  int32_t* probe = nullptr;      // [cap_probe]: D2 of voxel 0 per (width, support): >= SM_INF means an empty decimated support
-  int64_t cap_probe = 0;
-  float* mask = nullptr;         // [n^3]: hh_tfsm_soft_mask's staging
-  ~SmState() {
-    (void)hipFree(sup); (void)hipFree(g0); (void)hipFree(g1); (void)hipFree(taps); (void)hipFree(probe); (void)hipFree(mask);
-  }
+  DevBuf<int32_t> g0, g1;        // the transform's two grids
+  DevBuf<SmTap> taps;
+  DevBuf<int32_t> probe;         // D2 of voxel 0 per (width, support): >= SM_INF means an empty decimated support
+  DevBuf<float> mask;            // [n^3]: hh_tfsm_soft_mask's staging
 };
 
 void sm_release(SmState* s) { delete s; }
@@ -219,26 +213,11 @@ struct SmEvents {
 
 // the grids, tap tables and probes of a context, grown on demand
 int sm_reserve(SmState* s, int64_t cells, int64_t taps, int64_t probes) {
-  if (s->cap < cells) {
-    (void)hipFree(s->g0); (void)hipFree(s->g1);
-    s->g0 = s->g1 = nullptr; s->cap = 0;
-    HH_HIP(nullptr, hipMalloc(&s->g0, (size_t)cells * sizeof(int32_t)));
-    HH_HIP(nullptr, hipMalloc(&s->g1, (size_t)cells * sizeof(int32_t)));
-    s->cap = cells;
-  }
-  if (s->cap_taps < taps) {
-    (void)hipFree(s->taps);
-    s->taps = nullptr; s->cap_taps = 0;
-    HH_HIP(nullptr, hipMalloc(&s->taps, (size_t)taps * sizeof(SmTap)));
-    s->cap_taps = taps;
-  }
-  if (s->cap_probe < probes) {
-    (void)hipFree(s->probe);
-    s->probe = nullptr; s->cap_probe = 0;
-    HH_HIP(nullptr, hipMalloc(&s->probe, (size_t)probes * sizeof(int32_t)));
-    s->cap_probe = probes;
-  }
-  return HH_OK;
+  int rc = ensure(nullptr, s->g0, (size_t)cells);
+  if (!rc) rc = ensure(nullptr, s->g1, (size_t)cells);
+  if (!rc && taps > 0) rc = ensure(nullptr, s->taps, (size_t)taps);
+  if (!rc && probes > 0) rc = ensure(nullptr, s->probe, (size_t)probes);
+  return rc;
 }
 
 }  // namespace
@@ -265,7 +244,7 @@ extern "C" int hh_edt_3d(int device, const uint8_t* support, int32_t nz, int32_t
   const int64_t cells = (int64_t)mz * my * mx, per_map = (int64_t)nz * ny * nx;
   SmState s;
   SmEvents ev;
-  HH_HIP(nullptr, hipMalloc(&s.sup, (size_t)per_map));
+  if (int rc = ensure(nullptr, s.sup, (size_t)per_map)) return rc;
   if (int rc = sm_reserve(&s, cells, 0, 0)) return rc;
   HH_HIP(nullptr, hipEventCreate(&ev.e0));
   HH_HIP(nullptr, hipEventCreate(&ev.e1));
@@ -331,8 +310,8 @@ extern "C" int hh_soft_mask_3d(int device, const uint8_t* support, int32_t nz, i
   if (int rc = sm_device("hh_soft_mask_3d", device)) return rc;
   SmState s;
   SmEvents ev;
-  HH_HIP(nullptr, hipMalloc(&s.sup, (size_t)per_map));
-  HH_HIP(nullptr, hipMalloc(&s.mask, (size_t)per_map * sizeof(float)));
+  if (int rc = ensure(nullptr, s.sup, (size_t)per_map)) return rc;
+  if (int rc = ensure(nullptr, s.mask, (size_t)per_map)) return rc;
   HH_HIP(nullptr, hipEventCreate(&ev.e0));
   HH_HIP(nullptr, hipEventCreate(&ev.e1));
   HH_HIP(nullptr, hipMemcpy(s.sup, support, (size_t)per_map, hipMemcpyHostToDevice));
@@ -354,9 +333,9 @@ extern "C" int hh_tfsm_set_support(hh_tfsc* ctx, const uint8_t* support1, const 
   SmState* const s = c->soft;
   const int n_sup = support2 ? 2 : 1;
   if (s->n_sup != n_sup) {
-    (void)hipFree(s->sup);
-    s->sup = nullptr; s->n_sup = 0;
-    HH_HIP(nullptr, hipMalloc(&s->sup, (size_t)n_sup * (size_t)c->per_map));
+    s->sup.reset();
+    s->n_sup = 0;
+    if (int rc = ensure(nullptr, s->sup, (size_t)n_sup * (size_t)c->per_map)) return rc;
   }
   HH_HIP(nullptr, hipMemcpy(s->sup, support1, (size_t)c->per_map, hipMemcpyHostToDevice));
   if (support2) HH_HIP(nullptr, hipMemcpy(s->sup + c->per_map, support2, (size_t)c->per_map, hipMemcpyHostToDevice));
@@ -372,7 +351,7 @@ extern "C" int hh_tfsm_soft_mask(hh_tfsc* ctx, int which, double soft_width, flo
   SmState* const s = c->soft;
   if (!s || s->n_sup < 1) return fail(nullptr, HH_ERR_STATE, "hh_tfsm_soft_mask: no support is set (hh_tfsm_set_support)");
   HH_HIP(nullptr, hipSetDevice(c->device));
-  if (!s->mask) HH_HIP(nullptr, hipMalloc(&s->mask, (size_t)c->per_map * sizeof(float)));
+  if (int rc = ensure(nullptr, s->mask, (size_t)c->per_map)) return rc;
   const uint8_t* const sup = s->sup + (s->n_sup == 2 ? which : 0) * c->per_map;
   if (int rc = sm_one("hh_tfsm_soft_mask", s, sup, c->n, c->n, c->n, soft_width, s->mask)) return rc;
   HH_HIP(nullptr, hipMemcpy(mask_out, s->mask, (size_t)c->per_map * sizeof(float), hipMemcpyDeviceToHost));

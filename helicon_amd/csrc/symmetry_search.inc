@@ -35,16 +35,17 @@ struct hh_hs {
   int nz = 0, ny = 0, nx = 0;
   double apix = 0, fraction = 1;
   int z0 = 0, z1 = 0;            // source planes the operator reads: [z0, z1) (the 1 % profile rule and `fraction`)
-  float* d_map = nullptr;
+  DevBuf<float> d_map;
   // the scored region
-  int32_t* d_vox = nullptr;      // in-plane voxels of M, (j << 16) | i, row-major order
+  DevBuf<int32_t> d_vox;         // in-plane voxels of M, (j << 16) | i, row-major order
   int np = 0, kz0 = 0, nplanes = 0, ntiles = 0, nv = 0;
   int64_t region_voxels = 0;
   double sum_v = 0, sum_vv = 0;  // over M
   double rmin = 0, rmax = -1, z_fraction = 0.5;
   // work buffers, grown on demand
-  double* d_part = nullptr; size_t part_cap = 0;       // candidates the triples' buffer holds
-  double* d_params = nullptr; float* d_scores = nullptr; size_t list_cap = 0;
+  DevBuf<double> d_part;         // the triples of the candidates of one launch
+  DevBuf<double> d_params;       // the candidate list and its scores
+  DevBuf<float> d_scores;
   int64_t budget = (int64_t)64 << 20;                  // bytes of triples per launch
   double kernel_ms = 0;
   int64_t launches = 0;
@@ -274,8 +275,8 @@ __global__ __launch_bounds__(256) void k_hs_finalize(const double* __restrict__ 
 }
 
 void hs_free_region(hh_hs* p) {
-  (void)hipFree(p->d_vox); p->d_vox = nullptr;
-  (void)hipFree(p->d_part); p->d_part = nullptr; p->part_cap = 0;
+  p->d_vox.reset();
+  p->d_part.reset();
   p->np = p->nplanes = p->ntiles = p->nv = 0;
   p->region_voxels = 0;
 }
@@ -317,10 +318,13 @@ int hs_set_region(hh_hs* p, double rmin, double rmax, double z_fraction) {
   p->ntiles = (p->np + 256 * p->nv - 1) / (256 * p->nv);
   p->region_voxels = (int64_t)p->np * p->nplanes;
   const size_t n_part = (size_t)p->nplanes * p->ntiles;
-  double* d_mom = nullptr;
-  hipError_t e = hipMalloc(&p->d_vox, vox.size() * sizeof(int32_t));
-  if (e == hipSuccess) e = hipMalloc(&d_mom, n_part * 2 * sizeof(double));
-  if (e == hipSuccess) e = hipMemcpyAsync(p->d_vox, vox.data(), vox.size() * sizeof(int32_t), hipMemcpyHostToDevice, p->stream);
+  DevArena mem;
+  double* d_mom = mem.get<double>(n_part * 2);
+  if (!mem.ok() || !p->d_vox.ensure(vox.size())) {
+    hs_free_region(p);
+    return hs_fail(p, HH_ERR_NOMEM, "hh_hs_set_region: " + dev_alloc_failed(mem.ok() ? vox.size() * sizeof(int32_t) : mem.failed_bytes()));
+  }
+  hipError_t e = hipMemcpyAsync(p->d_vox, vox.data(), vox.size() * sizeof(int32_t), hipMemcpyHostToDevice, p->stream);
   std::vector<double> mom(n_part * 2);
   if (e == hipSuccess) {
     HsArgs a = hs_args(p);
@@ -330,7 +334,6 @@ int hs_set_region(hh_hs* p, double rmin, double rmax, double z_fraction) {
   }
   if (e == hipSuccess) e = hipMemcpyAsync(mom.data(), d_mom, mom.size() * sizeof(double), hipMemcpyDeviceToHost, p->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(p->stream);
-  (void)hipFree(d_mom);
   if (e != hipSuccess) {
     hs_free_region(p);
     return hs_fail(p, HH_ERR_HIP, std::string("hh_hs_set_region: ") + hipGetErrorString(e));
@@ -350,12 +353,11 @@ void hh_hs_destroy(hh_hs* p) try {
   if (!p) return;
   (void)hipSetDevice(p->device);
   if (p->stream) (void)hipStreamSynchronize(p->stream);
-  hs_free_region(p);
-  (void)hipFree(p->d_map); (void)hipFree(p->d_params); (void)hipFree(p->d_scores);
   if (p->ev0) (void)hipEventDestroy(p->ev0);
   if (p->ev1) (void)hipEventDestroy(p->ev1);
-  if (p->stream) (void)hipStreamDestroy(p->stream);
-  delete p;
+  const hipStream_t stream = p->stream;
+  delete p;                                   // frees the device buffers: before their stream goes
+  if (stream) (void)hipStreamDestroy(stream);
 } catch (...) {
 }
 
@@ -399,7 +401,10 @@ int hh_hs_create(hh_hs** out, int device, const float* map, const int32_t shape[
   if (e == hipSuccess) e = hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking);
   if (e == hipSuccess) e = hipEventCreate(&p->ev0);
   if (e == hipSuccess) e = hipEventCreate(&p->ev1);
-  if (e == hipSuccess) e = hipMalloc(&p->d_map, plane * nz * sizeof(float));
+  if (e == hipSuccess && !p->d_map.ensure(plane * nz)) {
+    hh_hs_destroy(p);
+    return hs_fail(nullptr, HH_ERR_NOMEM, "hh_hs_create: " + dev_alloc_failed(plane * nz * sizeof(float)));
+  }
   if (e == hipSuccess) e = hipMemcpyAsync(p->d_map, map, plane * nz * sizeof(float), hipMemcpyHostToDevice, p->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(p->stream);
   if (e != hipSuccess) {
@@ -463,18 +468,10 @@ int hh_hs_search(hh_hs* p, const double* params, int64_t g, float* scores) try {
   const size_t per_cand = n_part * 3 * sizeof(double);
   // 65535: the grid.z limit (pinned by tests/test_launch_cuts_host.py, crossed by tests/test_gpu_launch_cuts.py)
   const size_t per_launch = (size_t)std::max<int64_t>(1, std::min<int64_t>({(int64_t)(p->budget / (int64_t)per_cand), g, 65535}));
-  if (per_launch > p->part_cap) {
-    (void)hipFree(p->d_part); p->d_part = nullptr; p->part_cap = 0;
-    if (hipMalloc(&p->d_part, per_launch * per_cand) != hipSuccess) return hs_fail(p, HH_ERR_NOMEM, "hh_hs_search: out of device memory (partial sums)");
-    p->part_cap = per_launch;
-  }
-  if ((size_t)g > p->list_cap) {
-    (void)hipFree(p->d_params); (void)hipFree(p->d_scores);
-    p->d_params = nullptr; p->d_scores = nullptr; p->list_cap = 0;
-    if (hipMalloc(&p->d_params, (size_t)g * 3 * sizeof(double)) != hipSuccess || hipMalloc(&p->d_scores, (size_t)g * sizeof(float)) != hipSuccess)
-      return hs_fail(p, HH_ERR_NOMEM, "hh_hs_search: out of device memory (candidate list)");
-    p->list_cap = (size_t)g;
-  }
+  if (!p->d_part.ensure(per_launch * n_part * 3))
+    return hs_fail(p, HH_ERR_NOMEM, "hh_hs_search: partial sums: " + dev_alloc_failed(per_launch * per_cand));
+  if (!p->d_params.ensure((size_t)g * 3) || !p->d_scores.ensure((size_t)g))
+    return hs_fail(p, HH_ERR_NOMEM, "hh_hs_search: candidate list: " + dev_alloc_failed((size_t)g * (p->d_params ? sizeof(float) : 3 * sizeof(double))));
   HS_HIP(p, hipMemcpyAsync(p->d_params, params, (size_t)g * 3 * sizeof(double), hipMemcpyHostToDevice, p->stream));
   HS_HIP(p, hipEventRecord(p->ev0, p->stream));
   HsArgs a = hs_args(p);

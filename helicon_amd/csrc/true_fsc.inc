@@ -24,16 +24,14 @@ struct hh_tfsc {
   FcPlan plan;
   size_t o_izr = 0, o_izi = 0, o_iyr = 0, o_iyi = 0, o_xcw = 0, o_xsw = 0;   // inverse operators, after the plan's in fc.mats
   FcBuffers fc;              // the forward passes' scratch, the operators (fc.mats) and the events
-  float* maps = nullptr;     // [4][n^3]: map1, map2, map1r, map2r
-  float* spec = nullptr;     // [re | im][2 maps][n n][ncol]: the substituted half spectra
-  double* curves = nullptr;  // [2][nshell][3]
-  int64_t cap_masks = 0;
-  float* masks = nullptr;
+  DevBuf<float> maps;        // [4][n^3]: map1, map2, map1r, map2r
+  DevBuf<float> spec;        // [re | im][2 maps][n n][ncol]: the substituted half spectra
+  DevBuf<double> curves;     // [2][nshell][3]
+  DevBuf<float> masks;       // the masks of one chunk of hh_tfsc_masked
   SmState* soft = nullptr;
-  ~hh_tfsc() {   // (fc goes after this body, on the device set here)
+  ~hh_tfsc() {   // (the buffers and fc go after this body, on the device set here)
     (void)hipSetDevice(device);
     sm_release(soft);
-    (void)hipFree(maps); (void)hipFree(spec); (void)hipFree(curves); (void)hipFree(masks);
   }
 };
 
@@ -217,18 +215,17 @@ int tf_create(hh_tfsc* c, const float* map1, const float* map2, int64_t m_cut, c
   }
   const size_t map_bytes = (size_t)per_map * sizeof(float);
   FcBuffers& d = c->fc;
-  HH_HIP(nullptr, hipMalloc(&d.mats, mats.size() * sizeof(float)));
+  if (int rc = ensure(nullptr, d.mats, mats.size())) return rc;
   HH_HIP(nullptr, hipMemcpy(d.mats, mats.data(), mats.size() * sizeof(float), hipMemcpyHostToDevice));
-  HH_HIP(nullptr, hipMalloc(&c->maps, 4 * map_bytes));
-  HH_HIP(nullptr, hipMalloc(&c->spec, 4 * (size_t)per_spec * sizeof(float)));
-  HH_HIP(nullptr, hipMalloc(&c->curves, (size_t)2 * nshell * 3 * sizeof(double)));
+  if (int rc = ensure(nullptr, c->maps, 4 * (size_t)per_map)) return rc;
+  if (int rc = ensure(nullptr, c->spec, 4 * (size_t)per_spec)) return rc;
+  if (int rc = ensure(nullptr, c->curves, (size_t)2 * nshell * 3)) return rc;
   if (int rc = d.reserve(1, per_map, nshell, true, false)) return rc;   // create reads the resident maps in place
   HH_HIP(nullptr, hipMemcpy(c->maps, map1, map_bytes, hipMemcpyHostToDevice));
   HH_HIP(nullptr, hipMemcpy(c->maps + per_map, map2, map_bytes, hipMemcpyHostToDevice));
-  double* d_ph = nullptr;   // the host's angles: both maps, freed below
-  struct Free { double*& p; ~Free() { (void)hipFree(p); } } free_ph{d_ph};
+  DevBuf<double> d_ph;      // the host's angles: both maps, freed on the way out
   if (phases1) {
-    HH_HIP(nullptr, hipMalloc(&d_ph, 2 * (size_t)per_spec * sizeof(double)));
+    if (int rc = ensure(nullptr, d_ph, 2 * (size_t)per_spec)) return rc;
     HH_HIP(nullptr, hipMemcpy(d_ph, phases1, (size_t)per_spec * sizeof(double), hipMemcpyHostToDevice));
     HH_HIP(nullptr, hipMemcpy(d_ph + per_spec, phases2, (size_t)per_spec * sizeof(double), hipMemcpyHostToDevice));
   }
@@ -348,12 +345,7 @@ extern "C" int hh_tfsc_masked(hh_tfsc* ctx, const float* masks1, const float* ma
   FcBuffers& d = c->fc;
   if (int rc = d.reserve(2 * chunk, per_map, nshell, true, true)) return rc;
   const int n_sets = masks2 ? 2 : 1;
-  if (c->cap_masks < n_sets * chunk) {
-    (void)hipFree(c->masks);
-    c->masks = nullptr; c->cap_masks = 0;
-    HH_HIP(nullptr, hipMalloc(&c->masks, (size_t)(n_sets * chunk) * per_map * sizeof(float)));
-    c->cap_masks = n_sets * chunk;
-  }
+  if (int rc = ensure(nullptr, c->masks, (size_t)(n_sets * chunk) * per_map)) return rc;
   double ms_total = 0.0;
   for (int64_t b0 = 0; b0 < batch; b0 += chunk) {
     const int64_t nb = std::min(chunk, (int64_t)batch - b0);

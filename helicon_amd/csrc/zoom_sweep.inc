@@ -22,18 +22,16 @@ struct hh_zoom {
   double cutoff_y = 0, cutoff_x = 0;
   double apix_ref = 0;            // pixel size the reference was prepared with (the frequencies depend on it)
   int tiles_v = 0, n_tiles = 0;   // active output tiles (any masked bin)
-  float* d_img = nullptr;         // [S][ny][nx]
-  double2* d_r = nullptr;         // [ny][onx] row pass of one image
-  float* d_pwr = nullptr;         // [ony][onx] fftshifted spectrum of one image
-  unsigned* d_mm = nullptr;       // k_zoom_cols' min / max slots (unused here: Pearson drops the normalisation)
-  uint8_t* d_mask = nullptr;      // [ony][onx] fftshifted
-  float* d_w = nullptr;           // [ony][onx] unshifted mask weight
-  float* d_wec = nullptr;         // [S][ony][onx] unshifted w (E_s - Ebar_s)
-  RefConsts* d_ref = nullptr;     // [S]
-  int* d_tiles = nullptr;
-  double* d_partials = nullptr;   // [S][batch][n_tiles][3]
-  size_t cap_img = 0, cap_r = 0, cap_pwr = 0, cap_mm = 0, cap_mask = 0, cap_w = 0, cap_wec = 0, cap_ref = 0, cap_tiles = 0,
-         cap_partials = 0;
+  DevBuf<float> d_img;            // [S][ny][nx]
+  DevBuf<double2> d_r;            // [ny][onx] row pass of one image
+  DevBuf<float> d_pwr;            // [ony][onx] fftshifted spectrum of one image
+  DevBuf<unsigned> d_mm;          // k_zoom_cols' min / max slots (unused here: Pearson drops the normalisation)
+  DevBuf<uint8_t> d_mask;         // [ony][onx] fftshifted
+  DevBuf<float> d_w;              // [ony][onx] unshifted mask weight
+  DevBuf<float> d_wec;            // [S][ony][onx] unshifted w (E_s - Ebar_s)
+  DevBuf<RefConsts> d_ref;        // [S]
+  DevBuf<int> d_tiles;
+  DevBuf<double> d_partials;      // [S][batch][n_tiles][3]
   std::vector<RefConsts> ref;
   // the view the reference was prepared on: the zoom's, or the identity zoom (the image's own shape and Nyquist) when only
   // a spectrum filter is set
@@ -46,15 +44,14 @@ struct hh_zoom {
   int f_terms = 0;                // separable terms J of the operator: L q = c0 q + sum_j Ay_j q Ax_j^T
   float f_c0 = 0.f;
   int f_tiles_v = 0, f_n_tiles = 0;
-  float* d_ay = nullptr;          // [J][ony][ony]
-  float* d_ax = nullptr;          // [J][onx][onx], the term's sign folded in
-  float* d_fq = nullptr;          // [B][ony][onx] q of one batch (also: the filtered spectrum of a reference image)
-  float* d_ft = nullptr;          // [J][B][ony][onx] y pass of one batch
-  int* d_tiles_all = nullptr;     // every tile of k_zoom_sweep (the filter needs the whole plane)
-  int* d_ftiles = nullptr;        // x-pass tiles with a masked bin; behind them, at f_all_off, every x-pass tile
+  DevBuf<float> d_ay;             // [J][ony][ony]
+  DevBuf<float> d_ax;             // [J][onx][onx], the term's sign folded in
+  DevBuf<float> d_fq;             // [B][ony][onx] q of one batch (also: the filtered spectrum of a reference image)
+  DevBuf<float> d_ft;             // [J][B][ony][onx] y pass of one batch
+  DevBuf<int> d_tiles_all;        // every tile of k_zoom_sweep (the filter needs the whole plane)
+  DevBuf<int> d_ftiles;           // x-pass tiles with a masked bin; behind them, at f_all_off, every x-pass tile
   int f_all_off = 0, f_all_tiles = 0;
-  double* d_fpart = nullptr;      // [S][B][f_n_tiles][3]
-  size_t cap_ay = 0, cap_ax = 0, cap_fq = 0, cap_ft = 0, cap_tiles_all = 0, cap_ftiles = 0, cap_fpart = 0;
+  DevBuf<double> d_fpart;         // [S][B][f_n_tiles][3]
 };
 
 namespace {
@@ -378,13 +375,7 @@ __global__ __launch_bounds__(1024) void k_zoom_weights(const float* __restrict__
 }
 
 void zoom_free(hh_ctx* c) {
-  hh_zoom* z = c->zoom;
-  if (!z) return;
-  (void)hipFree(z->d_img); (void)hipFree(z->d_r); (void)hipFree(z->d_pwr); (void)hipFree(z->d_mm); (void)hipFree(z->d_mask);
-  (void)hipFree(z->d_w); (void)hipFree(z->d_wec); (void)hipFree(z->d_ref); (void)hipFree(z->d_tiles); (void)hipFree(z->d_partials);
-  (void)hipFree(z->d_ay); (void)hipFree(z->d_ax); (void)hipFree(z->d_fq); (void)hipFree(z->d_ft); (void)hipFree(z->d_tiles_all);
-  (void)hipFree(z->d_ftiles); (void)hipFree(z->d_fpart);
-  delete z;
+  delete c->zoom;   // its buffers free themselves
   c->zoom = nullptr;
 }
 
@@ -434,15 +425,15 @@ int zoom_set_reference(hh_ctx* c, const float* images, int n_segments, const uin
   if (tiles.empty()) return fail(c, HH_ERR_ARG, "hh_set_reference: the mask selects no Fourier bin");
   c->n_segments = 0;   // from here on the old reference is gone
   int rc;
-  if ((rc = ensure_bytes(c, (void**)&z->d_img, &z->cap_img, (size_t)n_segments * npix * sizeof(float)))) return rc;
-  if ((rc = ensure_bytes(c, (void**)&z->d_r, &z->cap_r, (size_t)ny * onx * sizeof(double2)))) return rc;
-  if ((rc = ensure_bytes(c, (void**)&z->d_pwr, &z->cap_pwr, plane * sizeof(float)))) return rc;
-  if ((rc = ensure_bytes(c, (void**)&z->d_mm, &z->cap_mm, 2 * sizeof(unsigned)))) return rc;
-  if ((rc = ensure_bytes(c, (void**)&z->d_mask, &z->cap_mask, plane))) return rc;
-  if ((rc = ensure_bytes(c, (void**)&z->d_w, &z->cap_w, plane * sizeof(float)))) return rc;
-  if ((rc = ensure_bytes(c, (void**)&z->d_wec, &z->cap_wec, (size_t)n_segments * plane * sizeof(float)))) return rc;
-  if ((rc = ensure_bytes(c, (void**)&z->d_ref, &z->cap_ref, (size_t)n_segments * sizeof(RefConsts)))) return rc;
-  if ((rc = ensure_bytes(c, (void**)&z->d_tiles, &z->cap_tiles, (size_t)tiles_u * tiles_v * sizeof(int)))) return rc;
+  if ((rc = ensure(c, z->d_img, (size_t)n_segments * npix))) return rc;
+  if ((rc = ensure(c, z->d_r, (size_t)ny * onx))) return rc;
+  if ((rc = ensure(c, z->d_pwr, plane))) return rc;
+  if ((rc = ensure(c, z->d_mm, 2))) return rc;
+  if ((rc = ensure(c, z->d_mask, plane))) return rc;
+  if ((rc = ensure(c, z->d_w, plane))) return rc;
+  if ((rc = ensure(c, z->d_wec, (size_t)n_segments * plane))) return rc;
+  if ((rc = ensure(c, z->d_ref, (size_t)n_segments))) return rc;
+  if ((rc = ensure(c, z->d_tiles, (size_t)tiles_u * tiles_v))) return rc;
   z->r_ony = ony;
   z->r_onx = onx;
   z->r_cy = cutoff_y;
@@ -519,7 +510,7 @@ int zoom_sweep(hh_ctx* c, const double* d_params, int64_t n_cand, float* d_score
   const int64_t stride = ld > 0 ? ld : n_cand;
   const int S = c->n_segments, npart = z->n_tiles;
   const int64_t cap = std::min<int64_t>(n_cand, ZS_BATCH);
-  if (int rc = ensure_bytes(c, (void**)&z->d_partials, &z->cap_partials, (size_t)S * cap * npart * 3 * sizeof(double))) return rc;
+  if (int rc = ensure(c, z->d_partials, (size_t)S * cap * npart * 3)) return rc;
   c->last_first_pass = 3;
   for (int64_t b0 = 0; b0 < n_cand; b0 += cap) {
     const int nb = (int)std::min<int64_t>(cap, n_cand - b0);
