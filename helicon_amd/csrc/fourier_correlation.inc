@@ -92,21 +92,26 @@ __device__ __forceinline__ void fc_pair_product(const float* const (&src)[4], co
     stage_cols(os, tab, ncol, k0, nx, col0, ncol, t.tid);
     __syncthreads();
     if (active) {
+      // The slice's products go into accumulators of their own and the slices are then added: a chain of at most 2 FC_K terms
+      // plus nx / FC_K slice sums.  One chain over all nx terms loses sqrt(nx) ulp of the LARGEST partial sum at a bin whose
+      // terms share a sign: 6.5 ulp at the DC bin of a 126^3 map with an offset (DESIGN.md, "True-FSC side census").
+      f32x16 sre1 = {0}, sim1 = {0}, sre2 = {0}, sim2 = {0};
 #pragma unroll
       for (int kk = 0; kk < FC_K; kk += 2) {
         const float c = os[0][kk + h][wp + r], s = os[1][kk + h][wp + r];
         const float a1 = as[0][wm + r][kk + h], b1 = as[1][wm + r][kk + h];
         const float a2 = as[2][wm + r][kk + h], b2 = as[3][wm + r][kk + h];
         // (a + i b)(c - i s) = (a c + b s) + i (b c - a s)
-        re1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, c, re1, 0, 0, 0);
-        re1 = __builtin_amdgcn_mfma_f32_32x32x2f32(b1, s, re1, 0, 0, 0);
-        im1 = __builtin_amdgcn_mfma_f32_32x32x2f32(b1, c, im1, 0, 0, 0);
-        im1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, -s, im1, 0, 0, 0);
-        re2 = __builtin_amdgcn_mfma_f32_32x32x2f32(a2, c, re2, 0, 0, 0);
-        re2 = __builtin_amdgcn_mfma_f32_32x32x2f32(b2, s, re2, 0, 0, 0);
-        im2 = __builtin_amdgcn_mfma_f32_32x32x2f32(b2, c, im2, 0, 0, 0);
-        im2 = __builtin_amdgcn_mfma_f32_32x32x2f32(a2, -s, im2, 0, 0, 0);
+        sre1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, c, sre1, 0, 0, 0);
+        sre1 = __builtin_amdgcn_mfma_f32_32x32x2f32(b1, s, sre1, 0, 0, 0);
+        sim1 = __builtin_amdgcn_mfma_f32_32x32x2f32(b1, c, sim1, 0, 0, 0);
+        sim1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, -s, sim1, 0, 0, 0);
+        sre2 = __builtin_amdgcn_mfma_f32_32x32x2f32(a2, c, sre2, 0, 0, 0);
+        sre2 = __builtin_amdgcn_mfma_f32_32x32x2f32(b2, s, sre2, 0, 0, 0);
+        sim2 = __builtin_amdgcn_mfma_f32_32x32x2f32(b2, c, sim2, 0, 0, 0);
+        sim2 = __builtin_amdgcn_mfma_f32_32x32x2f32(a2, -s, sim2, 0, 0, 0);
       }
+      re1 += sre1; im1 += sim1; re2 += sre2; im2 += sim2;
     }
     __syncthreads();
   }

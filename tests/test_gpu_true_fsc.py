@@ -2,7 +2,8 @@
 reference (tests/true_fsc_oracle.py, pinned to the reference by tests/golden/g20_true_fsc.npz) and against the reference's
 recorded curves.
 
-Inputs: ``make_map_pair(n, seed, dc="auto")``; the cutoff makes ``(apix / cutoff)^2 n^2 = (n / 4 + 1/2)^2``, a quarter-integer,
+Inputs: ``make_map_pair(n, seed, dc="auto")``; the cutoff makes ``(apix / cutoff)^2 n^2 = (n / 4 + 1/2)^2``, a quarter-integer
+for n divisible by 4 (every side here; for n = 4 j + 2 it is the integer (j + 1)^2: tests/true_fsc_sides.py has the rule for those),
 so no bin is a tie (asserted: the reference's float64 expression selects the integer rule's bins).  Every pair whose curve is
 compared keeps each shell's den1, den2 at least 1e-4 of the strongest shell's (asserted: the unmasked pair, the randomised
 pair and both masked pairs), the condition of tests/test_gpu_fsc.py.
