@@ -47,6 +47,7 @@
 
 #include "../../include/helicon_hip.h"
 #include "device_mem.h"  // DevBuf / DevArena: the owners of device memory
+#include "pab_plan.h"  // host arithmetic of the Path A batch set-up (path_a_batch.inc)
 #include "gen_rows.h"  // the general-size sweep's two-step row kernel (second translation unit, gen_rows.hip)
 
 // Tuning values are constants beside what they tune (the measured best).

@@ -1295,6 +1295,16 @@ void pab_lds_attr(hh_pab* p, K kernel, size_t bytes) {
   (void)hipFuncSetAttribute(key, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
   done.push_back({key, {p->device, bytes}});
 }
+// the separable form's planes per group (fac_G: 1 .. 4, anything else as 4) as a compile-time constant: f(integral_constant)
+template <class F>
+void pabf_with_G(int G, F f) {
+  switch (G) {
+    case 1: f(std::integral_constant<int, 1>{}); break;
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    case 3: f(std::integral_constant<int, 3>{}); break;
+    default: f(std::integral_constant<int, 4>{}); break;
+  }
+}
 template <int MODE, class P>
 void pab_matvec(hh_pab* p, int src, int dsc, int rootv, int dst, P pred) {
   const int nb = pab_nb_fwd(p, rootv >= 0);
@@ -1304,12 +1314,7 @@ void pab_matvec(hh_pab* p, int src, int dsc, int rootv, int dst, P pred) {
       pab_lds_attr(p, kernel, p->fac_lds);
       hipLaunchKernelGGL(kernel, pab_grid(p->fac_ng * p->fac_split, pab_slots(p)), dim3(PABS_THREADS), p->fac_lds, p->stream, pab_view(p), src, dsc, rootv, dst, pred);
     };
-    switch (p->fac_G) {
-      case 1: launch(k_pabf_matvec<MODE, 1, P>); break;
-      case 2: launch(k_pabf_matvec<MODE, 2, P>); break;
-      case 3: launch(k_pabf_matvec<MODE, 3, P>); break;
-      default: launch(k_pabf_matvec<MODE, 4, P>); break;
-    }
+    pabf_with_G(p->fac_G, [&](auto G) { launch(k_pabf_matvec<MODE, decltype(G)::value, P>); });
     pab_after_launch(p);
     if (nb > p->fac_ng * p->fac_split)
       hipLaunchKernelGGL((k_pabf_tail<MODE, P>), pab_grid(nb - p->fac_ng * p->fac_split, pab_slots(p)), dim3(256), 0, p->stream, pab_view(p), src, dsc, rootv, dst, pred);
@@ -1339,12 +1344,7 @@ void pab_rmatvec(hh_pab* p, int src, int dsc, int rootv, int dst, P pred) {
         pab_lds_attr(p, kernel, p->fac_lds);
         hipLaunchKernelGGL(kernel, pab_grid(p->fac_ng * p->fac_split, pab_slots(p)), dim3(PABS_THREADS), p->fac_lds, p->stream, pab_view(p), src, pred);
       };
-      switch (p->fac_G) {
-        case 1: launch(k_pabf_scatter<MODE, false, 1, P>); break;
-        case 2: launch(k_pabf_scatter<MODE, false, 2, P>); break;
-        case 3: launch(k_pabf_scatter<MODE, false, 3, P>); break;
-        default: launch(k_pabf_scatter<MODE, false, 4, P>); break;
-      }
+      pabf_with_G(p->fac_G, [&](auto G) { launch(k_pabf_scatter<MODE, false, decltype(G)::value, P>); });
     } else if (p->band_T) {
       pab_lds_attr(p, k_pabt_scatter<MODE, false, P>, p->band_lds);
       hipLaunchKernelGGL((k_pabt_scatter<MODE, false, P>), pab_grid(p->mz * p->band_T, pab_slots(p)), dim3(PABS_THREADS), p->band_lds, p->stream,
@@ -1589,6 +1589,965 @@ void pab_lsmr_ticks(hh_pab* p, int count, int maxiter) {
   }
 }
 
+// ---- the set-up of a batch (hh_pab_create_ex): phases, in the order they run ------------------------------------------------
+// Every phase returns HH_OK, or a code with p->err set; its temporaries are its locals and end with it on every way out.
+// PabBuild holds what more than one phase reads.  Two of its members are device / host memory that crosses phases and is
+// freed where it is last read: d_b_int (row phases -> pab_build_tables) and rows16_of (pab_build_sym_host -> pab_build_tables).
+struct PabBuild {
+  const hh_pa_params* qs;
+  int count, flags;
+  const float* image;
+  int ny, nx, d2, l2, l3, d3;
+  double rmin, rmax;
+  static constexpr int chunk = 8;          // operations per sweep of the row enumeration
+  std::vector<int> rank;                   // voxel ranks of the (L3d, D2d, D2d) box
+  std::vector<int> n_ops;
+  PabGeomRef gr{};
+  bool dev_rows = false, dev_sym = false;
+  std::vector<int> srow_h;                 // [count][mz + 1] (device rows)
+  DevBuf<float> d_b_int;                   // device-order b of the data rows
+  std::vector<std::vector<int>> ray_of_row;      // host rows, per candidate: ray, b, pixel id and slice of every row
+  std::vector<std::vector<float>> b_of;
+  std::vector<std::vector<int32_t>> pid_of;
+  std::vector<std::vector<short>> z_of;
+  std::vector<std::vector<int2>> pairs_of;       // host symmetry rows, per candidate
+  std::vector<std::vector<PaEll16>> rows16_of;   // (trilinear: the 16-entry rows)
+  bool timing = std::getenv("HH_PAB_TIMING") != nullptr;
+  std::chrono::steady_clock::time_point t_last = std::chrono::steady_clock::now();
+  size_t rays() const { return (size_t)l2 * d2; }
+  void lap(hh_pab* p, const char* what) {
+    if (!timing) return;
+    (void)hipStreamSynchronize(p->stream);
+    const auto now = std::chrono::steady_clock::now();
+    std::fprintf(stderr, "hh_pab_create[%d]: %-28s %8.2f ms\n", count, what, std::chrono::duration<double, std::milli>(now - t_last).count());
+    t_last = now;
+  }
+};
+
+// a buffer of the object holding a host table
+template <class T>
+int pab_upload(hh_pab* p, DevBuf<T>& buf, const std::vector<T>& v) {
+  if (int rc = pab_alloc(p, buf, v.size())) return rc;
+  return pab_to_device(p, buf, v.data(), v.size() * sizeof(T));
+}
+
+// the arguments of hh_pab_create_ex (no object yet: messages go to g_create_error); the box of the batch -> d2, l2, l3
+int pab_check_args(hh_pab** out, const float* image, int ny, int nx, const hh_pa_params* qs, int count, int flags, int& d2, int& l2, int& l3) {
+  if (!out || !image || !qs || count < 1) return pab_fail(nullptr, HH_ERR_ARG, "hh_pab_create: bad argument");
+  if (flags & ~(HH_PAB_ALLOW_BANDED | HH_PAB_FORCE_BANDED)) return pab_fail(nullptr, HH_ERR_ARG, "hh_pab_create_ex: unknown flags");
+  *out = nullptr;
+  const hh_pa_params& q0 = qs[0];
+  d2 = q0.reconstruct_diameter_2d_pixel > 0 ? q0.reconstruct_diameter_2d_pixel : ny;
+  l2 = q0.reconstruct_length_2d_pixel > 0 ? q0.reconstruct_length_2d_pixel : nx;
+  l3 = q0.reconstruct_length_3d_pixel > 0 ? q0.reconstruct_length_3d_pixel : l2;
+  if (d2 > ny || l2 > nx || d2 < 2 || l2 < 2) return pab_fail(nullptr, HH_ERR_ARG, "hh_pab_create: 2-D region does not fit the image");
+  for (int c = 0; c < count; ++c) {
+    const hh_pa_params& q = qs[c];
+    if (!(q.rise_pixel > 0) || q.csym < 1 || q.twist_degree == 0.0)
+      return pab_fail(nullptr, HH_ERR_ARG, "hh_pab_create: rise must be positive, csym >= 1, twist non-zero");
+    if ((q.interpolation != 0 && q.interpolation != 1) || q.interpolation != q0.interpolation)
+      return pab_fail(nullptr, HH_ERR_ARG, "hh_pab_create: interpolation must be 0 (nearest neighbour) or 1 (trilinear), the same for the whole batch");
+    if (q.reconstruct_diameter_2d_pixel != q0.reconstruct_diameter_2d_pixel || q.reconstruct_length_2d_pixel != q0.reconstruct_length_2d_pixel ||
+        q.reconstruct_diameter_3d_pixel != q0.reconstruct_diameter_3d_pixel || q.reconstruct_length_3d_pixel != q0.reconstruct_length_3d_pixel ||
+        q.reconstruct_diameter_3d_inner_pixel != q0.reconstruct_diameter_3d_inner_pixel)
+      return pab_fail(nullptr, HH_ERR_ARG, "hh_pab_create: the candidates of one batch share the reconstruction box");
+    if (q.fsc_half < 0 || q.fsc_half > 2 || (q.fsc_half > 0 && (q.fsc_mode < 1 || (q.fsc_mode == 1 && (!q.fsc_ids || q.n_fsc_ids < 0)))))
+      return pab_fail(nullptr, HH_ERR_ARG, "hh_pab_create: half sets need fsc_half 1 or 2 and fsc_mode 2, 3, 4, or 1 with fsc_ids");
+  }
+  return HH_OK;
+}
+
+// device and stream; the unknowns (shared by the batch): voxels of the cylinder in the (L3d, D2d, D2d) box, C-order rank
+// (solver:1375-1387); the form of the products
+int pab_build_form(hh_pab* p, PabBuild& b) {
+  const int device = p->device, count = b.count, d2 = b.d2, l3 = b.l3, flags = b.flags;
+  PAB_HIP(p, hipSetDevice(device));
+  PAB_HIP(p, hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking));
+  PAB_HIP(p, hipHostMalloc(reinterpret_cast<void**>(&p->h_flags), PAB_FLAG_WORDS * sizeof(int), hipHostMallocDefault));
+  p->n = pa_mask_rank(l3, d2, d2, b.rmin, b.rmax, b.rank);
+  if (p->n <= 0) return pab_fail(p, HH_ERR_ARG, "hh_pab_create: the cylinder holds no voxel");
+  p->mz = l3;
+  p->nslice = (int)(p->n / l3);   // the same disk in every slice
+  p->flat = 1;
+  for (int c = 0; c < count; ++c) p->flat = p->flat && b.qs[c].tilt_degree == 0.0 && b.qs[c].psi_degree == 0.0;
+  const bool flat = p->flat && std::getenv("HH_PAB_GENERAL") == nullptr;
+  p->sliced = flat && (int64_t)p->nslice * l3 == p->n && p->nslice < 0xffff && (size_t)p->nslice * sizeof(double) <= (size_t)60 << 10;
+  p->linear = b.qs[0].interpolation;
+  if (p->linear) {   // two planes of x and the disc's table in LDS; no general (tilt / psi) form of the trilinear products here
+    p->lin_lds = (size_t)2 * p->nslice * sizeof(double) + (size_t)d2 * d2 * sizeof(unsigned);
+    const bool slice_major = flat && (int64_t)p->nslice * l3 == p->n && p->nslice < 0xffff;
+    const bool lds_fits = p->lin_lds <= (size_t)150 << 10;
+    // (band_T is set once the bands are cut, in pab_build_banded; this marks the form)
+    p->band_T = slice_major && ((flags & HH_PAB_FORCE_BANDED) || (!lds_fits && (flags & HH_PAB_ALLOW_BANDED))) ? -1 : 0;
+    p->sliced = slice_major && (lds_fits || p->band_T);
+    if (!p->sliced)
+      return pab_fail(p, HH_ERR_ARG,
+                      slice_major ? "hh_pab_create: not sliceable — the batched trilinear projector's LDS form needs two planes of the cylinder in LDS "
+                                    "(hh_pab_create_ex with HH_PAB_ALLOW_BANDED has the banded form)"
+                                  : "hh_pab_create: not sliceable — the batched trilinear projector needs tilt = psi = 0 "
+                                    "(the single-candidate hh_pa has the general form)");
+  }
+  return pab_upload(p, p->d_rank, b.rank);
+}
+
+// geometry and symmetry operations of every candidate, in the reference's order (solver:1556-1571)
+int pab_build_geometry(hh_pab* p, PabBuild& b) {
+  const int count = b.count, d2 = b.d2, l2 = b.l2, l3 = b.l3;
+  std::vector<PaGeom> geoms((size_t)count);
+  std::vector<PaOp> ops;
+  std::vector<int64_t> op0((size_t)count);
+  b.n_ops.assign((size_t)count, 0);
+  for (int c = 0; c < count; ++c) {
+    const hh_pa_params& q = b.qs[c];
+    PaGeom& g = geoms[(size_t)c];
+    g.linear = q.interpolation;
+    g.L2 = l2; g.D2 = d2; g.mz = l3; g.my = d2; g.mx = d2;
+    g.scale = q.scale2d_to_3d;
+    g.dy = q.dy_pixel;
+    pa_euler1('y', 90.0, g.m_y90);
+    double qy[4], qx[4], qq[4];
+    pa_quat_axis('y', q.tilt_degree, qy);
+    pa_quat_axis('x', q.psi_degree, qx);
+    pa_quat_mul(qx, qy, qq);
+    pa_quat_matrix(qq, g.m_yx);
+    const int hmax = std::max(1, (int)(std::ceil((double)(l3 + l2)) / 2 / q.rise_pixel));
+    struct Hc { int h, c; };
+    std::vector<Hc> hcs;
+    for (int h = -hmax; h <= hmax; ++h)
+      for (int cc = 0; cc < q.csym; ++cc) hcs.push_back({h, cc});
+    std::stable_sort(hcs.begin(), hcs.end(), [](const Hc& a, const Hc& b) {
+      return std::abs(a.h) != std::abs(b.h) ? std::abs(a.h) < std::abs(b.h) : a.c < b.c;
+    });
+    const std::vector<int64_t> order = pa_halton((int64_t)hcs.size());
+    op0[(size_t)c] = (int64_t)ops.size();
+    b.n_ops[(size_t)c] = (int)order.size();
+    for (size_t i = 0; i < order.size(); ++i) {
+      const Hc& s = hcs[(size_t)order[i]];
+      PaOp op;
+      pa_euler1('z', q.twist_degree * s.h + 360.0 * s.c / q.csym, op.m_z);
+      op.shift = s.h * q.rise_pixel;
+      ops.push_back(op);
+    }
+  }
+  if (p->linear) {   // what pabl_ray / pabl_at drop from pa_coords must be exactly what it says
+    bool ok = true;
+    for (const PaGeom& g : geoms) {
+      const double id[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+      for (int t = 0; t < 9; ++t) ok = ok && g.m_yx[t] == id[t];
+    }
+    for (const PaOp& op : ops) ok = ok && op.m_z[2] == 0 && op.m_z[5] == 0 && op.m_z[6] == 0 && op.m_z[7] == 0;
+    if (!ok) return pab_fail(p, HH_ERR_STATE, "hh_pab_create: the rotations are not of the form the trilinear ray arithmetic assumes (internal)");
+  }
+  if (int rc = pab_upload(p, p->d_geom, geoms)) return rc;
+  if (int rc = pab_upload(p, p->d_ops, ops)) return rc;
+  if (int rc = pab_upload(p, p->d_op0, op0)) return rc;
+  b.gr = PabGeomRef{p->d_geom, p->d_ops, p->d_op0};
+  return HH_OK;
+}
+
+// The first pass of both row enumerations: which rays exist, operation chunk by chunk, until every candidate has passed
+// its row target (solver:1647).  Per chunk: the live candidates' codes (k_pab_has / k_pabl_has), read_back(live) brings
+// what the host looks at, and per_op(slot, candidate, operation of the chunk, lo) takes one operation in and returns the
+// candidate's rows so far.
+template <class ReadBack, class PerOp>
+int pab_rows_first_pass(hh_pab* p, PabBuild& b, int* d_cand, const int* d_nops, unsigned char* d_has, ReadBack read_back, PerOp per_op) {
+  const int count = b.count, chunk = b.chunk;
+  const size_t rays = b.rays();
+  std::vector<int> live((size_t)count);
+  for (int c = 0; c < count; ++c) live[(size_t)c] = c;
+  for (int lo = 0; !live.empty(); lo += chunk) {
+    if (int rc = pab_to_device(p, d_cand, live.data(), live.size() * sizeof(int))) return rc;
+    hipLaunchKernelGGL(p->linear ? k_pabl_has : k_pab_has, dim3((unsigned)((rays + 255) / 256), chunk, (unsigned)live.size()), dim3(256), 0, p->stream,
+                       b.gr, d_cand, lo, chunk, d_nops, p->d_rank, d_has);
+    if (int rc = read_back(live.size())) return rc;
+    std::vector<int> next;
+    for (size_t sl = 0; sl < live.size(); ++sl) {
+      const int c = live[sl];
+      bool done = false;
+      for (int o = 0; o < chunk && lo + o < b.n_ops[(size_t)c] && !done; ++o) {
+        const int64_t rows = per_op(sl, c, o, lo);
+        p->n_ops_used[(size_t)c] = lo + o + 1;
+        if (b.qs[c].min_projection_lines > 0 && rows > b.qs[c].min_projection_lines) done = true;
+      }
+      if (!done && lo + chunk < b.n_ops[(size_t)c]) next.push_back(c);
+    }
+    live.swap(next);
+  }
+  return HH_OK;
+}
+
+// Row enumeration on the device: per chunk of operations the codes are counted per slice, the host decides from the
+// counts alone which operations each candidate uses, and a second sweep over the used chunks writes the rows where they
+// belong — no per-ray data crosses PCIe.  Leaves d_b_int for pab_build_tables.
+int pab_build_rows_device(hh_pab* p, PabBuild& b) {
+  const int count = b.count, chunk = b.chunk, ny = b.ny, nx = b.nx, l2 = b.l2, d2 = b.d2;
+  const size_t rays = b.rays();
+  const int mz1 = p->mz + 1;
+  DevArena tmp;
+  int* d_cand = tmp.get<int>((size_t)count);
+  int* d_nops = tmp.get<int>((size_t)count);
+  unsigned char* d_has = tmp.get<unsigned char>((size_t)count * chunk * rays);
+  int* d_counts = tmp.get<int>((size_t)count * chunk * mz1);
+  int* d_bmax = tmp.get<int>((size_t)count);
+  float* d_image = tmp.get<float>((size_t)ny * nx);
+  long long* d_bref_t = tmp.get<long long>((size_t)count * chunk);
+  long long* d_bint_t = tmp.get<long long>((size_t)count * chunk * mz1);
+  long long* d_row0_t = tmp.get<long long>((size_t)count);
+  if (int rc = pab_arena_ok(p, tmp)) return rc;
+  if (int rc = pab_to_device(p, d_nops, b.n_ops.data(), b.n_ops.size() * sizeof(int))) return rc;
+  if (int rc = pab_to_device(p, d_image, b.image, (size_t)ny * nx * sizeof(float))) return rc;
+  // pass 1: counts per (candidate, operation, slice)
+  std::vector<std::vector<int>> cnt3((size_t)count);   // [operation][mz + 1], the operations used
+  std::vector<int64_t> rows_so_far((size_t)count, 0);
+  std::vector<int> counts_h;
+  const int rc1 = pab_rows_first_pass(
+      p, b, d_cand, d_nops, d_has,
+      [&](size_t nl) {
+        hipLaunchKernelGGL(k_pab_count_codes, dim3(chunk, (unsigned)nl), dim3(256), (size_t)mz1 * sizeof(int), p->stream, d_has, rays, chunk, p->mz,
+                           d_counts);
+        counts_h.resize(nl * chunk * mz1);
+        return pab_to_host(p, counts_h.data(), d_counts, counts_h.size() * sizeof(int));
+      },
+      [&](size_t sl, int c, int o, int) {
+        const int* cz = counts_h.data() + (sl * chunk + o) * mz1;
+        int64_t tot = 0;
+        for (int z = 0; z < mz1; ++z) tot += cz[z];
+        if (cz[p->mz] > 0) p->sliced = 0;   // a ray in two slices: the whole batch takes the general products
+        cnt3[(size_t)c].insert(cnt3[(size_t)c].end(), cz, cz + mz1);
+        return rows_so_far[(size_t)c] += tot;
+      });
+  if (rc1) return rc1;
+  // the row tables' geometry: first row of every candidate, of every slice (device order), of every operation
+  int max_used = 0;
+  b.srow_h.assign((size_t)count * mz1, 0);
+  for (int c = 0; c < count; ++c) {
+    if (rows_so_far[(size_t)c] == 0) return pab_fail(p, HH_ERR_ARG, "hh_pab_create: no projection ray of a candidate meets the cylinder");
+    PabState& st = p->st[(size_t)c];
+    st.m_data = rows_so_far[(size_t)c];
+    st.row0 = p->total_rows;
+    p->total_rows += st.m_data;
+    max_used = std::max(max_used, p->n_ops_used[(size_t)c]);
+    if (p->sliced) {
+      int* sr = b.srow_h.data() + (size_t)c * mz1;
+      for (int o = 0; o < p->n_ops_used[(size_t)c]; ++o)
+        for (int z = 0; z < p->mz; ++z) sr[z + 1] += cnt3[(size_t)c][(size_t)o * mz1 + z];
+      for (int z = 0; z < p->mz; ++z) sr[z + 1] += sr[z];
+    }
+  }
+  const size_t rows1 = std::max<size_t>((size_t)p->total_rows, 1);
+  if (!p->d_ray_of_row.ensure(rows1) || !b.d_b_int.ensure(rows1) || !p->d_bref.ensure(rows1) || !p->d_pidref.ensure(rows1))
+    return pab_fail(p, HH_ERR_NOMEM, "hh_pab_create: " + dev_alloc_failed(rows1 * 4));
+  if (hipError_t e2 = hipMemsetAsync(d_bmax, 0x80, (size_t)count * sizeof(int), p->stream))   // very negative ordered keys
+    return pab_fail(p, HH_ERR_HIP, std::string("hh_pab_create: ") + hipGetErrorString(e2));
+  p->device_bytes += (size_t)p->total_rows * 16;
+  // pass 2: the rows themselves, chunk by chunk over the operations that are used
+  std::vector<long long> bref_h, bint_h, row0_h;
+  std::vector<int> live;
+  for (int lo = 0; lo < max_used; lo += chunk) {
+    live.clear();
+    for (int c = 0; c < count; ++c)
+      if (p->n_ops_used[(size_t)c] > lo) live.push_back(c);
+    const size_t nl = live.size();
+    bref_h.assign(nl * chunk, -1);
+    bint_h.assign(nl * chunk * mz1, 0);
+    row0_h.resize(nl);
+    for (size_t sl = 0; sl < nl; ++sl) {
+      const int c = live[sl];
+      row0_h[sl] = p->st[(size_t)c].row0;
+      pab_row_offsets(cnt3[(size_t)c].data(), p->n_ops_used[(size_t)c], p->mz, p->sliced != 0, b.srow_h.data() + (size_t)c * mz1, lo, chunk,
+                      bref_h.data() + sl * chunk, bint_h.data() + sl * chunk * mz1);
+    }
+    if (int rc = pab_to_device(p, d_cand, live.data(), nl * sizeof(int))) return rc;
+    if (int rc = pab_to_device(p, d_bref_t, bref_h.data(), bref_h.size() * sizeof(long long))) return rc;
+    if (int rc = pab_to_device(p, d_bint_t, bint_h.data(), bint_h.size() * sizeof(long long))) return rc;
+    if (int rc = pab_to_device(p, d_row0_t, row0_h.data(), nl * sizeof(long long))) return rc;
+    hipLaunchKernelGGL(p->linear ? k_pabl_has : k_pab_has, dim3((unsigned)((rays + 255) / 256), chunk, (unsigned)nl), dim3(256), 0, p->stream, b.gr,
+                       d_cand, lo, chunk, d_nops, p->d_rank, d_has);
+    const PabEmit em{d_has, d_image, d_bref_t, d_bint_t, d_row0_t, d_cand, p->d_ray_of_row, b.d_b_int, p->d_bref, p->d_pidref, d_bmax,
+                     chunk, lo, p->mz, l2, d2, ny, nx};
+    hipLaunchKernelGGL(k_pab_emit, dim3(chunk, (unsigned)nl), dim3(1024), 0, p->stream, em);
+  }
+  std::vector<int> bm((size_t)count);
+  if (int rc = pab_to_host(p, bm.data(), d_bmax, bm.size() * sizeof(int))) return rc;
+  for (int c = 0; c < count; ++c) {
+    const int key = bm[(size_t)c], bits = key >= 0 ? key : key ^ 0x7fffffff;
+    float f;
+    std::memcpy(&f, &bits, sizeof(f));
+    p->st[(size_t)c].bmax = (double)f;
+  }
+  return HH_OK;
+}
+
+// Row enumeration on the host (half sets, whose pixel-id rules are host code, and HH_PAB_HOST_ROWS: the A/B reference of
+// the tests): the per-ray codes come back and the rows are listed here; then the half sets (split_A_b, solver:175-203)
+int pab_build_rows_host(hh_pab* p, PabBuild& b) {
+  const int count = b.count, chunk = b.chunk, ny = b.ny, nx = b.nx, l2 = b.l2, d2 = b.d2;
+  const size_t rays = b.rays();
+  b.ray_of_row.assign((size_t)count, {});
+  b.b_of.assign((size_t)count, {});
+  b.pid_of.assign((size_t)count, {});
+  b.z_of.assign((size_t)count, {});
+  {
+    std::vector<unsigned char> has;
+    DevArena tmp;
+    int* d_cand = tmp.get<int>((size_t)count);
+    int* d_nops = tmp.get<int>((size_t)count);
+    unsigned char* d_has = tmp.get<unsigned char>((size_t)count * chunk * rays);
+    if (int rc = pab_arena_ok(p, tmp)) return rc;
+    if (int rc = pab_to_device(p, d_nops, b.n_ops.data(), b.n_ops.size() * sizeof(int))) return rc;
+    const int rc1 = pab_rows_first_pass(
+        p, b, d_cand, d_nops, d_has,
+        [&](size_t nl) {
+          has.resize(nl * chunk * rays);
+          return pab_to_host(p, has.data(), d_has, has.size());
+        },
+        [&](size_t sl, int c, int o, int lo) {
+          const unsigned char* h = has.data() + (sl * chunk + o) * rays;
+          // rows of this operation, in (k, j) order; b = pixel_vals[j, k], pid = k * ny + j (solver:1548-1549)
+          for (int k = 0; k < l2; ++k)
+            for (int j = 0; j < d2; ++j)
+              if (h[(size_t)k * d2 + j]) {
+                const unsigned char code = h[(size_t)k * d2 + j];
+                if (code == 255) p->sliced = 0;   // a ray in two slices: the whole batch takes the general products
+                b.z_of[(size_t)c].push_back((short)(code - 1));
+                b.ray_of_row[(size_t)c].push_back((int)(((size_t)(lo + o) * l2 + k) * d2 + j));
+                b.b_of[(size_t)c].push_back(b.image[(size_t)(j - d2 / 2 + ny / 2) * nx + (k - l2 / 2 + nx / 2)]);
+                b.pid_of[(size_t)c].push_back(k * d2 + j);
+              }
+          return (int64_t)b.ray_of_row[(size_t)c].size();
+        });
+    if (rc1) return rc1;
+  }
+  b.lap(p, "rays that exist");
+  for (int c = 0; c < count; ++c) {
+    const hh_pa_params& q = b.qs[c];
+    std::vector<int>& rr = b.ray_of_row[(size_t)c];
+    std::vector<float>& bb = b.b_of[(size_t)c];
+    std::vector<int32_t>& pp = b.pid_of[(size_t)c];
+    std::vector<short>& zz = b.z_of[(size_t)c];
+    if (q.fsc_half > 0) {
+      const std::vector<size_t> keep = pab_half_rows(pp, q.fsc_mode, q.fsc_half, q.fsc_ids, q.n_fsc_ids);
+      for (size_t wr = 0; wr < keep.size(); ++wr) {
+        const size_t r = keep[wr];
+        rr[wr] = rr[r]; bb[wr] = bb[r]; pp[wr] = pp[r]; zz[wr] = zz[r];
+      }
+      rr.resize(keep.size()); bb.resize(keep.size()); pp.resize(keep.size()); zz.resize(keep.size());
+    }
+    if (rr.empty()) return pab_fail(p, HH_ERR_ARG, "hh_pab_create: no projection ray of a candidate meets the cylinder");
+    PabState& s = p->st[(size_t)c];
+    s.m_data = (int64_t)rr.size();
+    s.row0 = p->total_rows;
+    p->total_rows += s.m_data;
+    s.bmax = (double)*std::max_element(bb.begin(), bb.end());
+  }
+  return HH_OK;
+}
+
+// the data rows: on the device unless a candidate is a half set or HH_PAB_HOST_ROWS asks for the host path
+int pab_build_rows(hh_pab* p, PabBuild& b) {
+  p->n_ops_used.assign((size_t)b.count, 0);
+  p->st.assign((size_t)b.count, PabState{});
+  b.dev_rows = std::getenv("HH_PAB_HOST_ROWS") == nullptr;
+  for (int c = 0; c < b.count; ++c) b.dev_rows = b.dev_rows && b.qs[c].fsc_half == 0;
+  if (!b.dev_rows) return pab_build_rows_host(p, b);
+  if (int rc = pab_build_rows_device(p, b)) return rc;
+  b.lap(p, "rays and rows (device)");
+  return HH_OK;
+}
+
+// symmetry rows on host threads through the single-candidate builder, one candidate per thread (HH_PAB_HOST_SYM: the A/B
+// reference of the tests; trilinear: the 16-entry rows of solver:910-1140).  Leaves rows16_of for pab_build_tables.
+int pab_build_sym_host(hh_pab* p, PabBuild& b) {
+  const int count = b.count;
+  const unsigned hw = std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
+  const unsigned nt = std::min<unsigned>(hw, (unsigned)count);
+  std::atomic<int> next{0};
+  std::atomic<bool> threw{false};
+  auto work = [&] {   // (a thread's body must not let an exception out: that is std::terminate whatever the caller guards)
+    try {
+      for (int c = next.fetch_add(1); c < count; c = next.fetch_add(1)) {
+        const hh_pa_params& q = b.qs[c];
+        if (q.min_sym_pairs > 0)
+          pa_sym_pairs(b.l3, b.d3, b.d3, q.twist_degree, q.rise_pixel, q.csym, b.rmin, b.rmax, q.min_sym_pairs, b.pairs_of[(size_t)c],
+                       p->linear ? &b.rows16_of[(size_t)c] : nullptr);
+      }
+    } catch (...) {
+      threw = true;
+    }
+  };
+  {
+    std::vector<std::thread> pool;
+    struct Join { std::vector<std::thread>& p; ~Join() { for (auto& t : p) if (t.joinable()) t.join(); } } join{pool};
+    for (unsigned t = 1; t < nt; ++t) pool.emplace_back(work);
+    work();
+  }
+  if (threw) return pab_fail(p, HH_ERR_NOMEM, "hh_pab_create: out of host memory while building the symmetry pairs");
+  for (int c = 0; c < count; ++c) {
+    PabState& s = p->st[(size_t)c];
+    s.m_sym = (int64_t)(p->linear ? b.rows16_of[(size_t)c].size() : b.pairs_of[(size_t)c].size());
+    s.sym0 = p->total_sym;
+    p->total_sym += s.m_sym;
+  }
+  return HH_OK;
+}
+
+// symmetry pairs on the device (k_pab_sym): the walk of every candidate in chunks of operations, until it has its pairs
+int pab_build_sym_device(hh_pab* p, PabBuild& b) {
+  const int count = b.count, l3 = b.l3, d3 = b.d3;
+  const hh_pa_params* qs = b.qs;
+  int64_t want = 0;
+  for (int c = 0; c < count; ++c) want = std::max<int64_t>(want, qs[c].min_sym_pairs);
+  const int64_t cap = want > 0 ? want + p->n : 0;   // rows of a candidate: < min_sym_pairs before its last pair, which adds <= n
+  for (int c = 0; c < count; ++c) p->st[(size_t)c].sym0 = (int64_t)c * cap;
+  if (int rc = pab_alloc(p, p->d_pairs, (size_t)count * cap)) return rc;
+  if (cap <= 0) return HH_OK;
+  const int sym_chunk = 4;
+  const int64_t nbox = (int64_t)l3 * d3 * d3;
+  int* d_rank_sym = p->d_rank;
+  DevArena tmp;
+  int rc_rank = HH_OK;
+  if (d3 != b.d2) {   // the symmetry box has its own rank table (same cylinder, same ranks, other box)
+    std::vector<int> rank3;
+    const int64_t n3 = pa_mask_rank(l3, d3, d3, b.rmin, b.rmax, rank3);
+    if (n3 != p->n) return pab_fail(p, HH_ERR_ARG, "hh_pab_create: the cylinder does not fit the 2-D region's box");
+    d_rank_sym = tmp.get<int>(rank3.size());
+    if (tmp.ok()) rc_rank = pab_to_device(p, d_rank_sym, rank3.data(), rank3.size() * sizeof(int));
+  }
+  unsigned T = 1;
+  while ((int64_t)T < 2 * (want + (int64_t)sym_chunk * p->n)) T <<= 1;
+  unsigned long long* d_keys = tmp.get<unsigned long long>((size_t)count * T);
+  unsigned long long* d_tmin = tmp.get<unsigned long long>((size_t)count * T);
+  PaSymOp* d_sops = tmp.get<PaSymOp>((size_t)count * sym_chunk);
+  int* d_cand = tmp.get<int>((size_t)count);
+  int* d_nvalid = tmp.get<int>((size_t)count);
+  int* d_counts = tmp.get<int>((size_t)count * sym_chunk);
+  long long* d_base = tmp.get<long long>((size_t)count * sym_chunk);
+  unsigned char* d_flags8 = tmp.get<unsigned char>((size_t)count * sym_chunk * nbox);
+  int* d_err = tmp.get<int>(1);
+  if (rc_rank) return rc_rank;
+  if (int rc = pab_arena_ok(p, tmp)) return rc;
+  hipError_t e = hipMemsetAsync(d_keys, 0xff, (size_t)count * T * 8, p->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(d_tmin, 0xff, (size_t)count * T * 8, p->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(d_err, 0, sizeof(int), p->stream);
+  if (e != hipSuccess) return pab_fail(p, HH_ERR_HIP, std::string("hh_pab_create (symmetry pairs): ") + hipGetErrorString(e));
+  // the walk of every candidate (cheap: a few rotations per pair of operations)
+  std::vector<std::vector<PaSymOp>> walk((size_t)count);
+  std::vector<int> live;
+  for (int c = 0; c < count; ++c)
+    if (qs[c].min_sym_pairs > 0) {
+      walk[(size_t)c] = pa_sym_ops(l3, qs[c].twist_degree, qs[c].rise_pixel, qs[c].csym);
+      if (!walk[(size_t)c].empty()) live.push_back(c);
+    }
+  std::vector<int64_t> kept((size_t)count, 0);
+  std::vector<PaSymOp> ops_h;
+  std::vector<int> nvalid_h, counts_h;
+  std::vector<long long> base_h;
+  for (int p0 = 0; !live.empty(); p0 += sym_chunk) {
+    const size_t nl = live.size();
+    ops_h.assign(nl * sym_chunk, PaSymOp{});
+    nvalid_h.assign(nl, 0);
+    for (size_t sl = 0; sl < nl; ++sl) {
+      const std::vector<PaSymOp>& wk = walk[(size_t)live[sl]];
+      nvalid_h[sl] = (int)std::min<size_t>(sym_chunk, wk.size() - (size_t)p0);
+      for (int k = 0; k < nvalid_h[sl]; ++k) ops_h[sl * sym_chunk + k] = wk[(size_t)p0 + k];
+    }
+    if (int rc = pab_to_device(p, d_sops, ops_h.data(), ops_h.size() * sizeof(PaSymOp))) return rc;
+    if (int rc = pab_to_device(p, d_cand, live.data(), nl * sizeof(int))) return rc;
+    if (int rc = pab_to_device(p, d_nvalid, nvalid_h.data(), nl * sizeof(int))) return rc;
+    (void)hipMemsetAsync(d_counts, 0, nl * sym_chunk * sizeof(int), p->stream);
+    PabSymRef sr{d_sops, d_cand, d_nvalid, sym_chunk, p0, l3, d3, d3, d_rank_sym, d_keys, d_tmin, T, d_err};
+    const dim3 grid((unsigned)((nbox + 255) / 256), sym_chunk, (unsigned)nl);
+    hipLaunchKernelGGL(k_pab_sym<1>, grid, dim3(256), 0, p->stream, sr, (unsigned char*)nullptr, (int*)nullptr);
+    hipLaunchKernelGGL(k_pab_sym<2>, grid, dim3(256), 0, p->stream, sr, d_flags8, d_counts);
+    counts_h.resize(nl * sym_chunk);
+    if (int rc = pab_to_host(p, counts_h.data(), d_counts, counts_h.size() * sizeof(int))) return rc;
+    base_h.assign(nl * sym_chunk, -1);
+    std::vector<int> next;
+    for (size_t sl = 0; sl < nl; ++sl) {
+      const int c = live[sl];
+      bool done = false;
+      for (int k = 0; k < nvalid_h[sl] && !done; ++k) {   // row_count += added; if row_count >= min_pairs: break (solver:1275)
+        base_h[sl * sym_chunk + k] = (long long)(p->st[(size_t)c].sym0 + kept[(size_t)c]);
+        kept[(size_t)c] += counts_h[sl * sym_chunk + k];
+        if (kept[(size_t)c] >= qs[c].min_sym_pairs) done = true;
+      }
+      if (!done && (size_t)(p0 + sym_chunk) < walk[(size_t)c].size()) next.push_back(c);
+    }
+    if (int rc = pab_to_device(p, d_base, base_h.data(), base_h.size() * sizeof(long long))) return rc;
+    hipLaunchKernelGGL(k_pab_sym_emit, dim3(sym_chunk, (unsigned)nl), dim3(1024), 0, p->stream, sr, d_flags8, d_base, p->d_pairs);
+    live.swap(next);
+  }
+  int err_h = 0;
+  if (int rc = pab_to_host(p, &err_h, d_err, sizeof(int))) return rc;
+  if (err_h) return pab_fail(p, HH_ERR_STATE, "hh_pab_create: symmetry-pair table full (internal)");
+  for (int c = 0; c < count; ++c) {
+    p->st[(size_t)c].m_sym = kept[(size_t)c];
+    p->total_sym += kept[(size_t)c];
+    if (kept[(size_t)c] > cap) return pab_fail(p, HH_ERR_STATE, "hh_pab_create: more symmetry rows than planned (internal)");
+  }
+  return HH_OK;
+}
+
+// symmetry constraints (box (L3d, D3d, D3d) of lsq_reconstruct, solver:116-173): on the device, or with HH_PAB_HOST_SYM
+// (and for the trilinear rows) on host threads
+int pab_build_sym(hh_pab* p, PabBuild& b) {
+  if (p->linear && !p->sliced)
+    return pab_fail(p, HH_ERR_ARG, "hh_pab_create: not sliceable — a ray's samples lie in more than one cell layer (the single-candidate hh_pa has the general form)");
+  b.pairs_of.assign((size_t)b.count, {});
+  b.rows16_of.assign((size_t)(p->linear ? b.count : 0), {});
+  b.dev_sym = std::getenv("HH_PAB_HOST_SYM") == nullptr && !p->linear;
+  if (int rc = b.dev_sym ? pab_build_sym_device(p, b) : pab_build_sym_host(p, b)) return rc;
+  b.lap(p, b.dev_sym ? "symmetry pairs (device)" : "symmetry pairs (host)");
+  return HH_OK;
+}
+
+// the launch shapes: padded sizes and grid.x of every kind of launch
+int pab_build_shapes(hh_pab* p, PabBuild&) {
+  int64_t m_max = 0, md_max = 0, ms_max = 0;
+  for (const PabState& s : p->st) {
+    m_max = std::max(m_max, s.m_data + s.m_sym);
+    md_max = std::max(md_max, s.m_data * PAB_LANES + s.m_sym);
+    ms_max = std::max(ms_max, s.m_sym);
+  }
+  p->N = (p->n + 63) / 64 * 64;
+  p->M = (m_max + 63) / 64 * 64;
+  p->MA = p->M + p->N;
+  // (element-wise kernels: PAB_VEC_ELEMS elements per thread, for the same reason as PABS_TAIL_ROWS)
+  p->nb_n = (int)((p->n + 256 * PAB_VEC_ELEMS - 1) / (256 * PAB_VEC_ELEMS));
+  p->nb_m = (int)((m_max + p->n + 256 * PAB_VEC_ELEMS - 1) / (256 * PAB_VEC_ELEMS));
+  if (p->sliced) {   // one workgroup per slice, then 256 symmetry (/ augmented) rows per workgroup
+    // (symmetry / augmented rows: PABS_TAIL_ROWS per thread — a workgroup's fixed costs (control word, state, reductions)
+    // are a few microseconds whatever it does, and with one row per thread these workgroups took twice the slice
+    // workgroups' share of the device)
+    p->nb_mv = p->mz + (int)((ms_max + PABS_THREADS * PABS_TAIL_ROWS - 1) / (PABS_THREADS * PABS_TAIL_ROWS));
+    p->nb_mva = p->mz + (int)((ms_max + p->n + PABS_THREADS * PABS_TAIL_ROWS - 1) / (PABS_THREADS * PABS_TAIL_ROWS));
+  } else {
+    p->nb_mv = (int)((md_max + 255) / 256);
+    p->nb_mva = (int)((md_max + p->n + 255) / 256);
+  }
+  p->nb_fin = (int)((p->n + 256 * PABL_FIN_ELEMS - 1) / (256 * PABL_FIN_ELEMS));
+  p->RB = std::max(std::max(std::max(p->nb_n, p->nb_m), p->nb_mva), p->nb_fin);
+  if (p->linear)   // (the separable form's symmetry rows are 512 per block: k_pabf_tail)
+    p->RB = std::max(p->RB, 16 * p->mz + (int)((ms_max + p->n + 256 * PABF_TAIL_ROWS - 1) / (256 * PABF_TAIL_ROWS)));
+  return HH_OK;
+}
+
+// Row tables, resident buffers, right-hand sides.  The device keeps the rows slice-major on the sliced path ((z,
+// operation, k, j): a stable sort of the reference's (operation, k, j) order by slice); b and the pixel ids handed back
+// to the caller stay in the reference's.  Frees rows16_of and d_b_int.
+int pab_build_tables(hh_pab* p, PabBuild& b) {
+  const int count = b.count, d2 = b.d2;
+  const bool dev_rows = b.dev_rows, dev_sym = b.dev_sym;
+  std::vector<int> all_rows(dev_rows ? 0 : (size_t)p->total_rows);
+  std::vector<float> all_b(dev_rows ? 0 : (size_t)p->total_rows);
+  std::vector<int> srow((size_t)count * (p->mz + 1), 0);
+  if (dev_rows) srow = b.srow_h;
+  if (!dev_rows) {
+    p->b_data.resize((size_t)p->total_rows);
+    p->b_pid.resize((size_t)p->total_rows);
+  }
+  std::vector<int2> all_pairs(dev_sym || p->linear ? 0 : (size_t)p->total_sym);
+  std::vector<int> order;
+  for (int c = 0; c < count; ++c) {
+    const PabState& s = p->st[(size_t)c];
+    if (!dev_sym && !p->linear) std::copy(b.pairs_of[(size_t)c].begin(), b.pairs_of[(size_t)c].end(), all_pairs.begin() + s.sym0);
+    if (dev_rows) continue;
+    const std::vector<int>& rr = b.ray_of_row[(size_t)c];
+    const std::vector<float>& bb = b.b_of[(size_t)c];
+    std::copy(bb.begin(), bb.end(), p->b_data.begin() + s.row0);
+    std::copy(b.pid_of[(size_t)c].begin(), b.pid_of[(size_t)c].end(), p->b_pid.begin() + s.row0);
+    if (!p->sliced) {
+      std::copy(rr.begin(), rr.end(), all_rows.begin() + s.row0);
+      std::copy(bb.begin(), bb.end(), all_b.begin() + s.row0);
+      continue;
+    }
+    if (!pab_slice_order(b.z_of[(size_t)c], p->mz, srow.data() + (size_t)c * (p->mz + 1), order))
+      return pab_fail(p, HH_ERR_STATE, "hh_pab_create: a row without a slice (internal)");
+    for (size_t k = 0; k < rr.size(); ++k) {
+      all_rows[(size_t)s.row0 + k] = rr[(size_t)order[k]];
+      all_b[(size_t)s.row0 + k] = bb[(size_t)order[k]];
+    }
+  }
+  if (!dev_rows)
+    if (int rc = pab_upload(p, p->d_ray_of_row, all_rows)) return rc;
+  if (p->linear) {
+    if (int rc = pab_alloc(p, p->d_sym16, (size_t)p->total_sym)) return rc;
+    for (int c = 0; c < count; ++c)   // candidate by candidate through the staging buffer (7.5 MB each at the bench size)
+      if (int rc = pab_to_device(p, p->d_sym16 + p->st[(size_t)c].sym0, b.rows16_of[(size_t)c].data(), b.rows16_of[(size_t)c].size() * sizeof(PaEll16)))
+        return rc;
+    std::vector<std::vector<PaEll16>>().swap(b.rows16_of);   // the end of rows16_of: before the resident buffers below
+  } else if (!dev_sym) {
+    if (int rc = pab_upload(p, p->d_pairs, all_pairs)) return rc;
+  }
+  if (int rc = pab_upload(p, p->d_srow, srow)) return rc;
+  if (p->linear) {   // no map at all: the disc's table and the accumulator of A^T y
+    std::vector<unsigned> sidx2((size_t)d2 * d2);
+    for (int yy = 0; yy < d2; ++yy)
+      for (int xx = 0; xx < d2; ++xx) {
+        const int a = b.rank[(size_t)yy * d2 + xx], a1 = xx + 1 < d2 ? b.rank[(size_t)yy * d2 + xx + 1] : -1;   // plane 0: rank = index inside the plane
+        sidx2[(size_t)yy * d2 + xx] = (unsigned)(a < 0 ? 0xffff : a) | ((unsigned)(a1 < 0 ? 0xffff : a1) << 16);
+      }
+    if (int rc = pab_upload(p, p->d_sidx2, sidx2)) return rc;
+    if (int rc = pab_alloc(p, p->d_acc64, (size_t)count * ((p->n + 63) / 64 * 64))) return rc;
+    PAB_HIP(p, hipMemsetAsync(p->d_acc64, 0, (size_t)count * ((p->n + 63) / 64 * 64) * sizeof(long long), p->stream));
+  } else if (p->sliced) {
+    if (int rc = pab_alloc(p, p->d_map16, (size_t)p->total_rows * p->d2p)) return rc;
+    PAB_HIP(p, hipMemsetAsync(p->d_map16, 0xff, (size_t)p->total_rows * p->d2p * sizeof(uint16_t), p->stream));
+  } else {
+    if (int rc = pab_alloc(p, p->d_map, (size_t)p->total_rows * d2)) return rc;
+  }
+  if (int rc = pab_alloc(p, p->d_st, (size_t)count)) return rc;
+  if (int rc = pab_alloc(p, p->d_ctl, (size_t)count)) return rc;
+  PAB_HIP(p, hipMemsetAsync(p->d_ctl, 0, (size_t)count * sizeof(unsigned), p->stream));
+  if (int rc = pab_alloc(p, p->d_tptr, (size_t)count * (p->n + 1))) return rc;
+  if (int rc = pab_alloc(p, p->d_nv, (size_t)NV_COUNT * count * p->N)) return rc;
+  if (int rc = pab_alloc(p, p->d_mv, (size_t)MV_COUNT * count * p->MA)) return rc;
+  if (int rc = pab_alloc(p, p->d_red, (size_t)count * PAB_SLOTS * p->RB)) return rc;
+  if (int rc = pab_alloc(p, p->d_xf, (size_t)count * p->N)) return rc;   // rows padded to N floats: whole cache lines per candidate
+  if (int rc = pab_alloc(p, p->d_flags, PAB_FLAG_WORDS)) return rc;
+  if (int rc = pab_alloc(p, p->d_lists, (size_t)2 * count)) return rc;
+  PAB_HIP(p, hipMemsetAsync(p->d_nv, 0, (size_t)NV_COUNT * count * p->N * sizeof(double), p->stream));
+  PAB_HIP(p, hipMemsetAsync(p->d_mv, 0, (size_t)MV_COUNT * count * p->MA * sizeof(double), p->stream));
+  PAB_HIP(p, hipMemsetAsync(p->d_tptr, 0, (size_t)count * (p->n + 1) * sizeof(int), p->stream));
+  PAB_HIP(p, hipMemsetAsync(p->d_flags, 0, PAB_FLAG_WORDS * sizeof(int), p->stream));
+  if (int rc = pab_to_device(p, p->d_st, p->st.data(), p->st.size() * sizeof(PabState))) return rc;
+  // right-hand sides: b of the data rows (float32 pixel values -> float64), zeros for the symmetry rows (the memset above)
+  if (!dev_rows) {   // the host path's b takes the place the device path filled
+    if (!b.d_b_int.ensure(all_b.size())) return pab_fail(p, HH_ERR_NOMEM, "hh_pab_create: " + dev_alloc_failed(all_b.size() * sizeof(float)));
+    if (int rc = pab_to_device(p, b.d_b_int, all_b.data(), all_b.size() * sizeof(float))) return rc;
+  }
+  const float* bf = b.d_b_int;
+  pab_vec<0>(p, CNT_MDATA, PabRed<0>{}, [] __device__(const auto&) { return true; },
+             [bf] __device__(const PabView& w, int c, int64_t i, const PabState& s, double*) {
+               w.mvec(MV_B, c)[i] = (double)bf[s.row0 + i];
+             });
+  const hipError_t e = hipStreamSynchronize(p->stream);
+  b.d_b_int.reset();   // the end of d_b_int: MV_B is filled
+  if (e != hipSuccess) return pab_fail(p, HH_ERR_HIP, "hh_pab_create: right-hand sides failed");
+  b.lap(p, "row tables, buffers");
+  return HH_OK;
+}
+
+// the compact index map (nearest neighbour), and on the sliced path the shared map rows (k_pab_share_rows)
+int pab_build_map(hh_pab* p, PabBuild& b) {
+  const int count = b.count, d2 = b.d2, l2 = b.l2;
+  if (!p->linear) {
+    int64_t md = 0;
+    for (const PabState& s : p->st) md = std::max(md, s.m_data);
+    hipLaunchKernelGGL(k_pab_fill_map, pab_grid((int)((md * d2 + 255) / 256), count), dim3(256), 0, p->stream, b.gr, p->d_st, p->d_ray_of_row,
+                       p->d_rank, p->d_map, p->d_map16, p->d_srow, p->nslice, p->d2p, p->d_flags + 9, count);
+    PAB_HIP(p, hipGetLastError());
+    if (p->sliced) {
+      int f[PAB_FLAG_WORDS];
+      if (int rc = pab_poll(p, f)) return rc;
+      if (f[9]) return pab_fail(p, HH_ERR_STATE, "hh_pab_create: a ray left its slice (internal)");
+      // rows of one (operation, image row) read one copy of their map (k_pab_share_rows)
+      if (int rc = pab_alloc(p, p->d_maprow, (size_t)std::max<int64_t>(p->total_rows, 1))) return rc;
+      int max_ops_used = 0;
+      for (int c = 0; c < count; ++c) max_ops_used = std::max(max_ops_used, p->n_ops_used[(size_t)c]);
+      const size_t keys = (size_t)count * std::max(max_ops_used, 1) * d2;
+      {
+        DevArena tmp;
+        int* d_first = tmp.get<int>(keys);
+        int* d_second = tmp.get<int>(keys);
+        if (int rc = pab_arena_ok(p, tmp)) return rc;
+        hipError_t es = hipMemsetAsync(d_first, 0x7f, keys * sizeof(int), p->stream);
+        if (es == hipSuccess) es = hipMemsetAsync(d_second, 0x7f, keys * sizeof(int), p->stream);
+        if (es == hipSuccess) {
+          const dim3 grid = pab_grid((int)((md * 8 + 255) / 256), count);
+          hipLaunchKernelGGL(k_pab_share_rows<0>, grid, dim3(256), 0, p->stream, p->d_st, p->d_ray_of_row, p->d_map16, p->d2p, l2, d2, max_ops_used, d_first, d_second, p->d_maprow, count);
+          hipLaunchKernelGGL(k_pab_share_rows<1>, grid, dim3(256), 0, p->stream, p->d_st, p->d_ray_of_row, p->d_map16, p->d2p, l2, d2, max_ops_used, d_first, d_second, p->d_maprow, count);
+          hipLaunchKernelGGL(k_pab_share_rows<2>, grid, dim3(256), 0, p->stream, p->d_st, p->d_ray_of_row, p->d_map16, p->d2p, l2, d2, max_ops_used, d_first, d_second, p->d_maprow, count);
+          es = hipStreamSynchronize(p->stream);
+        }
+        if (es != hipSuccess) return pab_fail(p, HH_ERR_HIP, std::string("hh_pab_create (shared map rows): ") + hipGetErrorString(es));
+      }
+      if (b.timing) {
+        std::vector<int> mr((size_t)p->total_rows);
+        if (pab_to_host(p, mr.data(), p->d_maprow, mr.size() * sizeof(int)) == HH_OK) {
+          std::vector<int> u(mr);
+          std::sort(u.begin(), u.end());
+          const size_t distinct = (size_t)(std::unique(u.begin(), u.end()) - u.begin());
+          std::fprintf(stderr, "hh_pab_create[%d]: shared map rows: %zu rows read %zu distinct maps (%.1f rows per map)\n", count, mr.size(), distinct,
+                       (double)mr.size() / (double)std::max<size_t>(distinct, 1));
+        }
+      }
+    }
+  }
+  b.lap(p, "index map");
+  return HH_OK;
+}
+
+// the transposed pattern (sliced path: of the symmetry rows only): count, scan, fill, sort
+int pab_build_transposed(hh_pab* p, PabBuild& b) {
+  const int count = b.count, d2 = b.d2;
+  PabView w = pab_view(p);
+  int64_t span = 0;
+  for (const PabState& s : p->st) span = std::max(span, p->linear ? s.m_sym * 16 : (p->sliced ? 0 : s.m_data * d2) + s.m_sym);
+  const dim3 grid = pab_grid((int)std::max<int64_t>(1, (span + 255) / 256), count);
+  DevBuf<int> d_cursor;
+  if (!d_cursor.ensure((size_t)count * (p->n + 1)))
+    return pab_fail(p, HH_ERR_NOMEM, "hh_pab_create: " + dev_alloc_failed(d_cursor.bytes_for((size_t)count * (p->n + 1))));
+  if (p->linear) hipLaunchKernelGGL((k_pabl_transpose<false>), grid, dim3(256), 0, p->stream, w, p->d_tptr, (int2*)nullptr);
+  else if (p->sliced) hipLaunchKernelGGL((k_pab_transpose<false, false>), grid, dim3(256), 0, p->stream, w, p->d_tptr, (int*)nullptr);
+  else hipLaunchKernelGGL((k_pab_transpose<false, true>), grid, dim3(256), 0, p->stream, w, p->d_tptr, (int*)nullptr);
+  hipLaunchKernelGGL(k_pab_scan, dim3(count), dim3(1024), 0, p->stream, p->n, p->d_tptr, d_cursor);
+  // list lengths per candidate -> offsets of the concatenated entry array
+  std::vector<int> last((size_t)count);
+  hipError_t e = pab_stage(p, (size_t)count * sizeof(int)) ? hipErrorOutOfMemory : hipSuccess;
+  // the last entry of every candidate's scan = its number of list entries: one strided copy
+  if (e == hipSuccess)
+    e = hipMemcpy2DAsync(p->h_stage, sizeof(int), p->d_tptr + p->n, (size_t)(p->n + 1) * sizeof(int), sizeof(int), (size_t)count,
+                         hipMemcpyDeviceToHost, p->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(p->stream);
+  if (e != hipSuccess) return pab_fail(p, HH_ERR_HIP, std::string("hh_pab_create: ") + hipGetErrorString(e));
+  std::memcpy(last.data(), p->h_stage, (size_t)count * sizeof(int));
+  p->total_nnz = 0;
+  for (int c = 0; c < count; ++c) {
+    p->st[(size_t)c].t0 = p->total_nnz;
+    p->total_nnz += last[(size_t)c];
+  }
+  if (int rc = p->linear ? pab_alloc(p, p->d_tent2, (size_t)p->total_nnz) : pab_alloc(p, p->d_tent, (size_t)p->total_nnz)) return rc;
+  if (int rc = pab_to_device(p, p->d_st, p->st.data(), p->st.size() * sizeof(PabState))) return rc;
+  w = pab_view(p);
+  // the cursor of voxel v starts at tptr[v] (the scan is inclusive over cnt[v + 1], i.e. exclusive for v)
+  if (p->linear) {
+    hipLaunchKernelGGL((k_pabl_transpose<true>), grid, dim3(256), 0, p->stream, w, d_cursor, p->d_tent2);
+    hipLaunchKernelGGL(k_pabl_sort_lists, pab_grid((int)((p->n + 255) / 256), count), dim3(256), 0, p->stream, w, p->d_tent2);
+  } else {
+    if (p->sliced) hipLaunchKernelGGL((k_pab_transpose<true, false>), grid, dim3(256), 0, p->stream, w, d_cursor, p->d_tent);
+    else hipLaunchKernelGGL((k_pab_transpose<true, true>), grid, dim3(256), 0, p->stream, w, d_cursor, p->d_tent);
+    hipLaunchKernelGGL(k_pab_sort_lists, pab_grid((int)((p->n + 255) / 256), count), dim3(256), 0, p->stream, w, p->d_tent);
+  }
+  e = hipGetLastError();
+  if (e == hipSuccess) e = hipStreamSynchronize(p->stream);
+  if (e != hipSuccess) return pab_fail(p, HH_ERR_HIP, std::string("hh_pab_create: ") + hipGetErrorString(e));
+  b.lap(p, "transposed lists");
+  return HH_OK;
+}
+
+// ---- the separable form of the trilinear data rows (path_a_factored.inc) ----------------------------------------------------
+// per (candidate, operation, image column): axial data, the hash of its samples' cell decisions, its first row and the
+// image rows that have a ray — computed on the device, grouped into footprint lists and column groups on the host
+// (4k entries per candidate), then the lists' samples are written by the device
+int pab_build_separable(hh_pab* p, PabBuild& b) {
+  const int count = b.count, d2 = b.d2, l2 = b.l2;
+  int G = 4;   // (+ 26 KB for the group's list table, sized below)
+  while (G > 1 && (size_t)(G + 1) * p->nslice * sizeof(double) > ((size_t)120 << 10)) --G;
+  const int ng = std::max(1, (p->mz - 1 + G - 1) / G);
+  int max_ops = 0;
+  for (int c = 0; c < count; ++c) max_ops = std::max(max_ops, p->n_ops_used[(size_t)c]);
+  const size_t cells = (size_t)count * max_ops * l2;
+  std::vector<PabfZinfo> zi(cells);
+  std::vector<unsigned long long> hash(cells), jm(cells * 2);
+  std::vector<int> rb(cells);
+  {
+    DevArena tmp;
+    PabfZinfo* d_zi = tmp.get<PabfZinfo>(cells);
+    unsigned long long* d_hash = tmp.get<unsigned long long>(cells);
+    unsigned long long* d_jm = tmp.get<unsigned long long>(cells * 2);
+    int* d_rb = tmp.get<int>(cells);
+    int* d_nused = tmp.get<int>((size_t)count);
+    if (int rc = pab_arena_ok(p, tmp)) return rc;
+    hipError_t e = hipMemsetAsync(d_hash, 0, cells * 8, p->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(d_jm, 0, cells * 16, p->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(d_rb, 0x7f, cells * 4, p->stream);
+    if (e != hipSuccess) return pab_fail(p, HH_ERR_HIP, std::string("hh_pab_create (footprint lists): ") + hipGetErrorString(e));
+    if (int rc = pab_to_device(p, d_nused, p->n_ops_used.data(), (size_t)count * sizeof(int))) return rc;
+    hipLaunchKernelGGL(k_pabf_zinfo, dim3((unsigned)((l2 + 127) / 128), (unsigned)max_ops, (unsigned)count), dim3(128), 0, p->stream, b.gr, count, max_ops,
+                       d_nused, d_zi);
+    hipLaunchKernelGGL(k_pabf_cellhash, dim3((unsigned)l2, (unsigned)max_ops, (unsigned)count), dim3(128), 0, p->stream, b.gr, count, max_ops, d_nused,
+                       p->d_sidx2, d_hash);
+    int64_t md = 0;
+    for (const PabState& st : p->st) md = std::max(md, st.m_data);
+    hipLaunchKernelGGL(k_pabf_rowbase, pab_grid((int)((md + 255) / 256), count), dim3(256), 0, p->stream, pab_view(p), max_ops, d_rb, d_jm);
+    if (int rc = pab_to_host(p, zi.data(), d_zi, cells * sizeof(PabfZinfo))) return rc;
+    if (int rc = pab_to_host(p, hash.data(), d_hash, cells * 8)) return rc;
+    if (int rc = pab_to_host(p, jm.data(), d_jm, cells * 16)) return rc;
+    if (int rc = pab_to_host(p, rb.data(), d_rb, cells * 4)) return rc;
+  }
+  b.lap(p, "separable form: axial data, cell hashes");
+  // lists: (operation, z mask, cell hash) of the (o, k) that have rows; groups: home / G
+  std::vector<std::vector<PabfListRef>> lists((size_t)count);
+  std::vector<std::vector<std::vector<PabfGroupList>>> groups((size_t)count);
+  int max_lists = 1, max_gl = 1;
+  for (int c = 0; c < count; ++c) {
+    struct Key { int op; unsigned long long m0, m1, h; };
+    std::vector<Key> keys;
+    std::vector<PabfListRef>& ls = lists[(size_t)c];
+    std::vector<std::vector<PabfGroupList>>& gs = groups[(size_t)c];
+    gs.assign((size_t)ng, {});
+    for (int o = 0; o < p->n_ops_used[(size_t)c]; ++o)
+      for (int k = 0; k < l2; ++k) {
+        const size_t at = ((size_t)c * max_ops + o) * l2 + k;
+        if (rb[at] == 0x7f7f7f7f) continue;   // no ray of this (operation, column) has a row
+        const PabfZinfo& z = zi[at];
+        int li = -1;
+        for (size_t t = 0; t < keys.size(); ++t)
+          if (keys[t].op == o && keys[t].m0 == z.zmask[0] && keys[t].m1 == z.zmask[1] && keys[t].h == hash[at]) { li = (int)t; break; }
+        if (li < 0) {
+          li = (int)keys.size();
+          keys.push_back({o, z.zmask[0], z.zmask[1], hash[at]});
+          PabfListRef lr{};
+          lr.op = o; lr.k = k; lr.zmask[0] = z.zmask[0]; lr.zmask[1] = z.zmask[1];
+          ls.push_back(lr);
+        }
+        const int g = z.home / G;
+        if (g >= ng) return pab_fail(p, HH_ERR_STATE, "hh_pab_create: a home layer beyond the groups (internal)");
+        std::vector<PabfGroupList>& gg = gs[(size_t)g];
+        PabfGroupList* slot = nullptr;
+        for (PabfGroupList& cand_ : gg)
+          if (cand_.list == li && cand_.nk < PABF_KMAX) { slot = &cand_; break; }
+        if (!slot) { gg.push_back(PabfGroupList{}); slot = &gg.back(); slot->list = li; slot->nk = 0; }
+        PabfRowRef& r = slot->e[slot->nk++];
+        r.rowbase = rb[at];
+        r.hp = z.home - g * G;
+        r.jmask[0] = jm[2 * at]; r.jmask[1] = jm[2 * at + 1];
+        r.cz0 = z.cz0; r.cz1 = z.cz1;
+      }
+    max_lists = std::max<int>(max_lists, (int)ls.size());
+    for (const auto& gg : gs) max_gl = std::max<int>(max_gl, (int)gg.size());
+  }
+  {
+    std::vector<PabfListRef> all_lists((size_t)count * max_lists);
+    std::vector<int> n_lists((size_t)count), ngl((size_t)count * ng);
+    std::vector<PabfGroupList> all_gl((size_t)count * ng * max_gl);
+    for (int c = 0; c < count; ++c) {
+      n_lists[(size_t)c] = (int)lists[(size_t)c].size();
+      std::copy(lists[(size_t)c].begin(), lists[(size_t)c].end(), all_lists.begin() + (size_t)c * max_lists);
+      for (int g = 0; g < ng; ++g) {
+        const auto& gg = groups[(size_t)c][(size_t)g];
+        ngl[(size_t)c * ng + g] = (int)gg.size();
+        std::copy(gg.begin(), gg.end(), all_gl.begin() + ((size_t)c * ng + g) * max_gl);
+      }
+    }
+    DevArena tmp;
+    PabfListRef* d_lists = tmp.get<PabfListRef>(all_lists.size());
+    int* d_nlists = tmp.get<int>((size_t)count);
+    if (int rc = pab_arena_ok(p, tmp)) return rc;
+    if (int rc = pab_to_device(p, d_lists, all_lists.data(), all_lists.size() * sizeof(PabfListRef))) return rc;
+    if (int rc = pab_to_device(p, d_nlists, n_lists.data(), n_lists.size() * sizeof(int))) return rc;
+    if (int rc = pab_upload(p, p->d_fac_ngl, ngl)) return rc;
+    if (int rc = pab_upload(p, p->d_fac_gl, all_gl)) return rc;
+    if (int rc = pab_alloc(p, p->d_fac_entries, (size_t)count * max_lists * d2 * d2)) return rc;
+    if (int rc = pab_alloc(p, p->d_fac_count, (size_t)count * max_lists * d2)) return rc;
+    hipLaunchKernelGGL(k_pabf_entries, dim3((unsigned)((d2 + 63) / 64), (unsigned)max_lists, (unsigned)count), dim3(64), 0, p->stream, b.gr, count,
+                       max_lists, d_nlists, d_lists, p->d_sidx2, p->d_fac_entries, p->d_fac_count);
+    const hipError_t e3 = hipStreamSynchronize(p->stream);
+    if (e3 != hipSuccess) return pab_fail(p, HH_ERR_HIP, std::string("hh_pab_create (footprint lists): ") + hipGetErrorString(e3));
+  }
+  p->fac_G = G; p->fac_ng = ng; p->fac_max_gl = max_gl; p->fac_max_lists = max_lists;
+  p->fac_lds = (size_t)(G + 1) * p->nslice * sizeof(double) + (size_t)max_gl * sizeof(PabfGroupList);
+  if (p->fac_lds > ((size_t)160 << 10) && (b.flags & HH_PAB_ALLOW_BANDED)) {   // the banded form instead (pab_build_banded)
+    p->d_fac_ngl.reset(); p->d_fac_gl.reset(); p->d_fac_entries.reset(); p->d_fac_count.reset();
+    p->fac_G = 0;
+    p->band_T = -1;
+  } else if (p->fac_lds > ((size_t)160 << 10)) {
+    return pab_fail(p, HH_ERR_ARG, "hh_pab_create: not sliceable — the planes and the list table of a group do not fit the LDS");
+  }
+  // the forward product's blocks: the groups, then the symmetry (/ augmented) rows
+  if (p->fac_G) {
+    int64_t ms_max = 0;
+    for (const PabState& st : p->st) ms_max = std::max(ms_max, st.m_sym);
+    p->fac_split = std::max(1, std::min(8, (16 + ng - 1) / ng));   // about sixteen workgroups per candidate and product
+    p->nb_mv = ng * p->fac_split + (int)((ms_max + 256 * PABF_TAIL_ROWS - 1) / (256 * PABF_TAIL_ROWS));
+    p->nb_mva = ng * p->fac_split + (int)((ms_max + p->n + 256 * PABF_TAIL_ROWS - 1) / (256 * PABF_TAIL_ROWS));
+    if (p->nb_mva > p->RB) return pab_fail(p, HH_ERR_STATE, "hh_pab_create: more partial sums than planned (internal)");
+  }
+  if (b.timing && p->fac_G) {
+    size_t nl = 0, ngl_tot = 0, nk_tot = 0;
+    for (int c = 0; c < count; ++c) {
+      nl += lists[(size_t)c].size();
+      for (const auto& gg : groups[(size_t)c]) { ngl_tot += gg.size(); for (const auto& e_ : gg) nk_tot += (size_t)e_.nk; }
+    }
+    std::fprintf(stderr, "hh_pab_create[%d]: separable form: G %d, %d groups, lists per candidate %.1f (max %d), group lists per group %.1f (max %d), "
+                         "rows per group list %.2f, operations used (max) %d\n", count, G, ng, (double)nl / count, max_lists,
+                 (double)ngl_tot / count / ng, max_gl, ngl_tot ? (double)nk_tot / ngl_tot : 0.0, max_ops);
+  }
+  b.lap(p, "separable form: lists and column groups");
+  return HH_OK;
+}
+
+// ---- the banded form (path_a_banded.inc): the disc's rows cut into bands whose planes, halo row and table rows fit --------
+int pab_build_banded(hh_pab* p, PabBuild& b) {
+  const PabBandCut cut = pab_band_cut(b.rank, b.d2, (b.flags & HH_PAB_FORCE_BANDED) != 0);
+  if (cut.row_too_large) return pab_fail(p, HH_ERR_ARG, "hh_pab_create: not sliceable — one row of the disc does not fit the LDS");
+  p->band_T = (int)cut.band_y.size() - 1;
+  // the launch needs the largest band's bytes — each at most the budget; with the static state the whole must fit a
+  // compute unit's 160 KiB
+  p->band_lds = cut.band_lds;
+  if (p->band_lds > cut.budget || p->band_lds + sizeof(PabState) > ((size_t)160 << 10))
+    return pab_fail(p, HH_ERR_STATE, "hh_pab_create: not sliceable — a band of the disc does not fit the LDS (internal)");
+  if (int rc = pab_upload(p, p->d_band_y, cut.band_y)) return rc;
+  if (int rc = pab_upload(p, p->d_band_v, cut.vrow)) return rc;
+  if (int rc = pab_alloc(p, p->d_bpart, (size_t)b.count * p->band_T * p->M)) return rc;
+  if (b.timing) std::fprintf(stderr, "hh_pab_create[%d]: banded form: %d bands, %zu bytes of LDS\n", b.count, p->band_T, p->band_lds);
+  b.lap(p, "banded form");
+  return HH_OK;
+}
+
+// Largest column sum of |A_data| per candidate: sizes the fixed-point scale of A^T y.  launch(d_colmax) runs the
+// products' column-sum variants into d_colmax [count] (zeroed); colsum_of(max) makes st.colsum of a candidate's maximum.
+template <class T, class Launch, class ColsumOf>
+int pab_colsums(hh_pab* p, PabBuild& b, Launch launch, ColsumOf colsum_of) {
+  const int count = b.count;
+  std::vector<T> colmax((size_t)count, 0);
+  {
+    DevArena tmp;
+    T* d_colmax = tmp.get<T>((size_t)count);
+    if (int rc = pab_arena_ok(p, tmp)) return rc;
+    hipError_t e = hipMemsetAsync(d_colmax, 0, (size_t)count * sizeof(T), p->stream);
+    launch(d_colmax);
+    if (e == hipSuccess) e = hipGetLastError();
+    if (e != hipSuccess) return pab_fail(p, HH_ERR_HIP, hipGetErrorString(e));
+    if (int rc = pab_to_host(p, colmax.data(), d_colmax, colmax.size() * sizeof(T))) return rc;
+  }
+  for (int c = 0; c < count; ++c) {
+    PabState& s = p->st[(size_t)c];
+    s.colsum = colsum_of(colmax[(size_t)c]);
+    pab_fx_scale(s.colsum, 1.0, s.fx_scale, s.fx_inv);
+    s.fx_scale_r = s.fx_scale;
+    s.fx_inv_r = s.fx_inv;
+  }
+  if (int rc = pab_to_device(p, p->d_st, p->st.data(), p->st.size() * sizeof(PabState))) return rc;
+  b.lap(p, "column sums");
+  return HH_OK;
+}
+int pab_build_colsums(hh_pab* p, PabBuild& b) {
+  const int count = b.count;
+  auto all = [] __device__(const auto&) { return true; };
+  if (p->linear)   // in 2^-20 units (the trilinear weights are not counts)
+    return pab_colsums<long long>(
+        p, b,
+        [&](long long* d_colmax) {
+          if (p->fac_G) {
+            pabf_with_G(p->fac_G, [&](auto G) {
+              const auto kernel = k_pabf_scatter<0, true, decltype(G)::value, decltype(all)>;
+              pab_lds_attr(p, kernel, p->fac_lds);
+              hipLaunchKernelGGL(kernel, pab_grid(p->fac_ng * p->fac_split, count), dim3(PABS_THREADS), p->fac_lds, p->stream, pab_view(p), 0, all);
+            });
+          } else if (p->band_T) {
+            pab_lds_attr(p, k_pabt_scatter<0, true, decltype(all)>, p->band_lds);
+            hipLaunchKernelGGL((k_pabt_scatter<0, true, decltype(all)>), pab_grid(p->mz * p->band_T, count), dim3(PABS_THREADS), p->band_lds, p->stream,
+                               pab_view(p), 0, all);
+          } else {
+            pab_lds_attr(p, k_pabl_scatter<0, true, decltype(all)>, p->lin_lds);
+            hipLaunchKernelGGL((k_pabl_scatter<0, true, decltype(all)>), pab_grid(p->mz, count), dim3(PABS_THREADS), p->lin_lds, p->stream, pab_view(p), 0, all);
+          }
+          hipLaunchKernelGGL((k_pabl_finish<2, decltype(all)>), pab_grid(p->nb_fin, count), dim3(256), 0, p->stream, pab_view(p), 0, -1, -1, 0, d_colmax, all);
+        },
+        [](long long m) { return std::ldexp((double)m, -20) * (1.0 + 1e-3) + 1e-3; });   // (as hh_pa sizes it)
+  if (p->sliced)   // hit counts
+    return pab_colsums<int>(
+        p, b,
+        [&](int* d_colmax) {
+          hipLaunchKernelGGL((k_pabs_rmatvec<0, true, decltype(all)>), pab_grid(p->mz, count), dim3(PABS_THREADS), (size_t)p->nslice * sizeof(long long),
+                             p->stream, pab_view(p), 0, -1, -1, 0, d_colmax, all);
+        },
+        [](int m) { return (double)std::max(1, m); });
+  return HH_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1614,27 +2573,8 @@ int hh_pab_create(hh_pab** out, int device, const float* image, int ny, int nx, 
 // flags: HH_PAB_ALLOW_BANDED — the trilinear products take the banded form (path_a_banded.inc) where the LDS form cannot hold
 // the box; HH_PAB_FORCE_BANDED — always, with at least three bands (tests on small boxes).  0: hh_pab_create.
 int hh_pab_create_ex(hh_pab** out, int device, const float* image, int ny, int nx, const hh_pa_params* qs, int count, int flags) try {
-  if (!out || !image || !qs || count < 1) return pab_fail(nullptr, HH_ERR_ARG, "hh_pab_create: bad argument");
-  if (flags & ~(HH_PAB_ALLOW_BANDED | HH_PAB_FORCE_BANDED)) return pab_fail(nullptr, HH_ERR_ARG, "hh_pab_create_ex: unknown flags");
-  *out = nullptr;
-  const hh_pa_params& q0 = qs[0];
-  const int d2 = q0.reconstruct_diameter_2d_pixel > 0 ? q0.reconstruct_diameter_2d_pixel : ny;
-  const int l2 = q0.reconstruct_length_2d_pixel > 0 ? q0.reconstruct_length_2d_pixel : nx;
-  const int l3 = q0.reconstruct_length_3d_pixel > 0 ? q0.reconstruct_length_3d_pixel : l2;
-  if (d2 > ny || l2 > nx || d2 < 2 || l2 < 2) return pab_fail(nullptr, HH_ERR_ARG, "hh_pab_create: 2-D region does not fit the image");
-  for (int c = 0; c < count; ++c) {
-    const hh_pa_params& q = qs[c];
-    if (!(q.rise_pixel > 0) || q.csym < 1 || q.twist_degree == 0.0)
-      return pab_fail(nullptr, HH_ERR_ARG, "hh_pab_create: rise must be positive, csym >= 1, twist non-zero");
-    if ((q.interpolation != 0 && q.interpolation != 1) || q.interpolation != q0.interpolation)
-      return pab_fail(nullptr, HH_ERR_ARG, "hh_pab_create: interpolation must be 0 (nearest neighbour) or 1 (trilinear), the same for the whole batch");
-    if (q.reconstruct_diameter_2d_pixel != q0.reconstruct_diameter_2d_pixel || q.reconstruct_length_2d_pixel != q0.reconstruct_length_2d_pixel ||
-        q.reconstruct_diameter_3d_pixel != q0.reconstruct_diameter_3d_pixel || q.reconstruct_length_3d_pixel != q0.reconstruct_length_3d_pixel ||
-        q.reconstruct_diameter_3d_inner_pixel != q0.reconstruct_diameter_3d_inner_pixel)
-      return pab_fail(nullptr, HH_ERR_ARG, "hh_pab_create: the candidates of one batch share the reconstruction box");
-    if (q.fsc_half < 0 || q.fsc_half > 2 || (q.fsc_half > 0 && (q.fsc_mode < 1 || (q.fsc_mode == 1 && (!q.fsc_ids || q.n_fsc_ids < 0)))))
-      return pab_fail(nullptr, HH_ERR_ARG, "hh_pab_create: half sets need fsc_half 1 or 2 and fsc_mode 2, 3, 4, or 1 with fsc_ids");
-  }
+  int d2 = 0, l2 = 0, l3 = 0;
+  if (int rc = pab_check_args(out, image, ny, nx, qs, count, flags, d2, l2, l3)) return rc;
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
     return pab_fail(nullptr, HH_ERR_HIP, "hh_pab_create: no such HIP device (Path A has no CPU fallback)");
@@ -1644,960 +2584,30 @@ int hh_pab_create_ex(hh_pab** out, int device, const float* image, int ny, int n
   p->K = count;
   p->d2 = d2;
   p->d2p = (d2 + 63) / 64 * 64;
-  int rc = HH_OK;
-  const bool timing = std::getenv("HH_PAB_TIMING") != nullptr;
-  auto t_last = std::chrono::steady_clock::now();
-  auto lap = [&](const char* what) {
-    if (!timing) return;
-    (void)hipStreamSynchronize(p->stream);
-    const auto now = std::chrono::steady_clock::now();
-    std::fprintf(stderr, "hh_pab_create[%d]: %-28s %8.2f ms\n", count, what, std::chrono::duration<double, std::milli>(now - t_last).count());
-    t_last = now;
-  };
   struct Guard { hh_pab* p; ~Guard() { if (p) hh_pab_destroy(p); } } guard{p};   // an exception on the way releases the half-built object
-  auto bail = [&](int code) {
+  PabBuild b{qs, count, flags, image, ny, nx, d2, l2, l3, qs[0].reconstruct_diameter_3d_pixel,
+             qs[0].reconstruct_diameter_3d_inner_pixel / 2.0, (double)(qs[0].reconstruct_diameter_3d_pixel / 2 - 1)};
+  auto build = [&]() -> int {
+    if (int rc = pab_build_form(p, b)) return rc;
+    if (int rc = pab_build_geometry(p, b)) return rc;
+    if (int rc = pab_build_rows(p, b)) return rc;          // on the device, or on the host and then the half sets
+    if (int rc = pab_build_sym(p, b)) return rc;           // on the device, or on host threads
+    if (int rc = pab_build_shapes(p, b)) return rc;
+    if (int rc = pab_build_tables(p, b)) return rc;        // row tables, resident buffers, right-hand sides
+    if (int rc = pab_build_map(p, b)) return rc;
+    if (int rc = pab_build_transposed(p, b)) return rc;
+    if (p->linear && d2 <= 128 && !p->band_T)
+      if (int rc = pab_build_separable(p, b)) return rc;   // (may hand over to the banded form)
+    if (p->linear && p->band_T)
+      if (int rc = pab_build_banded(p, b)) return rc;
+    return pab_build_colsums(p, b);
+  };
+  if (const int rc = build()) {   // the one way out of a failed set-up
     g_create_error = p->err;
     guard.p = nullptr;
     hh_pab_destroy(p);
-    return code;
-  };
-#define PAB_TRY(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) { p->err = std::string(#call) + ": " + hipGetErrorString(e__); return bail(HH_ERR_HIP); } } while (0)
-#define PAB_RC(call) do { rc = (call); if (rc) return bail(rc); } while (0)
-  PAB_TRY(hipSetDevice(device));
-  PAB_TRY(hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking));
-  PAB_TRY(hipHostMalloc(reinterpret_cast<void**>(&p->h_flags), PAB_FLAG_WORDS * sizeof(int), hipHostMallocDefault));
-  // the unknowns (shared by the batch): voxels of the cylinder in the (L3d, D2d, D2d) box, C-order rank (solver:1375-1387)
-  std::vector<int> rank;
-  const double rmin = q0.reconstruct_diameter_3d_inner_pixel / 2.0;
-  const double rmax = (double)(q0.reconstruct_diameter_3d_pixel / 2 - 1);
-  p->n = pa_mask_rank(l3, d2, d2, rmin, rmax, rank);
-  if (p->n <= 0) { p->err = "hh_pab_create: the cylinder holds no voxel"; return bail(HH_ERR_ARG); }
-  p->mz = l3;
-  p->nslice = (int)(p->n / l3);   // the same disk in every slice
-  {
-    p->flat = 1;
-    for (int c = 0; c < count; ++c) p->flat = p->flat && qs[c].tilt_degree == 0.0 && qs[c].psi_degree == 0.0;
-    const bool flat = p->flat && std::getenv("HH_PAB_GENERAL") == nullptr;
-    p->sliced = flat && (int64_t)p->nslice * l3 == p->n && p->nslice < 0xffff && (size_t)p->nslice * sizeof(double) <= (size_t)60 << 10;
-    p->linear = q0.interpolation;
-    if (p->linear) {   // two planes of x and the disc's table in LDS; no general (tilt / psi) form of the trilinear products here
-      p->lin_lds = (size_t)2 * p->nslice * sizeof(double) + (size_t)d2 * d2 * sizeof(unsigned);
-      const bool slice_major = flat && (int64_t)p->nslice * l3 == p->n && p->nslice < 0xffff;
-      const bool lds_fits = p->lin_lds <= (size_t)150 << 10;
-      // (band_T is set once the bands are cut, below; this marks the form)
-      p->band_T = slice_major && ((flags & HH_PAB_FORCE_BANDED) || (!lds_fits && (flags & HH_PAB_ALLOW_BANDED))) ? -1 : 0;
-      p->sliced = slice_major && (lds_fits || p->band_T);
-      if (!p->sliced) {
-        p->err = slice_major ? "hh_pab_create: not sliceable — the batched trilinear projector's LDS form needs two planes of the cylinder in LDS "
-                               "(hh_pab_create_ex with HH_PAB_ALLOW_BANDED has the banded form)"
-                             : "hh_pab_create: not sliceable — the batched trilinear projector needs tilt = psi = 0 "
-                               "(the single-candidate hh_pa has the general form)";
-        return bail(HH_ERR_ARG);
-      }
-    }
+    return rc;
   }
-  PAB_RC(pab_alloc(p, p->d_rank, rank.size()));
-  PAB_RC(pab_to_device(p, p->d_rank, rank.data(), rank.size() * sizeof(int)));
-  // geometry and symmetry operations of every candidate, in the reference's order (solver:1556-1571)
-  std::vector<PaGeom> geoms((size_t)count);
-  std::vector<PaOp> ops;
-  std::vector<int64_t> op0((size_t)count);
-  std::vector<int> n_ops((size_t)count);
-  for (int c = 0; c < count; ++c) {
-    const hh_pa_params& q = qs[c];
-    PaGeom& g = geoms[(size_t)c];
-    g.linear = q.interpolation;
-    g.L2 = l2; g.D2 = d2; g.mz = l3; g.my = d2; g.mx = d2;
-    g.scale = q.scale2d_to_3d;
-    g.dy = q.dy_pixel;
-    pa_euler1('y', 90.0, g.m_y90);
-    double qy[4], qx[4], qq[4];
-    pa_quat_axis('y', q.tilt_degree, qy);
-    pa_quat_axis('x', q.psi_degree, qx);
-    pa_quat_mul(qx, qy, qq);
-    pa_quat_matrix(qq, g.m_yx);
-    const int hmax = std::max(1, (int)(std::ceil((double)(l3 + l2)) / 2 / q.rise_pixel));
-    struct Hc { int h, c; };
-    std::vector<Hc> hcs;
-    for (int h = -hmax; h <= hmax; ++h)
-      for (int cc = 0; cc < q.csym; ++cc) hcs.push_back({h, cc});
-    std::stable_sort(hcs.begin(), hcs.end(), [](const Hc& a, const Hc& b) {
-      return std::abs(a.h) != std::abs(b.h) ? std::abs(a.h) < std::abs(b.h) : a.c < b.c;
-    });
-    const std::vector<int64_t> order = pa_halton((int64_t)hcs.size());
-    op0[(size_t)c] = (int64_t)ops.size();
-    n_ops[(size_t)c] = (int)order.size();
-    for (size_t i = 0; i < order.size(); ++i) {
-      const Hc& s = hcs[(size_t)order[i]];
-      PaOp op;
-      pa_euler1('z', q.twist_degree * s.h + 360.0 * s.c / q.csym, op.m_z);
-      op.shift = s.h * q.rise_pixel;
-      ops.push_back(op);
-    }
-  }
-  if (p->linear) {   // what pabl_ray / pabl_at drop from pa_coords must be exactly what it says
-    bool ok = true;
-    for (const PaGeom& g : geoms) {
-      const double id[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
-      for (int t = 0; t < 9; ++t) ok = ok && g.m_yx[t] == id[t];
-    }
-    for (const PaOp& op : ops) ok = ok && op.m_z[2] == 0 && op.m_z[5] == 0 && op.m_z[6] == 0 && op.m_z[7] == 0;
-    if (!ok) { p->err = "hh_pab_create: the rotations are not of the form the trilinear ray arithmetic assumes (internal)"; return bail(HH_ERR_STATE); }
-  }
-  PAB_RC(pab_alloc(p, p->d_geom, geoms.size()));
-  PAB_RC(pab_to_device(p, p->d_geom, geoms.data(), geoms.size() * sizeof(PaGeom)));
-  PAB_RC(pab_alloc(p, p->d_ops, ops.size()));
-  PAB_RC(pab_to_device(p, p->d_ops, ops.data(), ops.size() * sizeof(PaOp)));
-  PAB_RC(pab_alloc(p, p->d_op0, op0.size()));
-  PAB_RC(pab_to_device(p, p->d_op0, op0.data(), op0.size() * sizeof(int64_t)));
-  const PabGeomRef gr{p->d_geom, p->d_ops, p->d_op0};
-  // which rays exist, operation chunk by chunk, until every candidate has passed its row target (solver:1647)
-  const size_t rays = (size_t)l2 * d2;
-  const int chunk = 8;
-  std::vector<std::vector<int>> ray_of_row((size_t)count);
-  std::vector<std::vector<float>> b_of((size_t)count);
-  std::vector<std::vector<int32_t>> pid_of((size_t)count);
-  std::vector<std::vector<short>> z_of((size_t)count);   // the slice of every row (sliced path)
-  p->n_ops_used.assign((size_t)count, 0);
-  p->st.assign((size_t)count, PabState{});
-  // Row enumeration on the device unless a candidate is a half set (the half sets' pixel-id rules are host code) or
-  // HH_PAB_HOST_ROWS asks for the host path (the A/B reference of the tests): per chunk of operations the codes are
-  // counted per slice, the host decides from the counts alone which operations each candidate uses (solver:1647), and a
-  // second sweep over the used chunks writes the rows where they belong — no per-ray data crosses PCIe.
-  bool dev_rows = std::getenv("HH_PAB_HOST_ROWS") == nullptr;
-  for (int c = 0; c < count; ++c) dev_rows = dev_rows && qs[c].fsc_half == 0;
-  DevBuf<float> d_b_int;                 // device-order b of the data rows (device path; freed once MV_B is filled)
-  std::vector<int> srow_h;               // [count][mz + 1] (device path)
-  if (dev_rows) {
-    const int mz1 = p->mz + 1;
-    DevArena tmp;   // freed on every way out
-    int* d_cand = tmp.get<int>((size_t)count);
-    int* d_nops = tmp.get<int>((size_t)count);
-    unsigned char* d_has = tmp.get<unsigned char>((size_t)count * chunk * rays);
-    int* d_counts = tmp.get<int>((size_t)count * chunk * mz1);
-    int* d_bmax = tmp.get<int>((size_t)count);
-    float* d_image = tmp.get<float>((size_t)ny * nx);
-    long long* d_bref_t = tmp.get<long long>((size_t)count * chunk);
-    long long* d_bint_t = tmp.get<long long>((size_t)count * chunk * mz1);
-    long long* d_row0_t = tmp.get<long long>((size_t)count);
-    PAB_RC(pab_arena_ok(p, tmp));
-    rc = pab_to_device(p, d_nops, n_ops.data(), n_ops.size() * sizeof(int));
-    if (rc == HH_OK) rc = pab_to_device(p, d_image, image, (size_t)ny * nx * sizeof(float));
-    // pass 1: counts per (candidate, operation, slice)
-    std::vector<std::vector<int>> cnt3((size_t)count);   // [operation][mz + 1], the operations used
-    std::vector<int64_t> rows_so_far((size_t)count, 0);
-    std::vector<int> live((size_t)count), counts_h;
-    for (int c = 0; c < count; ++c) live[(size_t)c] = c;
-    for (int lo = 0; rc == HH_OK && !live.empty(); lo += chunk) {
-      rc = pab_to_device(p, d_cand, live.data(), live.size() * sizeof(int));
-      if (rc) break;
-      hipLaunchKernelGGL(p->linear ? k_pabl_has : k_pab_has, dim3((unsigned)((rays + 255) / 256), chunk, (unsigned)live.size()), dim3(256), 0, p->stream,
-                         gr, d_cand, lo, chunk, d_nops, p->d_rank, d_has);
-      hipLaunchKernelGGL(k_pab_count_codes, dim3(chunk, (unsigned)live.size()), dim3(256), (size_t)mz1 * sizeof(int), p->stream, d_has, rays, chunk,
-                         p->mz, d_counts);
-      counts_h.resize(live.size() * chunk * mz1);
-      rc = pab_to_host(p, counts_h.data(), d_counts, counts_h.size() * sizeof(int));
-      if (rc) break;
-      std::vector<int> next;
-      for (size_t sl = 0; sl < live.size(); ++sl) {
-        const int c = live[sl];
-        bool done = false;
-        for (int o = 0; o < chunk && lo + o < n_ops[(size_t)c] && !done; ++o) {
-          const int* cz = counts_h.data() + (sl * chunk + o) * mz1;
-          int64_t tot = 0;
-          for (int z = 0; z < mz1; ++z) tot += cz[z];
-          if (cz[p->mz] > 0) p->sliced = 0;   // a ray in two slices: the whole batch takes the general products
-          cnt3[(size_t)c].insert(cnt3[(size_t)c].end(), cz, cz + mz1);
-          rows_so_far[(size_t)c] += tot;
-          p->n_ops_used[(size_t)c] = lo + o + 1;
-          if (qs[c].min_projection_lines > 0 && rows_so_far[(size_t)c] > qs[c].min_projection_lines) done = true;
-        }
-        if (!done && lo + chunk < n_ops[(size_t)c]) next.push_back(c);
-      }
-      live.swap(next);
-    }
-    // the row tables' geometry: first row of every candidate, of every slice (device order), of every operation
-    int max_used = 0;
-    if (rc == HH_OK) {
-      srow_h.assign((size_t)count * mz1, 0);
-      for (int c = 0; c < count; ++c) {
-        if (rows_so_far[(size_t)c] == 0) { rc = pab_fail(p, HH_ERR_ARG, "hh_pab_create: no projection ray of a candidate meets the cylinder"); break; }
-        PabState& st = p->st[(size_t)c];
-        st.m_data = rows_so_far[(size_t)c];
-        st.row0 = p->total_rows;
-        p->total_rows += st.m_data;
-        max_used = std::max(max_used, p->n_ops_used[(size_t)c]);
-        if (p->sliced) {
-          int* sr = srow_h.data() + (size_t)c * mz1;
-          for (int o = 0; o < p->n_ops_used[(size_t)c]; ++o)
-            for (int z = 0; z < p->mz; ++z) sr[z + 1] += cnt3[(size_t)c][(size_t)o * mz1 + z];
-          for (int z = 0; z < p->mz; ++z) sr[z + 1] += sr[z];
-        }
-      }
-    }
-    if (rc == HH_OK) {
-      const size_t rows1 = std::max<size_t>((size_t)p->total_rows, 1);
-      if (!p->d_ray_of_row.ensure(rows1) || !d_b_int.ensure(rows1) || !p->d_bref.ensure(rows1) || !p->d_pidref.ensure(rows1))
-        rc = pab_fail(p, HH_ERR_NOMEM, "hh_pab_create: " + dev_alloc_failed(rows1 * 4));
-      else if (hipError_t e2 = hipMemsetAsync(d_bmax, 0x80, (size_t)count * sizeof(int), p->stream))   // very negative ordered keys
-        rc = pab_fail(p, HH_ERR_HIP, std::string("hh_pab_create: ") + hipGetErrorString(e2));
-      p->device_bytes += (size_t)p->total_rows * 16;
-    }
-    // pass 2: the rows themselves, chunk by chunk over the operations that are used
-    std::vector<long long> bref_h, bint_h, row0_h;
-    for (int lo = 0; rc == HH_OK && lo < max_used; lo += chunk) {
-      live.clear();
-      for (int c = 0; c < count; ++c)
-        if (p->n_ops_used[(size_t)c] > lo) live.push_back(c);
-      const size_t nl = live.size();
-      bref_h.assign(nl * chunk, -1);
-      bint_h.assign(nl * chunk * mz1, 0);
-      row0_h.resize(nl);
-      for (size_t sl = 0; sl < nl; ++sl) {
-        const int c = live[sl];
-        const std::vector<int>& cz = cnt3[(size_t)c];
-        row0_h[sl] = p->st[(size_t)c].row0;
-        // rows before operation o: in the reference's order all of the earlier operations; in the device order, per
-        // slice, the earlier operations' rows of that slice (after the slice's first row) minus this operation's rows of
-        // the earlier slices (the rank the kernel adds counts all of the operation's earlier rays)
-        long long before_ref = 0;
-        std::vector<long long> before_z((size_t)mz1, 0);
-        for (int o = 0; o < p->n_ops_used[(size_t)c]; ++o) {
-          long long tot = 0, zoff = 0;
-          for (int z = 0; z < mz1; ++z) tot += cz[(size_t)o * mz1 + z];
-          if (o >= lo && o < lo + chunk) {
-            bref_h[sl * chunk + (size_t)(o - lo)] = before_ref;
-            for (int z = 0; z < mz1; ++z) {
-              long long v = before_ref;   // general path: device order = reference order
-              if (p->sliced) v = (z < p->mz ? srow_h[(size_t)c * mz1 + z] : 0) + before_z[(size_t)z] - zoff;
-              bint_h[(sl * chunk + (size_t)(o - lo)) * mz1 + z] = v;
-              zoff += cz[(size_t)o * mz1 + z];
-            }
-          }
-          for (int z = 0; z < mz1; ++z) before_z[(size_t)z] += cz[(size_t)o * mz1 + z];
-          before_ref += tot;
-        }
-      }
-      rc = pab_to_device(p, d_cand, live.data(), nl * sizeof(int));
-      if (rc == HH_OK) rc = pab_to_device(p, d_bref_t, bref_h.data(), bref_h.size() * sizeof(long long));
-      if (rc == HH_OK) rc = pab_to_device(p, d_bint_t, bint_h.data(), bint_h.size() * sizeof(long long));
-      if (rc == HH_OK) rc = pab_to_device(p, d_row0_t, row0_h.data(), nl * sizeof(long long));
-      if (rc) break;
-      hipLaunchKernelGGL(p->linear ? k_pabl_has : k_pab_has, dim3((unsigned)((rays + 255) / 256), chunk, (unsigned)nl), dim3(256), 0, p->stream, gr,
-                         d_cand, lo, chunk, d_nops, p->d_rank, d_has);
-      const PabEmit em{d_has, d_image, d_bref_t, d_bint_t, d_row0_t, d_cand, p->d_ray_of_row, d_b_int, p->d_bref, p->d_pidref, d_bmax,
-                       chunk, lo, p->mz, l2, d2, ny, nx};
-      hipLaunchKernelGGL(k_pab_emit, dim3(chunk, (unsigned)nl), dim3(1024), 0, p->stream, em);
-    }
-    if (rc == HH_OK) {
-      std::vector<int> bm((size_t)count);
-      rc = pab_to_host(p, bm.data(), d_bmax, bm.size() * sizeof(int));
-      for (int c = 0; c < count && rc == HH_OK; ++c) {
-        const int key = bm[(size_t)c], bits = key >= 0 ? key : key ^ 0x7fffffff;
-        float f;
-        std::memcpy(&f, &bits, sizeof(f));
-        p->st[(size_t)c].bmax = (double)f;
-      }
-    }
-    tmp.release();
-    if (rc) return bail(rc);
-    lap("rays and rows (device)");
-  } else {
-  {
-    std::vector<unsigned char> has;
-    std::vector<int> live((size_t)count);
-    for (int c = 0; c < count; ++c) live[(size_t)c] = c;
-    DevArena tmp;   // freed on every way out
-    int* d_cand = tmp.get<int>((size_t)count);
-    int* d_nops = tmp.get<int>((size_t)count);
-    unsigned char* d_has = tmp.get<unsigned char>((size_t)count * chunk * rays);
-    PAB_RC(pab_arena_ok(p, tmp));
-    rc = pab_to_device(p, d_nops, n_ops.data(), n_ops.size() * sizeof(int));
-    for (int lo = 0; rc == HH_OK && !live.empty(); lo += chunk) {
-      rc = pab_to_device(p, d_cand, live.data(), live.size() * sizeof(int));
-      if (rc) break;
-      hipLaunchKernelGGL(p->linear ? k_pabl_has : k_pab_has, dim3((unsigned)((rays + 255) / 256), chunk, (unsigned)live.size()), dim3(256), 0, p->stream,
-                         gr, d_cand, lo, chunk, d_nops, p->d_rank, d_has);
-      has.resize(live.size() * chunk * rays);
-      rc = pab_to_host(p, has.data(), d_has, has.size());
-      if (rc) break;
-      std::vector<int> next;
-      for (size_t sl = 0; sl < live.size(); ++sl) {
-        const int c = live[sl];
-        const hh_pa_params& q = qs[c];
-        bool done = false;
-        for (int o = 0; o < chunk && lo + o < n_ops[(size_t)c] && !done; ++o) {
-          const unsigned char* h = has.data() + (sl * chunk + o) * rays;
-          // rows of this operation, in (k, j) order; b = pixel_vals[j, k], pid = k * ny + j (solver:1548-1549)
-          for (int k = 0; k < l2; ++k)
-            for (int j = 0; j < d2; ++j)
-              if (h[(size_t)k * d2 + j]) {
-                const unsigned char code = h[(size_t)k * d2 + j];
-                if (code == 255) p->sliced = 0;   // a ray in two slices: the whole batch takes the general products
-                z_of[(size_t)c].push_back((short)(code - 1));
-                ray_of_row[(size_t)c].push_back((int)(((size_t)(lo + o) * l2 + k) * d2 + j));
-                b_of[(size_t)c].push_back(image[(size_t)(j - d2 / 2 + ny / 2) * nx + (k - l2 / 2 + nx / 2)]);
-                pid_of[(size_t)c].push_back(k * d2 + j);
-              }
-          p->n_ops_used[(size_t)c] = lo + o + 1;
-          if (q.min_projection_lines > 0 && (int64_t)ray_of_row[(size_t)c].size() > q.min_projection_lines) done = true;
-        }
-        if (!done && lo + chunk < n_ops[(size_t)c]) next.push_back(c);
-      }
-      live.swap(next);
-    }
-    if (rc) return bail(rc);
-  }
-  lap("rays that exist");
-  // half sets (split_A_b, solver:175-203), then the concatenated row tables
-  for (int c = 0; c < count; ++c) {
-    const hh_pa_params& q = qs[c];
-    std::vector<int>& rr = ray_of_row[(size_t)c];
-    std::vector<float>& bb = b_of[(size_t)c];
-    std::vector<int32_t>& pp = pid_of[(size_t)c];
-    std::vector<short>& zz = z_of[(size_t)c];
-    if (q.fsc_half > 0) {
-      std::vector<int32_t> ids(pp);
-      std::sort(ids.begin(), ids.end());
-      ids.erase(std::unique(ids.begin(), ids.end()), ids.end());
-      const size_t nn = ids.size();
-      std::vector<int32_t> set1;
-      if (q.fsc_mode == 1) { set1.assign(q.fsc_ids, q.fsc_ids + q.n_fsc_ids); std::sort(set1.begin(), set1.end()); }
-      else if (q.fsc_mode == 2) { for (size_t i = 0; i < nn; i += 2) set1.push_back(ids[i]); }
-      else if (q.fsc_mode == 3) { set1.assign(ids.begin(), ids.begin() + nn / 2); }
-      else { set1.assign(ids.begin(), ids.begin() + nn / 3); set1.insert(set1.end(), ids.begin() + nn * 2 / 3, ids.end()); }
-      size_t wr = 0;
-      for (size_t r = 0; r < rr.size(); ++r) {
-        const bool in1 = std::binary_search(set1.begin(), set1.end(), pp[r]);
-        if (in1 == (q.fsc_half == 1)) { rr[wr] = rr[r]; bb[wr] = bb[r]; pp[wr] = pp[r]; zz[wr] = zz[r]; ++wr; }
-      }
-      rr.resize(wr); bb.resize(wr); pp.resize(wr); zz.resize(wr);
-    }
-    if (rr.empty()) { p->err = "hh_pab_create: no projection ray of a candidate meets the cylinder"; return bail(HH_ERR_ARG); }
-    PabState& s = p->st[(size_t)c];
-    s.m_data = (int64_t)rr.size();
-    s.row0 = p->total_rows;
-    p->total_rows += s.m_data;
-    s.bmax = (double)*std::max_element(bb.begin(), bb.end());
-  }
-  }   // (host-side row enumeration)
-  // symmetry constraints (box (L3d, D3d, D3d) of lsq_reconstruct, solver:116-173): on the device (k_pab_sym), or with
-  // HH_PAB_HOST_SYM on host threads through the single-candidate builder (the A/B reference of the tests)
-  if (p->linear && !p->sliced) {
-    p->err = "hh_pab_create: not sliceable — a ray's samples lie in more than one cell layer (the single-candidate hh_pa has the general form)";
-    return bail(HH_ERR_ARG);
-  }
-  std::vector<std::vector<int2>> pairs_of((size_t)count);
-  std::vector<std::vector<PaEll16>> rows16_of((size_t)(p->linear ? count : 0));
-  // (trilinear: the 16-entry rows of solver:910-1140 come from the host builder, one candidate per thread)
-  const bool dev_sym = std::getenv("HH_PAB_HOST_SYM") == nullptr && !p->linear;
-  const int d3 = q0.reconstruct_diameter_3d_pixel;
-  if (!dev_sym) {
-    const unsigned hw = std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
-    const unsigned nt = std::min<unsigned>(hw, (unsigned)count);
-    std::atomic<int> next{0};
-    std::atomic<bool> threw{false};
-    auto work = [&] {   // (a thread's body must not let an exception out: that is std::terminate whatever the caller guards)
-      try {
-        for (int c = next.fetch_add(1); c < count; c = next.fetch_add(1)) {
-          const hh_pa_params& q = qs[c];
-          if (q.min_sym_pairs > 0)
-            pa_sym_pairs(l3, d3, d3, q.twist_degree, q.rise_pixel, q.csym, rmin, rmax, q.min_sym_pairs, pairs_of[(size_t)c],
-                         p->linear ? &rows16_of[(size_t)c] : nullptr);
-        }
-      } catch (...) {
-        threw = true;
-      }
-    };
-    {
-      std::vector<std::thread> pool;
-      struct Join { std::vector<std::thread>& p; ~Join() { for (auto& t : p) if (t.joinable()) t.join(); } } join{pool};
-      for (unsigned t = 1; t < nt; ++t) pool.emplace_back(work);
-      work();
-    }
-    if (threw) { p->err = "hh_pab_create: out of host memory while building the symmetry pairs"; return bail(HH_ERR_NOMEM); }
-    for (int c = 0; c < count; ++c) {
-      PabState& s = p->st[(size_t)c];
-      s.m_sym = (int64_t)(p->linear ? rows16_of[(size_t)c].size() : pairs_of[(size_t)c].size());
-      s.sym0 = p->total_sym;
-      p->total_sym += s.m_sym;
-    }
-  } else {
-    int64_t want = 0;
-    for (int c = 0; c < count; ++c) want = std::max<int64_t>(want, qs[c].min_sym_pairs);
-    const int64_t cap = want > 0 ? want + p->n : 0;   // rows of a candidate: < min_sym_pairs before its last pair, which adds <= n
-    for (int c = 0; c < count; ++c) p->st[(size_t)c].sym0 = (int64_t)c * cap;
-    PAB_RC(pab_alloc(p, p->d_pairs, (size_t)count * cap));
-    if (cap > 0) {
-      const int sym_chunk = 4;
-      const int64_t nbox = (int64_t)l3 * d3 * d3;
-      int* d_rank_sym = p->d_rank;
-      DevArena tmp;   // freed on every way out
-      if (d3 != d2) {   // the symmetry box has its own rank table (same cylinder, same ranks, other box)
-        std::vector<int> rank3;
-        const int64_t n3 = pa_mask_rank(l3, d3, d3, rmin, rmax, rank3);
-        if (n3 != p->n) { p->err = "hh_pab_create: the cylinder does not fit the 2-D region's box"; return bail(HH_ERR_ARG); }
-        d_rank_sym = tmp.get<int>(rank3.size());
-        if (tmp.ok()) rc = pab_to_device(p, d_rank_sym, rank3.data(), rank3.size() * sizeof(int));
-      }
-      unsigned T = 1;
-      while ((int64_t)T < 2 * (want + (int64_t)sym_chunk * p->n)) T <<= 1;
-      unsigned long long* d_keys = tmp.get<unsigned long long>((size_t)count * T);
-      unsigned long long* d_tmin = tmp.get<unsigned long long>((size_t)count * T);
-      PaSymOp* d_sops = tmp.get<PaSymOp>((size_t)count * sym_chunk);
-      int* d_cand = tmp.get<int>((size_t)count);
-      int* d_nvalid = tmp.get<int>((size_t)count);
-      int* d_counts = tmp.get<int>((size_t)count * sym_chunk);
-      long long* d_base = tmp.get<long long>((size_t)count * sym_chunk);
-      unsigned char* d_flags8 = tmp.get<unsigned char>((size_t)count * sym_chunk * nbox);
-      int* d_err = tmp.get<int>(1);
-      if (!rc) rc = pab_arena_ok(p, tmp);
-      if (rc) return bail(rc);
-      hipError_t e = hipMemsetAsync(d_keys, 0xff, (size_t)count * T * 8, p->stream);
-      if (e == hipSuccess) e = hipMemsetAsync(d_tmin, 0xff, (size_t)count * T * 8, p->stream);
-      if (e == hipSuccess) e = hipMemsetAsync(d_err, 0, sizeof(int), p->stream);
-      if (e != hipSuccess) { p->err = std::string("hh_pab_create (symmetry pairs): ") + hipGetErrorString(e); return bail(HH_ERR_HIP); }
-      // the walk of every candidate (cheap: a few rotations per pair of operations)
-      std::vector<std::vector<PaSymOp>> walk((size_t)count);
-      std::vector<int> live;
-      for (int c = 0; c < count; ++c)
-        if (qs[c].min_sym_pairs > 0) {
-          walk[(size_t)c] = pa_sym_ops(l3, qs[c].twist_degree, qs[c].rise_pixel, qs[c].csym);
-          if (!walk[(size_t)c].empty()) live.push_back(c);
-        }
-      std::vector<int64_t> kept((size_t)count, 0);
-      std::vector<PaSymOp> ops_h;
-      std::vector<int> nvalid_h, counts_h;
-      std::vector<long long> base_h;
-      for (int p0 = 0; rc == HH_OK && !live.empty(); p0 += sym_chunk) {
-        const size_t nl = live.size();
-        ops_h.assign(nl * sym_chunk, PaSymOp{});
-        nvalid_h.assign(nl, 0);
-        for (size_t sl = 0; sl < nl; ++sl) {
-          const std::vector<PaSymOp>& wk = walk[(size_t)live[sl]];
-          nvalid_h[sl] = (int)std::min<size_t>(sym_chunk, wk.size() - (size_t)p0);
-          for (int k = 0; k < nvalid_h[sl]; ++k) ops_h[sl * sym_chunk + k] = wk[(size_t)p0 + k];
-        }
-        rc = pab_to_device(p, d_sops, ops_h.data(), ops_h.size() * sizeof(PaSymOp));
-        if (rc == HH_OK) rc = pab_to_device(p, d_cand, live.data(), nl * sizeof(int));
-        if (rc == HH_OK) rc = pab_to_device(p, d_nvalid, nvalid_h.data(), nl * sizeof(int));
-        if (rc) break;
-        (void)hipMemsetAsync(d_counts, 0, nl * sym_chunk * sizeof(int), p->stream);
-        PabSymRef sr{d_sops, d_cand, d_nvalid, sym_chunk, p0, l3, d3, d3, d_rank_sym, d_keys, d_tmin, T, d_err};
-        const dim3 grid((unsigned)((nbox + 255) / 256), sym_chunk, (unsigned)nl);
-        hipLaunchKernelGGL(k_pab_sym<1>, grid, dim3(256), 0, p->stream, sr, (unsigned char*)nullptr, (int*)nullptr);
-        hipLaunchKernelGGL(k_pab_sym<2>, grid, dim3(256), 0, p->stream, sr, d_flags8, d_counts);
-        counts_h.resize(nl * sym_chunk);
-        rc = pab_to_host(p, counts_h.data(), d_counts, counts_h.size() * sizeof(int));
-        if (rc) break;
-        base_h.assign(nl * sym_chunk, -1);
-        std::vector<int> next;
-        for (size_t sl = 0; sl < nl; ++sl) {
-          const int c = live[sl];
-          bool done = false;
-          for (int k = 0; k < nvalid_h[sl] && !done; ++k) {   // row_count += added; if row_count >= min_pairs: break (solver:1275)
-            base_h[sl * sym_chunk + k] = (long long)(p->st[(size_t)c].sym0 + kept[(size_t)c]);
-            kept[(size_t)c] += counts_h[sl * sym_chunk + k];
-            if (kept[(size_t)c] >= qs[c].min_sym_pairs) done = true;
-          }
-          if (!done && (size_t)(p0 + sym_chunk) < walk[(size_t)c].size()) next.push_back(c);
-        }
-        rc = pab_to_device(p, d_base, base_h.data(), base_h.size() * sizeof(long long));
-        if (rc) break;
-        hipLaunchKernelGGL(k_pab_sym_emit, dim3(sym_chunk, (unsigned)nl), dim3(1024), 0, p->stream, sr, d_flags8, d_base, p->d_pairs);
-        live.swap(next);
-      }
-      int err_h = 0;
-      if (rc == HH_OK) rc = pab_to_host(p, &err_h, d_err, sizeof(int));
-      tmp.release();
-      if (rc) return bail(rc);
-      if (err_h) { p->err = "hh_pab_create: symmetry-pair table full (internal)"; return bail(HH_ERR_STATE); }
-      for (int c = 0; c < count; ++c) {
-        p->st[(size_t)c].m_sym = kept[(size_t)c];
-        p->total_sym += kept[(size_t)c];
-        if (kept[(size_t)c] > cap) { p->err = "hh_pab_create: more symmetry rows than planned (internal)"; return bail(HH_ERR_STATE); }
-      }
-    }
-  }
-  lap(dev_sym ? "symmetry pairs (device)" : "symmetry pairs (host)");
-  int64_t m_max = 0, md_max = 0, ms_max = 0;
-  for (int c = 0; c < count; ++c) {
-    PabState& s = p->st[(size_t)c];
-    m_max = std::max(m_max, s.m_data + s.m_sym);
-    md_max = std::max(md_max, s.m_data * PAB_LANES + s.m_sym);
-    ms_max = std::max(ms_max, s.m_sym);
-  }
-  p->N = (p->n + 63) / 64 * 64;
-  p->M = (m_max + 63) / 64 * 64;
-  p->MA = p->M + p->N;
-  // (element-wise kernels: PAB_VEC_ELEMS elements per thread, for the same reason as PABS_TAIL_ROWS)
-  p->nb_n = (int)((p->n + 256 * PAB_VEC_ELEMS - 1) / (256 * PAB_VEC_ELEMS));
-  p->nb_m = (int)((m_max + p->n + 256 * PAB_VEC_ELEMS - 1) / (256 * PAB_VEC_ELEMS));
-  if (p->sliced) {   // one workgroup per slice, then 256 symmetry (/ augmented) rows per workgroup
-    // (symmetry / augmented rows: PABS_TAIL_ROWS per thread — a workgroup's fixed costs (control word, state, reductions)
-    // are a few microseconds whatever it does, and with one row per thread these workgroups took twice the slice
-    // workgroups' share of the device)
-    p->nb_mv = p->mz + (int)((ms_max + PABS_THREADS * PABS_TAIL_ROWS - 1) / (PABS_THREADS * PABS_TAIL_ROWS));
-    p->nb_mva = p->mz + (int)((ms_max + p->n + PABS_THREADS * PABS_TAIL_ROWS - 1) / (PABS_THREADS * PABS_TAIL_ROWS));
-  } else {
-    p->nb_mv = (int)((md_max + 255) / 256);
-    p->nb_mva = (int)((md_max + p->n + 255) / 256);
-  }
-  p->nb_fin = (int)((p->n + 256 * PABL_FIN_ELEMS - 1) / (256 * PABL_FIN_ELEMS));
-  p->RB = std::max(std::max(std::max(p->nb_n, p->nb_m), p->nb_mva), p->nb_fin);
-  if (p->linear)   // (the separable form's symmetry rows are 512 per block: k_pabf_tail)
-    p->RB = std::max(p->RB, 16 * p->mz + (int)((ms_max + p->n + 256 * PABF_TAIL_ROWS - 1) / (256 * PABF_TAIL_ROWS)));
-  // uploads.  The device keeps the rows slice-major on the sliced path ((z, operation, k, j): a stable sort of the
-  // reference's (operation, k, j) order by slice); b and the pixel ids handed back to the caller stay in the reference's.
-  {
-    std::vector<int> all_rows(dev_rows ? 0 : (size_t)p->total_rows);
-    std::vector<float> all_b(dev_rows ? 0 : (size_t)p->total_rows);
-    std::vector<int> srow((size_t)count * (p->mz + 1), 0);
-    if (dev_rows) srow = srow_h;
-    if (!dev_rows) {
-      p->b_data.resize((size_t)p->total_rows);
-      p->b_pid.resize((size_t)p->total_rows);
-    }
-    std::vector<int2> all_pairs(dev_sym || p->linear ? 0 : (size_t)p->total_sym);
-    std::vector<int> order;
-    for (int c = 0; c < count; ++c) {
-      if (dev_rows) {
-        if (!dev_sym && !p->linear) std::copy(pairs_of[(size_t)c].begin(), pairs_of[(size_t)c].end(), all_pairs.begin() + p->st[(size_t)c].sym0);
-        continue;
-      }
-      const PabState& s = p->st[(size_t)c];
-      const std::vector<int>& rr = ray_of_row[(size_t)c];
-      const std::vector<float>& bb = b_of[(size_t)c];
-      std::copy(bb.begin(), bb.end(), p->b_data.begin() + s.row0);
-      std::copy(pid_of[(size_t)c].begin(), pid_of[(size_t)c].end(), p->b_pid.begin() + s.row0);
-      if (!dev_sym && !p->linear) std::copy(pairs_of[(size_t)c].begin(), pairs_of[(size_t)c].end(), all_pairs.begin() + s.sym0);
-      if (!p->sliced) {
-        std::copy(rr.begin(), rr.end(), all_rows.begin() + s.row0);
-        std::copy(bb.begin(), bb.end(), all_b.begin() + s.row0);
-        continue;
-      }
-      const std::vector<short>& zz = z_of[(size_t)c];
-      int* sr = srow.data() + (size_t)c * (p->mz + 1);
-      for (size_t r = 0; r < rr.size(); ++r) {
-        if (zz[r] < 0 || zz[r] >= p->mz) { p->err = "hh_pab_create: a row without a slice (internal)"; return bail(HH_ERR_STATE); }
-        ++sr[zz[r] + 1];
-      }
-      for (int z = 0; z < p->mz; ++z) sr[z + 1] += sr[z];
-      order.assign(rr.size(), 0);
-      std::vector<int> cur(sr, sr + p->mz);
-      for (size_t r = 0; r < rr.size(); ++r) order[(size_t)cur[zz[r]]++] = (int)r;   // counting sort: stable
-      for (size_t k = 0; k < rr.size(); ++k) {
-        all_rows[(size_t)s.row0 + k] = rr[(size_t)order[k]];
-        all_b[(size_t)s.row0 + k] = bb[(size_t)order[k]];
-      }
-    }
-    if (!dev_rows) {
-      PAB_RC(pab_alloc(p, p->d_ray_of_row, all_rows.size()));
-      PAB_RC(pab_to_device(p, p->d_ray_of_row, all_rows.data(), all_rows.size() * sizeof(int)));
-    }
-    if (p->linear) {
-      PAB_RC(pab_alloc(p, p->d_sym16, (size_t)p->total_sym));
-      for (int c = 0; c < count; ++c)   // candidate by candidate through the staging buffer (7.5 MB each at the bench size)
-        PAB_RC(pab_to_device(p, p->d_sym16 + p->st[(size_t)c].sym0, rows16_of[(size_t)c].data(), rows16_of[(size_t)c].size() * sizeof(PaEll16)));
-      std::vector<std::vector<PaEll16>>().swap(rows16_of);
-    } else if (!dev_sym) {
-      PAB_RC(pab_alloc(p, p->d_pairs, all_pairs.size()));
-      PAB_RC(pab_to_device(p, p->d_pairs, all_pairs.data(), all_pairs.size() * sizeof(int2)));
-    }
-    PAB_RC(pab_alloc(p, p->d_srow, srow.size()));
-    PAB_RC(pab_to_device(p, p->d_srow, srow.data(), srow.size() * sizeof(int)));
-    if (p->linear) {   // no map at all: the disc's table and the accumulator of A^T y
-      std::vector<unsigned> sidx2((size_t)d2 * d2);
-      for (int yy = 0; yy < d2; ++yy)
-        for (int xx = 0; xx < d2; ++xx) {
-          const int a = rank[(size_t)yy * d2 + xx], b = xx + 1 < d2 ? rank[(size_t)yy * d2 + xx + 1] : -1;   // plane 0: rank = index inside the plane
-          sidx2[(size_t)yy * d2 + xx] = (unsigned)(a < 0 ? 0xffff : a) | ((unsigned)(b < 0 ? 0xffff : b) << 16);
-        }
-      PAB_RC(pab_alloc(p, p->d_sidx2, sidx2.size()));
-      PAB_RC(pab_to_device(p, p->d_sidx2, sidx2.data(), sidx2.size() * sizeof(unsigned)));
-      PAB_RC(pab_alloc(p, p->d_acc64, (size_t)count * ((p->n + 63) / 64 * 64)));
-      PAB_TRY(hipMemsetAsync(p->d_acc64, 0, (size_t)count * ((p->n + 63) / 64 * 64) * sizeof(long long), p->stream));
-    } else if (p->sliced) {
-      PAB_RC(pab_alloc(p, p->d_map16, (size_t)p->total_rows * p->d2p));
-      PAB_TRY(hipMemsetAsync(p->d_map16, 0xff, (size_t)p->total_rows * p->d2p * sizeof(uint16_t), p->stream));
-    } else {
-      PAB_RC(pab_alloc(p, p->d_map, (size_t)p->total_rows * d2));
-    }
-    PAB_RC(pab_alloc(p, p->d_st, (size_t)count));
-    PAB_RC(pab_alloc(p, p->d_ctl, (size_t)count));
-    PAB_TRY(hipMemsetAsync(p->d_ctl, 0, (size_t)count * sizeof(unsigned), p->stream));
-    PAB_RC(pab_alloc(p, p->d_tptr, (size_t)count * (p->n + 1)));
-    PAB_RC(pab_alloc(p, p->d_nv, (size_t)NV_COUNT * count * p->N));
-    PAB_RC(pab_alloc(p, p->d_mv, (size_t)MV_COUNT * count * p->MA));
-    PAB_RC(pab_alloc(p, p->d_red, (size_t)count * PAB_SLOTS * p->RB));
-    PAB_RC(pab_alloc(p, p->d_xf, (size_t)count * p->N));   // rows padded to N floats: whole cache lines per candidate
-    PAB_RC(pab_alloc(p, p->d_flags, PAB_FLAG_WORDS));
-    PAB_RC(pab_alloc(p, p->d_lists, (size_t)2 * count));
-    PAB_TRY(hipMemsetAsync(p->d_nv, 0, (size_t)NV_COUNT * count * p->N * sizeof(double), p->stream));
-    PAB_TRY(hipMemsetAsync(p->d_mv, 0, (size_t)MV_COUNT * count * p->MA * sizeof(double), p->stream));
-    PAB_TRY(hipMemsetAsync(p->d_tptr, 0, (size_t)count * (p->n + 1) * sizeof(int), p->stream));
-    PAB_TRY(hipMemsetAsync(p->d_flags, 0, PAB_FLAG_WORDS * sizeof(int), p->stream));
-    PAB_RC(pab_to_device(p, p->d_st, p->st.data(), p->st.size() * sizeof(PabState)));
-    // right-hand sides: b of the data rows (float32 pixel values -> float64), zeros for the symmetry rows (the memset above)
-    if (!dev_rows) {   // the host path's b takes the place the device path filled
-      if (!d_b_int.ensure(all_b.size())) { p->err = "hh_pab_create: " + dev_alloc_failed(all_b.size() * sizeof(float)); return bail(HH_ERR_NOMEM); }
-      rc = pab_to_device(p, d_b_int, all_b.data(), all_b.size() * sizeof(float));
-    }
-    if (rc == HH_OK) {
-      const float* bf = d_b_int;
-      pab_vec<0>(p, CNT_MDATA, PabRed<0>{}, [] __device__(const auto&) { return true; },
-                 [bf] __device__(const PabView& w, int c, int64_t i, const PabState& s, double*) {
-                   w.mvec(MV_B, c)[i] = (double)bf[s.row0 + i];
-                 });
-      if (hipStreamSynchronize(p->stream) != hipSuccess) rc = pab_fail(p, HH_ERR_HIP, "hh_pab_create: right-hand sides failed");
-    }
-    d_b_int.reset();
-    if (rc) return bail(rc);
-  }
-  lap("row tables, buffers");
-  if (!p->linear) {  // the compact index map
-    int64_t md = 0;
-    for (const PabState& s : p->st) md = std::max(md, s.m_data);
-    hipLaunchKernelGGL(k_pab_fill_map, pab_grid((int)((md * d2 + 255) / 256), count), dim3(256), 0, p->stream, gr, p->d_st, p->d_ray_of_row,
-                       p->d_rank, p->d_map, p->d_map16, p->d_srow, p->nslice, p->d2p, p->d_flags + 9, count);
-    PAB_TRY(hipGetLastError());
-    if (p->sliced) {
-      int f[PAB_FLAG_WORDS];
-      PAB_RC(pab_poll(p, f));
-      if (f[9]) { p->err = "hh_pab_create: a ray left its slice (internal)"; return bail(HH_ERR_STATE); }
-      // rows of one (operation, image row) read one copy of their map (k_pab_share_rows)
-      PAB_RC(pab_alloc(p, p->d_maprow, (size_t)std::max<int64_t>(p->total_rows, 1)));
-      int max_ops_used = 0;
-      for (int c = 0; c < count; ++c) max_ops_used = std::max(max_ops_used, p->n_ops_used[(size_t)c]);
-      const size_t keys = (size_t)count * std::max(max_ops_used, 1) * d2;
-      DevArena tmp;
-      int* d_first = tmp.get<int>(keys);
-      int* d_second = tmp.get<int>(keys);
-      PAB_RC(pab_arena_ok(p, tmp));
-      hipError_t es = hipMemsetAsync(d_first, 0x7f, keys * sizeof(int), p->stream);
-      if (es == hipSuccess) es = hipMemsetAsync(d_second, 0x7f, keys * sizeof(int), p->stream);
-      if (es == hipSuccess) {
-        const dim3 grid = pab_grid((int)((md * 8 + 255) / 256), count);
-        hipLaunchKernelGGL(k_pab_share_rows<0>, grid, dim3(256), 0, p->stream, p->d_st, p->d_ray_of_row, p->d_map16, p->d2p, l2, d2, max_ops_used, d_first, d_second, p->d_maprow, count);
-        hipLaunchKernelGGL(k_pab_share_rows<1>, grid, dim3(256), 0, p->stream, p->d_st, p->d_ray_of_row, p->d_map16, p->d2p, l2, d2, max_ops_used, d_first, d_second, p->d_maprow, count);
-        hipLaunchKernelGGL(k_pab_share_rows<2>, grid, dim3(256), 0, p->stream, p->d_st, p->d_ray_of_row, p->d_map16, p->d2p, l2, d2, max_ops_used, d_first, d_second, p->d_maprow, count);
-        es = hipStreamSynchronize(p->stream);
-      }
-      tmp.release();
-      if (es != hipSuccess) { p->err = std::string("hh_pab_create (shared map rows): ") + hipGetErrorString(es); return bail(HH_ERR_HIP); }
-      if (timing) {
-        std::vector<int> mr((size_t)p->total_rows);
-        if (pab_to_host(p, mr.data(), p->d_maprow, mr.size() * sizeof(int)) == HH_OK) {
-          std::vector<int> u(mr);
-          std::sort(u.begin(), u.end());
-          const size_t distinct = (size_t)(std::unique(u.begin(), u.end()) - u.begin());
-          std::fprintf(stderr, "hh_pab_create[%d]: shared map rows: %zu rows read %zu distinct maps (%.1f rows per map)\n", count, mr.size(), distinct,
-                       (double)mr.size() / (double)std::max<size_t>(distinct, 1));
-        }
-      }
-    }
-  }
-  lap("index map");
-  {  // the transposed pattern (sliced path: of the symmetry rows only): count, scan, fill, sort
-    PabView w = pab_view(p);
-    int64_t span = 0;
-    for (const PabState& s : p->st) span = std::max(span, p->linear ? s.m_sym * 16 : (p->sliced ? 0 : s.m_data * d2) + s.m_sym);
-    const dim3 grid = pab_grid((int)std::max<int64_t>(1, (span + 255) / 256), count);
-    DevBuf<int> d_cursor;
-    if (!d_cursor.ensure((size_t)count * (p->n + 1))) { p->err = "hh_pab_create: " + dev_alloc_failed(d_cursor.bytes_for((size_t)count * (p->n + 1))); return bail(HH_ERR_NOMEM); }
-    if (p->linear) hipLaunchKernelGGL((k_pabl_transpose<false>), grid, dim3(256), 0, p->stream, w, p->d_tptr, (int2*)nullptr);
-    else if (p->sliced) hipLaunchKernelGGL((k_pab_transpose<false, false>), grid, dim3(256), 0, p->stream, w, p->d_tptr, (int*)nullptr);
-    else hipLaunchKernelGGL((k_pab_transpose<false, true>), grid, dim3(256), 0, p->stream, w, p->d_tptr, (int*)nullptr);
-    hipLaunchKernelGGL(k_pab_scan, dim3(count), dim3(1024), 0, p->stream, p->n, p->d_tptr, d_cursor);
-    // list lengths per candidate -> offsets of the concatenated entry array
-    std::vector<int> last((size_t)count);
-    rc = pab_stage(p, (size_t)count * sizeof(int));
-    hipError_t e = rc ? hipErrorOutOfMemory : hipSuccess;
-    // the last entry of every candidate's scan = its number of list entries: one strided copy
-    if (e == hipSuccess)
-      e = hipMemcpy2DAsync(p->h_stage, sizeof(int), p->d_tptr + p->n, (size_t)(p->n + 1) * sizeof(int), sizeof(int), (size_t)count,
-                           hipMemcpyDeviceToHost, p->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(p->stream);
-    if (e != hipSuccess) { p->err = std::string("hh_pab_create: ") + hipGetErrorString(e); return bail(HH_ERR_HIP); }
-    std::memcpy(last.data(), p->h_stage, (size_t)count * sizeof(int));
-    p->total_nnz = 0;
-    for (int c = 0; c < count; ++c) {
-      p->st[(size_t)c].t0 = p->total_nnz;
-      p->total_nnz += last[(size_t)c];
-    }
-    rc = p->linear ? pab_alloc(p, p->d_tent2, (size_t)p->total_nnz) : pab_alloc(p, p->d_tent, (size_t)p->total_nnz);
-    if (rc == HH_OK) rc = pab_to_device(p, p->d_st, p->st.data(), p->st.size() * sizeof(PabState));
-    if (rc) return bail(rc);
-    w = pab_view(p);
-    // the cursor of voxel v starts at tptr[v] (the scan is inclusive over cnt[v + 1], i.e. exclusive for v)
-    if (p->linear) {
-      hipLaunchKernelGGL((k_pabl_transpose<true>), grid, dim3(256), 0, p->stream, w, d_cursor, p->d_tent2);
-      hipLaunchKernelGGL(k_pabl_sort_lists, pab_grid((int)((p->n + 255) / 256), count), dim3(256), 0, p->stream, w, p->d_tent2);
-    } else {
-      if (p->sliced) hipLaunchKernelGGL((k_pab_transpose<true, false>), grid, dim3(256), 0, p->stream, w, d_cursor, p->d_tent);
-      else hipLaunchKernelGGL((k_pab_transpose<true, true>), grid, dim3(256), 0, p->stream, w, d_cursor, p->d_tent);
-      hipLaunchKernelGGL(k_pab_sort_lists, pab_grid((int)((p->n + 255) / 256), count), dim3(256), 0, p->stream, w, p->d_tent);
-    }
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipStreamSynchronize(p->stream);
-    d_cursor.reset();
-    if (e != hipSuccess) { p->err = std::string("hh_pab_create: ") + hipGetErrorString(e); return bail(HH_ERR_HIP); }
-  }
-  lap("transposed lists");
-  if (p->linear && d2 <= 128 && !p->band_T) {
-    // ---- the separable form of the trilinear data rows (path_a_factored.inc) ----------------------------------------------------
-    // per (candidate, operation, image column): axial data, the hash of its samples' cell decisions, its first row and the
-    // image rows that have a ray — computed on the device, grouped into footprint lists and column groups on the host
-    // (4k entries per candidate), then the lists' samples are written by the device
-    int G = 4;   // (+ 26 KB for the group's list table, sized below)
-    while (G > 1 && (size_t)(G + 1) * p->nslice * sizeof(double) > ((size_t)120 << 10)) --G;
-    const int ng = std::max(1, (p->mz - 1 + G - 1) / G);
-    int max_ops = 0;
-    for (int c = 0; c < count; ++c) max_ops = std::max(max_ops, p->n_ops_used[(size_t)c]);
-    const size_t cells = (size_t)count * max_ops * l2;
-    DevArena tmp;   // freed on every way out
-    PabfZinfo* d_zi = tmp.get<PabfZinfo>(cells);
-    unsigned long long* d_hash = tmp.get<unsigned long long>(cells);
-    unsigned long long* d_jm = tmp.get<unsigned long long>(cells * 2);
-    int* d_rb = tmp.get<int>(cells);
-    int* d_nused = tmp.get<int>((size_t)count);
-    PAB_RC(pab_arena_ok(p, tmp));
-    hipError_t e = hipMemsetAsync(d_hash, 0, cells * 8, p->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(d_jm, 0, cells * 16, p->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(d_rb, 0x7f, cells * 4, p->stream);
-    if (e != hipSuccess) { p->err = std::string("hh_pab_create (footprint lists): ") + hipGetErrorString(e); return bail(HH_ERR_HIP); }
-    PAB_RC(pab_to_device(p, d_nused, p->n_ops_used.data(), (size_t)count * sizeof(int)));
-    hipLaunchKernelGGL(k_pabf_zinfo, dim3((unsigned)((l2 + 127) / 128), (unsigned)max_ops, (unsigned)count), dim3(128), 0, p->stream, gr, count, max_ops,
-                       d_nused, d_zi);
-    hipLaunchKernelGGL(k_pabf_cellhash, dim3((unsigned)l2, (unsigned)max_ops, (unsigned)count), dim3(128), 0, p->stream, gr, count, max_ops, d_nused,
-                       p->d_sidx2, d_hash);
-    {
-      int64_t md = 0;
-      for (const PabState& st : p->st) md = std::max(md, st.m_data);
-      hipLaunchKernelGGL(k_pabf_rowbase, pab_grid((int)((md + 255) / 256), count), dim3(256), 0, p->stream, pab_view(p), max_ops, d_rb, d_jm);
-    }
-    std::vector<PabfZinfo> zi(cells);
-    std::vector<unsigned long long> hash(cells), jm(cells * 2);
-    std::vector<int> rb(cells);
-    rc = pab_to_host(p, zi.data(), d_zi, cells * sizeof(PabfZinfo));
-    if (rc == HH_OK) rc = pab_to_host(p, hash.data(), d_hash, cells * 8);
-    if (rc == HH_OK) rc = pab_to_host(p, jm.data(), d_jm, cells * 16);
-    if (rc == HH_OK) rc = pab_to_host(p, rb.data(), d_rb, cells * 4);
-    tmp.release();
-    if (rc) return bail(rc);
-    lap("separable form: axial data, cell hashes");
-    // lists: (operation, z mask, cell hash) of the (o, k) that have rows; groups: home / G
-    std::vector<std::vector<PabfListRef>> lists((size_t)count);
-    std::vector<std::vector<std::vector<PabfGroupList>>> groups((size_t)count);
-    int max_lists = 1, max_gl = 1;
-    for (int c = 0; c < count; ++c) {
-      struct Key { int op; unsigned long long m0, m1, h; };
-      std::vector<Key> keys;
-      std::vector<PabfListRef>& ls = lists[(size_t)c];
-      std::vector<std::vector<PabfGroupList>>& gs = groups[(size_t)c];
-      gs.assign((size_t)ng, {});
-      for (int o = 0; o < p->n_ops_used[(size_t)c]; ++o)
-        for (int k = 0; k < l2; ++k) {
-          const size_t at = ((size_t)c * max_ops + o) * l2 + k;
-          if (rb[at] == 0x7f7f7f7f) continue;   // no ray of this (operation, column) has a row
-          const PabfZinfo& z = zi[at];
-          int li = -1;
-          for (size_t t = 0; t < keys.size(); ++t)
-            if (keys[t].op == o && keys[t].m0 == z.zmask[0] && keys[t].m1 == z.zmask[1] && keys[t].h == hash[at]) { li = (int)t; break; }
-          if (li < 0) {
-            li = (int)keys.size();
-            keys.push_back({o, z.zmask[0], z.zmask[1], hash[at]});
-            PabfListRef lr{};
-            lr.op = o; lr.k = k; lr.zmask[0] = z.zmask[0]; lr.zmask[1] = z.zmask[1];
-            ls.push_back(lr);
-          }
-          const int g = z.home / G;
-          if (g >= ng) { p->err = "hh_pab_create: a home layer beyond the groups (internal)"; return bail(HH_ERR_STATE); }
-          std::vector<PabfGroupList>& gg = gs[(size_t)g];
-          PabfGroupList* slot = nullptr;
-          for (PabfGroupList& cand_ : gg)
-            if (cand_.list == li && cand_.nk < PABF_KMAX) { slot = &cand_; break; }
-          if (!slot) { gg.push_back(PabfGroupList{}); slot = &gg.back(); slot->list = li; slot->nk = 0; }
-          PabfRowRef& r = slot->e[slot->nk++];
-          r.rowbase = rb[at];
-          r.hp = z.home - g * G;
-          r.jmask[0] = jm[2 * at]; r.jmask[1] = jm[2 * at + 1];
-          r.cz0 = z.cz0; r.cz1 = z.cz1;
-        }
-      max_lists = std::max<int>(max_lists, (int)ls.size());
-      for (const auto& gg : gs) max_gl = std::max<int>(max_gl, (int)gg.size());
-    }
-    {
-      std::vector<PabfListRef> all_lists((size_t)count * max_lists);
-      std::vector<int> n_lists((size_t)count), ngl((size_t)count * ng);
-      std::vector<PabfGroupList> all_gl((size_t)count * ng * max_gl);
-      for (int c = 0; c < count; ++c) {
-        n_lists[(size_t)c] = (int)lists[(size_t)c].size();
-        std::copy(lists[(size_t)c].begin(), lists[(size_t)c].end(), all_lists.begin() + (size_t)c * max_lists);
-        for (int g = 0; g < ng; ++g) {
-          const auto& gg = groups[(size_t)c][(size_t)g];
-          ngl[(size_t)c * ng + g] = (int)gg.size();
-          std::copy(gg.begin(), gg.end(), all_gl.begin() + ((size_t)c * ng + g) * max_gl);
-        }
-      }
-      DevArena tmp;   // freed on every way out
-      PabfListRef* d_lists = tmp.get<PabfListRef>(all_lists.size());
-      int* d_nlists = tmp.get<int>((size_t)count);
-      PAB_RC(pab_arena_ok(p, tmp));
-      rc = pab_to_device(p, d_lists, all_lists.data(), all_lists.size() * sizeof(PabfListRef));
-      if (rc == HH_OK) rc = pab_to_device(p, d_nlists, n_lists.data(), n_lists.size() * sizeof(int));
-      if (rc == HH_OK) rc = pab_alloc(p, p->d_fac_ngl, ngl.size());
-      if (rc == HH_OK) rc = pab_to_device(p, p->d_fac_ngl, ngl.data(), ngl.size() * sizeof(int));
-      if (rc == HH_OK) rc = pab_alloc(p, p->d_fac_gl, all_gl.size());
-      if (rc == HH_OK) rc = pab_to_device(p, p->d_fac_gl, all_gl.data(), all_gl.size() * sizeof(PabfGroupList));
-      if (rc == HH_OK) rc = pab_alloc(p, p->d_fac_entries, (size_t)count * max_lists * d2 * d2);
-      if (rc == HH_OK) rc = pab_alloc(p, p->d_fac_count, (size_t)count * max_lists * d2);
-      if (rc) return bail(rc);
-      hipLaunchKernelGGL(k_pabf_entries, dim3((unsigned)((d2 + 63) / 64), (unsigned)max_lists, (unsigned)count), dim3(64), 0, p->stream, gr, count,
-                         max_lists, d_nlists, d_lists, p->d_sidx2, p->d_fac_entries, p->d_fac_count);
-      const hipError_t e3 = hipStreamSynchronize(p->stream);
-      if (e3 != hipSuccess) { p->err = std::string("hh_pab_create (footprint lists): ") + hipGetErrorString(e3); return bail(HH_ERR_HIP); }
-    }
-    p->fac_G = G; p->fac_ng = ng; p->fac_max_gl = max_gl; p->fac_max_lists = max_lists;
-    p->fac_lds = (size_t)(G + 1) * p->nslice * sizeof(double) + (size_t)max_gl * sizeof(PabfGroupList);
-    if (p->fac_lds > ((size_t)160 << 10) && (flags & HH_PAB_ALLOW_BANDED)) {   // the banded form instead (cut below)
-      p->d_fac_ngl.reset(); p->d_fac_gl.reset(); p->d_fac_entries.reset(); p->d_fac_count.reset();
-      p->fac_G = 0;
-      p->band_T = -1;
-    } else if (p->fac_lds > ((size_t)160 << 10)) {
-      p->err = "hh_pab_create: not sliceable — the planes and the list table of a group do not fit the LDS";
-      return bail(HH_ERR_ARG);
-    }
-    // the forward product's blocks: the groups, then the symmetry (/ augmented) rows
-    if (p->fac_G) {
-      int64_t ms_max = 0;
-      for (const PabState& st : p->st) ms_max = std::max(ms_max, st.m_sym);
-      p->fac_split = std::max(1, std::min(8, (16 + ng - 1) / ng));   // about sixteen workgroups per candidate and product
-      p->nb_mv = ng * p->fac_split + (int)((ms_max + 256 * PABF_TAIL_ROWS - 1) / (256 * PABF_TAIL_ROWS));
-      p->nb_mva = ng * p->fac_split + (int)((ms_max + p->n + 256 * PABF_TAIL_ROWS - 1) / (256 * PABF_TAIL_ROWS));
-      if (p->nb_mva > p->RB) { p->err = "hh_pab_create: more partial sums than planned (internal)"; return bail(HH_ERR_STATE); }
-    }
-    if (timing && p->fac_G) {
-      size_t nl = 0, ngl_tot = 0, nk_tot = 0;
-      for (int c = 0; c < count; ++c) {
-        nl += lists[(size_t)c].size();
-        for (const auto& gg : groups[(size_t)c]) { ngl_tot += gg.size(); for (const auto& e_ : gg) nk_tot += (size_t)e_.nk; }
-      }
-      std::fprintf(stderr, "hh_pab_create[%d]: separable form: G %d, %d groups, lists per candidate %.1f (max %d), group lists per group %.1f (max %d), "
-                           "rows per group list %.2f, operations used (max) %d\n", count, G, ng, (double)nl / count, max_lists,
-                   (double)ngl_tot / count / ng, max_gl, ngl_tot ? (double)nk_tot / ngl_tot : 0.0, max_ops);
-    }
-    lap("separable form: lists and column groups");
-  }
-  if (p->linear && p->band_T) {
-    // ---- the banded form (path_a_banded.inc): cut the disc's rows into bands whose planes, halo row and table rows fit --------
-    std::vector<int> vrow((size_t)d2 + 1, 0);   // first in-plane index of every row (plane 0: rank = index inside the plane)
-    for (int yy = 0; yy < d2; ++yy) {
-      int cnt = 0;
-      for (int xx = 0; xx < d2; ++xx) cnt += rank[(size_t)yy * d2 + xx] >= 0;
-      vrow[(size_t)yy + 1] = vrow[(size_t)yy] + cnt;
-    }
-    auto band_bytes = [&](int ya, int yb) {   // base rows [ya, yb): rows [ya, yb + 1) staged
-      const int ye = std::min(yb + 1, d2);
-      return (size_t)2 * (vrow[(size_t)ye] - vrow[(size_t)ya]) * sizeof(double) + (size_t)(ye - ya) * d2 * sizeof(unsigned);
-    };
-    size_t budget = (size_t)150 << 10;
-    if (flags & HH_PAB_FORCE_BANDED) {   // at least three bands, whatever the box
-      size_t row_max = 0;
-      for (int yy = 0; yy < d2; ++yy) row_max = std::max(row_max, band_bytes(yy, yy + 1));
-      budget = std::min(budget, std::max(row_max, band_bytes(0, d2) / 3));
-    }
-    std::vector<int> band_y{0};
-    while (band_y.back() < d2) {
-      const int ya = band_y.back();
-      if (band_bytes(ya, ya + 1) > budget) { p->err = "hh_pab_create: not sliceable — one row of the disc does not fit the LDS"; return bail(HH_ERR_ARG); }
-      int yb = ya + 1;
-      while (yb < d2 && band_bytes(ya, yb + 1) <= budget) ++yb;
-      band_y.push_back(yb);
-    }
-    p->band_T = (int)band_y.size() - 1;
-    // the kernels lay a band out by its own size (planes, then table rows), so the launch needs the largest band's bytes —
-    // each at most the budget; with the static state the whole must fit a compute unit's 160 KiB
-    p->band_lds = 0;
-    for (int t = 0; t < p->band_T; ++t) p->band_lds = std::max(p->band_lds, band_bytes(band_y[(size_t)t], band_y[(size_t)t + 1]));
-    if (p->band_lds > budget || p->band_lds + sizeof(PabState) > ((size_t)160 << 10)) {
-      p->err = "hh_pab_create: not sliceable — a band of the disc does not fit the LDS (internal)";
-      return bail(HH_ERR_STATE);
-    }
-    PAB_RC(pab_alloc(p, p->d_band_y, band_y.size()));
-    PAB_RC(pab_to_device(p, p->d_band_y, band_y.data(), band_y.size() * sizeof(int)));
-    PAB_RC(pab_alloc(p, p->d_band_v, vrow.size()));
-    PAB_RC(pab_to_device(p, p->d_band_v, vrow.data(), vrow.size() * sizeof(int)));
-    PAB_RC(pab_alloc(p, p->d_bpart, (size_t)count * p->band_T * p->M));
-    if (timing)
-      std::fprintf(stderr, "hh_pab_create[%d]: banded form: %d bands, %zu bytes of LDS\n", count, p->band_T, p->band_lds);
-    lap("banded form");
-  }
-  if (p->linear) {  // largest column sum of |A_data| per candidate, in 2^-20 units (the trilinear weights are not counts)
-    DevArena tmp;
-    long long* d_colmax = tmp.get<long long>((size_t)count);
-    PAB_RC(pab_arena_ok(p, tmp));
-    hipError_t e = hipMemsetAsync(d_colmax, 0, (size_t)count * sizeof(long long), p->stream);
-    auto all = [] __device__(const auto&) { return true; };
-    if (p->fac_G) {
-      auto launch = [&](auto kernel) {
-        pab_lds_attr(p, kernel, p->fac_lds);
-        hipLaunchKernelGGL(kernel, pab_grid(p->fac_ng * p->fac_split, count), dim3(PABS_THREADS), p->fac_lds, p->stream, pab_view(p), 0, all);
-      };
-      switch (p->fac_G) {
-        case 1: launch(k_pabf_scatter<0, true, 1, decltype(all)>); break;
-        case 2: launch(k_pabf_scatter<0, true, 2, decltype(all)>); break;
-        case 3: launch(k_pabf_scatter<0, true, 3, decltype(all)>); break;
-        default: launch(k_pabf_scatter<0, true, 4, decltype(all)>); break;
-      }
-    } else if (p->band_T) {
-      pab_lds_attr(p, k_pabt_scatter<0, true, decltype(all)>, p->band_lds);
-      hipLaunchKernelGGL((k_pabt_scatter<0, true, decltype(all)>), pab_grid(p->mz * p->band_T, count), dim3(PABS_THREADS), p->band_lds, p->stream,
-                         pab_view(p), 0, all);
-    } else {
-      pab_lds_attr(p, k_pabl_scatter<0, true, decltype(all)>, p->lin_lds);
-      hipLaunchKernelGGL((k_pabl_scatter<0, true, decltype(all)>), pab_grid(p->mz, count), dim3(PABS_THREADS), p->lin_lds, p->stream, pab_view(p), 0, all);
-    }
-    hipLaunchKernelGGL((k_pabl_finish<2, decltype(all)>), pab_grid(p->nb_fin, count), dim3(256), 0, p->stream, pab_view(p), 0, -1, -1, 0, d_colmax, all);
-    if (e == hipSuccess) e = hipGetLastError();
-    std::vector<long long> colmax((size_t)count, 0);
-    rc = e == hipSuccess ? pab_to_host(p, colmax.data(), d_colmax, colmax.size() * sizeof(long long)) : pab_fail(p, HH_ERR_HIP, hipGetErrorString(e));
-    tmp.release();
-    if (rc) return bail(rc);
-    for (int c = 0; c < count; ++c) {
-      PabState& s = p->st[(size_t)c];
-      s.colsum = std::ldexp((double)colmax[(size_t)c], -20) * (1.0 + 1e-3) + 1e-3;   // (as hh_pa sizes it)
-      pab_fx_scale(s.colsum, 1.0, s.fx_scale, s.fx_inv);
-      s.fx_scale_r = s.fx_scale;
-      s.fx_inv_r = s.fx_inv;
-    }
-    PAB_RC(pab_to_device(p, p->d_st, p->st.data(), p->st.size() * sizeof(PabState)));
-    lap("column sums");
-  } else if (p->sliced) {  // largest column sum of |A_data| per candidate (hit counts): sizes the fixed-point scale of A^T y
-    DevArena tmp;
-    int* d_colmax = tmp.get<int>((size_t)count);
-    PAB_RC(pab_arena_ok(p, tmp));
-    hipError_t e = hipMemsetAsync(d_colmax, 0, (size_t)count * sizeof(int), p->stream);
-    auto all = [] __device__(const auto&) { return true; };
-    hipLaunchKernelGGL((k_pabs_rmatvec<0, true, decltype(all)>), pab_grid(p->mz, count), dim3(PABS_THREADS), (size_t)p->nslice * sizeof(long long), p->stream,
-                       pab_view(p), 0, -1, -1, 0, d_colmax, all);
-    if (e == hipSuccess) e = hipGetLastError();
-    std::vector<int> colmax((size_t)count, 0);
-    rc = e == hipSuccess ? pab_to_host(p, colmax.data(), d_colmax, colmax.size() * sizeof(int)) : pab_fail(p, HH_ERR_HIP, hipGetErrorString(e));
-    tmp.release();
-    if (rc) return bail(rc);
-    for (int c = 0; c < count; ++c) {
-      PabState& s = p->st[(size_t)c];
-      s.colsum = (double)std::max(1, colmax[(size_t)c]);
-      pab_fx_scale(s.colsum, 1.0, s.fx_scale, s.fx_inv);
-      s.fx_scale_r = s.fx_scale;
-      s.fx_inv_r = s.fx_inv;
-    }
-    PAB_RC(pab_to_device(p, p->d_st, p->st.data(), p->st.size() * sizeof(PabState)));
-    lap("column sums");
-  }
-#undef PAB_TRY
-#undef PAB_RC
   guard.p = nullptr;
   *out = p;
   return HH_OK;
