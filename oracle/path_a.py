@@ -143,7 +143,9 @@ def hcsym_order(twist_degree, rise_pixel, csym, reconstruct_length_3d_pixel, nz)
 def build_A_data_matrix(image, scale2d_to_3d, twist_degree, rise_pixel, csym, tilt_degree, psi_degree, dy_pixel,
                         reconstruct_diameter_2d_pixel, reconstruct_length_2d_pixel, reconstruct_diameter_3d_pixel,
                         reconstruct_diameter_3d_inner_pixel, reconstruct_length_3d_pixel, min_projection_lines,
-                        interpolation="nn"):
+                        interpolation="nn", dtype=np.float32):
+    """``dtype=np.float64`` keeps the trilinear branch's summed float64 weights instead of rounding them to the float32 the
+    reference stores (hit counts are exact in either)."""
     assert interpolation in ("nn", "linear"), "the oracle restates the nearest-neighbour and the trilinear branch"
     (X0, Y0, Z0), pixel_vals = back_project_2d_coords_to_3d_coords(image, scale2d_to_3d, reconstruct_diameter_2d_pixel,
                                                                    reconstruct_length_2d_pixel)
@@ -190,7 +192,7 @@ def build_A_data_matrix(image, scale2d_to_3d, twist_degree, rise_pixel, csym, ti
             if n_rows:
                 m64 = csr_matrix((vals, (rows, cols)), shape=(n_rows, n_x), dtype=np.float64)
                 m64.sum_duplicates()
-                blocks.append(m64.astype(np.float32))
+                blocks.append(m64.astype(dtype))
         else:
             zi, yi, xi = np.rint(Z).astype(np.int64), np.rint(Y).astype(np.int64), np.rint(X).astype(np.int64)
             ok = (zi >= 0) & (zi <= mz - 1) & (yi >= 0) & (yi <= my - 1) & (xi >= 0) & (xi <= mx - 1)
@@ -204,8 +206,8 @@ def build_A_data_matrix(image, scale2d_to_3d, twist_degree, rise_pixel, csym, ti
             cols = idx[hit]
             n_rows = int(has.sum())
             if n_rows:
-                blocks.append(csr_matrix((np.ones(len(cols), dtype=np.float32), (rows, cols)), shape=(n_rows, n_x),
-                                         dtype=np.float32))   # duplicates add up: an entry is a hit count
+                blocks.append(csr_matrix((np.ones(len(cols), dtype=dtype), (rows, cols)), shape=(n_rows, n_x),
+                                         dtype=dtype))   # duplicates add up: an entry is a hit count
         if n_rows:
             k_idx, j_idx = np.nonzero(has)
             bs.append(pixel_vals[j_idx, k_idx].astype(np.float32))
@@ -216,7 +218,8 @@ def build_A_data_matrix(image, scale2d_to_3d, twist_degree, rise_pixel, csym, ti
     return vstack(blocks).tocsr(), np.concatenate(bs).astype(np.float32), np.concatenate(pids)
 
 
-def _build_A_helical_sym_matrix_linear(nz, ny, nx, twist_degree, rise_pixel, csym, rmin, rmax, min_sym_pairs):
+def _build_A_helical_sym_matrix_linear(nz, ny, nx, twist_degree, rise_pixel, csym, rmin, rmax, min_sym_pairs,
+                                       dtype=np.float32):
     """The trilinear branch (solver:910-1140), quirks included: a pair counts only when |dz|, |dy| and |dx| of the two
     truncated positions are all >= 3; de-duplication by the ROUNDED positions' ranks; the weights of corners 110 and 111
     are xf*yf*(1-xf) and xf*yf*zf."""
@@ -283,14 +286,17 @@ def _build_A_helical_sym_matrix_linear(nz, ny, nx, twist_degree, rise_pixel, csy
             break
     if not row_count:
         return None, None
-    A = csr_matrix((np.asarray(vals, dtype=np.float32), (r_idx, c_idx)), shape=(row_count, n_x), dtype=np.float32)
+    # (float32: every weight is rounded first, then duplicates add up in float32, as the reference's csr_matrix does; float64
+    # keeps the weights and their sums)
+    A = csr_matrix((np.asarray(vals, dtype=dtype), (r_idx, c_idx)), shape=(row_count, n_x), dtype=dtype)
     return A, np.zeros(row_count, dtype=np.float32)
 
 
 def build_A_helical_sym_matrix(nz, ny, nx, twist_degree, rise_pixel, csym, rmin, rmax, min_sym_pairs,
-                               interpolation="nn"):
+                               interpolation="nn", dtype=np.float32):
+    """``dtype=np.float64``: the trilinear rows keep their float64 weights (the +-1 pairs are exact in either)."""
     if interpolation == "linear":
-        return _build_A_helical_sym_matrix_linear(nz, ny, nx, twist_degree, rise_pixel, csym, rmin, rmax, min_sym_pairs)
+        return _build_A_helical_sym_matrix_linear(nz, ny, nx, twist_degree, rise_pixel, csym, rmin, rmax, min_sym_pairs, dtype)
     assert interpolation == "nn"
     pairs = sorted_hsym_csym_pairs(twist_degree, rise_pixel, csym, nz)
     mask, (Z, Y, X) = get_cylindrical_mask(nz, ny, nx, rmin=rmin, rmax=rmax, return_xyz=True)
@@ -337,8 +343,8 @@ def build_A_helical_sym_matrix(nz, ny, nx, twist_degree, rise_pixel, csym, rmin,
     if not row_count:
         return None, None
     r = np.arange(row_count)
-    A = csr_matrix((np.r_[np.ones(row_count, np.float32), -np.ones(row_count, np.float32)],
-                    (np.r_[r, r], np.r_[rows_i, rows_j])), shape=(row_count, n_x), dtype=np.float32)
+    A = csr_matrix((np.r_[np.ones(row_count, dtype), -np.ones(row_count, dtype)],
+                    (np.r_[r, r], np.r_[rows_i, rows_j])), shape=(row_count, n_x), dtype=dtype)
     return A, np.zeros(row_count, dtype=np.float32)
 
 

@@ -6,6 +6,7 @@ import pytest
 
 from helicon_amd.solver import PathABatch, PathAProblem, hh_pa_params, lsq_reconstruct, lsq_reconstruct_batch
 from oracle import path_a as A
+from tests import path_a_product_cases as C
 
 pytestmark = pytest.mark.gpu
 
@@ -39,6 +40,7 @@ def test_batch_reproduces_the_reference_scores(golden_dir, product_path):
         assert score == pytest.approx(float(want), abs=1e-4), tw
         if tw == 29.0:
             assert np.abs(maps[0] - g["helix_rec3d_29"]).max() < 5e-3 * np.abs(g["helix_rec3d_29"]).max()
+    assert stats["products"] == product_path      # the parameter means the form the solve ran
     assert stats["launches"] > 0 and stats["host_syncs"] < stats["launches"] / 8    # the host only polls
     assert all(st in (1, 2, 3, -1, 0) for st, *_ in stats["info"])
 
@@ -67,14 +69,25 @@ def test_batch_composition_and_runs_do_not_change_a_candidate(golden_dir):
 
 def test_batch_against_the_oracle_with_mixed_candidates(golden_dir, product_path):
     """Candidates that differ in twist, rise AND csym, bounded and unbounded, clipped prediction: each equals the oracle's
-    lsq_reconstruct (scores 1e-4; the unbounded ones 1e-5, they are a single LSMR solve)."""
+    lsq_reconstruct (scores 1e-4; the unbounded ones 1e-5, they are a single LSMR solve).
+
+    A rise of 2.5 puts the axial coordinate of every second operation on half-integers, where a ray rounds into two slices and
+    the whole batch silently takes the general products — under either parameter.  So the sliced parameter has a list of its
+    own, twist, rise and csym still all varying, with non-integer rises (2.4, 1.6) whose multiples never end in .5 (checked
+    below by the predicate of tests/path_a_product_cases.py over every operation), and both assert the form the solve ran."""
     g = np.load(golden_dir / "g5_lsq.npz")
     img = g["helix_image"]
     kw = dict(reconstruct_diameter_2d_pixel=20, reconstruct_diameter_3d_pixel=20, reconstruct_length_2d_pixel=32,
               reconstruct_length_3d_pixel=6)
     cands = [(29.0, 2.0, 1), (31.0, 2.5, 1), (58.0, 4.0, 2), (-29.0, 2.0, 1), (27.5, 1.7, 1)]
+    if product_path == "sliced":
+        cands = [(29.0, 2.0, 1), (31.0, 2.4, 1), (58.0, 4.0, 2), (-29.0, 2.0, 1), (27.5, 1.6, 1)]
+        for cand in cands:
+            assert C.stays_sliced(C.Case((20, 32, 20, 0, 6), cand, 1.0, 0.0, 0.0, 0.0, C.ALL, 0, "nn", 0, 0, "sliced", False)), cand
     for pc, tol in ((-1, 1e-4), (0, 1e-5), (1, 1e-4)):
-        res = lsq_reconstruct_batch(img, 1.0, cands, positive_constraint=pc, thresh_fraction=0.0, **kw)
+        stats = {}
+        res = lsq_reconstruct_batch(img, 1.0, cands, positive_constraint=pc, thresh_fraction=0.0, stats=stats, **kw)
+        assert stats["products"] == product_path
         for (maps, score), (tw, rs, cs) in zip(res, cands):
             (rec_o, _, _), s_o = A.lsq_reconstruct(img, 1.0, tw, rs, cs, positive_constraint=pc, thresh_fraction=0.0, **kw)
             assert score == pytest.approx(s_o, abs=tol), (pc, tw, rs, cs)

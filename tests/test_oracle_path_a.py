@@ -175,3 +175,54 @@ def test_g11_half_set_solves(golden_dir):
         for got, name in ((rec, "rec"), (r1, "rec1"), (r2, "rec2")):
             want = g[f"mode{mode}_{name}"]
             assert np.abs(got - want).max() < 1e-2 * np.abs(want).max(), (mode, name)
+
+
+def test_g22_grid_of_corners(golden_dir):
+    """Fixture G22 (tests/golden/make_golden_path_a_grid.py): the reference's own build_A_data_matrix and
+    build_A_helical_sym_matrix at the corners of tests/path_a_product_cases.py — scales 0.8 / 0.5 / 1.25, quarter turns, odd
+    sides, a hole, dy, tilt / psi, rises longer and much shorter than the box, both interpolations.  The default (float32)
+    oracle reproduces the reference's products to 1e-12 max(1, max |ref|); b, pixel ids and shapes exactly (the number of
+    stored entries is not compared: at scale 1.25 / twist 90 the two differ in ~1e-16 entries that one side stores and the
+    other has as exact zeros); and the float64 oracle rounds to the float32 one entry for entry."""
+    from tests import path_a_product_cases as C
+
+    g = np.load(golden_dir / "g22_path_a_grid.npz")
+    assert int(g["n_cases"][0]) == len(C.G22)
+
+    def check_products(M, tag, k):
+        assert M.shape == tuple(g[f"case{k}_{tag}_shape"])
+        M64 = M.tocsr().astype(np.float64)
+        for got, want in ((M64 @ g[f"case{k}_{tag}_x"], g[f"case{k}_{tag}_Ax"]), (M64.T @ g[f"case{k}_{tag}_y"], g[f"case{k}_{tag}_ATy"])):
+            assert np.abs(got - want).max() <= 1e-12 * max(1.0, np.abs(want).max()), (k, tag)
+
+    def check_rounding(M64, M32, k):
+        assert M64.dtype == np.float64 and M32.dtype == np.float32
+        # (entry for entry through the dense arrays: whether a ~1e-16 entry is stored does not matter)
+        np.testing.assert_array_equal(M64.toarray().astype(np.float32), M32.toarray(), err_msg=str(k))
+
+    for k, c in enumerate(C.G22):
+        img, interp = g[f"case{k}_image"], "linear" if g[f"case{k}_linear"][0] else "nn"
+        a = g[f"case{k}_args"]
+        args = (a[0], a[1], a[2], int(a[3]), a[4], a[5], a[6], *(int(v) for v in a[7:13]), interp)
+        assert args == C.data_args(c) and np.array_equal(img, C.image(c))      # the table's case is the fixture's
+        Ad, b, pid = A.build_A_data_matrix(img, *args)
+        np.testing.assert_array_equal(b, g[f"case{k}_b"])
+        np.testing.assert_array_equal(pid, g[f"case{k}_pid"])
+        assert b.dtype == g[f"case{k}_b"].dtype and Ad.dtype == np.float32
+        check_products(Ad, "data", k)
+        Ad64, b64, pid64 = A.build_A_data_matrix(img, *args, dtype=np.float64)
+        np.testing.assert_array_equal(b64, b)
+        np.testing.assert_array_equal(pid64, pid)
+        check_rounding(Ad64, Ad, k)
+        if not c.min_sym:
+            continue
+        s = g[f"case{k}_sym_args"]
+        sargs = (int(s[0]), int(s[1]), int(s[2]), s[3], s[4], int(s[5]), s[6], s[7], int(s[8]), interp)
+        assert sargs == C.sym_args(c)
+        As, _ = A.build_A_helical_sym_matrix(*sargs)
+        As64, _ = A.build_A_helical_sym_matrix(*sargs, dtype=np.float64)
+        if int(g[f"case{k}_sym_shape"][0]) == 0:
+            assert As is None and As64 is None
+            continue
+        check_products(As, "sym", k)
+        check_rounding(As64, As, k)
