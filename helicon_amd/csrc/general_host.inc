@@ -188,11 +188,6 @@ int gen_set_reference(hh_ctx* c, const float* images, int n_segments, const uint
   return HH_OK;
 }
 
-// The sweep: the list is cut into maximal runs of candidates that share (twist, csym, rot); consecutive runs go into
-// one batch (bounded by GEN_BATCH candidates): one table launch, one factor launch, one fused launch per segment.
-constexpr int64_t GEN_BATCH = 65536;
-constexpr int64_t GEN_SEG_BYTES = (int64_t)8 << 30;   // several segments: most bytes of masked q one batch may hold
-
 // Candidates with out-of-plane tilt or in-plane rotation on a general image size (simulate_helical_projection takes any
 // (ny, nx) with any tilt / psi, utils.py:31-47, 166-170): the shared-twist tables need tilt = psi = 0, so these go the
 // direct way, candidate by candidate — the lattice's centres and the pixel raster of hh_simulate, the float64 direct
@@ -248,36 +243,258 @@ int gen_sweep_direct(hh_ctx* c, const double* d_params, const double* h_params, 
   return HH_OK;
 }
 
-int gen_sweep(hh_ctx* c, const double* d_params, const double* h_params, int64_t n_cand, float* d_scores, int64_t ld) {
+// The HH_GEN_* switches (the A/B switches of the tests), read once per sweep.
+struct GenSwitches {
+  bool direct, seg_loop, stockham;
+};
+GenSwitches gen_switches() {
+  return GenSwitches{std::getenv("HH_GEN_DIRECT") != nullptr, std::getenv("HH_GEN_SEG_LOOP") != nullptr,
+                     std::getenv("HH_GEN_STOCKHAM") != nullptr};
+}
+
+auto gen_fused_kernel(const GenDims& d) -> void (*)(GenFusedArgs) {
+  return d.nx <= 256 ? k_gen_fused<4> : d.nx <= 512 ? k_gen_fused<8> : k_gen_fused<16>;
+}
+
+// The same list as last time (the reference app sweeps one grid over every class average): the run structure, the
+// launch plan and the small device arrays of the last sweep are still right — checked by comparing the list with the
+// copy kept from then (on the device for a device-only list: four bytes come back instead of the list).
+int gen_same_list(hh_ctx* c, const GenSwitches& sw, int64_t batch_cap, const double* d_params, const double* h_params,
+                  int64_t n_cand, bool* reuse) {
+  hh_gen* g = c->gen;
+  *reuse = false;
+  if (!(g->plan_valid && g->plan_n == n_cand && std::memcmp(&g->plan_geom, &c->geom, sizeof(DevGeom)) == 0 &&
+        g->plan_stockham == sw.stockham && g->plan_batch_cap == batch_cap))
+    return HH_OK;
+  if (h_params) {
+    *reuse = std::memcmp(h_params, g->plan_params.data(), (size_t)n_cand * 4 * sizeof(double)) == 0;
+    return HH_OK;
+  }
+  int differ = 1;
+  HH_HIP(c, hipMemsetAsync(g->d_differ, 0, sizeof(int), c->stream));
+  hipLaunchKernelGGL(k_gen_same_list, dim3((unsigned)std::min<int64_t>(1024, (n_cand * 4 + 255) / 256)), dim3(256), 0, c->stream,
+                     reinterpret_cast<const unsigned long long*>(d_params), reinterpret_cast<const unsigned long long*>(g->d_plan_params.get()),
+                     n_cand * 4, g->d_differ);
+  HH_HIP(c, hipMemcpyAsync(&differ, g->d_differ, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HH_HIP(c, hipStreamSynchronize(c->stream));
+  *reuse = differ == 0;
+  return HH_OK;
+}
+
+// One batch holds the whole list: keep its plan for the next sweep.
+int gen_keep_plan(hh_ctx* c, const GenSwitches& sw, int64_t batch_cap, const GenBatchPlan& bp, const double* d_params,
+                  const double* h_params, int64_t n_cand) {
+  hh_gen* g = c->gen;
+  g->last = bp;
+  g->plan_n = n_cand;
+  g->plan_geom = c->geom;
+  g->plan_stockham = sw.stockham;
+  g->plan_batch_cap = batch_cap;
+  g->plan_params.assign(h_params, h_params + (size_t)n_cand * 4);
+  if (int rc = ensure(c, g->d_differ, 1)) return rc;
+  if (int rc = ensure(c, g->d_plan_params, (size_t)n_cand * 4)) return rc;
+  HH_HIP(c, hipMemcpyAsync(g->d_plan_params, d_params, (size_t)n_cand * 4 * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+  g->plan_valid = true;
+  return HH_OK;
+}
+
+// Plans the batch that starts at candidate b0: its runs and sizes (sweep_plan.h), the buffers they need, the row kernel
+// with its resident workgroups — nx = R1 R2 with both <= 32 takes the two-step row kernel (gen_rows.hip), anything else
+// k_gen_fused — and the row launch's layers.  runs, layers: the plan's host arrays (reused from batch to batch).
+// -> HH_OK, an error, or GEN_TOO_WIDE: a row too wide (or a table slice too tall) for the Stockham kernel's LDS.
+constexpr int GEN_TOO_WIDE = 1;
+int gen_plan_batch(hh_ctx* c, const GenSwitches& sw, const double* h_params, int64_t n_cand, int64_t b0, int64_t batch_cap,
+                   GenRuns& runs_h, GenLayers& layers_h, GenBatchPlan* bp) {
   hh_gen* g = c->gen;
   const GenDims& d = g->d;
-  if (c->geom.has_rot || g->direct_only || std::getenv("HH_GEN_DIRECT")) return gen_sweep_direct(c, d_params, h_params, n_cand, d_scores, ld);   // (HH_GEN_DIRECT: the A/B switch of the tests)
-  // The same list as last time (the reference app sweeps one grid over every class average): the run structure, the
-  // launch plan and the small device arrays of the last sweep are still right — checked by comparing the list with the
-  // copy kept from then (on the device for a device-only list: four bytes come back instead of the list).
-  const int npart = d.nky;
-  const int64_t stride = ld > 0 ? ld : n_cand;
-  // several segments: one pass of the row kernel stores the masked q of a batch, one MFMA contraction scores it against
-  // every segment (as the tuned path does, §8 of DESIGN.md); the batch is bounded by the bytes of q
-  const bool seg_contract = c->n_segments > 1 && !std::getenv("HH_GEN_SEG_LOOP");
-  const int64_t batch_cap = seg_contract ? std::max<int64_t>(64, std::min<int64_t>(GEN_BATCH, GEN_SEG_BYTES / (int64_t)(g->kp * sizeof(float))) / 64 * 64)
-                                         : GEN_BATCH;
-  bool reuse = false;
-  if (g->plan_valid && g->plan_n == n_cand && std::memcmp(&g->plan_geom, &c->geom, sizeof(DevGeom)) == 0 &&
-      g->plan_stockham == (std::getenv("HH_GEN_STOCKHAM") != nullptr) && g->plan_batch_cap == batch_cap) {
-    if (h_params) {
-      reuse = std::memcmp(h_params, g->plan_params.data(), (size_t)n_cand * 4 * sizeof(double)) == 0;
-    } else {
-      int differ = 1;
-      HH_HIP(c, hipMemsetAsync(g->d_differ, 0, sizeof(int), c->stream));
-      hipLaunchKernelGGL(k_gen_same_list, dim3((unsigned)std::min<int64_t>(1024, (n_cand * 4 + 255) / 256)), dim3(256), 0, c->stream,
-                         reinterpret_cast<const unsigned long long*>(d_params), reinterpret_cast<const unsigned long long*>(g->d_plan_params.get()),
-                         n_cand * 4, g->d_differ);
-      HH_HIP(c, hipMemcpyAsync(&differ, g->d_differ, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-      HH_HIP(c, hipStreamSynchronize(c->stream));
-      reuse = differ == 0;
+  if (!gen_batch_runs(h_params, n_cand, b0, batch_cap, c->geom.height, runs_h))
+    return fail(c, HH_ERR_ARG, "rise too small for this image");
+  const int nb = (int)(runs_h.end - b0), runs = (int)runs_h.run_first.size();
+  const GenSizes z = gen_sizes(sweep_geom(c), runs_h.imax_all, runs_h.rise_all, d.nx, d.nxp);
+  if (!z.ok) return fail(c, HH_ERR_ARG, "rise too small for the general-size path (more than 32 table rows per column group)");
+  if (int rc = ensure(c, g->d_table, (size_t)runs * z.rows * d.nky)) return rc;
+  if (int rc = ensure(c, g->d_eg, (size_t)nb * z.kg * d.nxp)) return rc;
+  if (int rc = ensure(c, g->d_cgs, (size_t)nb * (d.nxp / 4 + 4))) return rc;
+  if (int rc = ensure(c, g->d_runs, (size_t)3 * runs)) return rc;
+  if (int rc = ensure(c, g->d_run_of, (size_t)nb)) return rc;
+  if (int rc = ensure(c, g->d_partials, (size_t)nb * d.nky * 3)) return rc;
+  GenRowsPlan rp{};
+  const bool two_step = !sw.stockham && gen_rows_plan(d.nx, z.rows_lds, z.kg, &rp);
+  if (two_step) {
+    if (g->slots == 0 || g->slots_lds != rp.lds || !g->slots_two_step) {
+      int per_cu = 0;
+      HH_HIP(c, gen_rows_prepare(rp, &per_cu));
+      g->slots = std::max(1, per_cu) * std::max(1, c->n_cu);
+      g->slots_lds = rp.lds;
+      g->slots_two_step = true;
+    }
+  } else {
+    if (z.lds > 160 * 1024) return GEN_TOO_WIDE;
+    if (int rc = ensure_lds_attr(c, reinterpret_cast<const void*>(gen_fused_kernel(d)), 160 * 1024)) return rc;
+    if (g->slots == 0 || g->slots_lds != z.lds || g->slots_two_step) {
+      int per_cu = 0;
+      HH_HIP(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, gen_fused_kernel(d), GEN_THREADS, z.lds));
+      g->slots = std::max(1, per_cu) * std::max(1, c->n_cu);
+      g->slots_lds = z.lds;
+      g->slots_two_step = false;
     }
   }
+  const int n_kb = two_step ? (d.nky + rp.rows_per_block - 1) / rp.rows_per_block : (d.nky + 7) / 8;
+  const int len_typ = *std::max_element(runs_h.run_count.begin(), runs_h.run_count.end());
+  gen_layers(runs_h.run_first, runs_h.run_count, fused_schedule(runs, len_typ, n_kb, g->slots), layers_h);
+  const int layers = (int)layers_h.layer_run.size();
+  if (int rc = ensure(c, g->d_layers, (size_t)3 * layers)) return rc;
+  *bp = GenBatchPlan{nb, runs, z.rows, z.kg, z.rows_lds, n_kb, layers, z.lds, two_step, rp};
+  return HH_OK;
+}
+
+// The plan's small arrays to the device: d_runs = [run_first, run_count, run_imax], d_run_of, d_layers = [layer_run,
+// layer_first, layer_count].  The previous batch's kernels may still read them: the copies are stream-ordered behind them.
+int gen_upload_plan(hh_ctx* c, const GenRuns& runs_h, const GenLayers& layers_h, const GenBatchPlan& bp) {
+  hh_gen* g = c->gen;
+  auto up = [&](int* dst, const std::vector<int>& src, int count) {
+    return hipMemcpyAsync(dst, src.data(), (size_t)count * sizeof(int), hipMemcpyHostToDevice, c->stream);
+  };
+  HH_HIP(c, up(g->d_runs, runs_h.run_first, bp.runs));
+  HH_HIP(c, up(g->d_runs + bp.runs, runs_h.run_count, bp.runs));
+  HH_HIP(c, up(g->d_runs + 2 * bp.runs, runs_h.run_imax, bp.runs));
+  HH_HIP(c, up(g->d_run_of, runs_h.run_of, bp.nb));
+  HH_HIP(c, up(g->d_layers, layers_h.layer_run, bp.layers));
+  HH_HIP(c, up(g->d_layers + bp.layers, layers_h.layer_first, bp.layers));
+  HH_HIP(c, up(g->d_layers + 2 * bp.layers, layers_h.layer_count, bp.layers));
+  HH_HIP(c, hipStreamSynchronize(c->stream));  // (pageable host vectors are reused by the next batch)
+  return HH_OK;
+}
+
+// The batch's run tables and column factors.  params: the batch's first candidate.
+int gen_tables_and_factors(hh_ctx* c, const double* params, const GenBatchPlan& bp) {
+  hh_gen* g = c->gen;
+  const GenDims& d = g->d;
+  int* const d_imax = g->d_runs + 2 * bp.runs;
+  GenTableArgs ta{};
+  ta.params = params;
+  ta.run_first = g->d_runs;
+  ta.run_imax = d_imax;
+  ta.units = c->d_units;
+  ta.tw_ny = g->d_tw_ny;
+  ta.table = g->d_table;
+  ta.cap = bp.rows;
+  ta.g = c->geom;
+  ta.d = d;
+  hipLaunchKernelGGL(k_gen_run_table, dim3((bp.rows + 3) / 4, bp.runs), dim3(256), 0, c->stream, ta);
+
+  GenFactorArgs fa{};
+  fa.params = params;
+  fa.units = c->d_units;
+  fa.run_of = g->d_run_of;
+  fa.run_imax = d_imax;
+  fa.eg = g->d_eg;
+  fa.cgs = g->d_cgs;
+  fa.kg = bp.kg;
+  fa.rows_lds = bp.rows_lds;
+  fa.g = c->geom;
+  fa.d = d;
+  hipLaunchKernelGGL(k_gen_column_factors, dim3(bp.nb), dim3(256), (size_t)(bp.rows_lds + 1) * sizeof(float), c->stream, fa);
+  HH_HIP(c, hipGetLastError());
+  return HH_OK;
+}
+
+// The row pass's arguments against segment s's weights, as either row kernel takes them (GenRowsArgs, GenFusedArgs: the
+// fields up to log_flag are the same).  q_out: where the pass stores the masked q of the batch (several segments in one
+// contraction; the mask weights are the same for every segment, so s = 0 does), or NULL.
+template <class Args>
+Args gen_row_args(const hh_ctx* c, const GenBatchPlan& bp, int s, float* q_out) {
+  const hh_gen* g = c->gen;
+  const GenDims& d = g->d;
+  Args a{};
+  a.table = g->d_table;
+  a.run_imax = g->d_runs + 2 * bp.runs;
+  a.layer_run = g->d_layers;
+  a.layer_first = g->d_layers + bp.layers;
+  a.layer_count = g->d_layers + 2 * bp.layers;
+  a.eg = g->d_eg;
+  a.cgs = g->d_cgs;
+  a.w2 = g->d_w2 + (size_t)s * d.nky * d.nx;
+  a.tw_nx = g->d_tw_nx;
+  a.partials = g->d_partials;
+  a.q_out = q_out;
+  a.q_stride = q_out ? (int64_t)g->kp : 0;
+  a.cap = bp.rows;
+  a.rows_lds = bp.rows_lds;
+  a.kg = bp.kg;
+  a.n_units = c->geom.n_units;
+  a.log_flag = c->log_flag;
+  if constexpr (std::is_same<Args, GenRowsArgs>::value) {
+    a.nky = d.nky;
+    a.nx = d.nx;
+    a.nxp = d.nxp;
+  } else {
+    a.plan = g->plan;
+    a.d = d;
+  }
+  return a;
+}
+
+// The row pass of the batch, two-step or Stockham as planned.
+int gen_row_pass(hh_ctx* c, const GenBatchPlan& bp, int s, float* q_out) {
+  if (bp.two_step) {
+    HH_HIP(c, gen_rows_launch(bp.rp, bp.n_kb, bp.layers, c->stream, gen_row_args<GenRowsArgs>(c, bp, s, q_out)));
+  } else {
+    hipLaunchKernelGGL(gen_fused_kernel(c->gen->d), dim3(bp.n_kb, bp.layers), dim3(GEN_THREADS), bp.lds, c->stream,
+                       gen_row_args<GenFusedArgs>(c, bp, s, q_out));
+  }
+  return HH_OK;
+}
+
+// Several segments: one pass of the row kernel stores the masked q of the batch, one MFMA contraction scores it against
+// every segment (as the tuned path does, §8 of DESIGN.md).
+int gen_scores_contracted(hh_ctx* c, const GenBatchPlan& bp, int64_t b0, float* d_scores, int64_t stride) {
+  hh_gen* g = c->gen;
+  const int nb = bp.nb, b_pad = (nb + 63) / 64 * 64;
+  const int rows_c = (int)(g->kp / GEN_SEG_NK);
+  if (b_pad > g->b_pad || !g->d_q) {
+    if (int rc = ensure(c, g->d_q, (size_t)b_pad * g->kp)) return rc;
+    if (int rc = ensure(c, g->d_cpart, (size_t)rows_c * b_pad * g->s_pad)) return rc;
+    if (int rc = ensure(c, g->d_psum, (size_t)b_pad * 3)) return rc;
+    HH_HIP(c, hipMemsetAsync(g->d_q, 0, (size_t)b_pad * g->kp * sizeof(float), c->stream));   // padding stays finite (and zero)
+    g->b_pad = b_pad;
+  }
+  if (int rc = gen_row_pass(c, bp, 0, g->d_q)) return rc;
+  hipLaunchKernelGGL(k_segment_corr, dim3(g->n_seg_slices, (nb + 255) / 256, g->s_pad / 64), dim3(256), 0, c->stream, g->d_q, g->d_wec,
+                     (int)GEN_SEG_NK, g->kp, g->b_pad, g->s_pad, g->d_cpart, g->d_seg_slices);
+  hipLaunchKernelGGL(k_sum_partials, dim3(std::min(1024, (nb + 3) / 4)), dim3(256), 0, c->stream, g->d_partials, g->d.nky, nb, g->d_psum);
+  const int total = nb * c->n_segments;
+  hipLaunchKernelGGL(k_finalize_segments, dim3((total + 255) / 256), dim3(256), 0, c->stream, g->d_psum, 1, g->d_cpart, g->n_seg_slices,
+                     g->b_pad, g->s_pad, nb, c->n_segments, g->d_ref, d_scores, stride, b0);
+  HH_HIP(c, hipGetLastError());
+  return HH_OK;
+}
+
+// One segment, or HH_GEN_SEG_LOOP: a row pass and a finalize per segment.
+int gen_scores_per_segment(hh_ctx* c, const GenBatchPlan& bp, int64_t b0, float* d_scores, int64_t stride) {
+  hh_gen* g = c->gen;
+  for (int s = 0; s < c->n_segments; ++s) {
+    if (int rc = gen_row_pass(c, bp, s, nullptr)) return rc;
+    hipLaunchKernelGGL(k_finalize, dim3(std::min(1024, (bp.nb + 3) / 4)), dim3(256), 0, c->stream, g->d_partials, g->d.nky,
+                       (int64_t)bp.nb, c->ref[s], d_scores + (size_t)s * stride + b0);
+    HH_HIP(c, hipGetLastError());
+  }
+  return HH_OK;
+}
+
+// The sweep: the list is cut into maximal runs of candidates that share (twist, csym, rot); consecutive runs go into
+// one batch (bounded by GEN_BATCH candidates): one table launch, one factor launch, one row launch per segment (or one
+// for all segments and a contraction).  Per batch: plan -> upload the plan's arrays -> tables + factors -> row pass +
+// scores; a list that is the last sweep's single batch skips the first two.
+int gen_sweep(hh_ctx* c, const double* d_params, const double* h_params, int64_t n_cand, float* d_scores, int64_t ld) {
+  hh_gen* g = c->gen;
+  const GenSwitches sw = gen_switches();
+  if (c->geom.has_rot || g->direct_only || sw.direct) return gen_sweep_direct(c, d_params, h_params, n_cand, d_scores, ld);
+  const int64_t stride = ld > 0 ? ld : n_cand;
+  const bool seg_contract = c->n_segments > 1 && !sw.seg_loop;
+  const int64_t batch_cap = gen_batch_cap(seg_contract, g->kp);
+  bool reuse = false;
+  if (int rc = gen_same_list(c, sw, batch_cap, d_params, h_params, n_cand, &reuse)) return rc;
   if (!reuse) g->plan_valid = false;
   if (!h_params && reuse) h_params = g->plan_params.data();
   if (!h_params) {  // a device-only list: bring it over once (the run structure is found on the host)
@@ -286,282 +503,27 @@ int gen_sweep(hh_ctx* c, const double* d_params, const double* h_params, int64_t
     HH_HIP(c, hipStreamSynchronize(c->stream));
     h_params = g->h_params.data();
   }
-  std::vector<int> run_first, run_count, run_imax, run_of, layer_run, layer_first, layer_count;
+  GenRuns runs_h;
+  GenLayers layers_h;
   for (int64_t b0 = 0; b0 < n_cand;) {
-    GenBatchPlan bp{};
-    int64_t b1 = b0;
-    int rc;
-    if (reuse) {
-      bp = g->last;
-      b1 = n_cand;
-    } else {
-    // ---- the batch's runs
-    run_first.clear(); run_count.clear(); run_imax.clear(); run_of.clear();
-    double rise_all = INFINITY;
-    int imax_all = 0;
-    while (b1 < n_cand && (int64_t)run_first.size() < 65535) {
-      const double* p = h_params + 4 * b1;
-      int64_t len = 1;
-      double rise_min = INFINITY;
-      auto usable = [](double r) { return r > 0.0 && r < INFINITY; };
-      if (usable(p[1])) rise_min = p[1];
-      while (b1 + len < n_cand) {
-        const double* q = p + 4 * len;
-        if (!(q[0] == p[0] && q[2] == p[2] && q[3] == p[3])) break;
-        if (usable(q[1])) rise_min = std::min(rise_min, q[1]);
-        ++len;
-      }
-      if (b1 + len - b0 > batch_cap && b1 > b0) break;   // the batch is full: this run opens the next one
-      len = std::min<int64_t>(len, batch_cap);            // (a run longer than a batch is swept in pieces)
-      double im = rise_min < INFINITY ? std::ceil(c->geom.height / rise_min) : 0.0;
-      if (im > 1048576.0) return fail(c, HH_ERR_ARG, "rise too small for this image");
-      run_first.push_back((int)(b1 - b0));
-      run_count.push_back((int)len);
-      run_imax.push_back((int)im);
-      for (int64_t k = 0; k < len; ++k) run_of.push_back((int)run_first.size() - 1);
-      imax_all = std::max(imax_all, (int)im);
-      if (rise_min < INFINITY) rise_all = std::min(rise_all, rise_min);
-      b1 += len;
+    GenBatchPlan bp = g->last;
+    int64_t b1 = n_cand;
+    if (!reuse) {
+      const int rc = gen_plan_batch(c, sw, h_params, n_cand, b0, batch_cap, runs_h, layers_h, &bp);
+      // too wide for the Stockham kernel: the whole list goes the direct way, as the lengths without a plan do (batches
+      // already launched are scored again: same values, stream-ordered)
+      if (rc == GEN_TOO_WIDE) { g->plan_valid = false; return gen_sweep_direct(c, d_params, h_params, n_cand, d_scores, ld); }
+      if (rc) return rc;
+      if (int rc2 = gen_upload_plan(c, runs_h, layers_h, bp)) return rc2;
+      b1 = runs_h.end;
     }
-    const int nb = (int)(b1 - b0), runs = (int)run_first.size();
-    // ---- sizes
-    const int rows = (2 * imax_all + 1) * c->geom.n_units;
-    const double span4 = (3.0 + 2.0 * c->geom.rpx) * c->geom.apix + 2.0 * c->geom.slack;
-    const double kgd = rise_all < INFINITY ? (std::floor(span4 / (double)(float)rise_all) + 2.0) * c->geom.n_units : 1.0;
-    if (kgd > 32.0) return fail(c, HH_ERR_ARG, "rise too small for the general-size path (more than 32 table rows per column group)");
-    const int kg = (int)kgd;
-    const int rows_lds = std::max(rows, kg);
-    const size_t lds = (size_t)16 * d.nxp * sizeof(float2) + (size_t)8 * rows_lds * sizeof(float2) +
-                       (size_t)((d.nx + 1) & ~1) * sizeof(float2) + (size_t)kg * d.nxp * sizeof(float) +
-                       (size_t)(d.nxp / 4 + 4) * sizeof(int);
-    if ((rc = ensure(c, g->d_table, (size_t)runs * rows * d.nky))) return rc;
-    if ((rc = ensure(c, g->d_eg, (size_t)nb * kg * d.nxp))) return rc;
-    if ((rc = ensure(c, g->d_cgs, (size_t)nb * (d.nxp / 4 + 4)))) return rc;
-    if ((rc = ensure(c, g->d_runs, (size_t)3 * runs))) return rc;
-    if ((rc = ensure(c, g->d_run_of, (size_t)nb))) return rc;
-    if ((rc = ensure(c, g->d_partials, (size_t)nb * npart * 3))) return rc;
-    // ---- the fused launch's layers: whole runs while they fill whole rounds of resident workgroups, the runs of the
-    // last round in shorter pieces (fused_schedule, as for the tuned kernels).  nx = R1 R2 with both <= 32 takes the
-    // two-step row kernel (gen_rows.hip), anything else k_gen_fused.
-    GenRowsPlan rp{};
-    const bool two_step = !std::getenv("HH_GEN_STOCKHAM") && gen_rows_plan(d.nx, rows_lds, kg, &rp);
-    void (*const fused_kernel)(GenFusedArgs) = d.nx <= 256 ? k_gen_fused<4> : d.nx <= 512 ? k_gen_fused<8> : k_gen_fused<16>;
-    if (two_step) {
-      if (g->slots == 0 || g->slots_lds != rp.lds || !g->slots_two_step) {
-        int per_cu = 0;
-        HH_HIP(c, gen_rows_prepare(rp, &per_cu));
-        g->slots = std::max(1, per_cu) * std::max(1, c->n_cu);
-        g->slots_lds = rp.lds;
-        g->slots_two_step = true;
-      }
-    } else {
-      // a row too wide (or a table slice too tall) for the Stockham kernel's LDS: the whole list goes the direct way, as
-      // the lengths without a plan do (batches already launched are scored again: same values, stream-ordered)
-      if (lds > 160 * 1024) { g->plan_valid = false; return gen_sweep_direct(c, d_params, h_params, n_cand, d_scores, ld); }
-      if ((rc = ensure_lds_attr(c, reinterpret_cast<const void*>(fused_kernel), 160 * 1024))) return rc;
-      if (g->slots == 0 || g->slots_lds != lds || g->slots_two_step) {
-        int per_cu = 0;
-        HH_HIP(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fused_kernel, GEN_THREADS, lds));
-        g->slots = std::max(1, per_cu) * std::max(1, c->n_cu);
-        g->slots_lds = lds;
-        g->slots_two_step = false;
-      }
-    }
-    const int n_kb = two_step ? (d.nky + rp.rows_per_block - 1) / rp.rows_per_block : (d.nky + 7) / 8;
-    {
-      const int len_typ = *std::max_element(run_count.begin(), run_count.end());
-      const FusedSchedule fs = fused_schedule(runs, len_typ, n_kb, g->slots);
-      for (int pass = 0; pass < 2; ++pass) {   // (second pass: one layer per run, if the cut-up list would not fit the grid)
-        layer_run.clear(); layer_first.clear(); layer_count.clear();
-        for (int r = 0; r < runs; ++r) {
-          const int groups = pass ? 1 : (r < fs.runs_a ? fs.groups_a : fs.groups_b);
-          const int cpw = (run_count[r] + groups - 1) / groups;
-          for (int o = 0; o < run_count[r]; o += cpw) {
-            layer_run.push_back(r);
-            layer_first.push_back(run_first[r] + o);
-            layer_count.push_back(std::min(cpw, run_count[r] - o));
-          }
-        }
-        if (layer_run.size() <= 65535) break;
-      }
-    }
-    const int layers = (int)layer_run.size();
-    if ((rc = ensure(c, g->d_layers, (size_t)3 * layers))) return rc;
-    int* const d_first = g->d_runs;
-    int* const d_count = g->d_runs + runs;
-    int* const d_imax = g->d_runs + 2 * runs;
-    // the previous batch's kernels may still read these small arrays: the copies below are stream-ordered behind them
-    HH_HIP(c, hipMemcpyAsync(d_first, run_first.data(), (size_t)runs * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    HH_HIP(c, hipMemcpyAsync(d_count, run_count.data(), (size_t)runs * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    HH_HIP(c, hipMemcpyAsync(d_imax, run_imax.data(), (size_t)runs * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    HH_HIP(c, hipMemcpyAsync(g->d_run_of, run_of.data(), (size_t)nb * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    HH_HIP(c, hipMemcpyAsync(g->d_layers, layer_run.data(), (size_t)layers * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    HH_HIP(c, hipMemcpyAsync(g->d_layers + layers, layer_first.data(), (size_t)layers * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    HH_HIP(c, hipMemcpyAsync(g->d_layers + 2 * layers, layer_count.data(), (size_t)layers * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    HH_HIP(c, hipStreamSynchronize(c->stream));  // (pageable host vectors are reused by the next batch)
-    bp = GenBatchPlan{nb, runs, rows, kg, rows_lds, n_kb, layers, lds, two_step, rp};
-    }
-    const int nb = bp.nb, runs = bp.runs, rows = bp.rows, kg = bp.kg, rows_lds = bp.rows_lds, n_kb = bp.n_kb, layers = bp.layers;
-    const size_t lds = bp.lds;
-    const bool two_step = bp.two_step;
-    const GenRowsPlan rp = bp.rp;
-    g->last_row_kernel[0] = two_step ? rp.r1 : 0;
-    g->last_row_kernel[1] = two_step ? rp.r2 : 0;
-    g->last_row_kernel[2] = (int32_t)(two_step ? rp.lds : lds);
-    void (*const fused_kernel)(GenFusedArgs) = d.nx <= 256 ? k_gen_fused<4> : d.nx <= 512 ? k_gen_fused<8> : k_gen_fused<16>;
-    int* const d_first = g->d_runs;
-    int* const d_imax = g->d_runs + 2 * runs;
-
-    GenTableArgs ta{};
-    ta.params = d_params + 4 * b0;
-    ta.run_first = d_first;
-    ta.run_imax = d_imax;
-    ta.units = c->d_units;
-    ta.tw_ny = g->d_tw_ny;
-    ta.table = g->d_table;
-    ta.cap = rows;
-    ta.g = c->geom;
-    ta.d = d;
-    hipLaunchKernelGGL(k_gen_run_table, dim3((rows + 3) / 4, runs), dim3(256), 0, c->stream, ta);
-
-    GenFactorArgs fa{};
-    fa.params = d_params + 4 * b0;
-    fa.units = c->d_units;
-    fa.run_of = g->d_run_of;
-    fa.run_imax = d_imax;
-    fa.eg = g->d_eg;
-    fa.cgs = g->d_cgs;
-    fa.kg = kg;
-    fa.rows_lds = rows_lds;
-    fa.g = c->geom;
-    fa.d = d;
-    hipLaunchKernelGGL(k_gen_column_factors, dim3(nb), dim3(256), (size_t)(rows_lds + 1) * sizeof(float), c->stream, fa);
-    HH_HIP(c, hipGetLastError());
-
-    if (seg_contract) {
-      const int b_pad = (nb + 63) / 64 * 64;
-      const int rows_c = (int)(g->kp / GEN_SEG_NK);
-      if (b_pad > g->b_pad || !g->d_q) {
-        if ((rc = ensure(c, g->d_q, (size_t)b_pad * g->kp))) return rc;
-        if ((rc = ensure(c, g->d_cpart, (size_t)rows_c * b_pad * g->s_pad))) return rc;
-        if ((rc = ensure(c, g->d_psum, (size_t)b_pad * 3))) return rc;
-        HH_HIP(c, hipMemsetAsync(g->d_q, 0, (size_t)b_pad * g->kp * sizeof(float), c->stream));   // padding stays finite (and zero)
-        g->b_pad = b_pad;
-      }
-      if (two_step) {
-        GenRowsArgs ra{};
-        ra.table = g->d_table;
-        ra.run_imax = d_imax;
-        ra.layer_run = g->d_layers;
-        ra.layer_first = g->d_layers + layers;
-        ra.layer_count = g->d_layers + 2 * layers;
-        ra.eg = g->d_eg;
-        ra.cgs = g->d_cgs;
-        ra.w2 = g->d_w2;                 // the mask weights are the same for every segment
-        ra.tw_nx = g->d_tw_nx;
-        ra.partials = g->d_partials;
-        ra.q_out = g->d_q;
-        ra.q_stride = (int64_t)g->kp;
-        ra.cap = rows;
-        ra.rows_lds = rows_lds;
-        ra.kg = kg;
-        ra.n_units = c->geom.n_units;
-        ra.log_flag = c->log_flag;
-        ra.nky = d.nky;
-        ra.nx = d.nx;
-        ra.nxp = d.nxp;
-        HH_HIP(c, gen_rows_launch(rp, n_kb, layers, c->stream, ra));
-      } else {
-        GenFusedArgs fu{};
-        fu.table = g->d_table;
-        fu.run_imax = d_imax;
-        fu.layer_run = g->d_layers;
-        fu.layer_first = g->d_layers + layers;
-        fu.layer_count = g->d_layers + 2 * layers;
-        fu.eg = g->d_eg;
-        fu.cgs = g->d_cgs;
-        fu.w2 = g->d_w2;
-        fu.tw_nx = g->d_tw_nx;
-        fu.partials = g->d_partials;
-        fu.q_out = g->d_q;
-        fu.q_stride = (int64_t)g->kp;
-        fu.cap = rows;
-        fu.rows_lds = rows_lds;
-        fu.kg = kg;
-        fu.n_units = c->geom.n_units;
-        fu.log_flag = c->log_flag;
-        fu.plan = g->plan;
-        fu.d = d;
-        hipLaunchKernelGGL(fused_kernel, dim3(n_kb, layers), dim3(GEN_THREADS), lds, c->stream, fu);
-      }
-      hipLaunchKernelGGL(k_segment_corr, dim3(g->n_seg_slices, (nb + 255) / 256, g->s_pad / 64), dim3(256), 0, c->stream, g->d_q, g->d_wec,
-                         (int)GEN_SEG_NK, g->kp, g->b_pad, g->s_pad, g->d_cpart, g->d_seg_slices);
-      hipLaunchKernelGGL(k_sum_partials, dim3(std::min(1024, (nb + 3) / 4)), dim3(256), 0, c->stream, g->d_partials, npart, nb, g->d_psum);
-      const int total = nb * c->n_segments;
-      hipLaunchKernelGGL(k_finalize_segments, dim3((total + 255) / 256), dim3(256), 0, c->stream, g->d_psum, 1, g->d_cpart, g->n_seg_slices,
-                         g->b_pad, g->s_pad, nb, c->n_segments, g->d_ref, d_scores, stride, b0);
-      HH_HIP(c, hipGetLastError());
-    } else
-    for (int s = 0; s < c->n_segments; ++s) {
-      if (two_step) {
-        GenRowsArgs ra{};
-        ra.table = g->d_table;
-        ra.run_imax = d_imax;
-        ra.layer_run = g->d_layers;
-        ra.layer_first = g->d_layers + layers;
-        ra.layer_count = g->d_layers + 2 * layers;
-        ra.eg = g->d_eg;
-        ra.cgs = g->d_cgs;
-        ra.w2 = g->d_w2 + (size_t)s * d.nky * d.nx;
-        ra.tw_nx = g->d_tw_nx;
-        ra.partials = g->d_partials;
-        ra.cap = rows;
-        ra.rows_lds = rows_lds;
-        ra.kg = kg;
-        ra.n_units = c->geom.n_units;
-        ra.log_flag = c->log_flag;
-        ra.nky = d.nky;
-        ra.nx = d.nx;
-        ra.nxp = d.nxp;
-        HH_HIP(c, gen_rows_launch(rp, n_kb, layers, c->stream, ra));
-      } else {
-        GenFusedArgs fu{};
-        fu.table = g->d_table;
-        fu.run_imax = d_imax;
-        fu.layer_run = g->d_layers;
-        fu.layer_first = g->d_layers + layers;
-        fu.layer_count = g->d_layers + 2 * layers;
-        fu.eg = g->d_eg;
-        fu.cgs = g->d_cgs;
-        fu.w2 = g->d_w2 + (size_t)s * d.nky * d.nx;
-        fu.tw_nx = g->d_tw_nx;
-        fu.partials = g->d_partials;
-        fu.cap = rows;
-        fu.rows_lds = rows_lds;
-        fu.kg = kg;
-        fu.n_units = c->geom.n_units;
-        fu.log_flag = c->log_flag;
-        fu.plan = g->plan;
-        fu.d = d;
-        hipLaunchKernelGGL(fused_kernel, dim3(n_kb, layers), dim3(GEN_THREADS), lds, c->stream, fu);
-      }
-      const int threads = 256;
-      hipLaunchKernelGGL(k_finalize, dim3(std::min(1024, (nb + 3) / 4)), dim3(threads), 0, c->stream, g->d_partials, npart,
-                         (int64_t)nb, c->ref[s], d_scores + (size_t)s * stride + b0);
-      HH_HIP(c, hipGetLastError());
-    }
-    if (!reuse && b0 == 0 && b1 == n_cand) {   // one batch holds the whole list: keep its plan for the next sweep
-      g->last = bp;
-      g->plan_n = n_cand;
-      g->plan_geom = c->geom;
-      g->plan_stockham = std::getenv("HH_GEN_STOCKHAM") != nullptr;
-      g->plan_batch_cap = batch_cap;
-      g->plan_params.assign(h_params, h_params + (size_t)n_cand * 4);
-      if ((rc = ensure(c, g->d_differ, 1))) return rc;
-      if ((rc = ensure(c, g->d_plan_params, (size_t)n_cand * 4))) return rc;
-      HH_HIP(c, hipMemcpyAsync(g->d_plan_params, d_params, (size_t)n_cand * 4 * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-      g->plan_valid = true;
-    }
+    g->last_row_kernel[0] = bp.two_step ? bp.rp.r1 : 0;
+    g->last_row_kernel[1] = bp.two_step ? bp.rp.r2 : 0;
+    g->last_row_kernel[2] = (int32_t)(bp.two_step ? bp.rp.lds : bp.lds);
+    if (int rc = gen_tables_and_factors(c, d_params + 4 * b0, bp)) return rc;
+    if (int rc = seg_contract ? gen_scores_contracted(c, bp, b0, d_scores, stride) : gen_scores_per_segment(c, bp, b0, d_scores, stride)) return rc;
+    if (!reuse && b0 == 0 && b1 == n_cand)
+      if (int rc = gen_keep_plan(c, sw, batch_cap, bp, d_params, h_params, n_cand)) return rc;
     b0 = b1;
   }
   c->last_first_pass = 2;

@@ -41,6 +41,7 @@
 #include <string>
 #include <system_error>
 #include <thread>
+#include <type_traits>
 #include <unordered_set>
 #include <utility>
 #include <vector>
@@ -48,6 +49,7 @@
 #include "../../include/helicon_hip.h"
 #include "device_mem.h"  // DevBuf / DevArena: the owners of device memory
 #include "pab_plan.h"  // host arithmetic of the Path A batch set-up (path_a_batch.inc)
+#include "sweep_plan.h"  // host arithmetic of the sweep drivers (sweep_runs, sweep_on_device, gen_sweep)
 #include "gen_rows.h"  // the general-size sweep's two-step row kernel (second translation unit, gen_rows.hip)
 
 // Tuning values are constants beside what they tune (the measured best).
@@ -848,7 +850,6 @@ struct TableArgs {
 __host__ __device__ inline size_t pair_slot(int64_t run, int ky, int row, int nky, int rows) {
   return ((((size_t)(run >> 1) * nky + ky) * rows + row) << 1) | (size_t)(run & 1);
 }
-inline size_t pair_table_words(int64_t runs, int nky, int rows) { return (size_t)((runs + 1) / 2) * 2 * nky * rows; }
 
 template <int N>
 struct KT {
@@ -1658,7 +1659,6 @@ struct KF {
     return LDS_BUF + (twists ? 2 * slice + set : slice + 2 * set) + LDS_R2;
   }
 };
-constexpr int WALK_RISES = 0, WALK_TWISTS = 1;  // k_fused_pass's candidate loop
 
 // WALK_RISES: a workgroup owns (run, ky block) and walks rises — the table slice stays, the factor set changes per
 // candidate (shared by the eight rows: one workgroup barrier per candidate).  WALK_TWISTS (factor_stride = 0, N <= 512):
@@ -2761,7 +2761,7 @@ struct hh_ctx {
   int last_fused_walk = 0;       // hh_last_fused_walk
   int fused_piece = 0;           // hh_set_fused_piece: runs per workgroup of the twist walk (0: fused_schedule's own cut)
   DevBuf<int> d_run_imax;        // [runs of the sweep]
-  std::vector<int> h_run_imax;
+  SweepSplit split;              // how the last sweep's list was taken (sweep_plan.h); its plan's run_imax is d_run_imax's source
   int table_path = 1;            // 0: never take the shared-twist first pass
   int fused_path = 1;            // 0: shared-twist runs go through the two-pass pipeline (k_first_pass_table + k_second_pass)
   DevBuf<float> d_eg;            // fused pass: column factors, [run_len][kg][N] shared by all runs or [2][batch][kg][N]
@@ -2849,16 +2849,25 @@ int hh_caught(Set&& set, const char* fn) noexcept {
 
 bool supported_n(int n) { return n == 32 || n == 64 || n == 128 || n == 256 || n == 512 || n == 1024; }
 
-int npart_for(int n) {  // partial-moment slots per candidate (KB<N>::NPART)
-  switch (n) {
-    case 32: return KB<32>::NPART;
-    case 64: return KB<64>::NPART;
-    case 128: return KB<128>::NPART;
-    case 256: return KB<256>::NPART;
-    case 512: return KB<512>::NPART;
-    default: return KB<1024>::NPART;
-  }
+// What the host reads of the kernels' per-size constants.  An unsupported side is refused at hh_create2; asking for one
+// here is a logic error, never another size's value.
+struct SizeConsts {
+  int n;
+  int npart;                              // partial-moment slots per candidate (KB<N>::NPART)
+  int table_cols;                         // KT<N>::COLS
+  size_t (*fused_lds)(int, int, bool);    // KF<N>::lds(rows_lds, kg, twists)
+};
+template <int N>
+constexpr SizeConsts size_consts_of() { return SizeConsts{N, KB<N>::NPART, KT<N>::COLS, &KF<N>::lds}; }
+constexpr SizeConsts SIZE_CONSTS[] = {size_consts_of<32>(),  size_consts_of<64>(),  size_consts_of<128>(),
+                                      size_consts_of<256>(), size_consts_of<512>(), size_consts_of<1024>()};
+const SizeConsts& size_consts(int n) {
+  for (const SizeConsts& s : SIZE_CONSTS)
+    if (s.n == n) return s;
+  throw std::logic_error("size_consts: unsupported image size");
 }
+int npart_for(int n) { return size_consts(n).npart; }
+size_t fused_lds(int n, int rows_lds, int kg, bool twists = false) { return size_consts(n).fused_lds(rows_lds, kg, twists); }
 
 #define HH_SWITCH_N(c, CALL)                                        \
   switch ((c)->n) {                                                 \
@@ -2931,28 +2940,16 @@ int launch_second(hh_ctx* c, const SecondArgs& a, int batch) {
 
 template <int MODE>
 int dispatch_first(hh_ctx* c, const FirstArgs& a, int batch) {
-  switch (c->n) {
-    case 32: return launch_first<32, MODE>(c, a, batch);
-    case 64: return launch_first<64, MODE>(c, a, batch);
-    case 128: return launch_first<128, MODE>(c, a, batch);
-    case 256: return launch_first<256, MODE>(c, a, batch);
-    case 512: return launch_first<512, MODE>(c, a, batch);
-    case 1024: return launch_first<1024, MODE>(c, a, batch);
-  }
-  return fail(c, HH_ERR_ARG, "unsupported image size");
+#define HH_CALL(NN) launch_first<NN, MODE>(c, a, batch)
+  HH_SWITCH_N(c, HH_CALL);
+#undef HH_CALL
 }
 
 template <int EPI, int LOG>
 int dispatch_second_n(hh_ctx* c, const SecondArgs& a, int batch) {
-  switch (c->n) {
-    case 32: return launch_second<32, EPI, LOG>(c, a, batch);
-    case 64: return launch_second<64, EPI, LOG>(c, a, batch);
-    case 128: return launch_second<128, EPI, LOG>(c, a, batch);
-    case 256: return launch_second<256, EPI, LOG>(c, a, batch);
-    case 512: return launch_second<512, EPI, LOG>(c, a, batch);
-    case 1024: return launch_second<1024, EPI, LOG>(c, a, batch);
-  }
-  return fail(c, HH_ERR_ARG, "unsupported image size");
+#define HH_CALL(NN) launch_second<NN, EPI, LOG>(c, a, batch)
+  HH_SWITCH_N(c, HH_CALL);
+#undef HH_CALL
 }
 
 template <int EPI>
@@ -3021,8 +3018,6 @@ int launch_first_table(hh_ctx* c, const TableArgs& a, int batch) {
   return HH_OK;
 }
 
-
-
 int dispatch_run_table(hh_ctx* c, const TableArgs& a, int runs, int rows) {
 #define HH_CALL(NN) launch_run_table<NN>(c, a, runs, rows)
   HH_SWITCH_N(c, HH_CALL);
@@ -3035,130 +3030,18 @@ int dispatch_first_table(hh_ctx* c, const TableArgs& a, int batch) {
 #undef HH_CALL
 }
 
-// A candidate list the shared-twist first pass can take: runs of `len` consecutive candidates with
-// identical (twist, csym, rot) and positive finite rises; h_run_imax[r] = the subunit index range
-// run r's table covers (table_extent of its smallest rise).
-struct RunPlan {
-  bool ok = false;
-  int64_t len = 0;
-  int rows = 0;      // table rows per run: (2 max imax + 1) * n_units
-  int rows_lds = 0;  // table rows a band of image columns can need (from the smallest rise); 0: too many
-  bool fused = false;  // the fused pass fits: whole table slice + column factors in LDS
-  int kg = 0;          // fused: table rows per group of four columns
-  int rows_f = 0;      // fused: table rows staged per ky
-  bool shared_factors = false;  // every run carries run 0's rise column (a twist-major grid): one set of column factors per rise
-};
-
-constexpr int64_t HH_MIN_RUN = 8;              // shorter runs do not amortise their table and workgroup granularity
-constexpr size_t HH_TABLE_BYTES_MAX = 1ull << 30;
-
-size_t fused_lds(int n, int rows_lds, int kg, bool twists = false) {
-  switch (n) {
-    case 32: return KF<32>::lds(rows_lds, kg, twists);
-    case 64: return KF<64>::lds(rows_lds, kg, twists);
-    case 128: return KF<128>::lds(rows_lds, kg, twists);
-    case 256: return KF<256>::lds(rows_lds, kg, twists);
-    case 512: return KF<512>::lds(rows_lds, kg, twists);
-    default: return KF<1024>::lds(rows_lds, kg, twists);
-  }
+// What sweep_plan.h reads of a context: its geometry as the device holds it, and the two per-size quantities.
+SweepGeom sweep_geom(const hh_ctx* c) {
+  return SweepGeom{c->n, (double)c->geom.apix, c->geom.rpx, (double)c->geom.slack, c->geom.height, c->geom.n_units,
+                   c->geom.has_rot != 0, c->table_path != 0, c->fused_path != 0};
 }
-
-// The fused pass's shape for a sweep whose smallest rise is rise_all and whose largest table has `rows` rows: table rows
-// per group of four columns (subunit indices i with lo <= i rise <= hi, hi - lo = (3 + 2 rpx) apix + 2 slack) and table
-// rows staged per ky.  False: the pass does not fit (more than 16 rows per group, or more LDS than a compute unit has).
+auto fused_lds_of(const hh_ctx* c) {
+  return [n = c->n](int rows_lds, int kg) { return fused_lds(n, rows_lds, kg); };
+}
 bool fused_shape(const hh_ctx* c, double rise_all, int rows, int* kg_out, int* rows_f_out) {
-  const double span4 = (3.0 + 2.0 * c->geom.rpx) * c->geom.apix + 2.0 * c->geom.slack;
-  const double kg = (std::floor(span4 / (double)(float)rise_all) + 2.0) * c->geom.n_units;
-  int rows_f = std::max(rows, (int)std::min(kg, 1.0e6));
-  rows_f += (4 - rows_f % 8 + 8) % 8;  // = 4 (mod 8): the eight ky rows of the slice start in different banks
-  if (!(kg <= 16.0 && fused_lds(c->n, rows_f, (int)kg) <= 160 * 1024 - 1024)) return false;
-  *kg_out = (int)kg;
-  *rows_f_out = rows_f;
-  return true;
+  return fused_shape(sweep_geom(c), rise_all, rows, fused_lds_of(c), kg_out, rows_f_out);
 }
 
-int table_cols(int n) {
-  switch (n) {
-    case 32: return KT<32>::COLS;
-    case 64: return KT<64>::COLS;
-    case 128: return KT<128>::COLS;
-    case 256: return KT<256>::COLS;
-    case 512: return KT<512>::COLS;
-    default: return KT<1024>::COLS;
-  }
-}
-
-// Whether every run of `len` candidates carries run 0's rise column, value for value (at least two runs).  The column
-// factors depend on the rise alone (column_factors_of reads neither twist, csym nor rot), so such a list needs one set
-// per rise, not one per candidate.  The driver's itertools.product(twists, rises) grid is of this shape.
-bool rise_columns_shared(const double* hp, int64_t g, int64_t len) {
-  if (!hp || len < 1 || g < 2 * len || g % len) return false;
-  for (int64_t i = len; i < g; ++i)
-    if (!(hp[4 * i + 1] == hp[4 * (i % len) + 1])) return false;
-  return true;
-}
-
-// Largest |i| a run's table has to cover.  The lattice of utils.py:153 spans ceil(height / rise) indices either side,
-// twice what the image holds; a row enters a column's sum only through the window test |x - cx| <= rpx with
-// cx = xc inv_apix + N/2 and xc = z_u + i rise, so for x in [0, N - 1] it needs |xc| <= (N/2 + rpx) apix and with it
-// |i| rise <= reach = (N/2 + rpx) apix + slack (slack >= |z_u|).  The device evaluates xc and cx in float32: the
-// product i rise, the sum with z_u, the product with inv_apix (itself a rounded reciprocal) and the sum with N/2 are
-// each off by at most 2^-24 of a magnitude below 2 reach, under 1e-6 reach together.  The bound allows 1e-5 reach and
-// one whole index more, so it also holds where reach / rise is an integer or one ulp from it.
-int64_t table_extent(int nx, double apix, int rpx, double slack, double height, double rise) {
-  const double full = std::ceil(height / rise);
-  const double reach = ((double)(nx / 2) + (double)rpx) * apix + slack;
-  const double cap = std::floor(reach * (1.0 + 1e-5) / rise) + 1.0;
-  return (int64_t)std::min(std::min(full, cap), 1048576.0);
-}
-
-RunPlan plan_runs(hh_ctx* c, const double* hp, int64_t g) {
-  RunPlan plan;
-  if (!hp || !c->table_path || c->geom.has_rot || g < HH_MIN_RUN) return plan;
-  int64_t len = 1;
-  while (len < g && hp[4 * len] == hp[0] && hp[4 * len + 2] == hp[2] && hp[4 * len + 3] == hp[3]) ++len;
-  if (len < HH_MIN_RUN || g % len) return plan;
-  const int64_t runs = g / len;
-  c->h_run_imax.assign((size_t)runs, 0);
-  int imax_all = 0;
-  double rise_all = INFINITY;
-  for (int64_t r = 0; r < runs; ++r) {
-    const double* p = hp + 4 * r * len;
-    double rise_min = INFINITY;
-    for (int64_t k = 0; k < len; ++k) {
-      const double* q = p + 4 * k;
-      if (!(q[0] == p[0] && q[2] == p[2] && q[3] == p[3])) return plan;
-      if (!(q[1] > 0.0) || !(q[1] < INFINITY)) return plan;
-      rise_min = std::min(rise_min, q[1]);
-    }
-    const double im = std::ceil(c->geom.height / rise_min);
-    if (im > 1048576.0) return plan;
-    const int ext = (int)table_extent(c->n, (double)c->geom.apix, c->geom.rpx, (double)c->geom.slack, c->geom.height, rise_min);
-    c->h_run_imax[(size_t)r] = ext;
-    imax_all = std::max(imax_all, ext);
-    rise_all = std::min(rise_all, rise_min);
-  }
-  // k_first_pass_table: rows = ceil(i1) - floor(i0) + 1 <= (i1 - i0) + 3 with
-  // i1 - i0 = ((COLS - 1) apix + 2 rpx apix + 2 slack) / rise; one more row for float32 rounding
-  const double span = ((double)(table_cols(c->n) - 1) + 2.0 * c->geom.rpx) * c->geom.apix + 2.0 * c->geom.slack;
-  const double need = (std::floor(span / (double)(float)rise_all) + 4.0) * c->geom.n_units;
-  plan.rows_lds = need <= 64.0 ? (int)need : 0;  // KT<N>::ROWS_MAX: one lane per staged row
-  plan.rows = (2 * imax_all + 1) * c->geom.n_units;
-  if ((size_t)plan.rows * (c->n / 2) * sizeof(float2) > HH_TABLE_BYTES_MAX) return plan;
-  if (c->fused_path) plan.fused = fused_shape(c, rise_all, plan.rows, &plan.kg, &plan.rows_f);
-  if (!plan.fused && plan.rows_lds == 0) return plan;
-  plan.shared_factors = plan.fused && rise_columns_shared(hp, g, len);
-  if (plan.shared_factors)  // equal columns have equal smallest rises: the shared cgs index ONE table geometry
-    for (int64_t r = 1; r < runs; ++r)
-      if (c->h_run_imax[(size_t)r] != c->h_run_imax[0]) throw std::logic_error("plan_runs: equal rise columns with unequal table extents");
-  plan.len = len;
-  plan.ok = true;
-  return plan;
-}
-
-// Second pass + scores of one batch whose intermediate is in c->d_inter.
-// Scores of one batch whose moments (and, with several segments, q) the second pass has left.
-// Second pass + scores of one batch whose intermediate is in c->d_inter.
 // Scores of one batch whose moments (and, with several segments, q) the second pass has left.
 int scores_tail(hh_ctx* c, int64_t g, int64_t g0, int nb, bool last, float* d_scores, FinArgs& pending,
                 const double* partials = nullptr) {
@@ -3308,70 +3191,11 @@ int fused_slots(hh_ctx* c, const FusedArgs& a, int* out, bool twists = false) {
   return rc;
 }
 
-// How the runs of a launch are cut into workgroups.  The grid is (layers of one run) x ky blocks workgroups, `slots`
-// of them resident at a time, each paying a fixed set-up (table slice, weights, twiddles: about four candidates'
-// worth) before its candidates; a launch lasts about ceil(workgroups / slots) x (candidates per workgroup + set-up).
-// Few, long workgroups amortise the set-up, but the last, partly filled round of a launch costs a whole one.  So the
-// runs that fill whole rounds get `groups_a` layers each, and the runs left over for the last round are cut finer
-// (`groups_b`), so that round is short.  C2 in one launch (400 runs of 250, 32 ky blocks, 512 slots) is exactly 25
-// rounds of whole runs; an eighth of it (50 runs) is 3 rounds of whole runs + 2 runs in 8 pieces each, 798 units
-// instead of 4 x 254.
-struct FusedSchedule { int runs_a, groups_a, cpw_a, groups_b, cpw_b, layers; double cost; };  // cost: the model's launch length, in candidates
-FusedSchedule fused_schedule(int64_t runs, int run_len, int n_kb, int slots) {
-  const int setup = 4, min_cpw = 16, gmax = std::max(1, run_len / min_cpw);
-  auto cpw_of = [&](int g) { return (run_len + g - 1) / g; };
-  auto groups_of = [&](int cpw) { return (run_len + cpw - 1) / cpw; };   // even groups: ceil(len / ceil(len / g)) <= g
-  FusedSchedule best{};
-  double best_t = 1e300;
-  for (int ga = 1; ga <= gmax; ++ga) {
-    const int cpw_a = cpw_of(ga), ga_e = groups_of(cpw_a);
-    const int64_t per_run = (int64_t)ga_e * n_kb;
-    const int64_t full = runs * per_run / slots;                          // whole rounds of region A
-    const int64_t runs_a = std::min<int64_t>(runs, full * slots / per_run);
-    const int64_t runs_b = runs - runs_a;
-    const double ta = (double)((runs_a * per_run + slots - 1) / slots) * (cpw_a + setup);
-    int gb = ga_e, cpw_b = cpw_a;
-    double tb = 0;
-    if (runs_b > 0) {
-      tb = 1e300;
-      for (int g = ga; g <= gmax; ++g) {
-        const int cw = cpw_of(g), ge = groups_of(cw);
-        const double t = (double)((runs_b * ge * n_kb + slots - 1) / slots) * (cw + setup);
-        if (t < tb * 0.995) { tb = t; gb = ge; cpw_b = cw; }
-      }
-    }
-    if (ta + tb < best_t * 0.995) {  // (near-ties go to the fewer, longer workgroups)
-      best_t = ta + tb;
-      best = FusedSchedule{(int)runs_a, ga_e, cpw_a, gb, cpw_b, (int)(runs_a * ga_e + runs_b * gb), ta + tb};
-    }
-  }
-  return best;
-}
-
 int dispatch_fused(hh_ctx* c, const FusedArgs& a, int layers, bool twists) {
   if (c->n_segments == 1) return c->log_flag ? dispatch_fused_n<EPI_SCORE, 1>(c, a, layers, twists) : dispatch_fused_n<EPI_SCORE, 0>(c, a, layers, twists);
   return c->log_flag ? dispatch_fused_n<EPI_QSTORE, 1>(c, a, layers, twists) : dispatch_fused_n<EPI_QSTORE, 0>(c, a, layers, twists);
 }
 
-// Which candidate loop a launch of `runs` whole runs of `run_len` candidates takes when every run shares one rise
-// column: the twist walk (workgroups own a rise and walk the runs; fused_schedule with the roles swapped) needs the
-// compute unit to hold as many of its workgroups as of the rise walk's (its table rows are double-buffered), and under
-// "auto" a schedule whose modelled length is not above the rise walk's — a grid of two or three twists would pay a
-// set-up per two or three candidates.  mode: hh_set_fused_walk.  Returns WALK_RISES or WALK_TWISTS.
-struct WalkChoice { int walk; FusedSchedule rises, twists; };
-WalkChoice choose_walk(int64_t runs, int run_len, int n_kb, int slots_rises, int slots_twists, int mode) {
-  WalkChoice w{};
-  w.walk = WALK_RISES;
-  w.rises = fused_schedule(runs, run_len, n_kb, slots_rises);
-  if (slots_twists <= 0 || runs < 2 || runs > (int64_t)1 << 30) { w.twists = FusedSchedule{}; return w; }
-  w.twists = fused_schedule(run_len, (int)runs, n_kb, slots_twists);
-  if (mode == 1 || slots_twists < slots_rises) return w;
-  if (mode == 2 || w.twists.cost <= w.rises.cost) w.walk = WALK_TWISTS;
-  return w;
-}
-
-// The sweep with the shared-twist first pass (plan.ok): batches are whole runs (or pieces of one
-// run); the tables of as many runs as fit HH_TABLE_BYTES_MAX are built by one launch ahead of them.
 // d_partials holds two halves of `batch` candidates each (zero-filled: rows of ky blocks the mask skips
 // are never written)
 int ensure_partials(hh_ctx* c, int batch) {
@@ -3399,137 +3223,86 @@ int ensure_segment_buffers(hh_ctx* c, int batch) {
   return HH_OK;
 }
 
-// several segments: candidates per launch of the shared-twist pipelines (q of a batch lives in HBM)
-constexpr int64_t SEG_BATCH = 24576;          // most candidates per launch (C5: 11.6 ms at 1024, 9.5 ms at 20k)
-constexpr int64_t SEG_BYTES = 12LL << 30;     // ... shortened so that the batch's masked q (0.5 MB per candidate at N = 512) fits this
-inline int seg_batch(int n) {
-  const int64_t per = (int64_t)(n / 2 + 1) * n * (int64_t)sizeof(float);
-  return (int)std::max<int64_t>(1024, std::min<int64_t>(SEG_BATCH, SEG_BYTES / per) / 64 * 64);
+// The sweep with the shared-twist first pass (plan.ok): batches are whole runs (or pieces of one
+// run); the tables of as many runs as fit HH_TABLE_BYTES_MAX are built by one launch ahead of them.
+// What the phases of one sweep_runs call share:
+struct RunSweep {
+  const double* d_params;          // the range's first candidate: the batches' indices are relative to the range
+  int64_t g, first_cand;           // ... scores and g0 get first_cand back
+  float* d_scores;
+  const RunPlan& plan;
+  SweepCaps caps;
+  std::vector<SweepBatch> batches;
+  std::vector<WalkChoice> walks;   // fused: the candidate loop of every launch
+  bool any_twists, any_rises;
+
+  int64_t per_group() const { return batches.front().nq; }   // runs of the largest table group, the first
+  bool twists(size_t bi) const { return walks[bi].walk == WALK_TWISTS; }
+  bool last(size_t bi) const { return bi + 1 == batches.size(); }
+};
+
+// The candidate loop of every fused launch (choose_walk): with one factor set per rise a launch holds whole runs whose
+// tables lie in one table group, so a workgroup can own a rise and walk the runs.
+int sweep_walks(hh_ctx* c, RunSweep& rs) {
+  rs.walks.assign(rs.batches.size(), WalkChoice{});
+  rs.any_twists = rs.any_rises = false;
+  if (!rs.plan.fused) return HH_OK;
+  FusedArgs shape{};
+  shape.rows_lds = rs.plan.rows_f;
+  shape.kg = rs.plan.kg;
+  int slots_r = 0, slots_t = 0;
+  if (int rc = fused_slots(c, shape, &slots_r)) return rc;
+  // Several segments: "auto" keeps the rise walk: the twist walk was measured slower there (C5: 8.04 -> 8.18 ms per
+  // step).  The reading that fits: the q of a candidate (0.4 MB at N = 512) is written by the 32 ky blocks' workgroups,
+  // which the rise walk places on one XCD and runs in step, and there the stores, not the factor copies, set the pace.
+  const int walk_mode = c->fused_walk == 0 && c->n_segments > 1 ? 1 : c->fused_walk;
+  if (rs.caps.shared && walk_mode != 1)
+    if (int rc = fused_slots(c, shape, &slots_t, true)) return rc;
+  for (size_t bi = 0; bi < rs.batches.size(); ++bi) {
+    const SweepBatch& bt = rs.batches[bi];
+    const int64_t runs_b = (bt.nb + bt.run_len - 1) / bt.run_len;
+    rs.walks[bi] = choose_walk(runs_b, bt.run_len, c->n_kb, slots_r, rs.caps.shared && bt.whole ? slots_t : 0, walk_mode);
+    (rs.twists(bi) ? rs.any_twists : rs.any_rises) = true;
+  }
+  c->last_fused_walk = rs.any_rises ? 1 : 2;
+  return HH_OK;
 }
 
-// Candidates [first, first + count) of the list of g (count = whole runs of plan.len).
-int sweep_runs(hh_ctx* c, const double* d_params, int64_t g, float* d_scores, const RunPlan& plan, int64_t first_cand,
-               int64_t count_cand) {
-  d_params += 4 * first_cand;  // indices below are relative to the range; scores and g0 get first_cand back
-  const int64_t runs = count_cand / plan.len;
-  const int nky = c->n / 2;
-  // The fused pass has no intermediate to hold, so its batches are not tied to max_batch: long
-  // launches even out the tail of the grid (C2: 3.2 M candidates/s at 250 per launch, 3.8 M at 4000).
-  constexpr int64_t FUSED_BATCH = 131072;       // most candidates per launch (whole runs); 6 GB of column factors + moments at N = 512
-  constexpr int64_t FUSED_BYTES = 8LL << 30;    // the launch is shortened so that its per-candidate column factors (two halves) fit this
-  // (never more than the sweep itself holds: the factor and moment buffers are sized by it and only grow)
-  auto bmax_of = [&](bool shared_sets) {
-    // one factor set per rise does not grow with the launch: only FUSED_BATCH and the moments bound it then
-    const int fused_cap = shared_sets ? (int)FUSED_BATCH
-                                      : (int)std::max<int64_t>(1024, std::min<int64_t>(FUSED_BATCH, FUSED_BYTES / ((int64_t)2 * std::max(1, plan.kg) * c->n * 4)));
-    return !plan.fused ? c->max_batch
-                       : (int)std::min<int64_t>(c->n_segments == 1 ? std::max(c->max_batch, fused_cap) : std::max(c->max_batch, seg_batch(c->n)),
-                                                std::max<int64_t>(count_cand, 16));
-  };
-  // One set of column factors per rise, computed once for the whole sweep, when every run carries the same rise column
-  // and a launch holds whole runs; a run cut into several launches keeps per-launch, per-candidate factors.
-  bool shared = plan.fused && plan.shared_factors && runs >= 2;
-  int bmax = bmax_of(shared);
-  if (shared && plan.len > bmax) {
-    shared = false;
-    bmax = bmax_of(false);
-  }
-  if (c->n_segments > 1) {
-    const int rcs = ensure_segment_buffers(c, bmax);
-    if (rcs) return rcs;
-  }
-  const int64_t per_batch = plan.len <= bmax ? bmax / plan.len : 1;
-  const size_t run_bytes = (size_t)plan.rows * nky * sizeof(float2);
-  int64_t per_group = std::max<int64_t>(1, (int64_t)(HH_TABLE_BYTES_MAX / run_bytes));
-  per_group = std::min<int64_t>(std::min<int64_t>(per_group, runs), 65535);
-  if (per_group > per_batch) per_group -= per_group % per_batch;
+// The sweep's buffers: per-batch q (several segments), factors and moments (fused), the runs' table extents.  The source
+// of the upload is the context's own plan (hh_ctx::split), which stays until the next sweep plans into it.
+int sweep_buffers(hh_ctx* c, const RunSweep& rs) {
+  const RunPlan& plan = rs.plan;
+  const size_t runs = plan.run_imax.size();
+  if (c->n_segments > 1)
+    if (int rc = ensure_segment_buffers(c, rs.caps.bmax)) return rc;
   if (plan.fused) {
     // shared: one set per rise; else two halves of a launch's candidates, alternating
-    const size_t sets = shared ? (size_t)plan.len : (size_t)2 * bmax;
-    int rc;
-    if ((rc = ensure(c, c->d_eg, sets * plan.kg * c->n))) return rc;
-    if ((rc = ensure(c, c->d_cgs, sets * (c->n / 4 + 4)))) return rc;
-    c->last_factor_sets = shared ? plan.len : count_cand;
-    if ((rc = ensure_partials(c, bmax))) return rc;
+    const size_t sets = rs.caps.shared ? (size_t)plan.len : (size_t)2 * rs.caps.bmax;
+    if (int rc = ensure(c, c->d_eg, sets * plan.kg * c->n)) return rc;
+    if (int rc = ensure(c, c->d_cgs, sets * (c->n / 4 + 4))) return rc;
+    c->last_factor_sets = rs.caps.shared ? plan.len : (int64_t)runs * plan.len;
+    if (int rc = ensure_partials(c, rs.caps.bmax)) return rc;
   }
-  if (int rc = ensure(c, c->d_run_imax, (size_t)runs)) return rc;
-  HH_HIP(c, hipMemcpyAsync(c->d_run_imax, c->h_run_imax.data(), (size_t)runs * sizeof(int), hipMemcpyHostToDevice,
-                           c->stream));
-  // the batches of the sweep: whole runs (or pieces of one run), in order
-  struct Batch {
-    int64_t g0;      // first candidate
-    int nb;          // candidates
-    int64_t r0;      // first run
-    int run_len;     // candidates per run inside the batch (a piece of one run counts as one run)
-    int64_t q0;      // first run of the table group the batch belongs to
-  };
-  std::vector<Batch> batches;
-  for (int64_t q0 = 0; q0 < runs; q0 += per_group) {
-    const int nq = (int)std::min<int64_t>(per_group, runs - q0);
-    for (int64_t r0 = q0; r0 < q0 + nq; r0 += per_batch) {
-      const int nr = (int)std::min<int64_t>(per_batch, q0 + nq - r0);
-      const int64_t first = r0 * plan.len, count = (int64_t)nr * plan.len;
-      for (int64_t g0 = first; g0 < first + count; g0 += bmax) {
-        const int nb = (int)std::min<int64_t>(bmax, first + count - g0);
-        batches.push_back(Batch{g0, nb, r0, (int)std::min<int64_t>(plan.len, nb), q0});
-      }
-    }
-  }
-  // The candidate loop of every fused launch (choose_walk): with one factor set per rise a launch holds whole runs whose
-  // tables lie in one table group, so a workgroup can own a rise and walk the runs.
-  std::vector<WalkChoice> walks(batches.size());
-  bool any_twists = false, any_rises = false;
-  if (plan.fused) {
-    FusedArgs shape{};
-    shape.rows_lds = plan.rows_f;
-    shape.kg = plan.kg;
-    int slots_r = 0, slots_t = 0;
-    int rc = fused_slots(c, shape, &slots_r);
-    if (rc) return rc;
-    // Several segments: "auto" keeps the rise walk: the twist walk was measured slower there (C5: 8.04 -> 8.18 ms per
-    // step).  The reading that fits: the q of a candidate (0.4 MB at N = 512) is written by the 32 ky blocks' workgroups,
-    // which the rise walk places on one XCD and runs in step, and there the stores, not the factor copies, set the pace.
-    const int walk_mode = c->fused_walk == 0 && c->n_segments > 1 ? 1 : c->fused_walk;
-    if (shared && walk_mode != 1) {
-      rc = fused_slots(c, shape, &slots_t, true);
-      if (rc) return rc;
-    }
-    for (size_t bi = 0; bi < batches.size(); ++bi) {
-      const Batch& bt = batches[bi];
-      const int len = std::min(bt.run_len, bt.nb);
-      const int64_t runs_b = (bt.nb + bt.run_len - 1) / bt.run_len;
-      const bool whole = shared && bt.run_len == plan.len && bt.nb % bt.run_len == 0;
-      walks[bi] = choose_walk(runs_b, len, c->n_kb, slots_r, whole ? slots_t : 0, walk_mode);
-      (walks[bi].walk == WALK_TWISTS ? any_twists : any_rises) = true;
-    }
-    c->last_fused_walk = any_rises ? 1 : 2;
-  }
-  // each table layout is allocated (and built, below) only where a launch reads it
-  const size_t need = (size_t)per_group * run_bytes;
-  if (!plan.fused || any_rises)
-    if (int rc = ensure(c, c->d_table, need / sizeof(float2))) return rc;
-  const bool ky_pairs = pair_walk_built(c->n);  // the twist walk of this size reads its tables two runs to an entry
-  if (any_twists) {
-    const size_t need_ky = ky_pairs ? pair_table_words(per_group, nky, plan.rows_f) : (size_t)per_group * nky * plan.rows_f;
+  if (int rc = ensure(c, c->d_run_imax, runs)) return rc;
+  HH_HIP(c, hipMemcpyAsync(c->d_run_imax, plan.run_imax.data(), runs * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  return HH_OK;
+}
+
+// ... and the tables of the largest group: each layout only where a launch reads it (it is built, below, under the same rule).
+int sweep_table_buffers(hh_ctx* c, const RunSweep& rs) {
+  const RunPlan& plan = rs.plan;
+  const int nky = c->n / 2;
+  if (!plan.fused || rs.any_rises)
+    if (int rc = ensure(c, c->d_table, (size_t)rs.per_group() * plan.rows * nky)) return rc;
+  if (rs.any_twists) {  // (the twist walk of the pair size reads its tables two runs to an entry)
+    const size_t need_ky = pair_walk_built(c->n) ? pair_table_words(rs.per_group(), nky, plan.rows_f) : (size_t)rs.per_group() * nky * plan.rows_f;
     if (int rc = ensure(c, c->d_table_ky, need_ky)) return rc;
   }
-  const size_t eg_half = (size_t)bmax * plan.kg * c->n;
-  const size_t cg_half = (size_t)bmax * (c->n / 4 + 4);  // cgs_stride<N>()
-  auto factor_args = [&](const Batch& bt, int half) {
-    FactorArgs fa{};
-    fa.params = d_params + 4 * bt.g0;
-    fa.units = c->d_units;
-    fa.run_imax = c->d_run_imax + bt.r0;
-    fa.eg = c->d_eg + half * eg_half;
-    fa.cgs = c->d_cgs + half * cg_half;
-    fa.run_len = bt.run_len;
-    fa.kg = plan.kg;
-    fa.rows_lds = plan.rows_f;
-    fa.count = bt.nb;
-    fa.g = c->geom;
-    return fa;
-  };
+  return HH_OK;
+}
 
+// what the table launch of a group (k_run_table) and the first pass of a batch (k_first_pass_table) both read
+TableArgs table_args_common(const hh_ctx* c, const RunPlan& plan) {
   TableArgs ta{};
   ta.units = c->d_units;
   ta.twtab = c->d_tw;
@@ -3537,105 +3310,167 @@ int sweep_runs(hh_ctx* c, const double* d_params, int64_t g, float* d_scores, co
   ta.kb_mask = c->kb_mask;
   ta.cap = plan.rows;
   ta.rows_lds = plan.rows_lds;
+  ta.rows_pad = plan.rows_f;
   ta.g = c->geom;
-  FinArgs pending{};
+  return ta;
+}
+
+// The tables of the group that batch bi opens, one launch: each layout only where a launch of the group reads it.
+int sweep_group_tables(hh_ctx* c, const RunSweep& rs, size_t bi) {
+  const RunPlan& plan = rs.plan;
+  const SweepBatch& bt = rs.batches[bi];
+  bool rows_major = !plan.fused, ky_major = false;
+  for (size_t bj = bi; bj < rs.batches.size() && rs.batches[bj].q0 == bt.q0; ++bj)
+    (plan.fused && rs.twists(bj) ? ky_major : rows_major) = true;
+  TableArgs ta = table_args_common(c, plan);
+  ta.params = rs.d_params + 4 * bt.q0 * plan.len;
+  ta.table = rows_major ? c->d_table : nullptr;
+  ta.table_ky = ky_major ? c->d_table_ky : nullptr;
+  ta.ky_pairs = ky_major && pair_walk_built(c->n);
+  ta.run_imax = c->d_run_imax + bt.q0;
+  ta.run_len = (int)std::min<int64_t>(plan.len, 1 << 30);
+  int rows = 0;
+  for (int r = 0; r < bt.nq; ++r) rows = std::max(rows, (2 * plan.run_imax[(size_t)(bt.q0 + r)] + 1) * c->geom.n_units);
+  return dispatch_run_table(c, ta, bt.nq, rows);
+}
+
+// where a batch's tables start in its group's, and its half of the factor and moment buffers
+float2* batch_table(const hh_ctx* c, const RunSweep& rs, const SweepBatch& bt) {
+  return c->d_table ? c->d_table + (size_t)(bt.r0 - bt.q0) * rs.plan.rows * (c->n / 2) : nullptr;
+}
+float* batch_eg(const hh_ctx* c, const RunSweep& rs, const SweepBatch& bt) {
+  return c->d_eg + bt.half * ((size_t)rs.caps.bmax * rs.plan.kg * c->n);
+}
+int* batch_cgs(const hh_ctx* c, const RunSweep& rs, const SweepBatch& bt) {
+  return c->d_cgs + bt.half * ((size_t)rs.caps.bmax * (c->n / 4 + 4));  // cgs_stride<N>()
+}
+double* batch_partials(const hh_ctx* c, const RunSweep& rs, const SweepBatch& bt) {
+  return c->d_partials + (size_t)bt.half * rs.caps.bmax * npart_for(c->n) * 3;
+}
+
+// k_first_pass_table's arguments for one batch
+TableArgs table_args(const hh_ctx* c, const RunSweep& rs, const SweepBatch& bt) {
+  TableArgs ta = table_args_common(c, rs.plan);
+  ta.params = rs.d_params + 4 * bt.g0;
+  ta.table = batch_table(c, rs, bt);
+  ta.run_imax = c->d_run_imax + bt.r0;
+  ta.run_len = rs.plan.len <= rs.caps.bmax ? (int)rs.plan.len : rs.caps.bmax + 1;
+  return ta;
+}
+
+// k_column_factors' arguments for one batch, into its half of the factor buffers.  Shared: the batch is at run 0, whose
+// candidates give the sweep's one set per rise.
+FactorArgs factor_args(const hh_ctx* c, const RunSweep& rs, const SweepBatch& bt) {
+  const RunPlan& plan = rs.plan;
+  FactorArgs fa{};
+  fa.params = rs.d_params + 4 * bt.g0;
+  fa.units = c->d_units;
+  fa.run_imax = c->d_run_imax + bt.r0;
+  fa.eg = batch_eg(c, rs, bt);
+  fa.cgs = batch_cgs(c, rs, bt);
+  fa.run_len = rs.caps.shared ? (int)plan.len : bt.run_len;
+  fa.kg = plan.kg;
+  fa.rows_lds = plan.rows_f;
+  fa.count = rs.caps.shared ? (int)plan.len : bt.nb;
+  fa.g = c->geom;
+  return fa;
+}
+
+// k_fused_pass's arguments for batch bi: build + transform + moments without an intermediate.  The batch's column
+// factors were computed by leading layers of the previous batch's launch (its own launch for the first), so unless the
+// factors are shared the launch carries the next batch's factor layers; fin: the previous batch's deferred finalize.
+// -> *layers: the grid layers of the batch's own work.
+FusedArgs fused_args(const hh_ctx* c, const RunSweep& rs, size_t bi, const FinArgs& fin, int* layers) {
+  const RunPlan& plan = rs.plan;
+  const SweepBatch& bt = rs.batches[bi];
+  const bool shared = rs.caps.shared, twists = rs.twists(bi), ky_pairs = pair_walk_built(c->n);
+  const int nky = c->n / 2;
+  FusedArgs fu{};
+  fu.params = rs.d_params + 4 * bt.g0;
+  fu.twtab = c->d_tw;
+  fu.table = batch_table(c, rs, bt);
+  // (pair layout: the group's base and the launch's first run in it: a launch may begin at the second run of a pair)
+  fu.table_ky = !twists ? nullptr : ky_pairs ? c->d_table_ky : c->d_table_ky + (size_t)(bt.r0 - bt.q0) * nky * plan.rows_f;
+  fu.ky_run0 = twists && ky_pairs ? (int)(bt.r0 - bt.q0) : 0;
+  fu.run_imax = c->d_run_imax + bt.r0;
+  fu.eg = shared ? c->d_eg : batch_eg(c, rs, bt);
+  fu.cgs = shared ? c->d_cgs : batch_cgs(c, rs, bt);
+  fu.w2 = c->d_w2;
+  fu.partials = batch_partials(c, rs, bt);
+  fu.q_out = c->n_segments > 1 ? c->d_q : nullptr;
+  fu.q_roff = c->n_segments > 1 && c->q_slices ? c->d_q_roff : nullptr;
+  fu.q_stride = c->q_stride;
+  fu.kb_list = c->d_kb_list;
+  fu.n_kb = c->n_kb;
+  fu.batch = bt.nb;
+  fu.run_len = bt.run_len;
+  fu.factor_stride = shared ? 0 : bt.run_len;
+  fu.cap = plan.rows;
+  fu.rows_lds = plan.rows_f;
+  fu.kg = plan.kg;
+  FusedSchedule fs = twists ? rs.walks[bi].twists : rs.walks[bi].rises;
+  if (twists && c->fused_piece > 0) {  // every rise's runs in pieces of fused_piece (the last piece: what is left)
+    const int runs_b = bt.nb / fu.run_len, g = (runs_b + c->fused_piece - 1) / c->fused_piece;
+    fs = FusedSchedule{fu.run_len, g, c->fused_piece, g, c->fused_piece, fu.run_len * g, 0.0};
+  }
+  fu.runs_a = fs.runs_a; fu.groups_a = fs.groups_a; fu.cpw_a = fs.cpw_a; fu.groups_b = fs.groups_b; fu.cpw_b = fs.cpw_b;
+  fu.n_runs = (int)((bt.nb + fu.run_len - 1) / fu.run_len);
+  *layers = fs.layers;
+  fu.n_units = c->geom.n_units;
+  fu.fin = fin;
+  if (!shared && !rs.last(bi)) {
+    fu.next = factor_args(c, rs, rs.batches[bi + 1]);
+    fu.factor_layers = (fu.next.count + c->n_kb - 1) / c->n_kb;
+  }
+  return fu;
+}
+
+// One batch through the fused pass: the first batch's own factors, the launch, the scores.
+int sweep_fused_batch(hh_ctx* c, const RunSweep& rs, size_t bi, FinArgs& pending) {
+  const SweepBatch& bt = rs.batches[bi];
+  if (bi == 0) {
+    const FactorArgs fa = factor_args(c, rs, bt);
+    if (int rc = dispatch_factors(c, fa, fa.count)) return rc;
+  }
+  int layers = 0;
+  const FusedArgs fu = fused_args(c, rs, bi, pending, &layers);
+  if (int rc = dispatch_fused(c, fu, layers, rs.twists(bi))) return rc;
+  pending = FinArgs{};
+  return scores_tail(c, rs.g, rs.first_cand + bt.g0, bt.nb, rs.last(bi), rs.d_scores, pending, fu.partials);
+}
+
+// One batch through the two-pass pipeline: first pass from the run tables, second pass, scores.
+int sweep_table_batch(hh_ctx* c, const RunSweep& rs, size_t bi, FinArgs& pending) {
+  const SweepBatch& bt = rs.batches[bi];
+  TableArgs ta = table_args(c, rs, bt);
+  ta.fin = pending;
+  if (int rc = dispatch_first_table(c, ta, bt.nb)) return rc;
+  pending = FinArgs{};
+  return second_and_scores(c, rs.g, rs.first_cand + bt.g0, bt.nb, rs.last(bi), rs.d_scores, pending);
+}
+
+// Candidates [first, first + count) of the list of g (count = whole runs of plan.len).
+int sweep_runs(hh_ctx* c, const double* d_params, int64_t g, float* d_scores, const RunPlan& plan, int64_t first_cand,
+               int64_t count_cand) {
+  const SweepCaps caps = sweep_caps(plan, c->max_batch, c->n, c->n_segments, count_cand);
+  const size_t run_bytes = (size_t)plan.rows * (c->n / 2) * sizeof(float2);
+  RunSweep rs{d_params + 4 * first_cand, g, first_cand, d_scores, plan, caps,
+              sweep_batches(count_cand / plan.len, plan.len, caps.bmax, run_bytes), {}, false, false};
+  if (int rc = sweep_buffers(c, rs)) return rc;
+  if (int rc = sweep_walks(c, rs)) return rc;
+  if (int rc = sweep_table_buffers(c, rs)) return rc;
+  FinArgs pending{};   // the finalize of the batch before, folded into the next launch's layer 0
   int64_t table_group = -1;
-  for (size_t bi = 0; bi < batches.size(); ++bi) {
-    const Batch& bt = batches[bi];
-    if (bt.q0 != table_group) {  // this group's tables, one launch
+  for (size_t bi = 0; bi < rs.batches.size(); ++bi) {
+    const SweepBatch& bt = rs.batches[bi];
+    if (bt.q0 != table_group) {
       table_group = bt.q0;
-      const int nq = (int)std::min<int64_t>(per_group, runs - bt.q0);
       c->prof_now = c->profiling > 0;
-      ta.params = d_params + 4 * bt.q0 * plan.len;
-      // each layout only where a launch of this group reads it
-      bool rows_major = !plan.fused, ky_major = false;
-      for (size_t bj = bi; bj < batches.size() && batches[bj].q0 == bt.q0; ++bj)
-        (plan.fused && walks[bj].walk == WALK_TWISTS ? ky_major : rows_major) = true;
-      ta.table = rows_major ? c->d_table : nullptr;
-      ta.table_ky = ky_major ? c->d_table_ky : nullptr;
-      ta.ky_pairs = ky_major && ky_pairs;
-      ta.rows_pad = plan.rows_f;
-      ta.run_imax = c->d_run_imax + bt.q0;
-      ta.run_len = (int)std::min<int64_t>(plan.len, 1 << 30);
-      ta.fin = FinArgs{};
-      int rows = 0;
-      for (int r = 0; r < nq; ++r) rows = std::max(rows, (2 * c->h_run_imax[(size_t)(bt.q0 + r)] + 1) * c->geom.n_units);
-      const int rc = dispatch_run_table(c, ta, nq, rows);
-      if (rc) return rc;
+      if (int rc = sweep_group_tables(c, rs, bi)) return rc;
     }
     c->prof_now = c->profiling > 0 && ((int64_t)bi % c->profiling) == 0;
     if (c->prof_now) c->prof_candidates += bt.nb;
-    ta.table = c->d_table ? c->d_table + (size_t)(bt.r0 - bt.q0) * plan.rows * nky : nullptr;
-    ta.table_ky = nullptr;
-    ta.run_imax = c->d_run_imax + bt.r0;
-    ta.run_len = plan.len <= bmax ? (int)plan.len : bmax + 1;
-    ta.params = d_params + 4 * bt.g0;
-    int rc;
-    if (plan.fused) {
-      // build + transform + moments without an intermediate.  The batch's column factors were
-      // computed by leading layers of the previous batch's launch (its own launch for the first).
-      const int half = (int)(bi & 1);
-      if (bi == 0) {
-        FactorArgs fa = factor_args(bt, half);  // shared: bt is at run 0, whose candidates give the sweep's one set per rise
-        if (shared) fa.run_len = fa.count = (int)plan.len;
-        rc = dispatch_factors(c, fa, fa.count);
-        if (rc) return rc;
-      }
-      FusedArgs fu{};
-      fu.params = ta.params;
-      fu.twtab = c->d_tw;
-      const bool twists = walks[bi].walk == WALK_TWISTS;
-      fu.table = ta.table;
-      // (pair layout: the group's base and the launch's first run in it: a launch may begin at the second run of a pair)
-      fu.table_ky = !twists ? nullptr : ky_pairs ? c->d_table_ky : c->d_table_ky + (size_t)(bt.r0 - bt.q0) * nky * plan.rows_f;
-      fu.ky_run0 = twists && ky_pairs ? (int)(bt.r0 - bt.q0) : 0;
-      fu.run_imax = ta.run_imax;
-      fu.eg = shared ? c->d_eg : c->d_eg + half * eg_half;
-      fu.cgs = shared ? c->d_cgs : c->d_cgs + half * cg_half;
-      fu.w2 = c->d_w2;
-      double* const part = c->d_partials + (size_t)half * bmax * npart_for(c->n) * 3;
-      fu.partials = part;
-      fu.q_out = c->n_segments > 1 ? c->d_q : nullptr;
-      fu.q_roff = c->n_segments > 1 && c->q_slices ? c->d_q_roff : nullptr;
-      fu.q_stride = c->q_stride;
-      fu.kb_list = c->d_kb_list;
-      fu.n_kb = c->n_kb;
-      fu.batch = bt.nb;
-      fu.run_len = bt.run_len;
-      fu.factor_stride = shared ? 0 : bt.run_len;
-      fu.cap = plan.rows;
-      fu.rows_lds = plan.rows_f;
-      fu.kg = plan.kg;
-      int work_layers = 0;
-      {
-        FusedSchedule fs = twists ? walks[bi].twists : walks[bi].rises;
-        if (twists && c->fused_piece > 0) {  // every rise's runs in pieces of fused_piece (the last piece: what is left)
-          const int runs_b = bt.nb / fu.run_len, g = (runs_b + c->fused_piece - 1) / c->fused_piece;
-          fs = FusedSchedule{fu.run_len, g, c->fused_piece, g, c->fused_piece, fu.run_len * g, 0.0};
-        }
-        fu.runs_a = fs.runs_a; fu.groups_a = fs.groups_a; fu.cpw_a = fs.cpw_a; fu.groups_b = fs.groups_b; fu.cpw_b = fs.cpw_b;
-        fu.n_runs = (int)((bt.nb + fu.run_len - 1) / fu.run_len);
-        work_layers = fs.layers;
-      }
-      fu.n_units = c->geom.n_units;
-      fu.fin = pending;
-      if (!shared && bi + 1 < batches.size()) {
-        fu.next = factor_args(batches[bi + 1], half ^ 1);
-        fu.factor_layers = (fu.next.count + c->n_kb - 1) / c->n_kb;
-      }
-      rc = dispatch_fused(c, fu, work_layers, twists);
-      if (rc) return rc;
-      pending = FinArgs{};
-      rc = scores_tail(c, g, first_cand + bt.g0, bt.nb, bi + 1 == batches.size(), d_scores, pending, part);
-      if (rc) return rc;
-      continue;
-    }
-    ta.fin = pending;
-    rc = dispatch_first_table(c, ta, bt.nb);
-    if (rc) return rc;
-    pending = FinArgs{};
-    rc = second_and_scores(c, g, first_cand + bt.g0, bt.nb, bi + 1 == batches.size(), d_scores, pending);
-    if (rc) return rc;
+    if (int rc = plan.fused ? sweep_fused_batch(c, rs, bi, pending) : sweep_table_batch(c, rs, bi, pending)) return rc;
   }
   c->prof_now = false;
   return HH_OK;
@@ -3676,47 +3511,15 @@ int sweep_on_device(hh_ctx* c, const double* d_params, const int64_t n_cand, flo
   if (phase_on(c)) return phase_sweep(c, d_params, n_cand, d_scores, ld);
   if (zoom_on(c)) return zoom_sweep(c, d_params, n_cand, d_scores, ld);
   if (c->general) return gen_sweep(c, d_params, h_params, n_cand, d_scores, ld);
-  RunPlan plan = plan_runs(c, h_params, n_cand);
-  c->last_first_pass = plan.ok ? (plan.fused ? 2 : 1) : 0;
-  const int64_t g = ld > 0 ? ld : n_cand;
-  if (plan.ok) return sweep_runs(c, d_params, g, d_scores, plan, 0, n_cand);
-  // A list that starts inside a run (a shard cut anywhere) or ends with a partial run: the whole runs in
-  // the middle still take the shared-twist pipeline, the two ragged ends the general one.
-  if (h_params && c->table_path && !c->geom.has_rot && n_cand >= 2 * HH_MIN_RUN) {
-    auto same = [&](int64_t i, int64_t j) {
-      return h_params[4 * i] == h_params[4 * j] && h_params[4 * i + 2] == h_params[4 * j + 2] &&
-             h_params[4 * i + 3] == h_params[4 * j + 3];
-    };
-    int64_t head = 1;
-    while (head < n_cand && same(head, 0)) ++head;
-    int64_t len = 1;
-    while (head + len < n_cand && same(head + len, head)) ++len;
-    const int64_t count = head < n_cand ? (n_cand - head) / len * len : 0;
-    if (head < n_cand && head < len && len >= HH_MIN_RUN && count >= len) {
-      plan = plan_runs(c, h_params + 4 * head, count);
-      if (plan.ok) {
-        c->last_first_pass = plan.fused ? 2 : 1;
-        int rc = sweep_transform(c, d_params, g, d_scores, 0, head);
-        if (rc) return rc;
-        rc = sweep_runs(c, d_params, g, d_scores, plan, head, count);
-        if (rc) return rc;
-        return head + count < n_cand ? sweep_transform(c, d_params, g, d_scores, head + count, n_cand - head - count) : HH_OK;
-      }
-    }
-    // aligned start, partial last run
-    len = head;
-    const int64_t whole = n_cand / len * len;
-    if (len >= HH_MIN_RUN && whole >= len && whole < n_cand) {
-      plan = plan_runs(c, h_params, whole);
-      if (plan.ok) {
-        c->last_first_pass = plan.fused ? 2 : 1;
-        const int rc = sweep_runs(c, d_params, g, d_scores, plan, 0, whole);
-        if (rc) return rc;
-        return sweep_transform(c, d_params, g, d_scores, whole, n_cand - whole);
-      }
-    }
-  }
-  return sweep_transform(c, d_params, g, d_scores, 0, n_cand);
+  // whole runs through the shared-twist pipeline, the ragged ends of the list (split_sweep) through the general one
+  const SweepSplit& sp = split_sweep(sweep_geom(c), size_consts(c->n).table_cols, fused_lds_of(c), h_params, n_cand, c->split);
+  c->last_first_pass = sp.plan.ok ? (sp.plan.fused ? 2 : 1) : 0;
+  const int64_t g = ld > 0 ? ld : n_cand, tail = sp.head + sp.count;
+  if (sp.head > 0 || !sp.plan.ok)
+    if (int rc = sweep_transform(c, d_params, g, d_scores, 0, sp.head)) return rc;
+  if (sp.plan.ok)
+    if (int rc = sweep_runs(c, d_params, g, d_scores, sp.plan, sp.head, sp.count)) return rc;
+  return tail < n_cand ? sweep_transform(c, d_params, g, d_scores, tail, n_cand - tail) : HH_OK;
 }
 
 int check_ready(hh_ctx* c, bool need_ref) {
