@@ -18,5 +18,8 @@ from .fsc import (calc_frc_2d, calc_fsc, calc_fsc_batch, calc_fsc_per_shell, frc
 # the function true_fsc.true_fsc is not re-exported under its own name: that would hide the module helicon_amd.true_fsc
 from .true_fsc import (TrueFSC, adaptive_mask_device, distance_transform_edt_sq, gaussian_filter_device, gaussian_taps, label_components,
                        otsu_from_counts, randomize_phases_lowpass, soft_mask_device)
+# the function fft_resample takes the package attribute of its module's name: reach the module's other names with
+# ``from helicon_amd.fft_resample import ...`` (the command line is ``python -m helicon_amd.fft_resample``)
+from .fft_resample import crop_operator, fft_crop, fft_rescale, fft_resample, resample_operator, rescale_operator
 
 __version__ = "0.1.0"

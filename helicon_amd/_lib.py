@@ -134,6 +134,9 @@ EXPORTS = {
                                             C.POINTER(C.c_int32), _f64p]),
     "hh_low_high_pass_filter_3d": (C.c_int, [C.c_int, _f32p, C.POINTER(C.c_int32), C.c_double, C.c_double, _f32p]),
     "hh_map_projections": (C.c_int, [C.c_int, _f32p, C.POINTER(C.c_int32), C.c_int32, C.c_int32, _f32p, _f32p, _f32p]),
+    "hh_separable_transform_3d": (C.c_int, [C.c_int, _f32p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(_f32p), C.POINTER(_f32p),
+                                            C.c_int, C.c_double, _f32p, _f32p]),
+    "hh_separable_transform_kernel_ms": (C.c_int, [_f64p]),
     "hh_synchronize": (C.c_int, [_ctx]),
     "hh_profile_enable": (C.c_int, [_ctx, C.c_int]),
     "hh_profile_reset": (C.c_int, [_ctx]),

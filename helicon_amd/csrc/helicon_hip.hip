@@ -4746,6 +4746,7 @@ int hh_profile_get(hh_ctx* c, hh_profile* out) try {
 #include "path_a_host.inc"  // Path A: host side and C ABI (hh_pa_*)
 #include "path_a_batch.inc"  // Path A for many candidates at once, device-resident solve (hh_pab_*)
 #include "map_filter.inc"  // the 3-D map input: separable Gaussian filter of a whole map on the f32 MFMA, axis projections
+#include "fourier_resample.inc"  // Fourier resampling of a map: a rectangular complex operator per axis, re and im accumulators from one staged slice, fused epilogue (hh_separable_transform_3d)
 #include "filtered_sweep.inc"  // the sweep on low / high-pass filtered spectra (hh_set_spectrum_filter): y pass + fused x pass / moments
 #include "phase_sweep.inc"  // the sweep's phase score across the meridian (hh_set_spectrum_phase): four real products kept apart, F and its partner at -f_y from the same MFMAs
 #include "symmetry_search.inc"  // helical symmetry search of a 3-D map: batched (twist, rise, Csym) scores of a device-resident map (hh_hs_*)

@@ -15,12 +15,16 @@ candidate costs its gathers over ``M`` and three sums, the symmetrised map is ne
 
     python -m helicon_amd.symmetry_search map.mrc [--apix A] --twist MIN MAX STEP --rise MIN MAX STEP [--csym 1 2 3]
            [--fraction F] [--rmin PX] [--rmax PX] [--z-fraction F] [--device 0] [--top 10] [--out scores.npz]
+           [--resample NZ NY NX]
 
 reads a ``.mrc`` / ``.map`` / ``.npy`` map (the header's voxel size unless ``--apix``), prints a JSON report in
 ``denovo3DBatch``'s layout (``n_candidates``, ``n_skipped``, ``best``, ``top``, and the region written out) and, with
 ``--out``, saves ``scores[C, T, R]``, ``twists``, ``rises``, ``csyms``, ``params``, ``valid``.  The grid and its skipped
-pairs are those of the 2-D sweep (``grid.build_grid`` with the map's length nz * apix as the tube length).  The report's
-``best`` is what ``python -m helicon_amd.denovo3DBatch map.mrc --from-map TWIST RISE CSYM`` takes as the map's symmetry.
+pairs are those of the 2-D sweep (``grid.build_grid`` with the map's length nz * apix as the tube length).  With
+``--resample`` the map is first Fourier-resampled to those sides on the device (``fft_resample`` with ``output="real"``;
+even sides and one ratio for all three axes only); the report's ``map`` entry then shows the new shape and voxel size
+and adds ``resampled_from``.  The report's ``best`` is what
+``python -m helicon_amd.denovo3DBatch map.mrc --from-map TWIST RISE CSYM`` takes as the map's symmetry.
 """
 from __future__ import annotations
 
@@ -241,6 +245,8 @@ def add_args(parser: argparse.ArgumentParser) -> argparse.ArgumentParser:
     parser.add_argument("--device", type=int, default=0)
     parser.add_argument("--top", type=int, default=10, help="how many best candidates to print")
     parser.add_argument("--out", default=None, help=".npz with scores[C, T, R], twists, rises, csyms, params, valid")
+    parser.add_argument("--resample", type=int, nargs=3, metavar=("NZ", "NY", "NX"), default=None,
+                        help="Fourier-resample the map to these sides before the search (even sides, one ratio for all axes)")
     return parser
 
 
@@ -261,9 +267,35 @@ def read_map(path, apix=None):
     return vol, float(apix)
 
 
-def run(args, engine_factory=None) -> dict:
-    """``engine_factory(vol, apix, fraction=, device=)`` stands in for ``SymmetrySearch`` (tests)."""
+def resample_map(vol, apix, new_size, device=0, resampler=None):
+    """The map at ``new_size`` and its voxel size, for ``--resample``.  Exits with a message on an odd side, old or new
+    (the transform keeps a phase factor there, so the result is not a resampled map), and on unequal ratios old / new
+    (the search takes one voxel size)."""
+    old, new = tuple(int(v) for v in vol.shape), tuple(int(v) for v in new_size)
+    if min(new) < 1:
+        raise SystemExit(f"--resample: the new sides must be positive; got {new}")
+    if any(v % 2 for v in old + new):
+        raise SystemExit(f"--resample: every side must be even, old and new (an odd side keeps a phase factor: the result "
+                         f"would not be a resampled map); got {old} -> {new}")
+    if any(n * new[0] != old[0] * on for n, on in zip(old, new)):
+        raise SystemExit(f"--resample: the three ratios old / new differ ({old} -> {new}): the search takes one voxel size")
+    if resampler is None:
+        from .fft_resample import fft_resample as resampler
+    try:
+        out, new_apix = resampler(vol, apix, new, output="real", device=device)
+    except ValueError as e:
+        raise SystemExit(str(e))
+    return out, float(new_apix)
+
+
+def run(args, engine_factory=None, resampler=None) -> dict:
+    """``engine_factory(vol, apix, fraction=, device=)`` stands in for ``SymmetrySearch`` and
+    ``resampler(vol, apix, new_size, output=, device=)`` for ``fft_resample`` (tests)."""
     vol, apix = read_map(args.map, args.apix)
+    resampled_from = None
+    if getattr(args, "resample", None):
+        resampled_from = dict(shape=[int(v) for v in vol.shape], apix=apix)
+        vol, apix = resample_map(np.asarray(vol), apix, args.resample, args.device, resampler)
     if any(c < 1 for c in args.csym):
         raise SystemExit(f"--csym must be >= 1; got {args.csym}")
     twists, rises = sweep_axis(*args.twist), sweep_axis(*args.rise)
@@ -292,6 +324,8 @@ def run(args, engine_factory=None) -> dict:
         "top": [dict(twist=float(res.grid.params[g, 0]), rise=float(res.grid.params[g, 1]), csym=int(res.grid.params[g, 2]),
                      score=float(flat[g])) for g in order],
     }
+    if resampled_from is not None:
+        report["map"]["resampled_from"] = resampled_from
     if args.out:
         np.savez_compressed(args.out, scores=res.scores[0], twists=twists, rises=rises, csyms=np.asarray(args.csym),
                             params=res.grid.params, valid=res.grid.valid)

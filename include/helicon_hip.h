@@ -16,6 +16,7 @@
  *   hh_transform_map       lib/transforms.py:168-235          transform_map (Euler ZYZ + scipy.ndimage.map_coordinates, cubic)
  *   hh_low_high_pass_filter_3d  lib/filters.py:349-372        low_high_pass_filter_3d (symmetrize_transform_map's 3-D filter)
  *   hh_map_projections     webApps/denovo3D/utils.py:336-345  generate_xyz_projections
+ *   hh_separable_transform_3d  lib/transforms.py:610-660, 714-743  fft_crop, fft_rescale (3-D); plugins/proc3d/fft_resample.py:97-109
  *   hh_warp_affine_2d      lib/transforms.py:238-312          transform_image (its skimage.transform.warp call)
  *   hh_rescale_2d          lib/filters.py:375-412             down_scale, and the app's binning (their skimage rescale call)
  *   hh_helix_moments       lib/analysis.py:645-728            estimate_helix_rotation_center_diameter (closing + moments)
@@ -427,6 +428,21 @@ int hh_low_high_pass_filter_3d(int device, const float* data, const int32_t shap
  * results.  Context-free: errors are read with hh_last_error(NULL). */
 int hh_map_projections(int device, const float* data, const int32_t shape[3], int32_t slab_begin, int32_t slab_end, float* out_x,
                        float* out_y, float* out_z);
+
+/* Fourier resampling of a 3-D map or a 2-D image: what fft_rescale's 3-D branch (lib/transforms.py:714-743), fft_crop
+ * (:610-660) and proc3d --fft_resample (plugins/proc3d/fft_resample.py:97-109) have in common.  One complex operator per
+ * axis, op[a] = op_re[a] + i op_im[a], host float32 [out_shape[a]][in_shape[a]] row-major, is applied along z, then y,
+ * then x on the exact-f32 MFMA; op_im[a] NULL: a real operator; both NULL: the identity (the axis is skipped and keeps
+ * its side).  The caller builds the operators in float64 and rounds them once (helicon_amd/fft_resample.py).  The last
+ * pass applies the epilogue to the complex product c: 0 store (out0 = Re c, out1 = Im c), 1 abs (out0 = |c| * scale),
+ * 2 real (out0 = Re c * scale; the imaginary part is not computed); out1 is read under store only.
+ * data: host float32 [in_shape]; out0 / out1: host float32 [out_shape]; every side, in and out, in [1, 1024].
+ * Context-free: errors are read with hh_last_error(NULL). */
+int hh_separable_transform_3d(int device, const float* data, const int32_t in_shape[3], const int32_t out_shape[3],
+                              const float* const op_re[3], const float* const op_im[3], int epilogue, double scale, float* out0,
+                              float* out1);
+/* device-event milliseconds of the last hh_separable_transform_3d call's passes (the copies of the map excluded) */
+int hh_separable_transform_kernel_ms(double* ms);
 
 int hh_synchronize(hh_ctx* ctx);
 
