@@ -392,11 +392,7 @@ struct AmScratch {
   DevBuf<int32_t> parent;
   DevBuf<uint8_t> above, keep, mask;
   DevBuf<unsigned long long> words;        // [AM_WORDS + 256]
-  hipEvent_t ev[AM_EVENTS] = {};
-  ~AmScratch() {
-    for (hipEvent_t e : ev)
-      if (e) (void)hipEventDestroy(e);
-  }
+  DevEvents<AM_EVENTS> ev;
   int* err() const { return reinterpret_cast<int*>(words + AM_W_ERR); }
 };
 
@@ -420,7 +416,7 @@ int am_reserve(AmScratch* s, int64_t n, bool planes, bool labels, bool keep, boo
   if (taps) {
     HH_HIP(nullptr, hipMemcpy(s->taps, taps, (size_t)(r + 1) * sizeof(double), hipMemcpyHostToDevice));
   }
-  for (hipEvent_t& e : s->ev) HH_HIP(nullptr, hipEventCreate(&e));
+  HH_HIP(nullptr, s->ev.create());
   return HH_OK;
 }
 
@@ -606,7 +602,7 @@ extern "C" int hh_am_gaussian_3d(int device, const double* vol, int32_t nz, int3
   if (n > AM_MAX_VOXELS) return fail(nullptr, HH_ERR_ARG, "hh_am_gaussian_3d: more than 2^28 voxels");
   const int r = am_radius(sigma);
   if (r < 0) return fail(nullptr, HH_ERR_ARG, "hh_am_gaussian_3d: sigma must be positive and finite with int(4 sigma + 0.5) <= 4096");
-  if (int rc = sm_device("hh_am_gaussian_3d", device)) return rc;
+  if (int rc = use_device("hh_am_gaussian_3d", device)) return rc;
   AmScratch s;
   if (int rc = am_reserve(&s, n, true, false, false, false, taps, r)) return rc;
   HH_HIP(nullptr, hipMemcpy(s.a, vol, (size_t)n * sizeof(double), hipMemcpyHostToDevice));
@@ -620,7 +616,7 @@ extern "C" int hh_am_label_3d(int device, const uint8_t* binary, int32_t nz, int
   if (!am_sides_ok(nz, ny, nx)) return fail(nullptr, HH_ERR_ARG, "hh_am_label_3d: the sides of the box must lie in [1, 1024]");
   const int64_t n = (int64_t)nz * ny * nx;
   if (n > AM_MAX_VOXELS) return fail(nullptr, HH_ERR_ARG, "hh_am_label_3d: more than 2^28 voxels");
-  if (int rc = sm_device("hh_am_label_3d", device)) return rc;
+  if (int rc = use_device("hh_am_label_3d", device)) return rc;
   AmScratch s;
   if (int rc = am_reserve(&s, n, false, true, false, false, nullptr, 0)) return rc;
   HH_HIP(nullptr, hipMemcpy(s.above, binary, (size_t)n, hipMemcpyHostToDevice));
@@ -638,7 +634,7 @@ extern "C" int hh_am_mask_3d(int device, const void* vol, int is_f64, int32_t nz
   if (!vol || !support_out) return fail(nullptr, HH_ERR_ARG, "hh_am_mask_3d: NULL argument");
   if (int rc = am_check_threshold_args("hh_am_mask_3d", sigma, taps, mode, value)) return rc;
   if (int rc = am_check_box("hh_am_mask_3d", nz, ny, nx, mode, value)) return rc;
-  if (int rc = sm_device("hh_am_mask_3d", device)) return rc;
+  if (int rc = use_device("hh_am_mask_3d", device)) return rc;
   const int64_t n = (int64_t)nz * ny * nx;
   AmScratch s;
   if (int rc = am_reserve(&s, n, true, true, true, true, sigma != 0.0 ? taps : nullptr, sigma != 0.0 ? am_radius(sigma) : 0)) return rc;

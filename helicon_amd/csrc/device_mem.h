@@ -5,7 +5,11 @@
 //   DevArena    the temporaries of one call: get<T>(count) allocates, and whatever it handed out is freed on every way
 //               out of the scope, early returns and exceptions included.
 //
-// Neither pools, caches, copies or grows geometrically: an allocation is exactly what was asked for.  A failure is
+// and, beside them, the owner of the timing events of a call or of a scratch:
+//
+//   DevEvents<N>  N events, created on demand by create() and destroyed with their owner.
+//
+// Neither memory type pools, caches, copies or grows geometrically: an allocation is exactly what was asked for.  A failure is
 // reported by value (false / nullptr); dev_alloc_failed() words it, and every caller returns it as HH_ERR_NOMEM.
 // Needs the HIP runtime API and the standard library only, so a host compiler can build it alone.
 #pragma once
@@ -99,6 +103,36 @@ class DevArena {
  private:
   std::vector<void*> held_;
   size_t failed_ = 0;
+};
+
+template <int N>
+class DevEvents {
+ public:
+  DevEvents() = default;
+  DevEvents(const DevEvents&) = delete;
+  DevEvents& operator=(const DevEvents&) = delete;
+  ~DevEvents() {
+    for (hipEvent_t e : ev_)
+      if (e) (void)hipEventDestroy(e);
+  }
+
+  // Creates the events that do not exist yet (so a second call costs nothing); the first failure is returned and what was
+  // created stays owned.
+  hipError_t create() {
+    for (hipEvent_t& e : ev_)
+      if (!e) {
+        const hipError_t rc = hipEventCreate(&e);
+        if (rc != hipSuccess) {
+          e = nullptr;
+          return rc;
+        }
+      }
+    return hipSuccess;
+  }
+  hipEvent_t operator[](int i) const { return ev_[i]; }
+
+ private:
+  hipEvent_t ev_[N] = {};
 };
 
 }  // namespace

@@ -4,13 +4,13 @@
 //
 // low_high_pass_filter (lib/filters.py:314-372) is Re ifft2(fft2(q) . w) with Gaussian weights: a linear circulant operator
 // L on the plane that commutes with fftshift, so it acts on the unshifted plane k_zoom_sweep works on.  Each Gaussian is
-// separable, G q = Re(Cy q Cx^T) with the circulant operators of map_filter.inc (c = ifft(w); real on an even side, complex
+// separable, G q = Re(Cy q Cx^T) with the circulant operators of axis_plan.h (c = ifft(w); real on an even side, complex
 // on an odd one, where fftshift is not ifftshift):
 //     low pass alone  G_a q        high pass alone  q - G_b q        both  G_a q - G_(a+b) q
 //     Re(Cy q Cx^T) = Cyr q Cxr^T - Cyi q Cxi^T   (the second product only when both sides are odd)
 // so L q = c0 q + sum_j Ay_j q Ax_j^T with J <= 4 terms, the signs folded into Ax_j.  Per batch of B candidates:
 //   1. k_zoom_sweep<QS>: the product kernel with the q-storing epilogue, every tile, q -> [B][ony][onx];
-//   2. k_circ_gemm per term: T_j = Ay_j q, batched over the candidates' planes;
+//   2. k_circ_gemm (axis_pass.inc) per term: T_j = Ay_j q, batched over the candidates' planes;
 //   3. k_filter_xpass: sum_j T_j Ax_j^T as ONE product with K = J onx on the exact-f32 MFMA, then in the accumulator
 //      registers + c0 q and the masked moments against {w, w (E - Ebar)} of every segment, reduced in float64 in a fixed
 //      order to one triple per (segment, candidate, tile): L q is never stored.  Tiles without a masked bin are not computed;
@@ -109,19 +109,9 @@ int filt_y_passes(hh_ctx* c, const float* src, int batch) {
   hh_zoom* z = c->zoom;
   const int ony = z->r_ony, onx = z->r_onx;
   const size_t plane = (size_t)ony * onx;
+  const AxisGeom pass = axis_geom(AxisView{batch, ony, ony, onx, false});
   for (int j = 0; j < z->f_terms; ++j) {
-    CircPass g{};
-    g.a = z->d_ay + (size_t)j * ony * ony;
-    g.b0 = src;
-    g.b1 = nullptr;
-    g.y = z->d_ft + (size_t)j * batch * plane;
-    g.n = ony;
-    g.ka = ony;
-    g.np = onx;
-    g.sk = onx;
-    g.sp = 1;
-    g.sb = (int64_t)plane;
-    hipLaunchKernelGGL(k_circ_gemm<false>, dim3((onx + MF_T - 1) / MF_T, (ony + MF_T - 1) / MF_T, batch), dim3(256), 0, c->stream, g);
+    launch_circ_pass(pass, z->d_ay + (size_t)j * ony * ony, ony, src, nullptr, z->d_ft + (size_t)j * batch * plane, c->stream);
     HH_HIP(c, hipGetLastError());
   }
   return HH_OK;
@@ -164,12 +154,12 @@ int filt_prepare(hh_ctx* c, const uint8_t* mask) {
     std::vector<double> yr, yi, xr, xi;
     circulant_column(ony, gs.second, yr, yi);
     circulant_column(onx, gs.second, xr, xi);
-    append_operator(ay, ony, yr, 1.0, nullptr, 0.0);
-    append_operator(ax, onx, xr, gs.first, nullptr, 0.0);
+    append_axis_operator(ay, ony, AxisIndex::Circulant, yr, 1.0, nullptr, 0.0);
+    append_axis_operator(ax, onx, AxisIndex::Circulant, xr, gs.first, nullptr, 0.0);
     ++terms;
     if (ony % 2 == 1 && onx % 2 == 1) {   // Re((Cyr + i Cyi) q (Cxr + i Cxi)^T): the imaginary parts' product, with a minus
-      append_operator(ay, ony, yi, 1.0, nullptr, 0.0);
-      append_operator(ax, onx, xi, -gs.first, nullptr, 0.0);
+      append_axis_operator(ay, ony, AxisIndex::Circulant, yi, 1.0, nullptr, 0.0);
+      append_axis_operator(ax, onx, AxisIndex::Circulant, xi, -gs.first, nullptr, 0.0);
       ++terms;
     }
   }

@@ -4,9 +4,8 @@
 // For every pair and every shell s the three sums
 //     num[s] = sum w Re(F1 conj F2),   den1[s] = sum w |F1|^2,   den2[s] = sum w |F2|^2      over the bins of shell s
 // are returned (the ratio and the `denominator > 0` rule stay on the host).  The transforms are per-axis matrix products
-// on the exact-f32 MFMA, like the map filter's circulant passes (k_circ_gemm, map_filter.inc): a DFT along one axis is the
-// product with [cos | -sin] blocks built in float64 on the host and rounded to float32, so any side works (odd and prime
-// included) and there is no FFT plan.
+// on the exact-f32 MFMA (k_circ_gemm, axis_pass.inc): a DFT along one axis is the product with [cos | -sin] blocks built in
+// float64 on the host (axis_plan.h) and rounded to float32, so any side works (odd and prime included) and there is no FFT plan.
 //     3-D, F(kz, ky, kx):  z pass on the real input (Re = C x, Im = -S x), y pass on the complex planes
 //                          (Re = [C | S][re; im], Im = [-S | C][re; im]), both through k_circ_gemm;
 //     2-D, F(ky, kx):      y pass on the real input;
@@ -184,30 +183,6 @@ __global__ __launch_bounds__(256) void k_fc_finish(const long long* __restrict__
   sums[i] = s == 0.0 ? 0.0 : (double)acc[i] / s;   // a NaN scale (a map that is not finite) gives NaN
 }
 
-// C[j][k] = cos(2 pi j k / n), S = sin, float64 tables indexed by j k mod n
-void fc_trig(int n, std::vector<double>& c, std::vector<double>& s) {
-  c.resize(n);
-  s.resize(n);
-  for (int t = 0; t < n; ++t) {
-    c[t] = std::cos(2.0 * M_PI * t / n);
-    s[t] = std::sin(2.0 * M_PI * t / n);
-  }
-}
-
-// Row-major n x ka operator block [sp p | sq q] (q only when ka = 2 n) of the pass along one axis, appended to `mats`
-size_t fc_operator(std::vector<float>& mats, int n, const std::vector<double>& p, double sp, const std::vector<double>* q, double sq) {
-  const size_t off = mats.size();
-  const int ka = q ? 2 * n : n;
-  mats.resize(off + (size_t)n * ka);
-  for (int i = 0; i < n; ++i)
-    for (int j = 0; j < n; ++j) {
-      const int t = (int)(((int64_t)i * j) % n);
-      mats[off + (size_t)i * ka + j] = (float)(sp * p[t]);
-      if (q) mats[off + (size_t)i * ka + n + j] = (float)(sq * (*q)[t]);
-    }
-  return off;
-}
-
 // the x pass's tables: [n][ncol]
 size_t fc_xtable(std::vector<float>& mats, int n, int ncol, const std::vector<double>& p) {
   const size_t off = mats.size();
@@ -227,7 +202,7 @@ struct FcBuffers {
   DevBuf<unsigned> amax;            // [pairs][2]: its size says how many pairs the scratch holds
   DevBuf<double> scale, sums;
   DevBuf<long long> acc;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  DevEvents<2> ev;
   int64_t shape_per_map = 0;        // the shape the scratch was sized for
   int shape_nshell = 0;
   void release() {                  // the scratch only: mats and shell are the caller's
@@ -238,8 +213,7 @@ struct FcBuffers {
   // one-pair context; a one-pair fc_run carries the second set unused, a few KB).  Only `pairs` may grow between calls:
   // per_map, nshell and cube are those of the holder's one plan.
   int reserve(int64_t pairs, int64_t per_map, int nshell, bool cube, bool with_in) {
-    if (!ev0) HH_HIP(nullptr, hipEventCreate(&ev0));
-    if (!ev1) HH_HIP(nullptr, hipEventCreate(&ev1));
+    HH_HIP(nullptr, ev.create());
     const int64_t cap = (int64_t)amax.size() / 2;
     if (cap > 0 && (per_map != shape_per_map || nshell != shape_nshell)) return fail(nullptr, HH_ERR_STATE, "FcBuffers::reserve: another shape than the holder's");
     if (pairs <= cap && (!with_in || in)) return HH_OK;
@@ -261,10 +235,6 @@ struct FcBuffers {
     shape_per_map = per_map; shape_nshell = nshell;
     return HH_OK;
   }
-  ~FcBuffers() {
-    if (ev0) (void)hipEventDestroy(ev0);
-    if (ev1) (void)hipEventDestroy(ev1);
-  }
 };
 
 // The operators of one shape, built in float64 on the host: first pass on the real input, (3-D) second pass on the complex
@@ -285,15 +255,15 @@ void fc_plan(FcPlan& p, int nz, int ny, int nx) {
   p.per_map = (int64_t)p.rows * nx;
   p.n1 = p.cube ? nz : ny;
   std::vector<double> c, s;
-  fc_trig(p.n1, c, s);
-  p.o_c = fc_operator(p.mats, p.n1, c, 1.0, nullptr, 0.0);
-  p.o_ms = fc_operator(p.mats, p.n1, s, -1.0, nullptr, 0.0);
+  unit_circle(p.n1, c, s);
+  p.o_c = append_axis_operator(p.mats, p.n1, AxisIndex::Dft, c, 1.0, nullptr, 0.0);
+  p.o_ms = append_axis_operator(p.mats, p.n1, AxisIndex::Dft, s, -1.0, nullptr, 0.0);
   if (p.cube) {
-    fc_trig(ny, c, s);
-    p.o_re = fc_operator(p.mats, ny, c, 1.0, &s, 1.0);
-    p.o_im = fc_operator(p.mats, ny, s, -1.0, &c, 1.0);
+    unit_circle(ny, c, s);
+    p.o_re = append_axis_operator(p.mats, ny, AxisIndex::Dft, c, 1.0, &s, 1.0);
+    p.o_im = append_axis_operator(p.mats, ny, AxisIndex::Dft, s, -1.0, &c, 1.0);
   }
-  fc_trig(nx, c, s);
+  unit_circle(nx, c, s);
   p.o_xc = fc_xtable(p.mats, nx, p.ncol, c);
   p.o_xs = fc_xtable(p.mats, nx, p.ncol, s);
 }
@@ -314,30 +284,16 @@ void fc_passes(const FcPlan& p, const float* in, const FcBuffers& d, int64_t nb,
                      in, per_map, amax);
   hipLaunchKernelGGL(k_fc_scales, dim3((unsigned)((nb + 63) / 64)), dim3(64), 0, nullptr, amax, (int)nb, (double)per_map, scale);
   // first pass: the real input along z (cubes: P = ny nx, one map per grid.z) or along y (images: P = nx)
-  for (int part = 0; part < 2; ++part) {
-    CircPass g{};
-    g.a = mats + (part == 0 ? p.o_c : p.o_ms);
-    g.b0 = in; g.b1 = nullptr;
-    g.y = part == 0 ? re1 : im1;
-    g.n = n1; g.ka = n1;
-    g.np = p.cube ? (int64_t)ny * nx : nx; g.sk = g.np; g.sp = 1; g.sb = per_map;
-    hipLaunchKernelGGL(k_circ_gemm<false>, dim3((unsigned)((g.np + MF_T - 1) / MF_T), (unsigned)((n1 + MF_T - 1) / MF_T), (unsigned)maps),
-                       dim3(256), 0, nullptr, g);
-  }
+  const AxisGeom first = axis_geom(AxisView{maps, n1, n1, p.cube ? (int64_t)ny * nx : nx, false});
+  for (int part = 0; part < 2; ++part)
+    launch_circ_pass(first, mats + (part == 0 ? p.o_c : p.o_ms), n1, in, nullptr, part == 0 ? re1 : im1, nullptr);
   *xre = re1; *xim = im1;
   if (p.cube) {   // second pass along y: one z slice of one map per grid.z, K = 2 ny over the [re; im] planes
     float* const re2 = p2;
     float* const im2 = p2 + maps * per_map;
-    for (int part = 0; part < 2; ++part) {
-      CircPass g{};
-      g.a = mats + (part == 0 ? p.o_re : p.o_im);
-      g.b0 = re1; g.b1 = im1;
-      g.y = part == 0 ? re2 : im2;
-      g.n = ny; g.ka = 2 * ny;
-      g.np = nx; g.sk = nx; g.sp = 1; g.sb = (int64_t)ny * nx;
-      hipLaunchKernelGGL(k_circ_gemm<false>, dim3((unsigned)((nx + MF_T - 1) / MF_T), (unsigned)((ny + MF_T - 1) / MF_T), (unsigned)(maps * nz)),
-                         dim3(256), 0, nullptr, g);
-    }
+    const AxisGeom second = axis_geom(AxisView{maps * nz, ny, ny, nx, false});
+    for (int part = 0; part < 2; ++part)
+      launch_circ_pass(second, mats + (part == 0 ? p.o_re : p.o_im), 2 * ny, re1, im1, part == 0 ? re2 : im2, nullptr);
     *xre = re2; *xim = im2;
   }
 }
@@ -372,10 +328,7 @@ int64_t fc_chunk(const FcPlan& p, int64_t batch) {
 // nz == 0: images [ny][nx] with the host's shell table; else cubes of side nz = ny = nx
 int fc_run(const char* name, int device, const float* a, const float* b, int64_t batch, int nz, int ny, int nx, const int32_t* shell,
            int nshell, bool weighted, double* sums, double* kernel_ms) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
-    return fail(nullptr, HH_ERR_HIP, std::string(name) + ": no such HIP device (there is no CPU fallback)");
-  HH_HIP(nullptr, hipSetDevice(device));
+  if (int rc = use_device(name, device)) return rc;
   FcPlan p;
   fc_plan(p, nz, ny, nx);
   const bool cube = p.cube;
@@ -395,13 +348,13 @@ int fc_run(const char* name, int device, const float* a, const float* b, int64_t
     const int64_t nb = std::min(chunk, batch - b0);
     HH_HIP(nullptr, hipMemcpy(d.in, a + b0 * per_map, (size_t)nb * map_bytes, hipMemcpyHostToDevice));
     HH_HIP(nullptr, hipMemcpy(d.in + nb * per_map, b + b0 * per_map, (size_t)nb * map_bytes, hipMemcpyHostToDevice));
-    HH_HIP(nullptr, hipEventRecord(d.ev0, nullptr));
+    HH_HIP(nullptr, hipEventRecord(d.ev[0], nullptr));
     fc_device(p, d.in, d, nb, nshell, weighted);
     HH_HIP(nullptr, hipGetLastError());
-    HH_HIP(nullptr, hipEventRecord(d.ev1, nullptr));
+    HH_HIP(nullptr, hipEventRecord(d.ev[1], nullptr));
     HH_HIP(nullptr, hipMemcpy(sums + b0 * nshell * 3, d.sums, (size_t)nb * nshell * 3 * sizeof(double), hipMemcpyDeviceToHost));
     float ms = 0.f;
-    HH_HIP(nullptr, hipEventElapsedTime(&ms, d.ev0, d.ev1));
+    HH_HIP(nullptr, hipEventElapsedTime(&ms, d.ev[0], d.ev[1]));
     ms_total += ms;
   }
   if (kernel_ms) *kernel_ms = ms_total;

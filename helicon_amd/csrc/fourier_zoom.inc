@@ -81,10 +81,7 @@ extern "C" int hh_power_spectrum_zoom(int device, const float* image, int ny, in
     return fail(nullptr, HH_ERR_ARG, "hh_power_spectrum_zoom: bad argument");
   if ((int64_t)ny * nx > (1LL << 26) || (int64_t)ony * onx > (1LL << 26))
     return fail(nullptr, HH_ERR_ARG, "hh_power_spectrum_zoom: image or output larger than 2^26 pixels");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
-    return fail(nullptr, HH_ERR_HIP, "hh_power_spectrum_zoom: no such HIP device (there is no CPU fallback)");
-  HH_HIP(nullptr, hipSetDevice(device));
+  if (int rc = use_device("hh_power_spectrum_zoom", device)) return rc;
   const ZoomDims d{ny, nx, ony, onx, 2 * apix / cutoff_y, 2 * apix / cutoff_x};
   const size_t n_in = (size_t)ny * nx, n_out = (size_t)ony * onx;
   DevArena mem;

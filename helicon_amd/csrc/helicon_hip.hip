@@ -50,6 +50,7 @@
 #include "device_mem.h"  // DevBuf / DevArena: the owners of device memory
 #include "pab_plan.h"  // host arithmetic of the Path A batch set-up (path_a_batch.inc)
 #include "sweep_plan.h"  // host arithmetic of the sweep drivers (sweep_runs, sweep_on_device, gen_sweep)
+#include "axis_plan.h"  // host arithmetic of the separable axis passes (axis_pass.inc): pass geometry, operator blocks, unit circle
 #include "gen_rows.h"  // the general-size sweep's two-step row kernel (second translation unit, gen_rows.hip)
 
 // Tuning values are constants beside what they tune (the measured best).
@@ -2847,6 +2848,15 @@ int hh_caught(Set&& set, const char* fn) noexcept {
       return fail(ctx, HH_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e__));            \
   } while (0)
 
+// The device of an entry point that has no context: refused under the entry point's name when there is no such device.
+int use_device(const char* fn, int device) {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
+    return fail(nullptr, HH_ERR_HIP, std::string(fn) + ": no such HIP device (there is no CPU fallback)");
+  HH_HIP(nullptr, hipSetDevice(device));
+  return HH_OK;
+}
+
 bool supported_n(int n) { return n == 32 || n == 64 || n == 128 || n == 256 || n == 512 || n == 1024; }
 
 // What the host reads of the kernels' per-size constants.  An unsupported side is refused at hh_create2; asking for one
@@ -4524,11 +4534,8 @@ int hh_affine_transform_2d(int device, const float* data, int ny, int nx, const 
                            float* out) try {
   if (!data || !out || !matrix || !offset || ny < 1 || nx < 1)
     return fail(nullptr, HH_ERR_ARG, "hh_affine_transform_2d: bad argument");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
-    return fail(nullptr, HH_ERR_HIP, "hh_affine_transform_2d: no such HIP device (there is no CPU fallback)");
+  if (int rc = use_device("hh_affine_transform_2d", device)) return rc;
   const size_t bytes = (size_t)ny * nx * sizeof(float);
-  HH_HIP(nullptr, hipSetDevice(device));
   DevArena mem;
   float *d_in = mem.get<float>((size_t)ny * nx), *d_out = mem.get<float>((size_t)ny * nx);
   if (int rc = arena_ok(nullptr, mem)) return rc;
@@ -4547,9 +4554,7 @@ int hh_transform_map(int device, const float* data, const int32_t shape[3], doub
                      double psi_degree, double dx, double dy, double dz, float* out) try {
   if (!data || !out || !shape || shape[0] < 1 || shape[1] < 1 || shape[2] < 1)
     return fail(nullptr, HH_ERR_ARG, "hh_transform_map: bad argument");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
-    return fail(nullptr, HH_ERR_HIP, "hh_transform_map: no such HIP device (there is no CPU fallback)");
+  if (int rc = use_device("hh_transform_map", device)) return rc;
   const int nz = shape[0], ny = shape[1], nx = shape[2];
   const int64_t total = (int64_t)nz * ny * nx;
   MapArgs a{};
@@ -4569,7 +4574,6 @@ int hh_transform_map(int device, const float* data, const int32_t shape[3], doub
     for (int r = 0; r < 3; ++r)
       for (int cidx = 0; cidx < 3; ++cidx) a.m[3 * r + cidx] = t[3 * r] * rz3[cidx] + t[3 * r + 1] * rz3[3 + cidx] + t[3 * r + 2] * rz3[6 + cidx];
   }
-  HH_HIP(nullptr, hipSetDevice(device));
   DevArena mem;
   float *d_in = mem.get<float>((size_t)total), *d_out = mem.get<float>((size_t)total);
   double* d_c = mem.get<double>((size_t)total);
@@ -4645,35 +4649,29 @@ int hh_apply_helical_symmetry(int device, const float* data, const int32_t in_sh
       rot[2 * ((size_t)(hi + a.hmax) * csym + ci)] = std::cos(r);
       rot[2 * ((size_t)(hi + a.hmax) * csym + ci) + 1] = std::sin(r);
     }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
-    return fail(nullptr, HH_ERR_HIP, "hh_apply_helical_symmetry: no such HIP device (no CPU fallback)");
-  HH_HIP(nullptr, hipSetDevice(device));
+  if (int rc = use_device("hh_apply_helical_symmetry", device)) return rc;
   const size_t n_in = (size_t)nz0 * ny0 * nx0, n_out = (size_t)a.oz * a.oy * a.ox;
   DevArena mem;
   float *d_in = mem.get<float>(n_in), *d_out = mem.get<float>(n_out);
   double* d_rot = mem.get<double>(rot.size());
   if (int rc = arena_ok(nullptr, mem)) return rc;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  hipError_t e = hipEventCreate(&e0);
-  if (e == hipSuccess) e = hipEventCreate(&e1);
+  DevEvents<2> ev;
+  hipError_t e = ev.create();
   if (e == hipSuccess) e = hipMemcpy(d_in, data, n_in * sizeof(float), hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(d_rot, rot.data(), rot.size() * sizeof(double), hipMemcpyHostToDevice);
   if (e == hipSuccess) {
     a.data = d_in; a.out = d_out; a.rot = d_rot;
-    (void)hipEventRecord(e0, nullptr);
+    (void)hipEventRecord(ev[0], nullptr);
     hipLaunchKernelGGL(k_apply_helical_symmetry, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, nullptr, a);
-    (void)hipEventRecord(e1, nullptr);
+    (void)hipEventRecord(ev[1], nullptr);
     e = hipGetLastError();
   }
   if (e == hipSuccess) e = hipMemcpy(out, d_out, n_out * sizeof(float), hipMemcpyDeviceToHost);
   if (e == hipSuccess && kernel_ms) {
     float ms = 0.f;
-    e = hipEventElapsedTime(&ms, e0, e1);
+    e = hipEventElapsedTime(&ms, ev[0], ev[1]);
     *kernel_ms = ms;
   }
-  if (e0) (void)hipEventDestroy(e0);
-  if (e1) (void)hipEventDestroy(e1);
   if (e != hipSuccess) return fail(nullptr, HH_ERR_HIP, std::string("hh_apply_helical_symmetry: ") + hipGetErrorString(e));
   return HH_OK;
 } HH_CATCH_CTX(nullptr, "hh_apply_helical_symmetry")
@@ -4745,6 +4743,7 @@ int hh_profile_get(hh_ctx* c, hh_profile* out) try {
 #include "zoom_sweep.inc"    // the sweep on those zoomed spectra: factors + complex product on the f32 MFMA + fused moments (hh_set_spectrum_zoom)
 #include "path_a_host.inc"  // Path A: host side and C ABI (hh_pa_*)
 #include "path_a_batch.inc"  // Path A for many candidates at once, device-resident solve (hh_pab_*)
+#include "axis_pass.inc"  // the separable axis passes on the f32 MFMA: k_circ_gemm, k_axis_gemm and the one launch of each (geometry: axis_plan.h)
 #include "map_filter.inc"  // the 3-D map input: separable Gaussian filter of a whole map on the f32 MFMA, axis projections
 #include "fourier_resample.inc"  // Fourier resampling of a map: a rectangular complex operator per axis, re and im accumulators from one staged slice, fused epilogue (hh_separable_transform_3d)
 #include "filtered_sweep.inc"  // the sweep on low / high-pass filtered spectra (hh_set_spectrum_filter): y pass + fused x pass / moments

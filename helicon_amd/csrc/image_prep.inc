@@ -19,14 +19,6 @@
 
 namespace {
 
-int prep_device(int device, const char* fn) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
-    return fail(nullptr, HH_ERR_HIP, std::string(fn) + ": no such HIP device (there is no CPU fallback)");
-  if (hipSetDevice(device) != hipSuccess) return fail(nullptr, HH_ERR_HIP, std::string(fn) + ": hipSetDevice failed");
-  return HH_OK;
-}
-
 // ---- range of an image (skimage's clip step: _clip_warp_output works from the INPUT image's minimum and maximum) ---------
 template <typename T>
 __global__ __launch_bounds__(1024) void k_prep_minmax(const T* __restrict__ in, int64_t n, double* __restrict__ out /*[2]*/) {
@@ -495,7 +487,7 @@ int hh_warp_affine_2d(int device, const void* data, int is_f64, int rows, int co
                       int clip, void* out) try {
   if (!data || !out || !inverse_matrix || rows < 1 || cols < 1 || (order != 0 && order != 1))
     return fail(nullptr, HH_ERR_ARG, "hh_warp_affine_2d: bad argument (orders 0 and 1 are provided)");
-  if (int rc = prep_device(device, "hh_warp_affine_2d")) return rc;
+  if (int rc = use_device("hh_warp_affine_2d", device)) return rc;
   return is_f64 ? prep_warp(static_cast<const double*>(data), rows, cols, inverse_matrix, order, cval, clip, static_cast<double*>(out))
                 : prep_warp(static_cast<const float*>(data), rows, cols, inverse_matrix, order, cval, clip, static_cast<float*>(out));
 } HH_CATCH_CTX(nullptr, "hh_warp_affine_2d")
@@ -504,14 +496,14 @@ int hh_rescale_2d(int device, const void* data, int is_f64, int rows, int cols, 
                   int clip, void* out) try {
   if (!data || !out || rows < 1 || cols < 1 || out_rows < 1 || out_cols < 1 || (order != 1 && order != 3))
     return fail(nullptr, HH_ERR_ARG, "hh_rescale_2d: bad argument (orders 1 and 3 are provided)");
-  if (int rc = prep_device(device, "hh_rescale_2d")) return rc;
+  if (int rc = use_device("hh_rescale_2d", device)) return rc;
   return is_f64 ? prep_rescale(static_cast<const double*>(data), rows, cols, out_rows, out_cols, order, anti_aliasing, clip, static_cast<double*>(out))
                 : prep_rescale(static_cast<const float*>(data), rows, cols, out_rows, out_cols, order, anti_aliasing, clip, static_cast<float*>(out));
 } HH_CATCH_CTX(nullptr, "hh_rescale_2d")
 
 int hh_affine_transform_2d_cubic(int device, const float* data, int ny, int nx, const double matrix[4], const double offset[2], float* out) try {
   if (!data || !out || !matrix || !offset || ny < 1 || nx < 1) return fail(nullptr, HH_ERR_ARG, "hh_affine_transform_2d_cubic: bad argument");
-  if (int rc = prep_device(device, "hh_affine_transform_2d_cubic")) return rc;
+  if (int rc = use_device("hh_affine_transform_2d_cubic", device)) return rc;
   const size_t n = (size_t)ny * nx;
   DevArena mem;
   float* d_in = mem.get<float>(n);
@@ -534,7 +526,7 @@ int hh_affine_transform_2d_cubic(int device, const float* data, int ny, int nx, 
 
 int hh_helix_moments(int device, const void* data, int is_f64, int rows, int cols, double threshold, double out[8]) try {
   if (!data || !out || rows < 1 || cols < 1) return fail(nullptr, HH_ERR_ARG, "hh_helix_moments: bad argument");
-  if (int rc = prep_device(device, "hh_helix_moments")) return rc;
+  if (int rc = use_device("hh_helix_moments", device)) return rc;
   return is_f64 ? prep_moments(static_cast<const double*>(data), rows, cols, threshold, out)
                 : prep_moments(static_cast<const float*>(data), rows, cols, threshold, out);
 } HH_CATCH_CTX(nullptr, "hh_helix_moments")
@@ -542,7 +534,7 @@ int hh_helix_moments(int device, const void* data, int is_f64, int rows, int col
 int hh_ssim_2d(int device, const float* a, const float* b, int rows, int cols, double data_range, double* out) try {
   if (!a || !b || !out || rows < 7 || cols < 7 || !(data_range > 0))
     return fail(nullptr, HH_ERR_ARG, "hh_ssim_2d: bad argument (the 7 x 7 window must fit the image, data_range > 0)");
-  if (int rc = prep_device(device, "hh_ssim_2d")) return rc;
+  if (int rc = use_device("hh_ssim_2d", device)) return rc;
   const size_t n = (size_t)rows * cols;
   DevArena mem;
   const dim3 g0((cols + 255) / 256, rows - 6), g1((cols - 6 + 255) / 256, rows - 6);
@@ -574,7 +566,7 @@ int hh_joint_histogram(int device, const float* a, const float* b, int64_t n, co
                        int64_t* hist) try {
   if (!a || !b || !edges_a || !edges_b || !hist || n < 1 || bins < 1 || bins > 4096)
     return fail(nullptr, HH_ERR_ARG, "hh_joint_histogram: bad argument");
-  if (int rc = prep_device(device, "hh_joint_histogram")) return rc;
+  if (int rc = use_device("hh_joint_histogram", device)) return rc;
   DevArena mem;
   const size_t nb = (size_t)bins * bins;
   float* d_a = mem.get<float>((size_t)n);

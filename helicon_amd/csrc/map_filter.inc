@@ -5,7 +5,8 @@
 // product w_z(kz) w_y(ky) w_x(kx) of three 1-D weights, so it is three 1-D circulant operators, one along each axis:
 //     C = F^-1 diag(w) F,   C[i][j] = c[(i - j) mod n],   c = ifft(w)
 // and the high pass folds into the same form: exp(-a R^2) (1 - exp(-b R^2)) = G_a - G_(a+b); high pass alone is x - G_b x.
-// Each axis pass is a plain GEMM on the volume as stored (no transposes), on the exact-f32 MFMA (32x32x2):
+// Each axis pass is a plain GEMM on the volume as stored (no transposes), on the exact-f32 MFMA (32x32x2): k_circ_gemm
+// (axis_pass.inc) in the geometry axis_plan.h gives for the axis,
 //     z: (nz x nz) . (nz x ny nx),   y: batched over z, (ny x ny) . (ny x nx),   x: (nz ny x nx) . (nx x nx)^T.
 // Any side works (primes included): there is no FFT plan.  The per-axis weights follow gen_pass_filter's rule: unshifted
 // index k takes the centred float32 coordinate of (k + ceil(n / 2)) mod n over n // 2 (fftshift, not ifftshift), which for
@@ -14,58 +15,6 @@
 // complex one) and the last pass computes the real plane alone.  c is built in float64 on the host and rounded to f32.
 
 namespace {
-
-constexpr int MF_T = 64;   // output tile of a workgroup: 64 rows of the operator x 64 columns of the volume
-constexpr int MF_K = 32;   // K slice staged through LDS per step
-
-struct CircPass {
-  const float* a;    // [n][ka] row-major operator block (ka = n, or 2n for [Cr | -Ci] / [Ci | Cr] on a complex input)
-  const float* b0;   // input plane for k < n
-  const float* b1;   // input plane for n <= k < 2n (imaginary part), or null when ka == n
-  float* y;          // output plane
-  int n, ka;
-  int64_t np;        // columns P of the product
-  int64_t sk, sp;    // element strides of B / Y along the operator's index and along P
-  int64_t sb;        // element stride of one batch (the y pass: one z slice)
-};
-
-// Y[b][m][p] = sum_k A[m][k] B[b][k][p] on the shared tile (mfma_tile.inc), one 32 x 32 accumulator per wavefront.  TR swaps
-// the MFMA's operands so that the accumulator's lane index runs along m: with the x pass's strides (sk = 1) the stores coalesce.
-template <bool TR>
-__global__ __launch_bounds__(256) void k_circ_gemm(CircPass g) {
-  __shared__ float as[MF_T][MF_K + 1];
-  __shared__ float bs[MF_K][MF_T + 1];
-  const Tile64 t = tile64();
-  const int tid = t.tid, r = t.r, h = t.h, wm = t.wm, wp = t.wp;
-  const int m0 = blockIdx.y * MF_T;
-  const int64_t p0 = (int64_t)blockIdx.x * MF_T, boff = (int64_t)blockIdx.z * g.sb;
-  const float* b0 = g.b0 + boff;
-  const float* b1 = g.b1 ? g.b1 + boff : nullptr;
-  f32x16 acc = {0};
-  for (int k0 = 0; k0 < g.ka; k0 += MF_K) {
-    stage_rows(as, g.a, g.ka, m0, g.n, k0, g.ka, tid);
-    for (int e = tid; e < MF_T * MF_K; e += 256) {   // its own: the stride along P and the split of K over b0 / b1
-      int kk, pp;
-      if (g.sp == 1) { kk = e / MF_T; pp = e % MF_T; }   // P contiguous: lanes along P
-      else { pp = e / MF_K; kk = e % MF_K; }             // the x pass: lanes along k
-      const int k = k0 + kk;
-      const int64_t p = p0 + pp;
-      float v = 0.f;
-      if (k < g.ka && p < g.np) v = k < g.n ? b0[(int64_t)k * g.sk + p * g.sp] : b1[(int64_t)(k - g.n) * g.sk + p * g.sp];
-      bs[kk][pp] = v;
-    }
-    __syncthreads();
-    tile_mac<TR>(acc, as, bs, t);
-    __syncthreads();
-  }
-#pragma unroll
-  for (int i = 0; i < 16; ++i) {
-    const int row = acc_row(i, h);
-    const int m = m0 + wm + (TR ? r : row);
-    const int64_t p = p0 + wp + (TR ? row : r);
-    if (m < g.n && p < g.np) g.y[boff + (int64_t)m * g.sk + p * g.sp] = acc[i];
-  }
-}
 
 __global__ __launch_bounds__(256) void k_map_axpy(float* __restrict__ acc, float coef, const float* __restrict__ src, int64_t total) {
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) acc[i] += coef * src[i];
@@ -100,45 +49,6 @@ __global__ __launch_bounds__(256) void k_map_proj_columns(const float* __restric
   out_z[q] = (float)acc;
 }
 
-// c = ifft(w) for one axis, w the reference's weight exp(-f2 u^2) on fftshifted float32 coordinates u (float64 sums).
-void circulant_column(int n, double f2, std::vector<double>& cr, std::vector<double>& ci) {
-  std::vector<double> w(n), cs(n), sn(n);
-  for (int k = 0; k < n; ++k) {
-    const int idx = (k + (n + 1) / 2) % n;
-    const float u = (float)(idx - n / 2) / (float)(n / 2);
-    w[k] = std::exp(-f2 * (double)(u * u));
-    cs[k] = std::cos(2.0 * M_PI * k / n);
-    sn[k] = std::sin(2.0 * M_PI * k / n);
-  }
-  cr.assign(n, 0.0);
-  ci.assign(n, 0.0);
-  for (int d = 0; d < n; ++d) {
-    double sr = 0, si = 0;
-    for (int k = 0; k < n; ++k) {
-      const int t = (int)(((int64_t)k * d) % n);
-      sr += w[k] * cs[t];
-      si += w[k] * sn[t];
-    }
-    cr[d] = sr / n;
-    ci[d] = si / n;
-  }
-}
-
-// Appends the n x ka operator block [p | q] (q only when ka = 2n), p[i][j] = sp * c_p[(i - j) mod n], to `mats`.
-size_t append_operator(std::vector<float>& mats, int n, const std::vector<double>& cp, double sp, const std::vector<double>* cq,
-                       double sq) {
-  const size_t off = mats.size();
-  const int ka = cq ? 2 * n : n;
-  mats.resize(off + (size_t)n * ka);
-  for (int i = 0; i < n; ++i)
-    for (int j = 0; j < n; ++j) {
-      const int d = ((i - j) % n + n) % n;
-      mats[off + (size_t)i * ka + j] = (float)(sp * cp[d]);
-      if (cq) mats[off + (size_t)i * ka + n + j] = (float)(sq * (*cq)[d]);
-    }
-  return off;
-}
-
 struct CircOp {
   int axis;
   size_t a_off;
@@ -155,11 +65,8 @@ extern "C" int hh_low_high_pass_filter_3d(int device, const float* data, const i
   for (int ax = 0; ax < 3; ++ax)
     if (side[ax] < 2 || side[ax] > 1024)
       return fail(nullptr, HH_ERR_ARG, "hh_low_high_pass_filter_3d: every side must lie in [2, 1024] (the reference divides by n // 2)");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
-    return fail(nullptr, HH_ERR_HIP, "hh_low_high_pass_filter_3d: no such HIP device (there is no CPU fallback)");
-  const int nz = side[0], ny = side[1], nx = side[2];
-  const int64_t total = (int64_t)nz * ny * nx;
+  if (int rc = use_device("hh_low_high_pass_filter_3d", device)) return rc;
+  const int64_t total = (int64_t)side[0] * side[1] * side[2];
   // filters.py:363-370: a fraction outside (0, 1) is ignored.  The result is sum_t coef_t G_(f2_t) x, G_0 = identity.
   const bool lp = 0 < low_pass_fraction && low_pass_fraction < 1, hp = 0 < high_pass_fraction && high_pass_fraction < 1;
   const double a = lp ? std::log(2.0) / (low_pass_fraction * low_pass_fraction) : 0.0;
@@ -183,25 +90,24 @@ extern "C" int hh_low_high_pass_filter_3d(int device, const float* data, const i
       std::vector<double> cr, ci;
       circulant_column(n, t.second, cr, ci);
       if (!odd) {   // C real (and symmetric): each plane on its own
-        const size_t off = append_operator(mats, n, cr, 1.0, nullptr, 0.0);
+        const size_t off = append_axis_operator(mats, n, AxisIndex::Circulant, cr, 1.0, nullptr, 0.0);
         ops.push_back({ax, off, n, re, -1, dre});
         if (im >= 0 && !last) ops.push_back({ax, off, n, im, -1, dim});
         im = (im >= 0 && !last) ? dim : -1;
       } else if (im < 0) {   // complex C on a real input: Re = Cr x, Im = Ci x
         any_odd = true;
-        ops.push_back({ax, append_operator(mats, n, cr, 1.0, nullptr, 0.0), n, re, -1, dre});
-        if (!last) ops.push_back({ax, append_operator(mats, n, ci, 1.0, nullptr, 0.0), n, re, -1, dim});
+        ops.push_back({ax, append_axis_operator(mats, n, AxisIndex::Circulant, cr, 1.0, nullptr, 0.0), n, re, -1, dre});
+        if (!last) ops.push_back({ax, append_axis_operator(mats, n, AxisIndex::Circulant, ci, 1.0, nullptr, 0.0), n, re, -1, dim});
         im = last ? -1 : dim;
       } else {   // complex C on a complex input: Re = [Cr | -Ci] [xr; xi], Im = [Ci | Cr] [xr; xi]
-        ops.push_back({ax, append_operator(mats, n, cr, 1.0, &ci, -1.0), 2 * n, re, im, dre});
-        if (!last) ops.push_back({ax, append_operator(mats, n, ci, 1.0, &cr, 1.0), 2 * n, re, im, dim});
+        ops.push_back({ax, append_axis_operator(mats, n, AxisIndex::Circulant, cr, 1.0, &ci, -1.0), 2 * n, re, im, dre});
+        if (!last) ops.push_back({ax, append_axis_operator(mats, n, AxisIndex::Circulant, ci, 1.0, &cr, 1.0), 2 * n, re, im, dim});
         im = last ? -1 : dim;
       }
       re = dre;
     }
     ops.push_back({-1, 0, 0, 5, -1, -1});   // marker: accumulate plane 5 with this term's coefficient
   }
-  HH_HIP(nullptr, hipSetDevice(device));
   DevArena mem;
   float* planes[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   float* d_mats = nullptr;
@@ -235,27 +141,8 @@ extern "C" int hh_low_high_pass_filter_3d(int device, const float* data, const i
         ++next_term;
         break;
       }
-      CircPass g{};
-      g.a = d_mats + op.a_off;
-      g.b0 = planes[op.src0];
-      g.b1 = op.src1 >= 0 ? planes[op.src1] : nullptr;
-      g.y = planes[op.dst];
-      g.n = side[op.axis];
-      g.ka = op.ka;
-      dim3 grid;
-      const unsigned mt = (unsigned)((g.n + MF_T - 1) / MF_T);
-      if (op.axis == 0) {        // (nz x nz) . (nz x ny nx)
-        g.np = (int64_t)ny * nx; g.sk = g.np; g.sp = 1; g.sb = 0;
-        grid = dim3((unsigned)((g.np + MF_T - 1) / MF_T), mt, 1);
-      } else if (op.axis == 1) { // per z slice: (ny x ny) . (ny x nx)
-        g.np = nx; g.sk = nx; g.sp = 1; g.sb = (int64_t)ny * nx;
-        grid = dim3((unsigned)((g.np + MF_T - 1) / MF_T), mt, (unsigned)nz);
-      } else {                   // (nz ny x nx) . (nx x nx)^T
-        g.np = (int64_t)nz * ny; g.sk = 1; g.sp = nx; g.sb = 0;
-        grid = dim3((unsigned)((g.np + MF_T - 1) / MF_T), mt, 1);
-      }
-      if (op.axis == 2) hipLaunchKernelGGL(k_circ_gemm<true>, grid, dim3(256), 0, nullptr, g);
-      else hipLaunchKernelGGL(k_circ_gemm<false>, grid, dim3(256), 0, nullptr, g);
+      launch_circ_pass(axis_geom(side, op.axis, side[op.axis], 1), d_mats + op.a_off, op.ka, planes[op.src0],
+                       op.src1 >= 0 ? planes[op.src1] : nullptr, planes[op.dst], nullptr);
       e = hipGetLastError();
     }
   }
@@ -272,10 +159,7 @@ extern "C" int hh_map_projections(int device, const float* data, const int32_t s
     return fail(nullptr, HH_ERR_ARG, "hh_map_projections: sides must lie in [1, 4096]");
   if (slab_begin >= 0 && (slab_end < slab_begin || slab_end > nz))
     return fail(nullptr, HH_ERR_ARG, "hh_map_projections: the slab must satisfy 0 <= begin <= end <= nz");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
-    return fail(nullptr, HH_ERR_HIP, "hh_map_projections: no such HIP device (there is no CPU fallback)");
-  HH_HIP(nullptr, hipSetDevice(device));
+  if (int rc = use_device("hh_map_projections", device)) return rc;
   const int64_t plane = (int64_t)ny * nx, total = plane * nz;
   DevArena mem;
   float* d_v = mem.get<float>((size_t)total);

@@ -2,7 +2,7 @@
 // chain) share: the accumulator type, a lane's place in a workgroup tile made of 32 x 32 wavefront sub-tiles, the
 // accumulator's row mapping, the two staging loops of a K slice through LDS, the single-accumulator K-slice step and the
 // float64 block reduction of an epilogue's sums.  Included inside helicon_hip.hip's unnamed namespace, ahead of
-// k_segment_corr.  Users: k_segment_corr (read-out), k_circ_gemm, k_axis_gemm, k_filter_xpass, k_zoom_sweep / k_phase_sweep,
+// k_segment_corr.  Users: k_segment_corr (read-out), k_circ_gemm and k_axis_gemm (axis_pass.inc), k_filter_xpass, k_zoom_sweep / k_phase_sweep,
 // k_fc_xpass / k_tfsc_xpass (fc_pair_product), k_tfsc_c2r.
 //
 // The LDS layout every user keeps: A as as[rows][K + 1] ("rows along K"), B as bs[K][columns + 1]; the MFMA takes two k per

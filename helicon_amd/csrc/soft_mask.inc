@@ -195,22 +195,6 @@ int sm_empty(const char* fn, int step) {
                                        std::to_string(step) + ": there is no distance to take");
 }
 
-int sm_device(const char* fn, int device) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
-    return fail(nullptr, HH_ERR_HIP, std::string(fn) + ": no such HIP device (there is no CPU fallback)");
-  HH_HIP(nullptr, hipSetDevice(device));
-  return HH_OK;
-}
-
-struct SmEvents {
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  ~SmEvents() {
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-  }
-};
-
 // the grids, tap tables and probes of a context, grown on demand
 int sm_reserve(SmState* s, int64_t cells, int64_t taps, int64_t probes) {
   int rc = ensure(nullptr, s->g0, (size_t)cells);
@@ -239,24 +223,23 @@ extern "C" int hh_edt_3d(int device, const uint8_t* support, int32_t nz, int32_t
   if (!support || !sqdist_out) return fail(nullptr, HH_ERR_ARG, "hh_edt_3d: NULL argument");
   if (!sm_sides_ok(nz, ny, nx)) return fail(nullptr, HH_ERR_ARG, "hh_edt_3d: the sides of the box must lie in [1, 1024]");
   if (stride < 1) return fail(nullptr, HH_ERR_ARG, "hh_edt_3d: stride must be >= 1");
-  if (int rc = sm_device("hh_edt_3d", device)) return rc;
+  if (int rc = use_device("hh_edt_3d", device)) return rc;
   const int mz = (nz + stride - 1) / stride, my = (ny + stride - 1) / stride, mx = (nx + stride - 1) / stride;
   const int64_t cells = (int64_t)mz * my * mx, per_map = (int64_t)nz * ny * nx;
   SmState s;
-  SmEvents ev;
+  DevEvents<2> ev;
   if (int rc = ensure(nullptr, s.sup, (size_t)per_map)) return rc;
   if (int rc = sm_reserve(&s, cells, 0, 0)) return rc;
-  HH_HIP(nullptr, hipEventCreate(&ev.e0));
-  HH_HIP(nullptr, hipEventCreate(&ev.e1));
+  HH_HIP(nullptr, ev.create());
   HH_HIP(nullptr, hipMemcpy(s.sup, support, (size_t)per_map, hipMemcpyHostToDevice));
-  HH_HIP(nullptr, hipEventRecord(ev.e0, nullptr));
+  HH_HIP(nullptr, hipEventRecord(ev[0], nullptr));
   sm_edt(s.sup, nz, ny, nx, stride, s.g0, s.g1);
   HH_HIP(nullptr, hipGetLastError());
-  HH_HIP(nullptr, hipEventRecord(ev.e1, nullptr));
+  HH_HIP(nullptr, hipEventRecord(ev[1], nullptr));
   HH_HIP(nullptr, hipMemcpy(sqdist_out, s.g0, (size_t)cells * sizeof(int32_t), hipMemcpyDeviceToHost));
   if (sqdist_out[0] >= SM_INF) return sm_empty("hh_edt_3d", stride);
   float ms = 0.f;
-  HH_HIP(nullptr, hipEventElapsedTime(&ms, ev.e0, ev.e1));
+  HH_HIP(nullptr, hipEventElapsedTime(&ms, ev[0], ev[1]));
   if (kernel_ms) *kernel_ms = ms;
   return HH_OK;
 } HH_CATCH_CTX(nullptr, "hh_edt_3d")
@@ -307,20 +290,19 @@ extern "C" int hh_soft_mask_3d(int device, const uint8_t* support, int32_t nz, i
     if (kernel_ms) *kernel_ms = 0.0;
     return HH_OK;
   }
-  if (int rc = sm_device("hh_soft_mask_3d", device)) return rc;
+  if (int rc = use_device("hh_soft_mask_3d", device)) return rc;
   SmState s;
-  SmEvents ev;
+  DevEvents<2> ev;
   if (int rc = ensure(nullptr, s.sup, (size_t)per_map)) return rc;
   if (int rc = ensure(nullptr, s.mask, (size_t)per_map)) return rc;
-  HH_HIP(nullptr, hipEventCreate(&ev.e0));
-  HH_HIP(nullptr, hipEventCreate(&ev.e1));
+  HH_HIP(nullptr, ev.create());
   HH_HIP(nullptr, hipMemcpy(s.sup, support, (size_t)per_map, hipMemcpyHostToDevice));
-  HH_HIP(nullptr, hipEventRecord(ev.e0, nullptr));
+  HH_HIP(nullptr, hipEventRecord(ev[0], nullptr));
   if (int rc = sm_one("hh_soft_mask_3d", &s, s.sup, nz, ny, nx, soft_width, s.mask)) return rc;
-  HH_HIP(nullptr, hipEventRecord(ev.e1, nullptr));
+  HH_HIP(nullptr, hipEventRecord(ev[1], nullptr));
   HH_HIP(nullptr, hipMemcpy(mask_out, s.mask, (size_t)per_map * sizeof(float), hipMemcpyDeviceToHost));
   float ms = 0.f;
-  HH_HIP(nullptr, hipEventElapsedTime(&ms, ev.e0, ev.e1));
+  HH_HIP(nullptr, hipEventElapsedTime(&ms, ev[0], ev[1]));
   if (kernel_ms) *kernel_ms = ms;
   return HH_OK;
 } HH_CATCH_CTX(nullptr, "hh_soft_mask_3d")
@@ -396,7 +378,7 @@ extern "C" int hh_tfsm_soft_masked(hh_tfsc* ctx, const double* soft_widths, int3
     }
     HH_HIP(nullptr, hipMemcpy(s->taps, taps.data(), (size_t)(nb * 3 * n) * sizeof(SmTap), hipMemcpyHostToDevice));
     HH_HIP(nullptr, hipMemsetAsync(s->probe, 0, (size_t)(nb * n_sup) * sizeof(int32_t), nullptr));
-    HH_HIP(nullptr, hipEventRecord(d.ev0, nullptr));
+    HH_HIP(nullptr, hipEventRecord(d.ev[0], nullptr));
     const int64_t P = 2 * nb;   // k_tfsc_mask's layout of `in`
     for (int64_t j = 0; j < nb; ++j) {
       const double w = soft_widths[b0 + j];
@@ -424,13 +406,13 @@ extern "C" int hh_tfsm_soft_masked(hh_tfsc* ctx, const double* soft_widths, int3
     HH_HIP(nullptr, hipGetLastError());
     fc_device(c->plan, d.in, d, 2 * nb, nshell, full_spectrum != 0);
     HH_HIP(nullptr, hipGetLastError());
-    HH_HIP(nullptr, hipEventRecord(d.ev1, nullptr));
+    HH_HIP(nullptr, hipEventRecord(d.ev[1], nullptr));
     HH_HIP(nullptr, hipMemcpy(probe.data(), s->probe, (size_t)(nb * n_sup) * sizeof(int32_t), hipMemcpyDeviceToHost));
     for (int64_t e = 0; e < nb * n_sup; ++e)
       if (probe[(size_t)e] >= SM_INF) return sm_empty("hh_tfsm_soft_masked", sm_step(soft_widths[b0 + e / n_sup]));
     HH_HIP(nullptr, hipMemcpy(sums + b0 * 2 * nshell * 3, d.sums, (size_t)(2 * nb) * nshell * 3 * sizeof(double), hipMemcpyDeviceToHost));
     float ms = 0.f;
-    HH_HIP(nullptr, hipEventElapsedTime(&ms, d.ev0, d.ev1));
+    HH_HIP(nullptr, hipEventElapsedTime(&ms, d.ev[0], d.ev[1]));
     ms_total += ms;
   }
   if (kernel_ms) *kernel_ms = ms_total;

@@ -204,10 +204,10 @@ int tf_create(hh_tfsc* c, const float* map1, const float* map2, int64_t m_cut, c
   std::vector<float> mats = c->plan.mats;
   {   // inverse passes: (c + i s)(a + i b) = (c a - s b) + i (s a + c b), 1 / n each
     std::vector<double> cs, sn;
-    fc_trig(n, cs, sn);
+    unit_circle(n, cs, sn);
     const double q = 1.0 / n;
-    c->o_izr = fc_operator(mats, n, cs, q, &sn, -q);
-    c->o_izi = fc_operator(mats, n, sn, q, &cs, q);
+    c->o_izr = append_axis_operator(mats, n, AxisIndex::Dft, cs, q, &sn, -q);
+    c->o_izi = append_axis_operator(mats, n, AxisIndex::Dft, sn, q, &cs, q);
     c->o_iyr = c->o_izr;
     c->o_iyi = c->o_izi;
     c->o_xcw = tf_c2r_table(mats, n, ncol, cs, q, false);
@@ -252,25 +252,12 @@ int tf_create(hh_tfsc* c, const float* map1, const float* map2, int64_t m_cut, c
   float* const zi = d.p1 + 2 * per_spec;
   float* const yr = d.p2;
   float* const yi = d.p2 + 2 * per_spec;
-  for (int part = 0; part < 2; ++part) {
-    CircPass g{};
-    g.a = d.mats + (part == 0 ? c->o_izr : c->o_izi);
-    g.b0 = sre; g.b1 = sim;
-    g.y = part == 0 ? zr : zi;
-    g.n = n; g.ka = 2 * n;
-    g.np = (int64_t)n * ncol; g.sk = g.np; g.sp = 1; g.sb = per_spec;
-    hipLaunchKernelGGL(k_circ_gemm<false>, dim3((unsigned)((g.np + MF_T - 1) / MF_T), (unsigned)((n + MF_T - 1) / MF_T), 2), dim3(256), 0, nullptr, g);
-  }
-  for (int part = 0; part < 2; ++part) {
-    CircPass g{};
-    g.a = d.mats + (part == 0 ? c->o_iyr : c->o_iyi);
-    g.b0 = zr; g.b1 = zi;
-    g.y = part == 0 ? yr : yi;
-    g.n = n; g.ka = 2 * n;
-    g.np = ncol; g.sk = ncol; g.sp = 1; g.sb = (int64_t)n * ncol;
-    hipLaunchKernelGGL(k_circ_gemm<false>, dim3((unsigned)((ncol + MF_T - 1) / MF_T), (unsigned)((n + MF_T - 1) / MF_T), (unsigned)(2 * n)), dim3(256), 0,
-                       nullptr, g);
-  }
+  const AxisGeom inv_z = axis_geom(AxisView{2, n, n, (int64_t)n * ncol, false});
+  for (int part = 0; part < 2; ++part)
+    launch_circ_pass(inv_z, d.mats + (part == 0 ? c->o_izr : c->o_izi), 2 * n, sre, sim, part == 0 ? zr : zi, nullptr);
+  const AxisGeom inv_y = axis_geom(AxisView{2 * (int64_t)n, n, n, ncol, false});
+  for (int part = 0; part < 2; ++part)
+    launch_circ_pass(inv_y, d.mats + (part == 0 ? c->o_iyr : c->o_iyi), 2 * n, zr, zi, part == 0 ? yr : yi, nullptr);
   TfC2R r{};
   r.re = yr; r.im = yi;
   r.cw = d.mats + c->o_xcw; r.sw = d.mats + c->o_xsw;
@@ -292,9 +279,7 @@ extern "C" int hh_tfsc_create(hh_tfsc** out, int device, const float* map1, cons
   if ((phases1 == nullptr) != (phases2 == nullptr)) return fail(nullptr, HH_ERR_ARG, "hh_tfsc_create: phases1 and phases2 go together (or both NULL)");
   if (n < 8 || n > 512 || (n & 1)) return fail(nullptr, HH_ERR_ARG, "hh_tfsc_create: the side of the cubes must be even and lie in [8, 512]");
   if (m_cut < 0) return fail(nullptr, HH_ERR_ARG, "hh_tfsc_create: m_cut must be >= 0");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
-    return fail(nullptr, HH_ERR_HIP, "hh_tfsc_create: no such HIP device (there is no CPU fallback)");
+  if (int rc = use_device("hh_tfsc_create", device)) return rc;
   std::unique_ptr<hh_tfsc> c(new hh_tfsc);
   c->device = device; c->n = n; c->ncol = n / 2 + 1; c->nshell = n / 2 + 1;
   c->per_map = (int64_t)n * n * n; c->per_spec = (int64_t)n * n * c->ncol;
@@ -353,15 +338,15 @@ extern "C" int hh_tfsc_masked(hh_tfsc* ctx, const float* masks1, const float* ma
     float* const d_m2 = masks2 ? c->masks + nb * per_map : nullptr;
     HH_HIP(nullptr, hipMemcpy(d_m1, masks1 + b0 * per_map, (size_t)nb * per_map * sizeof(float), hipMemcpyHostToDevice));
     if (masks2) HH_HIP(nullptr, hipMemcpy(d_m2, masks2 + b0 * per_map, (size_t)nb * per_map * sizeof(float), hipMemcpyHostToDevice));
-    HH_HIP(nullptr, hipEventRecord(d.ev0, nullptr));
+    HH_HIP(nullptr, hipEventRecord(d.ev[0], nullptr));
     hipLaunchKernelGGL(k_tfsc_mask, dim3((unsigned)std::min<int64_t>((per_map + 255) / 256, 4096), (unsigned)nb), dim3(256), 0, nullptr, c->maps, d_m1,
                        d_m2, per_map, (int)nb, d.in);
     fc_device(c->plan, d.in, d, 2 * nb, nshell, full_spectrum != 0);
     HH_HIP(nullptr, hipGetLastError());
-    HH_HIP(nullptr, hipEventRecord(d.ev1, nullptr));
+    HH_HIP(nullptr, hipEventRecord(d.ev[1], nullptr));
     HH_HIP(nullptr, hipMemcpy(sums + b0 * 2 * nshell * 3, d.sums, (size_t)(2 * nb) * nshell * 3 * sizeof(double), hipMemcpyDeviceToHost));
     float ms = 0.f;
-    HH_HIP(nullptr, hipEventElapsedTime(&ms, d.ev0, d.ev1));
+    HH_HIP(nullptr, hipEventElapsedTime(&ms, d.ev[0], d.ev[1]));
     ms_total += ms;
   }
   if (kernel_ms) *kernel_ms = ms_total;

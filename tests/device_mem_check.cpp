@@ -1,5 +1,6 @@
 // Stand-alone check of helicon_amd/csrc/device_mem.h on the host: hipMalloc / hipFree are the stubs below (malloc / free
-// with a live-allocation counter and a switch that makes the n-th allocation fail), so no HIP runtime is linked.  Built
+// with a live-allocation counter and a switch that makes the n-th allocation fail), hipEventCreate / hipEventDestroy
+// likewise, so no HIP runtime is linked.  Built
 // with -fsanitize=address,undefined and run as a child process by tests/test_device_mem_host.py.
 #include "device_mem.h"
 
@@ -37,6 +38,21 @@ extern "C" hipError_t hipFree(void* ptr) {
     ++g_frees;
     std::free(ptr);
   }
+  return hipSuccess;
+}
+
+static int g_events = 0, g_event_fail_at = 0;   // live events; > 0: that creation from now fails, once
+
+extern "C" hipError_t hipEventCreate(hipEvent_t* event) {
+  if (g_event_fail_at > 0 && --g_event_fail_at == 0) return hipErrorOutOfMemory;
+  *event = reinterpret_cast<hipEvent_t>(std::malloc(1));
+  ++g_events;
+  return hipSuccess;
+}
+
+extern "C" hipError_t hipEventDestroy(hipEvent_t event) {
+  --g_events;
+  std::free(event);
   return hipSuccess;
 }
 
@@ -139,6 +155,28 @@ static void arena_scopes() {
   CHECK(g_live == 0);
 }
 
+static_assert(!std::is_copy_constructible<DevEvents<2>>::value && !std::is_copy_assignable<DevEvents<2>>::value, "DevEvents must not copy");
+
+static void events_on_demand() {
+  {
+    DevEvents<3> ev;
+    CHECK(g_events == 0 && ev[0] == nullptr && ev[2] == nullptr);   // nothing until create()
+    CHECK(ev.create() == hipSuccess && g_events == 3 && ev[0] && ev[1] && ev[2] && ev[0] != ev[1]);
+    const hipEvent_t first = ev[0];
+    CHECK(ev.create() == hipSuccess && g_events == 3 && ev[0] == first);   // a second call keeps them
+  }
+  CHECK(g_events == 0);
+  {
+    DevEvents<2> ev;
+    g_event_fail_at = 2;
+    CHECK(ev.create() == hipErrorOutOfMemory && g_events == 1 && ev[0] && ev[1] == nullptr);
+    CHECK(ev.create() == hipSuccess && g_events == 2 && ev[1]);   // a later call creates only what is missing
+  }
+  CHECK(g_events == 0);
+  { DevEvents<2> never; }   // never created: nothing to destroy
+  CHECK(g_events == 0);
+}
+
 struct Holder {   // what the library's long-lived objects look like: freed by delete
   DevBuf<int> a;
   DevBuf<double> b;
@@ -152,6 +190,7 @@ int main() {
   buf_moves();
   CHECK(g_live == 0);
   arena_scopes();
+  events_on_demand();
   Holder* h = new Holder;
   CHECK(h->a.ensure(3) && h->b.ensure(3) && g_live == 2);
   delete h;
