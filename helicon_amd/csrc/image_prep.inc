@@ -469,6 +469,9 @@ int prep_moments(const T* data, int rows, int cols, double threshold, double* ou
   hipError_t e = hipMemcpy(d_in, data, n * sizeof(T), hipMemcpyHostToDevice);
   if (e == hipSuccess) {
     const dim3 grid((cols + 255) / 256, rows);
+    // `data > threshold` is NumPy's comparison of an array with a Python scalar: made in the IMAGE's type, so the threshold is
+    // rounded to it first (a float32 pixel equal to float32(0.3) is not above 0.3)
+    threshold = (double)(T)threshold;
     hipLaunchKernelGGL((k_closing_cross<T, 0>), grid, dim3(256), 0, 0, d_in, (const unsigned char*)nullptr, rows, cols, threshold, d_dil);
     hipLaunchKernelGGL((k_closing_cross<T, 1>), grid, dim3(256), 0, 0, d_in, d_dil, rows, cols, threshold, d_clo);
     hipLaunchKernelGGL(k_helix_moments<T>, dim3(1), dim3(1024), 0, 0, d_in, d_clo, rows, cols, d_out);
