@@ -93,6 +93,8 @@ EXPORTS = {
     "hh_last_factor_sets": (C.c_int64, [_ctx]),
     "hh_set_fused_walk": (C.c_int, [_ctx, C.c_int]),
     "hh_last_fused_walk": (C.c_int, [_ctx]),
+    "hh_last_fused_packed": (C.c_int, [_ctx]),
+    "hh_lattice_centrosymmetric": (C.c_int, [C.POINTER(hh_geom), C.c_int, C.c_int, _f64p, C.c_int64]),
     "hh_set_fused_piece": (C.c_int, [_ctx, C.c_int]),
     "hh_fused_lds_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "hh_fused_walk_choice": (C.c_int, [C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64)]),

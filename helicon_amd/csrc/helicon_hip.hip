@@ -1670,14 +1670,21 @@ struct KF {
 // one buffer and builds both runs in one pass over the factor rows — per table row and column group one 16-byte read of
 // the two table values and one of the four factors for 16 FMAs, where a run alone reads the factors again — then hands A
 // and B to the transform one after the other, B's 16 sums waiting in registers.
+// WALK_PACKED (N = 512, EPI_SCORE) is that pair walk on a centrosymmetric lattice: A and B go through one transform as
+// z = A + i B (see PACK below); the launch shape, the LDS and the build are the pair walk's.
 template <int N, int EPI, int LOG, int WALK>
 __global__ __launch_bounds__(N, (N >= 256 ? KF<N>::WPS : 1)) void k_fused_pass(FusedArgs a) {
   using K = KF<N>;
   using KP = KB<N>;  // the partial-moment layout is k_second_pass's
   constexpr int T = K::T, TL = T < 64 ? T : 64, NKY = N / 2;
-  constexpr bool TW = WALK == WALK_TWISTS;
+  constexpr bool TW = WALK == WALK_TWISTS || WALK == WALK_PACKED;
   static_assert(!TW || N <= 512, "the twist walk has no SPLIT form");
   constexpr bool PAIR = TW && N == 512;  // two runs per pass over the factor rows (one spectrum row per wavefront)
+  // PACK: the pair walk on a centrosymmetric lattice (sweep_plan.h: geometry_centrosymmetric, list_rot_zero).  A row of H is
+  // then Hermitian about column N/2 but for column 0, so its transform is real but for the constant Im H[0]: rows A and B
+  // of a pair go through ONE transform as z = A + i B, and |F_A|^2 = Re(C)^2 + Im(H_A[0])^2, |F_B|^2 = Im(C)^2 + Im(H_B[0])^2.
+  constexpr bool PACK = WALK == WALK_PACKED;
+  static_assert(!PACK || (N == 512 && EPI == EPI_SCORE), "the packed pair walk is built at N = 512 for one segment");
   constexpr int GBUF = TW ? 2 : 1, FBUF = TW ? 1 : 2;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   float2* const bufs = reinterpret_cast<float2*>(smem);
@@ -2187,6 +2194,77 @@ __global__ __launch_bounds__(N, (N >= 256 ? KF<N>::WPS : 1)) void k_fused_pass(F
     }
   };
 
+  // PACK: the rest of the one transform of z = A + i B and both runs' moments.  ca: A's candidate number in the piece (B's
+  // is ca + 1; a half outside [0, nc) is computed and not stored); ima2, imb2: Im(H_A[0])^2 and Im(H_B[0])^2, wave-uniform.
+  // The copy of the next pair is retired in front of the stores, which are all of this pair's.
+  [[maybe_unused]] auto part_b_packed = [&](int ca, float ima2, float imb2, bool wait_copy) {
+    if constexpr (PACK) {
+      float2 v[8];
+      fft_lanes_part<NF, true, TwRegs, 2, 1>(v, twsrc, tf, fbuf);  // Re v[m] = Re F_A[kx], Im v[m] = Re F_B[kx], kx = t + m T
+      // (run A's sums are finished before run B's begin: three running sums at a time, as in part_b)
+      float a1 = 0.f, a2 = 0.f, a3 = 0.f, b1 = 0.f, b2 = 0.f, b3 = 0.f;
+#pragma unroll
+      for (int m = 0; m < 8; ++m) {
+        const float f = __builtin_amdgcn_sqrtf(fmaf(v[m].x, v[m].x, ima2));
+        const float q = LOG ? __log2f(1.0f + f) : f;   // amp_to_q's second half
+        a1 += w[m].x * q;
+        a2 += w[m].x * q * q;
+        a3 += w[m].y * q;
+      }
+      group_sum3<TL>(a1, a2, a3);
+#pragma unroll
+      for (int m = 0; m < 8; ++m) {
+        const float f = __builtin_amdgcn_sqrtf(fmaf(v[m].y, v[m].y, imb2));
+        const float q = LOG ? __log2f(1.0f + f) : f;
+        b1 += w[m].x * q;
+        b2 += w[m].x * q * q;
+        b3 += w[m].y * q;
+      }
+      group_sum3<TL>(b1, b2, b3);
+      if (wait_copy) lds_dma_wait();
+      if (writer) {
+        if (ca >= 0) {
+          double* const o = a.partials + (cand_of(ca) * KP::NPART + (size_t)row * KP::WPR + wave_in_row) * 3;
+          o[0] = a1;
+          o[1] = a2;
+          o[2] = a3;
+        }
+        if (ca + 1 < nc) {
+          double* const o = a.partials + (cand_of(ca + 1) * KP::NPART + (size_t)row * KP::WPR + wave_in_row) * 3;
+          o[0] = b1;
+          o[1] = b2;
+          o[2] = b3;
+        }
+      }
+    }
+  };
+
+  if constexpr (PACK) {
+    // The pair loop of PAIR below, with one transform per pair.  The wavefront that owns the packed row (ky = 0 and
+    // ky = N/2 in one complex row: two real sequences, no Hermitian row) keeps the two transforms: it takes PAIR's loop,
+    // a choice that is the wavefront's own and the same for every pair.
+    if (!(kb == 0 && gi == 0)) {
+      const int pair_end = (pr_first + nc + 1) >> 1;
+#pragma unroll 1
+      for (int p = pr_first >> 1; p < pair_end; ++p) {
+        f32x4 acc[8];
+        build_pair(acc);
+        const bool more = p + 1 < pair_end;
+        if (more) stage_pair(p + 1);
+        // column 0 is lane 0 of tile 0: its imaginary parts leave the transform and come back in the amplitudes
+        // (squared in the lane, then made scalar: the epilogue's fused multiply-adds take them as scalar operands)
+        const float ima2 = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(acc[0][1] * acc[0][1])));
+        const float imb2 = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(acc[0][3] * acc[0][3])));
+        if (t == 0) acc[0][1] = 0.f, acc[0][3] = 0.f;
+        float2 z[8];
+#pragma unroll
+        for (int m = 0; m < 8; ++m) z[m] = make_float2(acc[m][0] - acc[m][3], acc[m][1] + acc[m][2]);
+        first_stage_regs(z);
+        part_b_packed(2 * p - pr_first, ima2, imb2, more);
+      }
+      return;
+    }
+  }
   if constexpr (PAIR) {
     // Pair p holds runs 2 p (A) and 2 p + 1 (B) of the table group; the piece may begin at a B and end at an A, and the half
     // that is not its own is built with the other (the build's cost is the reads, which serve both) and dropped.  One
@@ -2758,8 +2836,10 @@ struct hh_ctx {
   int n_kb = 0;
   DevBuf<float2> d_table;        // shared-twist first pass: [runs per batch][rows][N/2] column-transform table
   DevBuf<float2> d_table_ky;     // the same tables ky-major, [runs][N/2][rows_f] (N = 512: [pairs][N/2][rows_f][2]), for the fused pass's twist walk
-  int fused_walk = 0;            // hh_set_fused_walk: 0 auto, 1 rises, 2 twists
+  int fused_walk = 0;            // hh_set_fused_walk: 0 auto, 1 rises, 2 twists, 3 packed (twists, one row transform per pair)
   int last_fused_walk = 0;       // hh_last_fused_walk
+  int last_fused_packed = 0;     // hh_last_fused_packed
+  bool geom_centro = false;      // geometry_centrosymmetric of hh_set_geometry's lattice
   int fused_piece = 0;           // hh_set_fused_piece: runs per workgroup of the twist walk (0: fused_schedule's own cut)
   DevBuf<int> d_run_imax;        // [runs of the sweep]
   SweepSplit split;              // how the last sweep's list was taken (sweep_plan.h); its plan's run_imax is d_run_imax's source
@@ -3127,9 +3207,20 @@ constexpr bool pair_walk_built(int n) { return n == 512; }
 constexpr bool twist_walk_built(int n) { return n <= 512; }
 
 template <int N, int EPI, int LOG>
-int launch_fused(hh_ctx* c, const FusedArgs& a, int layers, bool twists) {
+int launch_fused(hh_ctx* c, const FusedArgs& a, int layers, bool twists, bool packed) {
   using K = KF<N>;
   const dim3 grid(a.n_kb, a.factor_layers + layers + (a.fin.n > 0 ? 1 : 0));
+  if (twists && packed) {   // the pair walk's launch shape and LDS; one row transform per pair
+    if constexpr (pair_walk_built(N) && EPI == EPI_SCORE) {
+      if (int rc = ensure_lds_attr(c, reinterpret_cast<const void*>(&k_fused_pass<N, EPI, LOG, WALK_PACKED>), 160 * 1024)) return rc;
+      ProfScope ps(c, 1);
+      hipLaunchKernelGGL((k_fused_pass<N, EPI, LOG, WALK_PACKED>), grid, dim3(K::THREADS), K::lds(a.rows_lds, a.kg, true), c->stream, a);
+      HH_HIP(c, hipGetLastError());
+      return HH_OK;
+    } else {
+      return fail(c, HH_ERR_STATE, "k_fused_pass has no packed pair walk for this size or epilogue");
+    }
+  }
   if (twists) {
     if constexpr (twist_walk_built(N)) {
       if (int rc = ensure_lds_attr(c, reinterpret_cast<const void*>(&k_fused_pass<N, EPI, LOG, WALK_TWISTS>), 160 * 1024)) return rc;
@@ -3155,8 +3246,8 @@ int dispatch_factors(hh_ctx* c, const FactorArgs& a, int batch) {
 }
 
 template <int EPI, int LOG>
-int dispatch_fused_n(hh_ctx* c, const FusedArgs& a, int layers, bool twists) {
-#define HH_CALL(NN) launch_fused<NN, EPI, LOG>(c, a, layers, twists)
+int dispatch_fused_n(hh_ctx* c, const FusedArgs& a, int layers, bool twists, bool packed) {
+#define HH_CALL(NN) launch_fused<NN, EPI, LOG>(c, a, layers, twists, packed)
   HH_SWITCH_N(c, HH_CALL);
 #undef HH_CALL
 }
@@ -3201,9 +3292,9 @@ int fused_slots(hh_ctx* c, const FusedArgs& a, int* out, bool twists = false) {
   return rc;
 }
 
-int dispatch_fused(hh_ctx* c, const FusedArgs& a, int layers, bool twists) {
-  if (c->n_segments == 1) return c->log_flag ? dispatch_fused_n<EPI_SCORE, 1>(c, a, layers, twists) : dispatch_fused_n<EPI_SCORE, 0>(c, a, layers, twists);
-  return c->log_flag ? dispatch_fused_n<EPI_QSTORE, 1>(c, a, layers, twists) : dispatch_fused_n<EPI_QSTORE, 0>(c, a, layers, twists);
+int dispatch_fused(hh_ctx* c, const FusedArgs& a, int layers, bool twists, bool packed = false) {
+  if (c->n_segments == 1) return c->log_flag ? dispatch_fused_n<EPI_SCORE, 1>(c, a, layers, twists, packed) : dispatch_fused_n<EPI_SCORE, 0>(c, a, layers, twists, packed);
+  return c->log_flag ? dispatch_fused_n<EPI_QSTORE, 1>(c, a, layers, twists, false) : dispatch_fused_n<EPI_QSTORE, 0>(c, a, layers, twists, false);
 }
 
 // d_partials holds two halves of `batch` candidates each (zero-filled: rows of ky blocks the mask skips
@@ -3245,9 +3336,13 @@ struct RunSweep {
   std::vector<SweepBatch> batches;
   std::vector<WalkChoice> walks;   // fused: the candidate loop of every launch
   bool any_twists, any_rises;
+  const double* hp = nullptr;      // host mirror of the range's candidates, g_count of them
+  int64_t g_count = 0;
+  bool pack = false;               // the twist-walking launches transform one row per pair (WALK_PACKED)
 
   int64_t per_group() const { return batches.front().nq; }   // runs of the largest table group, the first
   bool twists(size_t bi) const { return walks[bi].walk == WALK_TWISTS; }
+  bool packed(size_t bi) const { return pack && twists(bi); }
   bool last(size_t bi) const { return bi + 1 == batches.size(); }
 };
 
@@ -3265,7 +3360,8 @@ int sweep_walks(hh_ctx* c, RunSweep& rs) {
   // Several segments: "auto" keeps the rise walk: the twist walk was measured slower there (C5: 8.04 -> 8.18 ms per
   // step).  The reading that fits: the q of a candidate (0.4 MB at N = 512) is written by the 32 ky blocks' workgroups,
   // which the rise walk places on one XCD and runs in step, and there the stores, not the factor copies, set the pace.
-  const int walk_mode = c->fused_walk == 0 && c->n_segments > 1 ? 1 : c->fused_walk;
+  // ("packed" is the twist walk to choose_walk)
+  const int walk_mode = c->fused_walk == 0 && c->n_segments > 1 ? 1 : std::min(c->fused_walk, 2);
   if (rs.caps.shared && walk_mode != 1)
     if (int rc = fused_slots(c, shape, &slots_t, true)) return rc;
   for (size_t bi = 0; bi < rs.batches.size(); ++bi) {
@@ -3275,6 +3371,11 @@ int sweep_walks(hh_ctx* c, RunSweep& rs) {
     (rs.twists(bi) ? rs.any_twists : rs.any_rises) = true;
   }
   c->last_fused_walk = rs.any_rises ? 1 : 2;
+  // One row transform per pair: the pair walk (N = 512), one segment, a centrosymmetric lattice (hh_set_geometry's part of
+  // the gate) and rot = 0 on every candidate of the list; forced, or under "auto" where AUTO_PACKS_PAIRS says so.
+  rs.pack = rs.any_twists && pair_walk_built(c->n) && c->n_segments == 1 && c->geom_centro &&
+            (c->fused_walk == 3 || (c->fused_walk == 0 && AUTO_PACKS_PAIRS)) && list_rot_zero(rs.hp, rs.g_count);
+  c->last_fused_packed = rs.pack && !rs.any_rises ? 1 : 0;
   return HH_OK;
 }
 
@@ -3444,7 +3545,7 @@ int sweep_fused_batch(hh_ctx* c, const RunSweep& rs, size_t bi, FinArgs& pending
   }
   int layers = 0;
   const FusedArgs fu = fused_args(c, rs, bi, pending, &layers);
-  if (int rc = dispatch_fused(c, fu, layers, rs.twists(bi))) return rc;
+  if (int rc = dispatch_fused(c, fu, layers, rs.twists(bi), rs.packed(bi))) return rc;
   pending = FinArgs{};
   return scores_tail(c, rs.g, rs.first_cand + bt.g0, bt.nb, rs.last(bi), rs.d_scores, pending, fu.partials);
 }
@@ -3461,11 +3562,13 @@ int sweep_table_batch(hh_ctx* c, const RunSweep& rs, size_t bi, FinArgs& pending
 
 // Candidates [first, first + count) of the list of g (count = whole runs of plan.len).
 int sweep_runs(hh_ctx* c, const double* d_params, int64_t g, float* d_scores, const RunPlan& plan, int64_t first_cand,
-               int64_t count_cand) {
+               int64_t count_cand, const double* h_params) {
   const SweepCaps caps = sweep_caps(plan, c->max_batch, c->n, c->n_segments, count_cand);
   const size_t run_bytes = (size_t)plan.rows * (c->n / 2) * sizeof(float2);
   RunSweep rs{d_params + 4 * first_cand, g, first_cand, d_scores, plan, caps,
               sweep_batches(count_cand / plan.len, plan.len, caps.bmax, run_bytes), {}, false, false};
+  rs.hp = h_params ? h_params + 4 * first_cand : nullptr;
+  rs.g_count = count_cand;
   if (int rc = sweep_buffers(c, rs)) return rc;
   if (int rc = sweep_walks(c, rs)) return rc;
   if (int rc = sweep_table_buffers(c, rs)) return rc;
@@ -3518,6 +3621,7 @@ int sweep_on_device(hh_ctx* c, const double* d_params, const int64_t n_cand, flo
                     const double* h_params = nullptr, int64_t ld = 0) {
   c->last_factor_sets = 0;
   c->last_fused_walk = 0;
+  c->last_fused_packed = 0;
   if (phase_on(c)) return phase_sweep(c, d_params, n_cand, d_scores, ld);
   if (zoom_on(c)) return zoom_sweep(c, d_params, n_cand, d_scores, ld);
   if (c->general) return gen_sweep(c, d_params, h_params, n_cand, d_scores, ld);
@@ -3528,7 +3632,7 @@ int sweep_on_device(hh_ctx* c, const double* d_params, const int64_t n_cand, flo
   if (sp.head > 0 || !sp.plan.ok)
     if (int rc = sweep_transform(c, d_params, g, d_scores, 0, sp.head)) return rc;
   if (sp.plan.ok)
-    if (int rc = sweep_runs(c, d_params, g, d_scores, sp.plan, sp.head, sp.count)) return rc;
+    if (int rc = sweep_runs(c, d_params, g, d_scores, sp.plan, sp.head, sp.count, h_params)) return rc;
   return tail < n_cand ? sweep_transform(c, d_params, g, d_scores, tail, n_cand - tail) : HH_OK;
 }
 
@@ -3891,6 +3995,7 @@ int hh_set_geometry(hh_ctx* c, const hh_geom* g) try {
   HH_HIP(c, hipStreamSynchronize(c->stream));
   if ((zoom_on(c) || phase_on(c)) && g->apix != c->apix) c->n_segments = 0;   // the zoomed frequencies scale with the pixel size: new reference
   c->geom = d;
+  c->geom_centro = geometry_centrosymmetric(d.n_units, units.data(), units[0], d.dy, d.has_rot != 0, g->apix, d.rpx, c->ny);
   c->apix = g->apix;
   c->have_geom = true;
   return HH_OK;
@@ -4076,11 +4181,21 @@ int hh_last_first_pass(const hh_ctx* c) { return c ? c->last_first_pass : HH_ERR
 int64_t hh_last_factor_sets(const hh_ctx* c) { return c ? c->last_factor_sets : HH_ERR_ARG; }
 int hh_set_fused_walk(hh_ctx* c, int mode) try {
   if (!c) return HH_ERR_ARG;
-  if (mode < 0 || mode > 2) return fail(c, HH_ERR_ARG, "hh_set_fused_walk: mode is 0 (auto), 1 (rises) or 2 (twists)");
+  if (mode < 0 || mode > 3) return fail(c, HH_ERR_ARG, "hh_set_fused_walk: mode is 0 (auto), 1 (rises), 2 (twists) or 3 (packed)");
   c->fused_walk = mode;
   return HH_OK;
 } HH_CATCH_CTX(c, "hh_set_fused_walk")
 int hh_last_fused_walk(const hh_ctx* c) { return c ? c->last_fused_walk : HH_ERR_ARG; }
+int hh_last_fused_packed(const hh_ctx* c) { return c ? c->last_fused_packed : HH_ERR_ARG; }
+int hh_lattice_centrosymmetric(const hh_geom* g, int ny, int nx, const double* params, int64_t count) try {
+  if (!g || !params || count < 1 || ny < 2 || nx < 2 || !(g->apix > 0) || !(g->ball_radius > 0)) return HH_ERR_ARG;
+  if (g->n_units > 1 && !g->units) return HH_ERR_ARG;
+  const bool has_rot = g->tilt != 0.0 || g->psi != 0.0;
+  const int rpx = truncation_rpx(g->apix, g->ball_radius, g->tail_bits, std::max(ny, nx));
+  const bool explicit_units = !(g->n_units <= 1 && !g->units);
+  return geometry_centrosymmetric(std::max(1, (int)g->n_units), explicit_units ? g->units : nullptr, g->helical_diameter / 2.0, g->dy,
+                                  has_rot, g->apix, rpx, ny) && list_rot_zero(params, count) ? 1 : 0;
+} HH_CATCH_CTX(nullptr, "hh_lattice_centrosymmetric")
 int hh_set_fused_piece(hh_ctx* c, int runs_per_workgroup) try {
   if (!c) return HH_ERR_ARG;
   if (runs_per_workgroup < 0) return fail(c, HH_ERR_ARG, "hh_set_fused_piece: runs per workgroup >= 0");

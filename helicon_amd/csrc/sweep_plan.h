@@ -12,6 +12,11 @@
 #include <vector>
 
 constexpr int WALK_RISES = 0, WALK_TWISTS = 1;  // k_fused_pass's candidate loop
+constexpr int WALK_PACKED = 2;                  // the pair twist walk with one row transform per pair (N = 512, one segment)
+
+// Whether "auto" (hh_set_fused_walk 0) takes the packed form where its gate holds and choose_walk picks the twist walk
+// ("One transform per pair": the measurement that decided it).
+constexpr bool AUTO_PACKS_PAIRS = true;
 
 constexpr int64_t HH_MIN_RUN = 8;              // shorter runs do not amortise their table and workgroup granularity
 constexpr size_t HH_TABLE_BYTES_MAX = 1ull << 30;
@@ -43,6 +48,41 @@ inline bool rise_columns_shared(const double* hp, int64_t g, int64_t len) {
   if (!hp || len < 1 || g < 2 * len || g % len) return false;
   for (int64_t i = len; i < g; ++i)
     if (!(hp[4 * i + 1] == hp[4 * (i % len) + 1])) return false;
+  return true;
+}
+
+// Truncation half-window of a ball in pixels: exp(-(rpx apix)^2 / sigma2) < 2^-bits, sigma2 = ball_radius^2 / ln 2
+// (hh_set_geometry's value; side: the longer image side).
+inline int truncation_rpx(double apix, double ball_radius, int tail_bits, int side) {
+  const double sigma2 = ball_radius * ball_radius / std::log(2.0);
+  const int bits = tail_bits > 0 ? tail_bits : 24;
+  int rpx = (int)std::ceil(std::sqrt(sigma2 * bits * std::log(2.0)) / apix);
+  if (rpx < 1) rpx = 1;
+  if (rpx > side) rpx = side;
+  return rpx;
+}
+
+// Whether the simulated lattice is centrosymmetric about the pixel (ny/2, nx/2) for every twist, rise and csym: one unit at
+// azimuth 0 and axial offset 0, no tilt, psi or dy.  Lattice point -i of csym copy csym - s is then the mirror of point i of
+// copy s, and row ky of the column-transformed image obeys H[ky][nx/2 - a] = conj(H[ky][nx/2 + a]) for |a| < nx/2: a row
+// transform that is real up to the term of column 0, whose mirror (column nx) the image does not hold.  Image row 0 has no
+// mirror either, so no ball may reach it: radius / apix + rpx + 1 <= ny / 2.  units: n_units x 3 (radius, azimuth,
+// axial offset) or NULL for the single unit at (radius, 0, 0).  The candidates' own condition is list_rot_zero.
+inline bool geometry_centrosymmetric(int n_units, const double* units, double radius, double dy, bool has_rot, double apix,
+                                     int rpx, int ny) {
+  if (n_units > 1 || has_rot || !(dy == 0.0) || !(apix > 0.0)) return false;
+  double r = radius;
+  if (units) {
+    if (!(units[1] == 0.0) || !(units[2] == 0.0)) return false;
+    r = units[0];
+  }
+  return std::fabs(r) / apix + (double)rpx + 1.0 <= (double)(ny / 2);
+}
+// ... and every candidate of the list has rot = 0 (hp: count x 4, the host mirror of the list)
+inline bool list_rot_zero(const double* hp, int64_t count) {
+  if (!hp || count < 1) return false;
+  for (int64_t i = 0; i < count; ++i)
+    if (!(hp[4 * i + 3] == 0.0)) return false;
   return true;
 }
 

@@ -392,8 +392,14 @@ class SweepEngine:
         """How the fused pipeline walks a list with one set of column factors per rise (``hh_set_fused_walk``): "rises" — a
         workgroup keeps a run's table slice and fetches a factor set per candidate; "twists" — it keeps a rise's factor
         set and its wavefronts fetch their own table rows per candidate; "auto" (default) — twists where they can run and
-        are not estimated slower.  A forced "twists" that cannot run falls back to "rises".  Scores are the same bits."""
-        mode = {"auto": 0, "rises": 1, "twists": 2}.get(mode, mode)
+        are not estimated slower.  A forced "twists" that cannot run falls back to "rises".  "rises" and "twists" give
+        the same bits.  "packed" — the twist walk at N = 512 with one row transform for the two runs of a pair, on a
+        centrosymmetric lattice (one unit at azimuth 0 and z 0, no tilt, psi or dy, rot 0 on every candidate) and one
+        segment; elsewhere it is "twists" (``last_fused_packed`` tells).  There the two runs of a pair share one
+        transform's roundings: the same list gives the same bits whatever the workgroups' cut, another list or shard may
+        differ in the last float32 bits.  "auto" packs wherever it walks twists and the packed form can run; force
+        "twists" for scores that do not depend on the list."""
+        mode = {"auto": 0, "rises": 1, "twists": 2, "packed": 3}.get(mode, mode)
         with self._lock:
             self._check(self._L.hh_set_fused_walk(self._ctx, int(mode)))
 
@@ -407,6 +413,12 @@ class SweepEngine:
         """Candidate loop of the last sweep's fused launches (``hh_last_fused_walk``): "twists" when all of them walked
         twists, "rises" when one of them walked rises, "none" when the sweep ran another pipeline."""
         return {1: "rises", 2: "twists"}.get(self._L.hh_last_fused_walk(self._ctx), "none")
+
+    @property
+    def last_fused_packed(self) -> bool:
+        """Whether every fused launch of the last sweep walked twists with one row transform per pair
+        (``hh_last_fused_packed``)."""
+        return self._L.hh_last_fused_packed(self._ctx) == 1
 
     def fused_walk_footprint(self, rise_min: float) -> dict:
         """The fused pass's shape for a sweep whose smallest rise is ``rise_min`` (``hh_fused_walk_footprint``): table rows

@@ -255,11 +255,26 @@ int64_t hh_last_factor_sets(const hh_ctx* ctx);
  * table rows are double-buffered: 16 bytes per table row and ky instead of 8) and the schedule's estimate is not above
  * the rise walk's; rises otherwise, and always with several segments (their q stores were measured slower on the twist
  * walk).  A forced 2 that cannot run (per-candidate factors, N = 1024, the footprint) falls
- * back to 1.  Scores do not depend on the walk, bit for bit.
- * hh_last_fused_walk: 2 when every fused launch of the last sweep walked twists, 1 when one of them walked rises, 0 when
- * the sweep ran another pipeline. */
+ * back to 1.  Scores do not depend on the walk, bit for bit, under modes 1 and 2.
+ * 3 = packed: the twist walk at n = 512 with ONE row transform for the two runs of a pair ("One
+ * transform per pair").  It needs a centrosymmetric lattice (hh_lattice_centrosymmetric), one segment and the pair walk;
+ * where one of them fails it is mode 2.  The two runs of a pair share one transform's roundings, so a score depends, in
+ * its last float32 bits, on the run it is paired with: the same list gives the same bits whatever the workgroups' cut
+ * (pairs are counted from the first run of a table group), another list or shard may not.  Mode 0 takes the packed form
+ * wherever it takes the twist walk and the packed form can run; a caller who needs scores that do not depend on the
+ * list forces 2.
+ * hh_last_fused_walk: 2 when every fused launch of the last sweep walked twists (packed or not), 1 when one of them walked
+ * rises, 0 when the sweep ran another pipeline.  hh_last_fused_packed: 1 when every fused launch of the last sweep walked
+ * twists with one transform per pair, else 0. */
 int hh_set_fused_walk(hh_ctx* ctx, int mode);
 int hh_last_fused_walk(const hh_ctx* ctx);
+int hh_last_fused_packed(const hh_ctx* ctx);
+/* Whether a sweep of `params` (count x 4 float64: twist, rise, csym, rot) under geometry `geom` on ny x nx images simulates
+ * a lattice that is centrosymmetric about the pixel (ny/2, nx/2): one unit at azimuth 0 and axial offset 0, no tilt, psi or
+ * dy, no ball within reach of image row 0 (radius / apix + truncation half-window + 1 <= ny / 2), and rot = 0 on every
+ * candidate; csym is free.  Rows of the column-transformed image are then Hermitian about column nx/2 but for column 0.
+ * 1 / 0, HH_ERR_ARG on a bad argument.  Pure host arithmetic: the geometry and list part of the packed walk's gate. */
+int hh_lattice_centrosymmetric(const hh_geom* geom, int ny, int nx, const double* params, int64_t count);
 /* Test and tuning hook: the twist walk cuts every rise's runs into workgroups of runs_per_workgroup runs (the last one
  * takes what is left) instead of the cut of hh_fused_walk_choice; 0 (default) = the schedule's own cut.  The choice of
  * the walk is not affected. */
