@@ -21,5 +21,7 @@ from .true_fsc import (TrueFSC, adaptive_mask_device, distance_transform_edt_sq,
 # the function fft_resample takes the package attribute of its module's name: reach the module's other names with
 # ``from helicon_amd.fft_resample import ...`` (the command line is ``python -m helicon_amd.fft_resample``)
 from .fft_resample import crop_operator, fft_crop, fft_rescale, fft_resample, resample_operator, rescale_operator
+from .structure_factor import (StructureFactorMatcher, calculate_structural_factor, match_structural_factors,
+                               set_structural_factors)
 
 __version__ = "0.1.0"

@@ -206,6 +206,12 @@ EXPORTS = {
                                 C.POINTER(C.c_uint8), _f64p]),
     "hh_am_context_support": (C.c_int, [C.c_void_p, C.c_int, C.c_double, _f64p, C.c_int, C.c_double, _f64p]),
     "hh_am_context_get_support": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_uint8)]),
+    # structure factors of maps and images (helicon_amd/structure_factor.py, csrc/structure_factor.inc)
+    "hh_sf_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int32, C.POINTER(C.c_int32), C.c_double, C.c_int32, _f64p, _f64p, _f64p]),
+    "hh_sf_profile": (C.c_int, [C.c_void_p, _f32p, C.c_int32, _f32p, C.c_int, C.c_double, _f64p, _f32p]),
+    "hh_sf_match": (C.c_int, [C.c_void_p, _f32p, C.c_int32, _f32p, C.c_int, C.c_double, _f32p, _f64p]),
+    "hh_sf_kernel_ms": (C.c_int, [C.c_void_p, _f64p]),
+    "hh_sf_destroy": (C.c_int, [C.c_void_p]),
 }
 
 _lib = None

@@ -726,6 +726,39 @@ int hh_am_context_support(hh_tfsc* ctx, int one_mask, double sigma, const double
 /* the context's support for member `which` (0 / 1), uint8 [n][n][n] */
 int hh_am_context_get_support(hh_tfsc* ctx, int which, uint8_t* support_out);
 
+/*
+ * Structure factors (csrc/structure_factor.inc; lib/filters.py:22-208 calculate_structural_factor, set_structural_factors,
+ * match_structural_factors): the power |F|^2 of 3-D maps (nz, ny, nx; sides in [2, 512]) or 2-D images (ny, nx; sides in
+ * [2, 1024]) summed over the full spectrum into the reference's bins, and the maps scaled so that their profile becomes a
+ * target's.  Any sides, odd, prime and unequal included.  The binning tables are the host's, so that they are NumPy's own
+ * values: qbins = np.linspace(0, nbins qstep, nbins) [nbins] (2 <= nbins <= 726, qbins[0] = 0, increasing), freq = the
+ * np.fft.fftfreq tables of the axes, concatenated in the order of the shape.  A bin (kz, ky, kx) has the radius
+ * qr = sqrt(qx^2 + qy^2 [+ qz^2]) / apix in float64, formed as NumPy forms it (ties are real), and the label
+ * searchsorted(qbins, qr, "right") - 1; the last bin is open-ended.  target (may be NULL: a context for profiles only):
+ * the target profile on qbins [nbins].  A context keeps the operators and a grow-only scratch; a batch is cut into chunks
+ * of the scratch cap.  Errors: hh_last_error(NULL).
+ */
+typedef struct hh_sf hh_sf;
+int hh_sf_create(hh_sf** out, int device, int32_t ndim, const int32_t* shape, double apix, int32_t nbins, const double* qbins,
+                 const double* target, const double* freq);
+/* maps: host float32 [batch][shape].  has_thresh != 0: clip(x, thresh, None) - thresh first; mask (may be NULL, [shape], one
+ * for the batch): then x mask.  sums: float64 [batch][nbins], bit-identical from run to run and independent of the batch and
+ * of a map's place in it; a map with a NaN gives NaN sums.  spec_out (may be NULL): the half spectrum of the prepared maps,
+ * interleaved complex64 [batch][shape with nx / 2 + 1 for nx][2] */
+int hh_sf_profile(hh_sf* ctx, const float* maps, int32_t batch, const float* mask, int has_thresh, double thresh, double* sums,
+                  float* spec_out);
+/* maps_out [batch][shape]: irfftn(F ratio_interp(qr)), ratio = sqrt(target / sums) per map (0 where sums == 0),
+ * ratio_interp linear between the edges of qbins, ratio[nbins - 1] at qr == qbins[nbins - 1] and 0 above.  F is the spectrum
+ * of the thresholded maps, or, when a mask is given, of the RAW maps (the profile still comes from the thresholded and masked
+ * ones).  sums (may be NULL): the profile of every map, as hh_sf_profile returns it.  The same guarantees: bit-identical
+ * from run to run and independent of the batch.  HH_ERR_STATE on a context without a target. */
+int hh_sf_match(hh_sf* ctx, const float* maps, int32_t batch, const float* mask, int has_thresh, double thresh, float* maps_out,
+                double* sums);
+/* device-event milliseconds of the last call, [4]: the profile (prologue, forward passes, sums, ratio), the second transform
+ * of a masked match, the scaling, the inverse passes */
+int hh_sf_kernel_ms(hh_sf* ctx, double* ms);
+int hh_sf_destroy(hh_sf* ctx);
+
 #ifdef __cplusplus
 }
 #endif
