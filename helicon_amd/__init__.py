@@ -23,5 +23,8 @@ from .true_fsc import (TrueFSC, adaptive_mask_device, distance_transform_edt_sq,
 from .fft_resample import crop_operator, fft_crop, fft_rescale, fft_resample, resample_operator, rescale_operator
 from .structure_factor import (StructureFactorMatcher, calculate_structural_factor, match_structural_factors,
                                set_structural_factors)
+# the function local_resolution takes the package attribute of its module's name, as fft_resample does: reach the module's
+# other names with ``from helicon_amd.local_resolution import ...`` (the command line is ``python -m helicon_amd.local_resolution``)
+from .local_resolution import LocalFSC, local_resolution, resolution_from_curve, taper_profile, window_centres
 
 __version__ = "0.1.0"

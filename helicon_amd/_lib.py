@@ -212,6 +212,14 @@ EXPORTS = {
     "hh_sf_match": (C.c_int, [C.c_void_p, _f32p, C.c_int32, _f32p, C.c_int, C.c_double, _f32p, _f64p]),
     "hh_sf_kernel_ms": (C.c_int, [C.c_void_p, _f64p]),
     "hh_sf_destroy": (C.c_int, [C.c_void_p]),
+    # local resolution of two half maps (helicon_amd/local_resolution.py, csrc/local_resolution.inc)
+    "hh_lres_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, _f32p, _f32p, C.c_int32, C.c_int32, C.c_int32]),
+    "hh_lres_destroy": (C.c_int, [C.c_void_p]),
+    "hh_lres_run": (C.c_int, [C.c_void_p, C.c_int32, _f32p, C.POINTER(C.c_int32), C.c_int64, C.c_double, C.c_double, C.c_int, _f64p, _f64p,
+                              _f64p]),
+    "hh_lres_set_budget": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64]),
+    "hh_lres_plan": (C.c_int, [C.c_int32, C.c_int, C.c_int64, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "hh_lres_upsample": (C.c_int, [C.c_int, _f64p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _f32p]),
 }
 
 _lib = None

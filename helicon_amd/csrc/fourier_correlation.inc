@@ -50,10 +50,8 @@ __global__ __launch_bounds__(256) void k_fc_absmax(const float* __restrict__ v, 
 
 // scale[b][q] = 2^(61 - ilogb(bound)), bound = 2 (voxels)^2 max|a| max|b| >= sum w |products| of the pair; 0 when the
 // bound is 0 (every product is 0 then), NaN when a map holds a NaN or an infinity (the sums come back as NaN)
-__global__ void k_fc_scales(const unsigned* __restrict__ amax, int batch, double voxels, double* __restrict__ scale) {
-  const int b = blockIdx.x * blockDim.x + threadIdx.x;
-  if (b >= batch) return;
-  const double a1 = (double)__uint_as_float(amax[b]), a2 = (double)__uint_as_float(amax[batch + b]);
+__device__ __forceinline__ void fc_pair_scales(unsigned amax1, unsigned amax2, double voxels, double* scale) {
+  const double a1 = (double)__uint_as_float(amax1), a2 = (double)__uint_as_float(amax2);
   const double pr[3] = {a1 * a2, a1 * a1, a2 * a2};
   for (int q = 0; q < 3; ++q) {
     const double bound = 2.0 * voxels * voxels * pr[q];
@@ -61,8 +59,14 @@ __global__ void k_fc_scales(const unsigned* __restrict__ amax, int batch, double
     if (!(bound == bound) || bound > 1.7e308) s = __longlong_as_double(0x7ff8000000000000ll);
     else if (bound == 0.0) s = 0.0;
     else s = ldexp(1.0, 61 - ilogb(bound));
-    scale[b * 3 + q] = s;
+    scale[q] = s;
   }
+}
+
+__global__ void k_fc_scales(const unsigned* __restrict__ amax, int batch, double voxels, double* __restrict__ scale) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= batch) return;
+  fc_pair_scales(amax[b], amax[batch + b], voxels, scale + b * 3);
 }
 
 __device__ __forceinline__ int fc_shell_3d(int kz, int ky, int kx, int n) {

@@ -4865,6 +4865,7 @@ int hh_profile_get(hh_ctx* c, hh_profile* out) try {
 #include "phase_sweep.inc"  // the sweep's phase score across the meridian (hh_set_spectrum_phase): four real products kept apart, F and its partner at -f_y from the same MFMAs
 #include "symmetry_search.inc"  // helical symmetry search of a 3-D map: batched (twist, rise, Csym) scores of a device-resident map (hh_hs_*)
 #include "fourier_correlation.inc"  // Fourier shell / ring correlation of batches of map or image pairs: DFT passes on the f32 MFMA, fused last pass (hh_fsc_3d, hh_frc_2d)
+#include "local_resolution.inc"  // local resolution of two half maps: windowed FSC on resident maps, gathered windows through the passes above or one workgroup per window pair with both half spectra in LDS, crossing rule, trilinear map (hh_lres_*)
 #include "true_fsc.inc"  // phase-randomised (noise-substituted) true FSC of two half maps on a resident context: stored spectrum, inverse passes, masked curves (hh_tfsc_*)
 #include "soft_mask.inc"  // the true FSC's soft masks built on the device from a resident support: exact distance transform, zoom(order=1) taps, cosine edge (hh_edt_3d, hh_soft_mask_3d, hh_tfsm_set_support / _soft_mask / _soft_masked)
 #include "adaptive_mask.inc"  // the true FSC's adaptive mask built on the device: float64 Gaussian with SciPy's reflect boundary, exact order statistics, Otsu by edges, 26-connected labelling (hh_am_*)

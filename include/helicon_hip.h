@@ -759,6 +759,40 @@ int hh_sf_match(hh_sf* ctx, const float* maps, int32_t batch, const float* mask,
 int hh_sf_kernel_ms(hh_sf* ctx, double* ms);
 int hh_sf_destroy(hh_sf* ctx);
 
+/* ---------------------------------------------------------------------------------------------
+ * Local resolution of two half maps (csrc/local_resolution.inc): the FSC of every window pair of even side w around a list of
+ * centres, and the resolution at which each curve first falls below a threshold.  A window is lib/transforms.py:516-555
+ * get_clip3d(map, c - w / 2, w) (zeros outside the map) times taper[z] taper[y] taper[x] (the 1-D profile of
+ * lib/filters.py:415-466 generate_tapering_filter, built by the caller); its curve fsc[0 .. w / 2] is calc_fsc_per_shell's
+ * (hh_fsc_3d with full_spectrum = 1, and 1.0 where the denominator is not positive); with saxis[k] = k / (w apix) and k* the
+ * smallest k >= 1 with fsc[k] < threshold its resolution is 1 / saxis[w / 2] when there is no k*, w apix when k* = 1, else
+ * 1 / (saxis[k* - 1] + (threshold - fsc[k* - 1]) (saxis[k*] - saxis[k* - 1]) / (fsc[k*] - fsc[k* - 1])).
+ * A context keeps both maps [nz][ny][nx], sides in [8, 512], on the device.  Errors: hh_last_error(NULL). */
+typedef struct hh_lres hh_lres;
+int hh_lres_create(hh_lres** out, int device, const float* map1, const float* map2, int32_t nz, int32_t ny, int32_t nx);
+int hh_lres_destroy(hh_lres* ctx);
+/* window: even, in [8, 64]; taper: [window]; centres: [n][3] (z, y, x), inside the map; threshold in (-1, 1);
+ * route: 0 automatic, 1 one workgroup per window pair with both half spectra in LDS (window <= 24), 2 gathered windows
+ * through the passes of hh_fsc_3d (any window).  resolution: [n]; curves: [n][window / 2 + 1] or NULL; kernel_ms: device-event
+ * milliseconds of the launches, or NULL.  A route's results are bit-identical from run to run and do not depend on the
+ * budget or on the order of the centres.  HH_ERR_ARG: an odd or out-of-range window, a centre outside the map, a route
+ * that cannot take the window, a threshold that is NaN or outside (-1, 1), a NULL. */
+int hh_lres_run(hh_lres* ctx, int32_t window, const float* taper, const int32_t* centres, int64_t n, double apix, double threshold,
+                int route, double* resolution, double* curves, double* kernel_ms);
+/* caps of the later runs: device scratch of one chunk of the passes route, windows of one launch of either route
+ * (0: the defaults) */
+int hh_lres_set_budget(hh_lres* ctx, int64_t scratch_bytes, int64_t max_windows_per_launch);
+/* host arithmetic only: the route a run would take (1 / 2), the LDS route's bytes per workgroup for this window (0 above 24)
+ * and the windows of one launch under the budget; every output may be NULL.  HH_ERR_ARG as hh_lres_run. */
+int hh_lres_plan(int32_t window, int route, int64_t scratch_bytes, int64_t max_windows_per_launch, int32_t* route_out,
+                 int64_t* lds_bytes, int64_t* windows_per_launch);
+/* grid: host float64 [gz][gy][gx], NaN = not evaluated, the value of centre step / 2 + i step along each axis; out: host
+ * float32 [nz][ny][nx], trilinear between the centres: per axis u = clip((p - step / 2) / step, 0, g - 1),
+ * i0 = min(floor(u), g - 2) (g == 1: that one corner), NaN corners dropped and the other weights renormalised, NaN where
+ * the remaining weights sum to 0.  Map sides in [1, 512]. */
+int hh_lres_upsample(int device, const double* grid, int32_t gz, int32_t gy, int32_t gx, int32_t step, int32_t nz, int32_t ny,
+                     int32_t nx, float* out);
+
 #ifdef __cplusplus
 }
 #endif
