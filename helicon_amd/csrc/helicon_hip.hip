@@ -4738,6 +4738,10 @@ int hh_apply_helical_symmetry(int device, const float* data, const int32_t in_sh
   }
   out_shape[0] = a.oz; out_shape[1] = a.oy; out_shape[2] = a.ox;
   if (!out) return HH_OK;  // shape query
+  if (a.oz == 0 || a.oy == 0 || a.ox == 0) {  // a requested side of 1 crops to [n/2 : n/2]: the reference returns the empty array
+    if (kernel_ms) *kernel_ms = 0.0;
+    return HH_OK;
+  }
   a.apix = apix; a.new_apix = new_apix; a.rise = rise_angstrom; a.csym = csym;
   a.hmax = std::max(1, (int)((double)a.nz * new_apix / rise_angstrom));  // transforms.py:88
   // z range of the input that carries density (transforms.py:92-99)
