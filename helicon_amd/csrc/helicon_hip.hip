@@ -1713,20 +1713,16 @@ __global__ __launch_bounds__(N, (N >= 256 ? KF<N>::WPS : 1)) void k_fused_pass(F
   // neighbouring 64-byte pieces of the same table rows; mapping a layer's blocks to ids of ONE residue class lets the
   // XCD's L2 fetch them once instead of all eight L2s once each (placement is a speed matter only).
   // Twist walk: what workgroups share is the table rows of one ky block and one piece of runs, whatever their rise.
-  // The first region's layers (whole multiples of 8) are dealt so that XCD x gets the x-th eighth of them in ky-block-major
-  // order: the workgroups resident on an XCD at one time are then consecutive rises of ONE ky block, walking the same
-  // table rows at about the same pace.  The last region (the short workgroups that fill the launch's tail) keeps the
-  // dispatch order, so it still runs last.
+  // twist_walk_place (sweep_plan.h) puts block 0, whose workgroups last longest, at the head of each region and over all
+  // XCDs, and gives XCD x the x-th eighth of the first region's other blocks in ky-block-major order.  The last region
+  // (the short workgroups that fill the launch's tail) still runs last.
   int gy = blockIdx.y - a.factor_layers - (a.fin.n > 0 ? 1 : 0);
   int kbi = blockIdx.x;
   if constexpr (TW) {
-    const int nkb = gridDim.x, la8 = (a.runs_a * a.groups_a) & ~7;
-    const int lw = gy * nkb + kbi;
-    if (lw < la8 * nkb) {
-      const int j = (lw & 7) * (la8 / 8 * nkb) + (lw >> 3);
-      kbi = j / la8;
-      gy = j % la8;
-    }
+    const int nkb = gridDim.x, work_layers = gridDim.y - a.factor_layers - (a.fin.n > 0 ? 1 : 0);
+    const WalkPlace wp = twist_walk_place(gy * nkb + kbi, nkb, a.runs_a * a.groups_a, work_layers);
+    kbi = wp.kbi;
+    gy = wp.gy;
   } else {
     const int nkb = gridDim.x, work_layers = gridDim.y - a.factor_layers - (a.fin.n > 0 ? 1 : 0);
     const int lw = gy * nkb + kbi;

@@ -140,6 +140,49 @@ inline FusedSchedule fused_schedule(int64_t runs, int run_len, int n_kb, int slo
   return best;
 }
 
+// Where the twist walk's workgroups stand in the launch: work id lw = layer x nkb + block in dispatch order -> (ky block
+// index kbi, layer gy).  Workgroups are dealt round-robin over the 8 XCDs by id, so ids equal mod 8 (a "class") share an
+// L2 and a pool of slots, handed out in id order.  `layers` layers of nkb blocks; the first `la` layers are the long
+// workgroups of region A (fused_schedule's runs_a x groups_a), the rest the short pieces of region B.  In id order:
+//   [0, la)                    block 0 of every region-A layer;
+//   la8 (nkb - 1) more         blocks 1 .. nkb - 1 of the first la8 = la & ~7 layers: each class a contiguous eighth of them
+//                              in ky-block-major order, layers ascending inside a block — what an XCD holds at one time is
+//                              then consecutive rises of ONE ky block, walking the same table rows at about the same pace;
+//   up to la nkb               blocks 1 .. nkb - 1 of the la - la8 layers left over, in dispatch order;
+//   [la nkb, la nkb + lb)      block 0 of every region-B layer (lb = layers - la);
+//   the rest                   blocks 1 .. nkb - 1 of region B in dispatch order: the short pieces still run last.
+// Block 0 leads both regions because its workgroups last longest: their first wavefront owns ky = 0 AND ky = N/2 and
+// transforms both, so the workgroup holds its slot for about twice a sibling's time.  Consecutive ids give every class
+// its share of them (counts differ by at most one), and first in line they are not what the launch ends on.
+// (kbi indexes the launch's list of live ky blocks.  Its entry 0 is always block 0 — hh_set_reference keeps that block
+// whatever the mask — so testing kbi == 0 here is testing kb == 0 in the kernel.)
+#if defined(__HIPCC__)
+#define HH_PLAN_FN __host__ __device__ inline
+#else
+#define HH_PLAN_FN inline
+#endif
+struct WalkPlace { int kbi, gy; };
+HH_PLAN_FN WalkPlace twist_walk_place(int lw, int nkb, int la, int layers) {
+  const int rest = nkb - 1;   // blocks per layer besides block 0
+  int first = 0, n = la;      // the region's first layer and its layer count
+  const bool region_b = lw >= la * nkb;
+  if (region_b) {
+    lw -= la * nkb;
+    first = la;
+    n = layers - la;
+  }
+  if (lw < n) return WalkPlace{0, first + lw};
+  lw -= n;
+  const int n8 = region_b ? 0 : n & ~7;   // layers dealt in eighths
+  if (lw < n8 * rest) {
+    const int j = (lw & 7) * (n8 / 8 * rest) + (lw >> 3);
+    return WalkPlace{1 + j / n8, j % n8};
+  }
+  lw -= n8 * rest;
+  return WalkPlace{1 + lw % rest, first + n8 + lw / rest};
+}
+#undef HH_PLAN_FN
+
 // Which candidate loop a launch of `runs` whole runs of `run_len` candidates takes when every run shares one rise
 // column: the twist walk (workgroups own a rise and walk the runs; fused_schedule with the roles swapped) needs the
 // compute unit to hold as many of its workgroups as of the rise walk's (its table rows are double-buffered), and under
