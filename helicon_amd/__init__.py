@@ -26,5 +26,6 @@ from .structure_factor import (StructureFactorMatcher, calculate_structural_fact
 # the function local_resolution takes the package attribute of its module's name, as fft_resample does: reach the module's
 # other names with ``from helicon_amd.local_resolution import ...`` (the command line is ``python -m helicon_amd.local_resolution``)
 from .local_resolution import LocalFSC, local_resolution, resolution_from_curve, taper_profile, window_centres
+from .align import AlignContext, align_images, align_images_grid
 
 __version__ = "0.1.0"

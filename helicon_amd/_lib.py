@@ -220,6 +220,14 @@ EXPORTS = {
     "hh_lres_set_budget": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64]),
     "hh_lres_plan": (C.c_int, [C.c_int32, C.c_int, C.c_int64, C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "hh_lres_upsample": (C.c_int, [C.c_int, _f64p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _f32p]),
+    # batched 2-D image alignment on a resident context (helicon_amd/align.py, csrc/align.inc)
+    "hh_align_chunk": (C.c_int, []),
+    "hh_align_create": (C.c_int, [C.c_int, C.c_int32, C.c_int32, _f32p, C.c_int32, _f32p, _f32p, C.POINTER(C.c_void_p)]),
+    "hh_align_destroy": (C.c_int, [C.c_void_p]),
+    "hh_align_eval": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(C.c_int32), _f64p, C.POINTER(C.c_int32), _f64p, _f32p, C.POINTER(C.c_int32)]),
+    "hh_align_correlation": (C.c_int, [C.c_void_p, C.c_int32, _f64p, _f32p]),
+    "hh_align_warp_wrap": (C.c_int, [C.c_void_p, _f32p, C.c_int32, C.c_int, _f64p, C.POINTER(C.c_int32), _f32p]),
+    "hh_align_profile": (C.c_int, [C.c_void_p, C.c_int, _f64p]),
 }
 
 _lib = None

@@ -8,7 +8,7 @@
 //                 tf_create) and the filtered sweep's y pass (filtered_sweep.inc: filt_y_passes).
 //   k_axis_gemm   Y = (Ar + i Ai) (Xr + i Xi): a rectangular complex operator (M x K), re and im accumulators fed from one
 //                 staged slice, the products interleaved per K slice, a fused epilogue.  User: Fourier resampling
-//                 (fourier_resample.inc: hh_separable_transform_3d).
+//                 (fourier_resample.inc: hh_separable_transform_3d) and the 2-D transforms of image alignment (align.inc).
 //
 // The two bodies differ in how the sum over k is ordered, so neither can stand in for the other (DESIGN.md, "Separable axis
 // passes").  Included into helicon_hip.hip after fail / HH_HIP and ahead of every file that launches a pass.
@@ -84,7 +84,9 @@ void launch_circ_pass(const AxisGeom& v, const float* a, int ka, const float* b0
   else hipLaunchKernelGGL(k_circ_gemm<false>, grid, dim3(256), 0, stream, g);
 }
 
-enum { FR_STORE = 0, FR_ABS = 1, FR_REAL = 2 };   // k_axis_gemm's epilogues
+// k_axis_gemm's epilogues.  FR_CROSS: P = E conj(Y) / max(|P|, scale) with E = (er, ei) a resident spectrum of one batch's
+// shape, the phase-normalised cross-power spectrum of image alignment (align.inc); only P is stored.
+enum { FR_STORE = 0, FR_ABS = 1, FR_REAL = 2, FR_CROSS = 3 };
 
 struct AxisPass {
   const float* ar;    // [M][K] row-major operator planes: real, imaginary (null: a real operator) ...
@@ -92,8 +94,10 @@ struct AxisPass {
   const float* na;    // ... and -imaginary (read on a complex input only)
   const float* xr;    // input planes; xi is read by the CX kernels only
   const float* xi;
-  float* yr;          // output planes; yi is written under FR_STORE only
+  float* yr;          // output planes; yi is written under FR_STORE and FR_CROSS only
   float* yi;
+  const float* er;    // FR_CROSS only: the planes of E, indexed as one batch of Y
+  const float* ei;
   int M, K;
   int64_t np;             // columns P of the product
   int64_t sk;             // element stride along the operator's index, the same in X (k) and Y (m)
@@ -161,6 +165,12 @@ __global__ __launch_bounds__(256) void k_axis_gemm(AxisPass g) {
         g.yi[off] = im[i];
       } else if (EPI == FR_ABS) {
         g.yr[off] = sqrtf(re[i] * re[i] + im[i] * im[i]) * g.scale;
+      } else if (EPI == FR_CROSS) {
+        const float er = g.er[off - bout], ei = g.ei[off - bout];
+        const float pr = er * re[i] + ei * im[i], pi = ei * re[i] - er * im[i];
+        const float d = fmaxf(hypotf(pr, pi), g.scale);
+        g.yr[off] = pr / d;
+        g.yi[off] = pi / d;
       } else {
         g.yr[off] = re[i] * g.scale;
       }
@@ -172,14 +182,17 @@ template <bool TR, bool CX>
 void launch_axis_gemm(int epi, dim3 grid, const AxisPass& g, hipStream_t stream) {
   if (epi == FR_STORE) hipLaunchKernelGGL((k_axis_gemm<TR, CX, FR_STORE>), grid, dim3(256), 0, stream, g);
   else if (epi == FR_ABS) hipLaunchKernelGGL((k_axis_gemm<TR, CX, FR_ABS>), grid, dim3(256), 0, stream, g);
+  else if (epi == FR_CROSS) hipLaunchKernelGGL((k_axis_gemm<TR, CX, FR_CROSS>), grid, dim3(256), 0, stream, g);
   else hipLaunchKernelGGL((k_axis_gemm<TR, CX, FR_REAL>), grid, dim3(256), 0, stream, g);
 }
 
 // One k_axis_gemm pass in the geometry `v`: op = {Ar, Ai, -Ai} (Ai and -Ai null: a real operator), x = {re, im} (im null:
-// a real input), y = {re, im} (im written under FR_STORE only).
+// a real input), y = {re, im} (im written under FR_STORE and FR_CROSS only); cross = {re, im} of FR_CROSS's resident spectrum.
 void launch_axis_pass(const AxisGeom& v, const float* const (&op)[3], const float* const (&x)[2], float* const (&y)[2], int epi,
-                      float scale, hipStream_t stream) {
+                      float scale, hipStream_t stream, const float* const* cross = nullptr) {
+  if ((epi == FR_CROSS) != (cross != nullptr)) throw std::logic_error("launch_axis_pass: FR_CROSS and its spectrum go together");
   AxisPass g{};
+  if (cross) { g.er = cross[0]; g.ei = cross[1]; }
   g.ar = op[0]; g.ai = op[1]; g.na = op[2];
   g.xr = x[0]; g.xi = x[1];
   g.yr = y[0]; g.yi = y[1];

@@ -4870,3 +4870,4 @@ int hh_profile_get(hh_ctx* c, hh_profile* out) try {
 #include "soft_mask.inc"  // the true FSC's soft masks built on the device from a resident support: exact distance transform, zoom(order=1) taps, cosine edge (hh_edt_3d, hh_soft_mask_3d, hh_tfsm_set_support / _soft_mask / _soft_masked)
 #include "adaptive_mask.inc"  // the true FSC's adaptive mask built on the device: float64 Gaussian with SciPy's reflect boundary, exact order statistics, Otsu by edges, 26-connected labelling (hh_am_*)
 #include "structure_factor.inc"  // structure factors: |F|^2 in the reference's float64 bins fused into the last forward pass, ratio, scaled inverse transform with irfftn's semantics, any sides (hh_sf_*)
+#include "align.inc"  // batched 2-D image alignment on a resident context: batched warp, phase-normalised cross-power epilogue of the last forward pass, arg-max fused into the c2r pass, wrap-mode score pass that stores no warped plane (hh_align_*)

@@ -22,6 +22,7 @@
  *   hh_helix_moments       lib/analysis.py:645-728            estimate_helix_rotation_center_diameter (closing + moments)
  *   hh_ssim_2d,            lib/analysis.py:487-613            ssim_score / ms_ssim_score / mutual_information_score: the non-cosine
  *   hh_joint_histogram                                        scores of lsq_reconstruct (solver_linear_regression.py:484-524)
+ *   hh_align_eval          lib/alignment.py:8-239             align_images (one evaluation of its objective, for many candidates)
  *   hh_set_reference +     webApps/denovo3D/app.py:2455-2523  reconstruction_task (the pool over
  *   hh_sweep[_device]                                         candidates) scoring each candidate by
  *                                                             cc(ref[mask], pwr[mask])
@@ -792,6 +793,33 @@ int hh_lres_plan(int32_t window, int route, int64_t scratch_bytes, int64_t max_w
  * the remaining weights sum to 0.  Map sides in [1, 512]. */
 int hh_lres_upsample(int device, const double* grid, int32_t gz, int32_t gy, int32_t gx, int32_t step, int32_t nz, int32_t ny,
                      int32_t nx, float* out);
+
+/* Batched 2-D image alignment (lib/alignment.py:8-239, align_images): one evaluation of the reference's objective — warp the
+ * moving plane by xform.inverse (order 1, mode "constant"), integer shift by phase cross-correlation (skimage's
+ * normalization = "phase", upsample_factor 1, no disambiguation), warp the plane and its taper again with that shift in mode
+ * "wrap", Pearson coefficient of (reference, warped)[warped taper > 0] — for many candidates at once.  A context keeps the
+ * prepared float32 reference plane [ny][nx] (and its half spectrum), n_moving prepared moving planes and their taper planes
+ * (already padded to the reference's shape), each plane's range and the transform tables; sides in [2, 1024], odd or even.
+ * inv_matrix: the first two rows of xform.inverse of the UNSHIFTED transform, float64, (x, y, 1) columns as scikit-image keeps
+ * them.  shift_out: [n][2] (y, x); score_out: [n] (0 when the norm is 0, NaN on an empty mask); peak_out: [n] the maximum of
+ * |c| (or NULL); nmask_out: [n] pixels under the warped taper (or NULL).  A result is bit-identical from run to run and does
+ * not depend on the other candidates of the call or on its place among them.  Errors: hh_last_error(NULL). */
+typedef struct hh_align hh_align;
+int hh_align_chunk(void);   /* candidates of one launch group (compiled in) */
+int hh_align_create(int device, int32_t ny, int32_t nx, const float* ref_work, int32_t n_moving, const float* moving_work,
+                    const float* taper, hh_align** out);
+int hh_align_destroy(hh_align* ctx);
+int hh_align_eval(hh_align* ctx, int64_t n, const int32_t* moving_index, const double* inv_matrix, int32_t* shift_out,
+                  double* score_out, float* peak_out, int32_t* nmask_out);
+/* the correlation surface c [ny][nx] of one candidate (the arg-max of |c| is its shift) */
+int hh_align_correlation(hh_align* ctx, int32_t moving_index, const double* inv_matrix, float* out);
+/* the second warp (mode "wrap", the transform shifted by shift = (y, x)) of a resident plane (plane NULL; which: 0 the moving
+ * plane, 1 its taper) or of the caller's plane [ny][nx] */
+int hh_align_warp_wrap(hh_align* ctx, const float* plane, int32_t moving_index, int which, const double* inv_matrix,
+                       const int32_t* shift, float* out);
+/* phase_ms (or NULL): [5] device-event milliseconds of hh_align_eval since the last reset: warp, forward passes, inverse y
+ * pass, c2r + arg-max, score.  enable: 1 / 0 switches the timing (each chunk is then synchronised) and resets, < 0 leaves it. */
+int hh_align_profile(hh_align* ctx, int enable, double* phase_ms);
 
 #ifdef __cplusplus
 }
