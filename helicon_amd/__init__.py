@@ -27,5 +27,6 @@ from .structure_factor import (StructureFactorMatcher, calculate_structural_fact
 # other names with ``from helicon_amd.local_resolution import ...`` (the command line is ``python -m helicon_amd.local_resolution``)
 from .local_resolution import LocalFSC, local_resolution, resolution_from_curve, taper_profile, window_centres
 from .align import AlignContext, align_images, align_images_grid
+from .pixel_size import calibrate_pixel_size, fft_resolution_range, nudft2d2, ring_maximum, ring_power_curve
 
 __version__ = "0.1.0"

@@ -228,6 +228,9 @@ EXPORTS = {
     "hh_align_correlation": (C.c_int, [C.c_void_p, C.c_int32, _f64p, _f32p]),
     "hh_align_warp_wrap": (C.c_int, [C.c_void_p, _f32p, C.c_int32, C.c_int, _f64p, C.POINTER(C.c_int32), _f32p]),
     "hh_align_profile": (C.c_int, [C.c_void_p, C.c_int, _f64p]),
+    "hh_nudft_chunk": (C.c_int, []),
+    "hh_nudft2d2": (C.c_int, [C.c_int, C.c_int32, C.c_int32, C.c_int32, _f32p, C.c_int64, _f64p, _f64p, C.c_int, C.c_int32, C.c_void_p]),
+    "hh_nudft_kernel_ms": (C.c_int, [_f64p]),
 }
 
 _lib = None

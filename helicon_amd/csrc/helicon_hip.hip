@@ -4871,3 +4871,4 @@ int hh_profile_get(hh_ctx* c, hh_profile* out) try {
 #include "adaptive_mask.inc"  // the true FSC's adaptive mask built on the device: float64 Gaussian with SciPy's reflect boundary, exact order statistics, Otsu by edges, 26-connected labelling (hh_am_*)
 #include "structure_factor.inc"  // structure factors: |F|^2 in the reference's float64 bins fused into the last forward pass, ratio, scaled inverse transform with irfftn's semantics, any sides (hh_sf_*)
 #include "align.inc"  // batched 2-D image alignment on a resident context: batched warp, phase-normalised cross-power epilogue of the last forward pass, arg-max fused into the c2r pass, wrap-mode score pass that stores no warped plane (hh_align_*)
+#include "nudft.inc"  // type-2 non-uniform DFT of image stacks at arbitrary points (the pixel-size calibration's polar band): columns contracted on the f32 MFMA with float64-reduced phases, row factor on the accumulator tile, complex / abs / ring-maximum epilogues (hh_nudft2d2)

@@ -23,6 +23,8 @@
  *   hh_ssim_2d,            lib/analysis.py:487-613            ssim_score / ms_ssim_score / mutual_information_score: the non-cosine
  *   hh_joint_histogram                                        scores of lsq_reconstruct (solver_linear_regression.py:484-524)
  *   hh_align_eval          lib/alignment.py:8-239             align_images (one evaluation of its objective, for many candidates)
+ *   hh_nudft2d2            plugins/images2star/calibratepixelsize.py:88-156  fft_resolution_range (its finufft.nufft2d2 call) and
+ *                                                             the ring maximum of calibrateMag_process_one_micrograph
  *   hh_set_reference +     webApps/denovo3D/app.py:2455-2523  reconstruction_task (the pool over
  *   hh_sweep[_device]                                         candidates) scoring each candidate by
  *                                                             cc(ref[mask], pwr[mask])
@@ -820,6 +822,24 @@ int hh_align_warp_wrap(hh_align* ctx, const float* plane, int32_t moving_index, 
 /* phase_ms (or NULL): [5] device-event milliseconds of hh_align_eval since the last reset: warp, forward passes, inverse y
  * pass, c2r + arg-max, score.  enable: 1 / 0 switches the timing (each chunk is then synchronised) and resets, < 0 leaves it. */
 int hh_align_profile(hh_align* ctx, int enable, double* phase_ms);
+
+/* Type-2 non-uniform DFT of a stack of images at arbitrary points (plugins/images2star/calibratepixelsize.py:88-156): what
+ * finufft.nufft2d2(x, y, f, eps = 1e-6) approximates, as the direct sum (isign = -1, centred modes, x with the FIRST axis)
+ *     F[b][p] = sum_a sum_c images[b][a][c] exp(-i (x[p] (a - ny / 2) + y[p] (c - nx / 2)))      (integer halves)
+ * images: host float32 [n_img][ny][nx], sides in [1, 16384]; x, y: host float64 [n_pts], radians per pixel, any real value
+ * (phases are reduced in float64 before a sine is taken).  The columns are contracted on the f32 MFMA on images whose
+ * float64 mean was removed; the mean's separable term is added in float64, so the result is the full sum.
+ * mode 0: out = complex64 [n_img][n_pts] (re, im pairs); 1: out = float32 [n_img][n_pts], |F|; 2: out = float32 [group], the
+ * ring maximum max over b and over p with p % group == r of |F| (1 <= group <= n_pts; no F is stored), equal bit for bit to
+ * the maximum of mode 1's values.  Points and images are cut into launch groups of hh_nudft_chunk() (compiled in).  A value
+ * is bit-identical from run to run and depends neither on the other points or images of the call nor on its place among
+ * them.  HH_ERR_ARG: a NULL, n_img < 1, n_pts < 1, a side outside [1, 16384], another mode, a group outside [1, n_pts].
+ * Errors: hh_last_error(NULL). */
+int hh_nudft_chunk(void);
+int hh_nudft2d2(int device, int32_t n_img, int32_t ny, int32_t nx, const float* images, int64_t n_pts, const double* x,
+                const double* y, int mode, int32_t group, void* out);
+/* device-event milliseconds of the calling thread's last hh_nudft2d2 (centring, axis sums and products; no copies) */
+int hh_nudft_kernel_ms(double* ms);
 
 #ifdef __cplusplus
 }
