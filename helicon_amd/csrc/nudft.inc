@@ -14,16 +14,19 @@
 // offsets j it supplies to the MFMA; per slice of NU_K columns it takes ONE float64 sincospi (the slice's first column) and
 // forms each entry of E by one complex multiplication with its table: no chain, so no error builds up along the side.  The
 // row factor is formed the same way: one float64 sincospi per row tile and a table of the accumulator's 16 row offsets, kept
-// per point in LDS (it is read once per row tile).
+// per point in LDS (it is read once per fold: every NU_FOLD columns of a row tile).
 //
 // The mean.  The product runs on f - mean(f) (float64 mean per image, subtracted in float64, rounded once); the mean's own
 // term is separable, mean * sum_a e^{-i x (a - ny // 2)} * sum_c e^{-i y (c - nx // 2)}, and is evaluated in float64 per point
 // (k_nudft_axis) and added in the epilogue: the result is the full sum, axis leakage included.
 //
 // Order.  A slice's products go into accumulators of their own (a chain of NU_K terms) which are then added, as in
-// fc_pair_product; row tiles are added in float64 in ascending order; the four partial sums of a point (two accumulator row
-// halves x two wavefronts) are added in a fixed order.  A lane's arithmetic depends on its own point and image only, so a
-// value does not depend on the other points or images of the call, on its place among them, or on the run.
+// fc_pair_product, in float32 over at most NU_FOLD columns: then the row factor takes the tile into the float64 sum.  (Where
+// the addends repeat, a float32 sum rounds the same way at every step: over the 512 slices of a 16384-column row a delta on
+// the mean's floor, seen from the origin, lost 4e-6 of sum |f - mean|.)  Row tiles follow each other in ascending order; the
+// four partial sums of a point (two accumulator row halves x two wavefronts) are added in a fixed order.  A lane's arithmetic
+// depends on its own point and image only, so a value does not depend on the other points or images of the call, on its
+// place among them, or on the run.
 
 namespace {
 
@@ -31,6 +34,7 @@ constexpr int NUDFT_CHUNK = 32768;    // points of one launch (grid x = NUDFT_CH
 constexpr int NU_T = 64;              // points, and image rows, of a workgroup's tile
 constexpr int NU_K = 32;              // columns of one accumulator slice (one base sincospi each)
 constexpr int NU_KS = 128;            // columns staged at once
+constexpr int NU_FOLD = 512;          // columns whose slices are added in float32 before the row factor folds them into float64
 constexpr int NU_MAX_SIDE = 16384;
 constexpr double NU_2PI = 6.283185307179586476925286766559;
 
@@ -138,6 +142,8 @@ __global__ __launch_bounds__(256, 2) void k_nudft(NuArgs g) {
       float pre[NU_T / 2];
       nu_fetch(pre, img, ny, nx, a0 + srow, scol);
       float2 eb = nu_unit_f(uy, -(nx / 2));
+      // the row factor of the accumulator tile: rows a0 + wm + 4 h + {0..3, 8..11, 16..19, 24..27}
+      const float2 rb = nu_unit_f(ux, a0 + t.wm + 4 * t.h - ny / 2);
       for (int c0 = 0; c0 < nx; c0 += NU_KS) {
         nu_store(as, pre, ny, nx, srow, scol, a0 + srow, c0 + scol);
         __syncthreads();
@@ -157,16 +163,18 @@ __global__ __launch_bounds__(256, 2) void k_nudft(NuArgs g) {
           tim += sim;
           eb = en;
         }
-        __syncthreads();
-      }
-      // the row factor on the accumulator tile: rows a0 + wm + 4 h + {0..3, 8..11, 16..19, 24..27}
-      const float2 rb = nu_unit_f(ux, a0 + t.wm + 4 * t.h - ny / 2);
+        if ((c0 + NU_KS) % NU_FOLD == 0 || c0 + NU_KS >= nx) {   // fold: once a row tile for a side up to NU_FOLD
 #pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        const float2 rt = rtab[i][t.wp + t.r];
-        const float rr = rb.x * rt.x - rb.y * rt.y, ri = rb.x * rt.y + rb.y * rt.x;
-        fre += (double)tre[i] * (double)rr - (double)tim[i] * (double)ri;
-        fim += (double)tre[i] * (double)ri + (double)tim[i] * (double)rr;
+          for (int i = 0; i < 16; ++i) {
+            const float2 rt = rtab[i][t.wp + t.r];
+            const float rr = rb.x * rt.x - rb.y * rt.y, ri = rb.x * rt.y + rb.y * rt.x;
+            fre += (double)tre[i] * (double)rr - (double)tim[i] * (double)ri;
+            fim += (double)tre[i] * (double)ri + (double)tim[i] * (double)rr;
+          }
+          tre = f32x16{0};
+          tim = f32x16{0};
+        }
+        __syncthreads();
       }
     }
     // red is free: the image's stages, each with two barriers, lie between this store and the last image's reads

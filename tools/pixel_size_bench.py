@@ -2,6 +2,7 @@
 and speed.
 
     python tools/pixel_size_bench.py [--out profiles/pixel_size.json] [--reps 2] [--sample 512] [--accuracy-only] [--speed-only]
+    python tools/pixel_size_bench.py --probes [--out profiles/pixel_size.json]
 
 ``accuracy``: over every comparison of tests/test_gpu_pixel_size.py (``pixel_size_cases.accuracy_cases``: the point shapes,
 counts and stacks, the long sides, the offset image, the full band) the largest ``|F_device - F_yardstick| / sum |f - mean|``
@@ -12,6 +13,10 @@ micrograph and of 256 particles of 256 x 256: wall clock of the call (upload and
 device-event milliseconds of its kernels, best of ``--reps``; the product's share of the MI355X's f32 matrix peak (4 FLOP
 per point, pixel: a real image value times a complex factor, multiply and add); and the NumPy two-stage composition (the
 yardstick) timed in the same run on ``--sample`` points and scaled to the band.  A run without a GPU fails.
+
+``--probes``: the closed-form probe list of tests/nudft_probes.py, as tests/test_gpu_nudft_probes.py walks it: per family the
+largest error over that list's own allowance (complex and abs outputs), and the probe it occurs on.  Only the ``probes`` key
+of ``--out`` is rewritten; the file's other keys stay.  It is a record: no tolerance is derived from it.
 """
 import argparse
 import json
@@ -88,6 +93,29 @@ def speed(reps, sample):
     return out
 
 
+def probes():
+    import nudft_probes as Q
+    from helicon_amd import pixel_size as PS
+
+    assert PS.nudft_chunk() == Q.CHUNK
+    out = dict(bound="B sum|f - mean| + 2^-23 |want| + ny nx (ny + nx) 2^-53 |mean|", families={})
+    for probe in Q.probes():
+        f, (x, y) = Q.images(probe), Q.points(probe)
+        idx = slice(None) if probe.pick is None else np.array(probe.pick)
+        want = Q.expect(probe, None if probe.pick is None else idx)
+        lim = Q.allowance(f, want)
+        e_c = Q.share(PS.nudft2d2(x, y, f)[:, idx].astype(np.complex128), want, lim)
+        e_a = Q.share(PS.nudft2d2(x, y, f, output="abs")[:, idx].astype(np.float64), np.abs(want), lim)
+        row = out["families"].setdefault(probe.family, dict(probes=0, images=0, complex=0.0, abs=0.0, worst_probe=None))
+        if max(e_c, e_a) > max(row["complex"], row["abs"]) or row["worst_probe"] is None:
+            row["worst_probe"] = probe.label
+        row.update(probes=row["probes"] + 1, images=row["images"] + len(f), complex=max(row["complex"], e_c), abs=max(row["abs"], e_a))
+    for family, row in out["families"].items():
+        print(f"{family}: {json.dumps(row)}", flush=True)
+    out["max_error_over_allowance"] = max(max(r["complex"], r["abs"]) for r in out["families"].values())
+    return out
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--out", default=None)
@@ -95,7 +123,16 @@ def main(argv=None):
     ap.add_argument("--sample", type=int, default=512)
     ap.add_argument("--accuracy-only", action="store_true")
     ap.add_argument("--speed-only", action="store_true")
+    ap.add_argument("--probes", action="store_true", help="walk tests/nudft_probes.py and rewrite the 'probes' key of --out alone")
     args = ap.parse_args(argv)
+    if args.probes:
+        res = json.loads(Path(args.out).read_text()) if args.out and Path(args.out).exists() else {}
+        res["probes"] = probes()
+        if args.out:
+            Path(args.out).parent.mkdir(parents=True, exist_ok=True)
+            Path(args.out).write_text(json.dumps(res, indent=1) + "\n")
+        print(json.dumps({k: v for k, v in res["probes"].items() if k != "families"}))
+        return 0
     res = dict(f32_matrix_peak_flops=F32_MATRIX_PEAK)
     if not args.speed_only:
         res["accuracy"] = accuracy()
