@@ -2197,7 +2197,15 @@ __global__ __launch_bounds__(N, (N >= 256 ? KF<N>::WPS : 1)) void k_fused_pass(F
     if constexpr (PACK) {
       float2 v[8];
       fft_lanes_part<NF, true, TwRegs, 2, 1>(v, twsrc, tf, fbuf);  // Re v[m] = Re F_A[kx], Im v[m] = Re F_B[kx], kx = t + m T
-      // (run A's sums are finished before run B's begin: three running sums at a time, as in part_b)
+      // The pair's six sums (s = 0..2: A's, 3..5: B's) meet in the wavefront's exchange buffer, which is idle from the
+      // transform's last exchange to the next pair's first: lane L stores sum s at float 64 s + L (packed_sum_slot), and
+      // lane L < 48 — sum L >> 3, part L & 7 — reads back floats 8 L .. 8 L + 7, the sums of lanes 8 (L & 7) .. + 7, as two
+      // 16-byte halves.  At a 32-byte lane stride the sixteen lanes one LDS cycle serves would read one half each of eight
+      // bank slots twice over, so lanes 16-31 and 48-63 take the upper half first (packed_sum_first_half); the halves are
+      // summed apart, (e0 + e1 + e2 + e3) + (e4 + e5 + e6 + e7), and float addition commutes, so nothing is selected back.
+      // Three DPP adds then close the 8-lane group, and lane 8 s holds sum s: eight in the lane, eight in a row of slots,
+      // eight across — an order that depends on nothing but the lane.  (Run A's first two sums leave before run B's bins.)
+      float* const sums = reinterpret_cast<float*>(fbuf);
       float a1 = 0.f, a2 = 0.f, a3 = 0.f, b1 = 0.f, b2 = 0.f, b3 = 0.f;
 #pragma unroll
       for (int m = 0; m < 8; ++m) {
@@ -2207,7 +2215,9 @@ __global__ __launch_bounds__(N, (N >= 256 ? KF<N>::WPS : 1)) void k_fused_pass(F
         a2 += w[m].x * q * q;
         a3 += w[m].y * q;
       }
-      group_sum3<TL>(a1, a2, a3);
+      group_sync<TL>();   // the transform's last exchange has been read
+      sums[packed_sum_slot(0, t)] = a1;
+      sums[packed_sum_slot(1, t)] = a2;
 #pragma unroll
       for (int m = 0; m < 8; ++m) {
         const float f = __builtin_amdgcn_sqrtf(fmaf(v[m].y, v[m].y, imb2));
@@ -2216,21 +2226,36 @@ __global__ __launch_bounds__(N, (N >= 256 ? KF<N>::WPS : 1)) void k_fused_pass(F
         b2 += w[m].x * q * q;
         b3 += w[m].y * q;
       }
-      group_sum3<TL>(b1, b2, b3);
+      sums[packed_sum_slot(2, t)] = a3;
+      sums[packed_sum_slot(3, t)] = b1;
+      sums[packed_sum_slot(4, t)] = b2;
+      sums[packed_sum_slot(5, t)] = b3;
+      group_sync<TL>();
+      const int fh = packed_sum_first_half(t);
+      const float4 e0 = *reinterpret_cast<const float4*>(sums + 8 * t + 4 * fh);   // (lanes 48-63: floats the six sums do not use)
+      const float4 e1 = *reinterpret_cast<const float4*>(sums + 8 * t + 4 * (fh ^ 1));
+      group_sync<TL>();   // both reads are done before the next pair's first exchange writes
+      float tot = (((e0.x + e0.y) + e0.z) + e0.w) + (((e1.x + e1.y) + e1.z) + e1.w);
+      // (every lane has its three partners: bound_ctrl lets each step be one v_add_f32_dpp)
+#define HH_DPP_ADD(CTRL) tot += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(tot), CTRL, 0xF, 0xF, true))
+      HH_DPP_ADD(0xB1);   // quad_perm [1,0,3,2]
+      HH_DPP_ADD(0x4E);   // quad_perm [2,3,0,1]
+      HH_DPP_ADD(0x141);  // row_half_mirror: every lane of the group of eight holds sum s
+#undef HH_DPP_ADD
       if (wait_copy) lds_dma_wait();
-      if (writer) {
-        if (ca >= 0) {
-          double* const o = a.partials + (cand_of(ca) * KP::NPART + (size_t)row * KP::WPR + wave_in_row) * 3;
-          o[0] = a1;
-          o[1] = a2;
-          o[2] = a3;
-        }
-        if (ca + 1 < nc) {
-          double* const o = a.partials + (cand_of(ca + 1) * KP::NPART + (size_t)row * KP::WPR + wave_in_row) * 3;
-          o[0] = b1;
-          o[1] = b2;
-          o[2] = b3;
-        }
+      // Lane 8 s stores sum s, one double of its run's triple (PACKED_SUM_LANES_A / _B; a half outside [0, nc) is not stored).
+      // The lanes' places are fixed, so which of them store is a scalar mask of the pair's two tests, and a lane's address
+      // is A's scalar one plus its own bytes: 8 k, and for a B lane the distance from A's triple to B's.
+      static_assert((uint64_t)FUSED_BATCH * KP::NPART * 3 * sizeof(double) < (1ull << 32), "a launch's partials are addressed with 32-bit byte offsets");
+      const unsigned long long stores = (ca >= 0 ? PACKED_SUM_LANES_A : 0ull) | (ca + 1 < nc ? PACKED_SUM_LANES_B : 0ull);
+      if ((stores >> t) & 1ull) {
+        const int64_t first = ((int64_t)cfirst + (int64_t)ca * a.run_len) * KP::NPART + (int64_t)row * KP::WPR + wave_in_row;   // A's triple
+        const unsigned b_bytes = (unsigned)a.run_len * (unsigned)(KP::NPART * 3 * sizeof(double));
+        const unsigned lane_bytes = t < 24 ? (unsigned)t : b_bytes + (unsigned)t - 24u;   // 8 k, k = t / 8 - (B: 3)
+        // (ca = -1 in a launch's first run: A's triple lies before the partials and only B's lanes store; the address is
+        // an integer sum that b_bytes brings back inside — intended, and what the hardware's base + offset computes)
+        char* const o = reinterpret_cast<char*>(a.partials) + first * (int64_t)(3 * sizeof(double));
+        *reinterpret_cast<double*>(o + lane_bytes) = tot;
       }
     }
   };

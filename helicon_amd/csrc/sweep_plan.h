@@ -181,6 +181,20 @@ HH_PLAN_FN WalkPlace twist_walk_place(int lw, int nkb, int la, int layers) {
   lw -= n8 * rest;
   return WalkPlace{1 + lw % rest, first + n8 + lw / rest};
 }
+
+// The packed pair walk's six sums of a pair (s = 0..2: run A's three moments, s = 3..5: run B's) on their way through the
+// wavefront's exchange buffer (tests/packed_reduce_cases.py is this map in numpy).
+//   packed_sum_slot        the float lane `lane` stores its sum s to: a row of 64 per sum.
+//   packed_sum_first_half  lane L reads floats 8 L .. 8 L + 7 as two 16-byte halves; the half (0: lower, 1: upper) it takes
+//                          with its FIRST read.  The LDS serves a 16-byte read in four groups of sixteen lanes, {0-3, 12-15,
+//                          20-27}, {4-11, 16-19, 28-31} and the same of lanes 32-63, a group's sixteen reads on the sixteen
+//                          4-bank slots of the 64 banks: with lanes 16-31 and 48-63 on the other half every group fills
+//                          them once.
+//   PACKED_SUM_LANES_A, _B the lanes that store: lane 8 s stores sum s, moment k = s % 3 of candidate ca (A: lanes 0, 8, 16)
+//                          or ca + 1 (B: lanes 24, 32, 40) of the workgroup's piece, where that candidate is the piece's.
+HH_PLAN_FN int packed_sum_slot(int s, int lane) { return 64 * s + lane; }
+HH_PLAN_FN int packed_sum_first_half(int lane) { return (lane >> 4) & 1; }
+constexpr unsigned long long PACKED_SUM_LANES_A = 0x010101ull, PACKED_SUM_LANES_B = PACKED_SUM_LANES_A << 24;
 #undef HH_PLAN_FN
 
 // Which candidate loop a launch of `runs` whole runs of `run_len` candidates takes when every run shares one rise
