@@ -2680,27 +2680,36 @@ __global__ __launch_bounds__(N / 8) void k_inverse_cols(const float2* __restrict
   }
 }
 
-// threshold_data: max over the array (non-negative-safe float ordering via two atomics), then clip - thresh
-__global__ void k_array_max(const float* __restrict__ x, size_t n, int* __restrict__ out /*[2]: max of >=0 as int, min of <0 as uint*/) {
-  float m = -INFINITY;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) m = fmaxf(m, x[i]);
-  for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_down(m, off, 64));
-  if ((threadIdx.x & 63) == 0) {
-    // float bits order like signed ints for non-negative values and reversed for negative ones
-    if (m >= 0.f) atomicMax(&out[0], __float_as_int(m));
-    else atomicMin(reinterpret_cast<unsigned*>(&out[1]), __float_as_uint(m));
-  }
+// threshold_data: np.max over the array, then clip - thresh.  The maximum is taken on one unsigned key per value that
+// orders like the floats do: the bits with the sign bit set for a cleared sign bit, all bits inverted for a set one, so
+// -inf < ... < -0.0 < +0.0 < ... < +inf, and above them all 0xFFFFFFFF for any NaN (np.max returns NaN when one is
+// present).  No value has key 0, the slot's initial value, so a maximum of -0.0 or of negative values is recorded like
+// any other; the key of a NaN decodes to the NaN 0x7FFFFFFF.
+__device__ __forceinline__ unsigned max_key(float v) {
+  const unsigned u = __float_as_uint(v);
+  return v != v ? 0xFFFFFFFFu : (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
-__global__ void k_threshold(const float* __restrict__ x, size_t n, const int* __restrict__ mx, float fraction, float value,
+__device__ __forceinline__ float max_key_value(unsigned key) {
+  return __uint_as_float((key & 0x80000000u) ? (key ^ 0x80000000u) : ~key);
+}
+
+__global__ void k_array_max(const float* __restrict__ x, size_t n, unsigned* __restrict__ out /*[1]: largest max_key, from 0*/) {
+  unsigned m = 0;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) m = max(m, max_key(x[i]));
+  for (int off = 32; off > 0; off >>= 1) m = max(m, (unsigned)__shfl_down(m, off, 64));
+  if ((threadIdx.x & 63) == 0 && m != 0) atomicMax(out, m);  // (m == 0: a wavefront without an element)
+}
+
+__global__ void k_threshold(const float* __restrict__ x, size_t n, const unsigned* __restrict__ mx, float fraction, float value,
                             int use_fraction, float* __restrict__ out) {
-  float thresh = value;
-  if (use_fraction) {
-    const float vmax = mx[0] >= 0 ? __int_as_float(mx[0]) : __uint_as_float((unsigned)mx[1]);
-    thresh = vmax * fraction;
+  const float thresh = use_fraction ? max_key_value(mx[0]) * fraction : value;
+  // np.clip(data, thresh, None) - thresh; a NaN in x[i] or in thresh fails the comparison and comes out of the
+  // subtraction as NaN, as np.maximum hands it on (fmaxf would drop it)
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    const float v = x[i];
+    out[i] = (v < thresh ? thresh : v) - thresh;
   }
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
-    out[i] = fmaxf(x[i], thresh) - thresh;  // np.clip(data, thresh, None) - thresh
 }
 
 // ------------------------------------------------------------------------------------------
@@ -4517,11 +4526,10 @@ int hh_threshold_data(hh_ctx* c, const float* data, int64_t n, int use_fraction,
   HH_HIP(c, hipSetDevice(c->device));
   DevArena mem;
   float *d_x = mem.get<float>((size_t)n), *d_y = mem.get<float>((size_t)n);
-  int* d_mx = mem.get<int>(2);
+  unsigned* d_mx = mem.get<unsigned>(1);
   if (int rc = arena_ok(c, mem)) return rc;
-  const int init[2] = {(int)0x80000000, -1};  // below every non-negative float's bits; above every negative float's (as unsigned)
   hipError_t e = hipMemcpyAsync(d_x, data, (size_t)n * sizeof(float), hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_mx, init, sizeof(init), hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipMemsetAsync(d_mx, 0, sizeof(unsigned), c->stream);  // below every value's max_key
   if (e == hipSuccess) {
     const int grid = (int)std::min<int64_t>(1024, (n + 255) / 256);
     if (use_fraction) hipLaunchKernelGGL(k_array_max, dim3(grid), dim3(256), 0, c->stream, d_x, (size_t)n, d_mx);

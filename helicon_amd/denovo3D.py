@@ -685,7 +685,10 @@ def low_high_pass_filter(data, low_pass_fraction=0, high_pass_fraction=0, *, dev
 
 def threshold_data(data, thresh_fraction=None, thresh_value=None, *, device=0):
     """``helicon.threshold_data`` (lib/filters.py:283-311) on the device; returns the input unchanged
-    when neither threshold applies, like the reference."""
+    when neither threshold applies, like the reference.  Computed in float32: ``np.clip(x, t, None) - t`` with
+    ``t = x.max() * float32(thresh_fraction)`` or ``float32(thresh_value)``.  As in NumPy, the maximum of an all-negative
+    array is its value nearest zero (``-0.0`` included), a NaN anywhere makes the fraction threshold and so every output
+    NaN, and with ``thresh_value`` a NaN stays NaN where it is."""
     d = np.asarray(data)
     if not ((thresh_fraction is not None and thresh_fraction >= 0) or thresh_value is not None):
         return data

@@ -307,8 +307,11 @@ int hh_last_row_kernel(const hh_ctx* ctx, int32_t out[3]);
  * hh_low_high_pass_filter: helicon.low_high_pass_filter (lib/filters.py:314-372) for one N x N float32 image
  * (host in, host out): Gaussian low pass exp(-ln2 R^2 / lp^2) and / or high pass 1 - exp(-ln2 R^2 / hp^2),
  * R = radius as a fraction of Nyquist; a fraction outside (0, 1) switches that filter off.
- * hh_threshold_data: helicon.threshold_data (lib/filters.py:283-311): out = clip(data, t, None) - t with
- * t = max(data) * thresh (use_fraction != 0) or t = thresh. */
+ * hh_threshold_data: helicon.threshold_data (lib/filters.py:283-311) for n float32 values (host in, host out):
+ * out = clip(data, t, None) - t in float32 with t = max(data) * (float)thresh (use_fraction != 0) or t = (float)thresh.
+ * The maximum is np.max's: of negative values the one nearest zero, -0.0 where that is the largest value (+0.0 counts
+ * as above -0.0), NaN when any element is NaN — every output is then NaN, as from NumPy.  With a number for t a NaN
+ * element stays NaN at its own position and nowhere else. */
 int hh_low_high_pass_filter(hh_ctx* ctx, const float* image, double low_pass_fraction, double high_pass_fraction,
                             float* out);
 int hh_threshold_data(hh_ctx* ctx, const float* data, int64_t n, int use_fraction, double thresh, float* out);
